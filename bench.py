@@ -15,7 +15,12 @@ all-reduce of each layer's output (strong scaling; `value`), and the same K step
 equivalent all-gather of the row slices (`value_allgather`).  `python bench.py --gpus N` without a
 launcher starts its own N ranks (torch.distributed.run as a child process).
 
-Extra objects on the JSON line: ``roofline`` for the u_mul_e_sum SpMM at D = 64 on the timed
+A plain run (no ``--full``) does only what the headline needs: it sets up, runs W warm-up and K
+timed steps, writes the last timed step's outputs if ``--dump-outputs DIR`` is given, and prints
+the headline fields (``metric``, ``value``, ``unit``, ``ms_per_step``, ...).  Everything else below
+is measured with ``--full``.
+
+Extra objects on the ``--full`` JSON line: ``roofline`` for the u_mul_e_sum SpMM at D = 64 on the timed
 workload (HBM bound; algorithmic bytes E*(4D+8) + N*(4D+4); on the amazon-book /
 last-fm shapes X sits in the Infinity Cache, flagged ``cache_served``), ``roofline_hbm`` for the
 same kernel on an HBM-resident graph built on the device after the timed region (BASELINE
@@ -74,7 +79,44 @@ def parse():
     ap.add_argument("--hbm-epilogue", action="store_true",
                     help="also time the HBM-resident SpMM with the h*h_N epilogue (off by default: it is the kernel "
                          "instantiation of the timed step, and would mix into its rocprof average)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: the steady-state repeat, the "
+                         "deferred-weights and propagation-only steps, per-kernel and roofline figures, the training "
+                         "leg, the HBM-resident SpMM leg, the CPU baselines (checked against the GPU step) and, for "
+                         "N > 1, the exchange alternatives and the unsharded comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32): readout.npy (the gnn "
+                         "output, N x sum of layer widths) and, for N = 1, attention.npy (the edge weights); an array "
+                         "over its share of the 64 MiB budget is a fixed, seeded sample of its rows, whose indices "
+                         "go to DIR/<name>_rows.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+# --dump-outputs: bytes per array (data + sampled-row indices); together below 64 MiB
+DUMP_BUDGET = {"readout": 44_000_000, "attention": 16_000_000}
+
+
+def dump_outputs(path, arrays, seed=2024):
+    """Write each (name, device tensor) as path/<name>.npy in float32.  A tensor larger than its
+    DUMP_BUDGET share is sampled on the device: rows drawn without replacement by a generator
+    seeded with `seed` (the same rows for the same shape), kept in ascending order, their indices
+    written beside it as <name>_rows.npy (float64, exact for any row count)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        t = t.detach()
+        rows = t.shape[0]
+        row_bytes = 4 * (t.numel() // max(rows, 1))
+        if rows * row_bytes <= DUMP_BUDGET[name]:
+            np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+            continue
+        k = DUMP_BUDGET[name] // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(rows, k, replace=False))
+        pick = torch.as_tensor(idx, device=t.device)
+        np.save(os.path.join(path, name + ".npy"), t.index_select(0, pick).float().cpu().numpy())
+        np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
 
 
 def source_hash(*names):
@@ -626,7 +668,7 @@ def main():
     torch.manual_seed(1234)
     model = K.KGATPropagation(n, n_rel, input_node_dim=args.dim, relation_dim=args.dim,
                               num_gnn_layers=args.layers, n_hidden=args.dim, dropout=0.0)
-    params = {k: v.detach().numpy().copy() for k, v in model.state_dict().items()}
+    params = {k: v.detach().numpy().copy() for k, v in model.state_dict().items()} if args.full else None
     model = model.to(dev)
     keep_full = world == 1 or E <= args.ref_edge_bound   # the unsharded reference pass needs the whole graph
     if world > 1:
@@ -708,13 +750,17 @@ def main():
     # that is part of what the driver's command measures)
     dt, (out, a) = timed_steps()          # N > 1: the north_star exchange (all-reduce of the zero-padded layer output)
     ms_per_step = dt / args.steps * 1e3
-    # ... then --prewarm untimed steps (default 30 = 15 ms; 3 on graphs beyond 20 M edges) and the same
+    if args.dump_outputs and rank == 0:   # what a caller of the timed path received in the last timed step
+        dump_outputs(args.dump_outputs, [("readout", out)] + ([("attention", a)] if world == 1 else []))
+    # --full: --prewarm untimed steps (default 30 = 15 ms; 3 on graphs beyond 20 M edges) and the same
     # protocol again: the steady state, reported beside the headline as ms_per_step_steady_state.
-    prewarm = args.prewarm if E <= 20_000_000 else min(args.prewarm, 3)
-    for _ in range(prewarm):
-        out, a = step()
-    sync()
-    dt_steady, (out, a) = timed_steps()
+    prewarm, dt_steady = None, None
+    if args.full:
+        prewarm = args.prewarm if E <= 20_000_000 else min(args.prewarm, 3)
+        for _ in range(prewarm):
+            out, a = step()
+        sync()
+        dt_steady, (out, a) = timed_steps()
     # The same protocol with the step's launches captured once as HIP graphs and replayed (dgl_kgat_amd.GraphedForward:
     # one graph on one GPU; one per stretch between two layer-output exchanges on N > 1, the collectives staying
     # ordinary calls between the replays): the same kernels on the same buffers, the same bits.  Informational - the
@@ -744,7 +790,7 @@ def main():
     def core_line():
         """The contract's fields of the JSON line, from the measurement above (also what a watchdog prints
         when a later, optional leg stalls)."""
-        return {
+        line = {
             "metric": METRIC,
             "value": round(args.layers * E / (dt / args.steps), 1),
             "unit": "edges/s",
@@ -753,9 +799,23 @@ def main():
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "hip_graphs": hip_graphs,
-            "ms_per_step_steady_state": round(dt_steady / args.steps * 1e3, 4),
-            "value_steady_state": round(args.layers * E / (dt_steady / args.steps), 1),
         }
+        if dt_steady is not None:
+            line["ms_per_step_steady_state"] = round(dt_steady / args.steps * 1e3, 4)
+            line["value_steady_state"] = round(args.layers * E / (dt_steady / args.steps), 1)
+        return line
+
+    if not args.full:
+        if rank == 0:
+            line = core_line()
+            line.update({"status": "ok", "config": {
+                "workload": "%s N=%d E=%d R=%d, %d layers, embed_dim=%d, fp32" % (name, n, E, n_rel, args.layers, args.dim),
+                "partition": "none" if world == 1 else "dst-range x%d, all-reduce of layer outputs" % world,
+                "setup_steps": 1, "full": False}})
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # N > 1: the same K steps with the equivalent slice exchange (every row has one owner, so the sum
     # is an assembly): all-gather of the owned row slices - RCCL runs unequal slices as one group of

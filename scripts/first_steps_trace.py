@@ -1,5 +1,5 @@
 """Which kernels make the first ~15 steps after the setup step slower than steady state (task 6e)?
-Reads a rocprofv3 kernel trace (CSV) of `bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-leg --no-train-leg`,
+Reads a rocprofv3 kernel trace (CSV) of `bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-leg --no-train-leg`,
 cuts it into steps at the attention launch, and prints per step the wall time (start of its attention launch to the
 start of the next one), the sum of its kernels' durations, and per kernel name the mean duration over step ranges."""
 import csv

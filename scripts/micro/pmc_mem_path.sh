@@ -5,7 +5,7 @@ cd /tmp; export TMPDIR=/tmp
 rocprofv3 --list-avail > $O/avail.txt 2>&1
 grep -o "TCP_[A-Z_0-9a-z]*\|TCC_[A-Z_0-9a-z]*\|TA_[A-Z_0-9a-z]*\|SQ_LDS[A-Z_0-9a-z]*" $O/avail.txt | sort -u > $O/avail_names.txt
 wc -l $O/avail_names.txt
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-hbm-leg --no-train-leg"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-hbm-leg --no-train-leg"
 i=0
 for set in "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCC_REQ_sum TCC_HIT_sum" "TCC_MISS_sum TCC_READ_sum TCP_TA_TCP_STATE_READ_sum TCP_PENDING_STALL_CYCLES_sum" "TA_TA_BUSY_sum TA_BUSY_avr TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_GATE_EN1_sum" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_LDS" "TA_BUFFER_WAVEFRONTS_sum TA_FLAT_READ_WAVEFRONTS_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum"; do
   i=$((i+1))

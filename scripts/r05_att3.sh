@@ -4,7 +4,7 @@ TAG=${1:-att3}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || { echo build failed; tail $O/build.log; exit 1; }
 timeout 1200 python -m pytest tests/test_gpu_parity.py -m gpu -q -k "att" -s > $O/pytest_att.log 2>&1; echo "pytest rc $?" >> $O/pytest_att.log
 grep -n "att products\|passed\|failed\|rc " $O/pytest_att.log | tail -70
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-leg --no-train-leg"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-leg --no-train-leg"
 $B > $O/d64.json 2> $O/d64.err
 KGAT_ATT_TILES32=1 $B > $O/d64_tiles32.json 2> $O/d64_tiles32.err
 $B --dim 128 > $O/d128.json 2> $O/d128.err

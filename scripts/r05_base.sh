@@ -5,7 +5,7 @@ mkdir -p $O
 cd $R
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1
 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc $?" >> $O/pytest_gpu.log
-python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc $?" >> $O/bench_line.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc $?" >> $O/bench_line.err
 python scripts/surface_time.py > $O/surface_vs_fused.txt 2>&1
 python scripts/kbench.py train --rounds 10 > $O/kbench_train.txt 2>&1
 python scripts/kbench.py kg --rounds 30 > $O/kbench_kg.txt 2>&1

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
 python3 -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || { echo build failed; exit 1; }
-python3 bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"
 python3 - <<PY
 import json
 d=json.load(open("$O/bench_line.json"))
@@ -15,7 +15,7 @@ print("hbm", (d.get("roofline_hbm") or {}).get("frac"), "cpu", (d.get("cpu_basel
 print("keys", list(d.keys()))
 PY
 cd /tmp; export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/step_stats -o step --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-leg --no-train-leg > $O/bench_line_profiled.json 2> $O/bench_profiled.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/step_stats -o step --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-leg --no-train-leg > $O/bench_line_profiled.json 2> $O/bench_profiled.err
 cp $O/step_stats/step_kernel_stats.csv $O/r06_bench_kernel_stats_step_only.csv
 python3 $R/scripts/first_steps_trace.py $O/step_stats/step_kernel_trace.csv > $O/r06_first_steps_trace.txt 2>&1
 rm -f $O/step_stats/step_kernel_trace.csv
