@@ -25,6 +25,7 @@ SOURCES = {
     "kgat_eval.hip": [],
     "kgat_optim.hip": [],
     "kgat_bpr.hip": [],
+    "kgat_sage.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -118,6 +119,12 @@ SIGNATURES = {
                                          _p, _sz, _p]),
     "kgat_adam_max_tensors": (_i32, []),
     "kgat_adam_step_f32": (_i32, [_i32, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _i32, _p]),
+    "kgat_copy_reduce_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _sz, _p]),
+    "kgat_sage_dense_supported": (_i32, [_i32, _i32]),
+    "kgat_sage_dense_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i64, _p, _i64, _p]),
+    "kgat_dropout_rows_f32": (_i32, [_i64, _i32, _p, _p, C.c_float, C.c_uint64, _p, _p]),
+    "kgat_sage_bwd_input_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "kgat_sage_bwd_weight_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "kgat_eval_recall_ndcg_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p,
                                          _p, _p, _p]),
 }
@@ -138,7 +145,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def source_hash():

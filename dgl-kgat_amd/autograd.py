@@ -1,10 +1,12 @@
-"""Autograd glue for the two differentiable sparse operators of the path.
+"""Autograd glue for the differentiable sparse operators of the path.
 
 * ``u_mul_e_sum`` - update_all(u_mul_e, sum), reference models.py:63.  Backward w.r.t. the
   node features is the same SpMM kernel on the reversed graph's CSR;
   backward w.r.t. the edge weight is an SDDMM (only when the weight requires grad - in the
   reference it never does, kgat.py:142-144).
 * ``edge_softmax`` - reference models.py:153; backward as DGL 0.4.x EdgeSoftmax.backward.
+* ``copy_reduce`` - update_all(copy_src, sum | mean), the aggregation of DGL's SAGEConv (gnn_model
+  "graphsage"); backward over the reversed graph's CSR.
 """
 import torch
 
@@ -57,6 +59,54 @@ def u_mul_e_sum(g, x, w, mul_self=False):
     if w.shape[0] != g.number_of_edges():
         raise ValueError("edge weight has %d rows, graph has %d edges" % (w.shape[0], g.number_of_edges()))
     return _UMulESum.apply(x, w, g, mul_self)
+
+
+class _CopyReduce(torch.autograd.Function):
+    """update_all(copy_src, sum | mean) (kgat_copy_reduce_f32).  Backward w.r.t. the node feature: the sum over the
+    reversed graph's CSR - of the incoming gradient itself (sum), or through the aggregation with the weights
+    1 / max(in_deg(dst), 1) (mean; kgat_spmm_umule_sum_f32 with a graph-static weight array)."""
+
+    @staticmethod
+    def forward(ctx, x, g, reduce):
+        st = g._st
+        x2 = x if x.dim() == 2 else x.unsqueeze(1)
+        x2 = x2.contiguous()
+        if x2.dtype != torch.float32:
+            raise TypeError("node features must be float32, got %s" % x2.dtype)
+        csr = st.csr(x2.device)
+        out = ops.copy_reduce(csr.indptr, csr.col, csr.row_of, x2.detach(), reduce)
+        ctx.g, ctx.reduce, ctx.squeeze = g, reduce, x.dim() == 1
+        return out.squeeze(1) if x.dim() == 1 else out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        st = ctx.g._st
+        dev = grad_out.device
+        go = (grad_out.unsqueeze(1) if ctx.squeeze else grad_out).contiguous()
+        rev = st.csr_rev(dev)
+        if ctx.reduce == "sum":
+            grad_x = ops.copy_reduce(rev.indptr, rev.col, rev.row_of, go, "sum")
+        else:
+            grad_x = ops.spmm(rev.indptr, rev.col, rev.row_of, go, rev_inv_degree(st, dev))
+        return (grad_x.squeeze(1) if ctx.squeeze else grad_x), None, None
+
+
+def rev_inv_degree(st, device):
+    """1 / max(in_deg(v), 1) of every reversed-CSR position's column v (the destination of the forward edge): the
+    weights that turn the mean's backward into a weighted sum over the reversed CSR.  Graph-static, cached."""
+    c = st._cache(device)
+    if "rev_inv_deg" not in c:
+        indptr = st.csr(device).indptr
+        inv = 1.0 / (indptr[1:] - indptr[:-1]).clamp(min=1).to(torch.float32)
+        c["rev_inv_deg"] = inv[st.csr_rev(device).col.long()].contiguous()
+    return c["rev_inv_deg"]
+
+
+def copy_reduce(g, x, reduce="sum"):
+    """h_N[v] = sum | mean_{e:u->v} x[u]  (update_all(fn.copy_src, fn.sum | fn.mean))."""
+    if x.shape[0] != g.number_of_nodes():
+        raise ValueError("node feature has %d rows, graph has %d nodes" % (x.shape[0], g.number_of_nodes()))
+    return _CopyReduce.apply(x, g, reduce)
 
 
 class _EdgeSoftmax(torch.autograd.Function):

@@ -11,6 +11,7 @@ def install_as_dgl(force=False):
         raise RuntimeError("a real `dgl` is already imported; pass force=True to shadow it")
     import dgl_kgat_amd as pkg
     from . import function, graph, softmax
+    from .sage_layer import SAGEConv
 
     dgl = types.ModuleType("dgl")
     dgl._kgat_amd = True
@@ -19,12 +20,7 @@ def install_as_dgl(force=False):
     nn = types.ModuleType("dgl.nn")
     pt = types.ModuleType("dgl.nn.pytorch")
     conv = types.ModuleType("dgl.nn.pytorch.conv")
-
-    class SAGEConv:  # models.py:6 imports it; the graphsage branch is outside the KGAT path
-        def __init__(self, *a, **k):
-            raise NotImplementedError("SAGEConv (--gnn_model graphsage) is outside the KGAT path")
-
-    conv.SAGEConv = SAGEConv
+    conv.SAGEConv = SAGEConv  # models.py:6; the graphsage branch (sage_layer.py)
     nn.pytorch, pt.softmax, pt.conv = pt, softmax, conv
     dgl.nn = nn
     mods = {"dgl": dgl, "dgl.function": function, "dgl.nn": nn, "dgl.nn.pytorch": pt,
@@ -37,16 +33,18 @@ def accelerate(model, lazy_edge_weights=None):
     """Route a reference-shaped model's two hot-path methods to the fused kernels, in place.
 
     `model` is an instance of the reference's ``models.Model`` (unmodified; constructed with
-    ``gnn_model="kgat"``, ``use_KG=True``) or anything with the same attribute layout:
-    ``entity_embed``, ``relation_embed``, ``W_R``, ``layers[i].res_fc_2`` / ``.mess_drop``.  After
-    the call
+    ``gnn_model="kgat"`` or ``"graphsage"``, ``use_KG=True``) or anything with the same attribute layout:
+    ``entity_embed``, ``relation_embed``, ``W_R``, ``layers[i].res_fc_2`` / ``.mess_drop`` (or every layer this
+    package's ``SAGEConv``, what ``install_as_dgl`` registers).  After the call
 
     * ``model.compute_attention(g)`` (models.py:146-154) is one fused attention-logit launch + the
       destination softmax (``DGLGraph.kgat_attention``) instead of R rounds of ``filter_edges`` /
       ``apply_edges`` through Python (72 ms -> 0.26 ms on the amazon-book-shaped CKG), and
     * ``model.gnn(g, x)`` (models.py:156-168) is the aggregation with the ``h * h_N`` epilogue +
       the bi-interaction kernel per layer (the whole stack as one autograd unit when gradients
-      are enabled)
+      are enabled) - on a graphsage model the mean aggregation + the SAGE dense kernel per layer
+      (one autograd function per layer when gradients are enabled; kgat.py still refreshes the
+      attention, which the SAGE layers do not read)
 
     with the same parameters (shared, not copied), the same call signatures and the same results.
     This is the one line a maintainer adds after ``model = Model(...)`` in kgat.py:95-98; the
@@ -59,6 +57,7 @@ def accelerate(model, lazy_edge_weights=None):
     import types
 
     from .kgat_layer import KGATPropagation
+    from .sage_layer import SAGEConv
 
     if lazy_edge_weights is not None:
         from . import lazy
@@ -66,10 +65,11 @@ def accelerate(model, lazy_edge_weights=None):
     for attr in ("entity_embed", "relation_embed", "W_R", "layers"):
         if not hasattr(model, attr):
             raise TypeError("accelerate(): the model has no attribute %r (not a KGAT Model)" % attr)
+    sage = len(model.layers) > 0 and all(isinstance(layer, SAGEConv) for layer in model.layers)
     for layer in model.layers:
-        if not (hasattr(layer, "res_fc_2") and hasattr(layer, "mess_drop")):
-            raise TypeError("accelerate(): layer %s is not a bi-interaction KGATConv (gnn_model='kgat', res_type='Bi')"
-                            % type(layer).__name__)
+        if not sage and not (hasattr(layer, "res_fc_2") and hasattr(layer, "mess_drop")):
+            raise TypeError("accelerate(): layer %s is neither a bi-interaction KGATConv (gnn_model='kgat', "
+                            "res_type='Bi') nor this package's SAGEConv (gnn_model='graphsage')" % type(layer).__name__)
     if getattr(model, "_use_KG", True) is False:
         raise TypeError("accelerate(): use_KG=False models build their input from item/user projections; outside the path")
     if not hasattr(model, "_n_entities") or model._n_entities is None:
@@ -82,7 +82,7 @@ def accelerate(model, lazy_edge_weights=None):
         return KGATPropagation.compute_attention(self, g, algo)
 
     for name in ("_can_fuse_readout", "_can_fuse_training", "_gnn_fused", "_gnn_fused_sharded", "_gnn_train_sharded",
-                 "_node_embeddings"):
+                 "_node_embeddings", "_sage_stack", "_can_fuse_sage_readout", "_gnn_sage", "_gnn_sage_fused"):
         setattr(model, name, types.MethodType(getattr(KGATPropagation, name), model))
     model.gnn = types.MethodType(gnn, model)
     model.compute_attention = types.MethodType(compute_attention, model)

@@ -1,6 +1,6 @@
 """Builtin message / reduce descriptors, the counterpart of ``dgl.function`` for the calls
 the reference makes (``fn.u_mul_e('h','w','m')``, ``fn.sum('m','h_neighbor')``,
-models.py:4,63).  They are plain descriptors: ``DGLGraph.update_all`` maps the pair to the
+models.py:4,63; ``fn.copy_src`` / ``fn.mean`` of DGL's SAGEConv, the graphsage branch).  They are plain descriptors: ``DGLGraph.update_all`` maps the pair to the
 HIP aggregation kernel."""
 
 
@@ -31,3 +31,16 @@ src_mul_edge = u_mul_e  # DGL 0.4 alias
 def sum(msg, out):  # noqa: A001 - mirrors dgl.function.sum
     """reduce = sum of the incoming messages of each destination."""
     return BuiltinReduce("sum", msg, out)
+
+
+def copy_src(src, out):
+    """message = source feature (DGL 0.4 fn.copy_src; SAGEConv's mean aggregator sends it)."""
+    return BuiltinMessage("copy_src", src, None, out)
+
+
+copy_u = copy_src  # DGL >= 0.4.2 name
+
+
+def mean(msg, out):
+    """reduce = mean of the incoming messages of each destination (0 where there is none)."""
+    return BuiltinReduce("mean", msg, out)

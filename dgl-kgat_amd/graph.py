@@ -483,6 +483,10 @@ class DGLGraph:
     def edata(self):
         return self._edge_frame
 
+    # DGL >= 0.4.2 layer code writes its inputs to srcdata / dstdata; on a homogeneous graph both are ndata
+    srcdata = ndata
+    dstdata = ndata
+
     def local_var(self):
         """A view whose feature writes do not leak to this graph (models.py:61,148,157)."""
         g = DGLGraph(self._st, self._node_frame.clone(), self._edge_frame.clone())
@@ -563,20 +567,25 @@ class DGLGraph:
         if not (isinstance(message_func, BuiltinMessage) and isinstance(reduce_func, BuiltinReduce)):
             raise NotImplementedError("only builtin message/reduce pairs run on the HIP kernels; "
                                       "python UDF message passing is outside the KGAT path")
-        if message_func.name != "u_mul_e" or reduce_func.name != "sum":
-            raise NotImplementedError("the KGAT path uses update_all(fn.u_mul_e, fn.sum); got %s/%s"
-                                      % (message_func.name, reduce_func.name))
+        pair = (message_func.name, reduce_func.name)
+        if pair not in (("u_mul_e", "sum"), ("copy_src", "sum"), ("copy_src", "mean")):
+            raise NotImplementedError("update_all runs (fn.u_mul_e, fn.sum) and (fn.copy_src, fn.sum | fn.mean) on the "
+                                      "HIP kernels; got %s/%s" % pair)
         if message_func.out_field != reduce_func.msg_field:
             raise DGLError("reduce reads message field %r but the message function writes %r"
                            % (reduce_func.msg_field, message_func.out_field))
         if message_func.src_field not in self._node_frame:
             raise KeyError(message_func.src_field)
-        if message_func.edge_field not in self._edge_frame:
+        if message_func.edge_field is not None and message_func.edge_field not in self._edge_frame:
             raise KeyError(message_func.edge_field)
-        from .autograd import u_mul_e_sum
         x = self._node_frame[message_func.src_field]
-        w = self._edge_frame[message_func.edge_field]
-        self._node_frame[reduce_func.out_field] = u_mul_e_sum(self, x, w)
+        if message_func.name == "copy_src":
+            from .autograd import copy_reduce
+            self._node_frame[reduce_func.out_field] = copy_reduce(self, x, reduce_func.name)
+        else:
+            from .autograd import u_mul_e_sum
+            w = self._edge_frame[message_func.edge_field]
+            self._node_frame[reduce_func.out_field] = u_mul_e_sum(self, x, w)
         if apply_node_func is not None:
             raise NotImplementedError("apply_node_func is outside the KGAT path")
 

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from . import function as fn
 from .autograd import edge_softmax, u_mul_e_sum
 from .options import options
+from .sage_layer import SAGEConv, draw_seed
 
 
 def ops_transr_supported(model, h):
@@ -114,8 +115,11 @@ class KGATPropagation(nn.Module):
     training-step test needs a scalar to differentiate."""
 
     def __init__(self, n_entities, n_relations, input_node_dim=64, relation_dim=64, num_gnn_layers=3,
-                 n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01):
+                 n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01, gnn_model="kgat"):
         super().__init__()
+        if gnn_model not in ("kgat", "graphsage"):
+            raise NotImplementedError("gnn_model must be 'kgat' or 'graphsage', got %r" % (gnn_model,))
+        self._gnn_model = gnn_model
         self._n_entities, self._n_relations = n_entities, n_relations
         self._reg_lambda_gnn = reg_lambda_gnn
         self.entity_embed = nn.Embedding(n_entities, input_node_dim)
@@ -125,7 +129,12 @@ class KGATPropagation(nn.Module):
         self.layers = nn.ModuleList()
         for i in range(num_gnn_layers):  # widths: models.py:91-111
             d_in = input_node_dim if i == 0 else n_hidden // int(math.pow(2, i - 1))
-            self.layers.append(KGATConv(d_in, n_hidden // int(math.pow(2, i)), dropout))
+            if gnn_model == "graphsage":  # models.py:98-100,107-109: ReLU on every layer but the last
+                act = None if i + 1 == num_gnn_layers else F.relu
+                self.layers.append(SAGEConv(d_in, n_hidden // int(math.pow(2, i)), aggregator_type="mean",
+                                            feat_drop=dropout, activation=act))
+            else:
+                self.layers.append(KGATConv(d_in, n_hidden // int(math.pow(2, i)), dropout))
 
     # -- attention (models.py:135-154)
     def _att_score(self, edges):
@@ -153,6 +162,8 @@ class KGATPropagation(nn.Module):
 
     # -- propagation (models.py:156-168)
     def gnn(self, g, x=None, fused=None):
+        if self._sage_stack():
+            return self._gnn_sage(g, fused)
         auto = fused is None
         if auto:
             fused = not torch.is_grad_enabled()
@@ -199,6 +210,8 @@ class KGATPropagation(nn.Module):
 
     def _can_fuse_training(self, g, sharded=False):
         from . import ops
+        if not all(isinstance(layer, KGATConv) or hasattr(layer, "res_fc_2") for layer in self.layers):
+            return False
         w = self.entity_embed.weight
         return ((g.partition is None) != sharded and w.is_cuda and w.dtype == torch.float32 and "w" in g.edata and
                 not g.edata["w"].requires_grad and
@@ -220,6 +233,8 @@ class KGATPropagation(nn.Module):
 
     def _can_fuse_readout(self):
         from . import ops
+        if not all(isinstance(layer, KGATConv) or hasattr(layer, "res_fc_2") for layer in self.layers):
+            return False
         drop_off = all((not layer.training) or layer.mess_drop.p == 0 for layer in self.layers)
         return drop_off and all(ops.bi_interaction_supported(layer.res_fc_2.in_features, layer.res_fc_2.out_features)
                                 for layer in self.layers)
@@ -302,6 +317,58 @@ class KGATPropagation(nn.Module):
         # the attention launch measured 0.231 ms inside the step against 0.19 ms on its own)
         if not copy_self:
             out[:, :widths[0]] = h0
+        return out
+
+    # -- GraphSAGE stack (gnn_model="graphsage", models.py:98-100,107-109; the same readout, models.py:156-168)
+    def _sage_stack(self):
+        return len(self.layers) > 0 and all(isinstance(layer, SAGEConv) for layer in self.layers)
+
+    def _can_fuse_sage_readout(self):
+        from . import ops
+        w = self.entity_embed.weight
+        return (w.is_cuda and w.dtype == torch.float32 and
+                all(layer.drop_p() == 0 and layer.norm is None and layer.fused_activation() is not False and
+                    ops.sage_dense_supported(layer._in_feats, layer._out_feats) and
+                    layer.fc_self.bias is not None and layer.fc_neigh.bias is not None for layer in self.layers))
+
+    def _gnn_sage(self, g, fused=None):
+        """The readout [h0 | normalize(h1) | ...] over a SAGEConv stack.  No-grad (fused=None outside autograd): one
+        aggregation + one dense launch per layer, the dense kernel writing its normalised slice of the readout (and,
+        in layer 0, the ego block).  Otherwise the layers' autograd functions with torch's normalize / cat; the
+        dropout seed is one draw from torch's CPU generator per call, layer i uses seed + i."""
+        from .graph import DGLError
+        if g.partition is not None:
+            raise DGLError("GraphSAGE on a partitioned graph is not supported (sharded GraphSAGE is out of scope)")
+        if fused is None:
+            fused = not torch.is_grad_enabled()
+        if fused and self._can_fuse_sage_readout():
+            return self._gnn_sage_fused(g)
+        seed = draw_seed() if any(layer.drop_p() > 0 for layer in self.layers) else 0
+        h = self._node_embeddings(g)
+        cache = [h]
+        for li, layer in enumerate(self.layers):
+            h = layer(g, h, seed=seed + li)
+            cache.append(F.normalize(h, p=2, dim=1))
+        return torch.cat(cache, 1)
+
+    def _gnn_sage_fused(self, g):
+        from . import ops
+        h = self._node_embeddings(g).detach().contiguous()
+        widths = [h.shape[1]] + [layer._out_feats for layer in self.layers]
+        out = torch.empty((h.shape[0], sum(widths)), dtype=torch.float32, device=h.device)
+        aligned = widths[0] % 4 == 0 and out.shape[1] % 4 == 0
+        csr = g._st.csr(h.device)
+        off = widths[0]
+        for li, layer in enumerate(self.layers):
+            last = li + 1 == len(self.layers)
+            hn = ops.copy_reduce(csr.indptr, csr.col, csr.row_of, h, "mean")
+            h = ops.sage_dense(h, hn, layer.fc_self.weight.detach(), layer.fc_neigh.weight.detach(),
+                               layer.fc_self.bias.detach(), layer.fc_neigh.bias.detach(), layer.fused_activation(),
+                               want_h=not last, norm_out=out[:, off:off + widths[li + 1]],
+                               self_out=out[:, :widths[0]] if (li == 0 and aligned) else None)
+            off += widths[li + 1]
+        if not aligned:
+            out[:, :widths[0]] = self._node_embeddings(g).detach()
         return out
 
     def transR(self, h, r, pos_t, neg_t, reg_lambda_kg=0.01, fused=None):

@@ -621,6 +621,131 @@ def spmm(indptr, col, row_of, X, w, eid=None, out=None, order=None, mul_self=Fal
     return out
 
 
+REDUCE = {"sum": 0, "mean": 1}
+ACT = {None: 0, "none": 0, "relu": 1}
+
+
+def copy_reduce(indptr, col, row_of, X, reduce="sum", out=None, rows=None, e_range=None, workspace=None):
+    """out[v - row0] = sum | mean_p X[col[p]] over the CSR rows `rows` = (row0, n_rows) whose CSR positions are
+    `e_range` (kgat_copy_reduce_f32: update_all(copy_src, sum | mean); no edge weight is read; the mean divides by the
+    row's number of positions, rows without in-edges are 0)."""
+    X = _need(X, torch.float32, "X")
+    if X.dim() != 2:
+        raise ValueError("X must be (N, D)")
+    if reduce not in REDUCE:
+        raise ValueError("reduce must be 'sum' or 'mean', got %r" % (reduce,))
+    D = X.shape[1]
+    indptr = _need(indptr, torch.int32, "indptr")
+    col = _need(col, torch.int32, "col")
+    if row_of is not None:
+        row_of = _need(row_of, torch.int32, "row_of", col.shape)
+    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
+    e0, e1 = (0, col.numel()) if e_range is None else e_range
+    if out is None:
+        out = torch.empty((n_rows, D), dtype=torch.float32, device=X.device)
+    else:
+        out = _need(out, torch.float32, "out", (n_rows, D))
+    if workspace is None:
+        workspace = spmm_workspace(e1 - e0, D, X.device)
+    with _timed("copy_reduce", (e1 - e0, n_rows, D, reduce)):
+        check(_lib.load().kgat_copy_reduce_f32(n_rows, row0, e0, e1, D, _ptr(indptr), _ptr(col), _ptr(row_of), _ptr(X),
+                                               _ptr(out), REDUCE[reduce], _ptr(workspace), workspace.numel(),
+                                               _stream(X)),
+              "kgat_copy_reduce_f32")
+    return out
+
+
+def sage_dense_supported(d_in, d_out):
+    return bool(_lib.load().kgat_sage_dense_supported(int(d_in), int(d_out)))
+
+
+def sage_dense(H, HN, W_self, W_neigh, b_self=None, b_neigh=None, act=None, want_h=True, norm_out=None, self_out=None):
+    """Z = act(H W_self^T + HN W_neigh^T + b_self + b_neigh) (kgat_sage_dense_f32; act None or 'relu'); returns Z (None
+    with want_h=False) and writes Z / ||Z_row|| into `norm_out` and H into `self_out` (column slices of a wider
+    row-major buffer) where given."""
+    H = _need(H, torch.float32, "H")
+    if H.dim() != 2:
+        raise ValueError("H must be (N, d_in)")
+    n, d_in = H.shape
+    HN = _need(HN, torch.float32, "HN", (n, d_in))
+    W_self = _need(W_self, torch.float32, "W_self")
+    d_out = W_self.shape[0]
+    if W_self.shape != (d_out, d_in):
+        raise ValueError("W_self has shape %s, expected (*, %d)" % (tuple(W_self.shape), d_in))
+    W_neigh = _need(W_neigh, torch.float32, "W_neigh", (d_out, d_in))
+    if b_self is not None:
+        b_self = _need(b_self, torch.float32, "b_self", (d_out,))
+    if b_neigh is not None:
+        b_neigh = _need(b_neigh, torch.float32, "b_neigh", (d_out,))
+    h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device) if want_h else None
+    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
+    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    with _timed("sage_dense", (n, d_in, d_out)):
+        check(_lib.load().kgat_sage_dense_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W_self), _ptr(W_neigh),
+                                              _ptr(b_self), _ptr(b_neigh), ACT[act], _ptr(h_out), _ptr(norm_out), stride,
+                                              _ptr(self_out), self_stride, _stream(H)),
+              "kgat_sage_dense_f32")
+    return h_out
+
+
+def dropout_rows(x, drop_p, seed, x2=None):
+    """(x + x2) * keep / (1 - p) with the mask of dropout_keep_mask(seed, *x.shape, p) (kgat_dropout_rows_f32)."""
+    x = _need(x, torch.float32, "x")
+    if x.dim() != 2:
+        raise ValueError("x must be (N, d)")
+    if x2 is not None:
+        x2 = _need(x2, torch.float32, "x2", x.shape)
+    out = torch.empty_like(x)
+    with _timed("dropout_rows", tuple(x.shape)):
+        check(_lib.load().kgat_dropout_rows_f32(x.shape[0], x.shape[1], _ptr(x), _ptr(x2), float(drop_p),
+                                                int(seed) & (2 ** 64 - 1), _ptr(out), _stream(x)),
+              "kgat_dropout_rows_f32")
+    return out
+
+
+def sage_bwd_input(grad_pre, W_self, W_neigh, indptr):
+    """(grad_pre @ W_self, (grad_pre @ W_neigh) / max(deg, 1)) in one pass (kgat_sage_bwd_input_f32)."""
+    grad_pre = _need(grad_pre, torch.float32, "grad_pre")
+    n, d_out = grad_pre.shape
+    W_self = _need(W_self, torch.float32, "W_self")
+    d_in = W_self.shape[1]
+    if W_self.shape[0] != d_out:
+        raise ValueError("W_self has shape %s, expected (%d, *)" % (tuple(W_self.shape), d_out))
+    W_neigh = _need(W_neigh, torch.float32, "W_neigh", (d_out, d_in))
+    indptr = _need(indptr, torch.int32, "indptr")
+    if indptr.numel() < n + 1:
+        raise ValueError("indptr has %d entries, expected %d" % (indptr.numel(), n + 1))
+    g_self = torch.empty((n, d_in), dtype=torch.float32, device=grad_pre.device)
+    g_agg = torch.empty_like(g_self)
+    with _timed("sage_bwd_input", (n, d_in, d_out)):
+        check(_lib.load().kgat_sage_bwd_input_f32(n, d_in, d_out, _ptr(grad_pre), _ptr(W_self), _ptr(W_neigh),
+                                                  _ptr(indptr), _ptr(g_self), _ptr(g_agg), _stream(grad_pre)),
+              "kgat_sage_bwd_input_f32")
+    return g_self, g_agg
+
+
+def sage_bwd_weight(grad_pre, H, HN, want_partials=False):
+    """(grad_pre^T H, grad_pre^T HN, column sums of grad_pre) (kgat_sage_bwd_weight_f32's partials, summed by
+    kgat_sum_partials_f32 - or, want_partials=True, handed back)."""
+    grad_pre = _need(grad_pre, torch.float32, "grad_pre")
+    n, d_out = grad_pre.shape
+    H = _need(H, torch.float32, "H")
+    d_in = H.shape[1]
+    if H.shape[0] != n:
+        raise ValueError("H has %d rows, grad_pre %d" % (H.shape[0], n))
+    HN = _need(HN, torch.float32, "HN", (n, d_in))
+    lib = _lib.load()
+    nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
+    ps = torch.empty((nb, d_out, d_in), dtype=torch.float32, device=H.device)
+    pn = torch.empty_like(ps)
+    pb = torch.empty((nb, d_out), dtype=torch.float32, device=H.device)
+    with _timed("sage_bwd_weight", (n, d_in, d_out)):
+        check(lib.kgat_sage_bwd_weight_f32(n, d_in, d_out, _ptr(grad_pre), _ptr(H), _ptr(HN), _ptr(ps), _ptr(pn),
+                                           _ptr(pb), nb, _stream(H)), "kgat_sage_bwd_weight_f32")
+    parts = [ps, pn, pb]
+    return parts if want_partials else sum_partials(parts)
+
+
 def spmm_bi_fused_supported(d_in, d_out):
     return bool(_lib.load().kgat_spmm_bi_fused_supported(int(d_in), int(d_out)))
 

@@ -131,6 +131,8 @@ def main(argv=None):
     ap.add_argument("--relation_embed_dim", type=int, default=64)
     ap.add_argument("--gnn_num_layer", type=int, default=3)
     ap.add_argument("--gnn_hidden_size", type=int, default=64)
+    ap.add_argument("--gnn_model", choices=("kgat", "graphsage"), default="kgat",
+                    help="propagation layers (reference kgat.py:23): bi-interaction KGATConv or SAGEConv (mean)")
     ap.add_argument("--dropout_rate", type=float, default=0.1)
     ap.add_argument("--lr", type=float, default=0.0001)
     ap.add_argument("--batch_size", type=int, default=10240)
@@ -171,7 +173,8 @@ def main(argv=None):
     say("users %d items %d | CKG: %d entities, %d relations, %d train triplets" % (
         ds.n_users, ds.n_items, ds.n_KG_entity, ds.n_KG_relation, len(ds.train_KG_triplet)))
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
-                              args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate).to(dev)
+                              args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
+                              gnn_model=args.gnn_model).to(dev)
     K.enable_lazy_edge_weights()   # the attention refresh hands back its edge-id-ordered copy unwritten (nothing here reads it)
 
     def replicas_agree(tag):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define KGAT_ABI_VERSION 10
+#define KGAT_ABI_VERSION 11
 
 enum {
   KGAT_OK = 0,
@@ -77,6 +77,18 @@ enum {
                              * rows - scaled per row to [2^13, 2^14) - and the tanh values 2^14 two: five piece products
                              * each).  Opt-in (KGAT_ATT_TILES32=1): 25 % fewer vector and 55 % fewer matrix instructions per launch at the
                              * same run time as the 16-group kernel (profiles/r05_att32_experiments.txt). */
+};
+
+/* reduce of kgat_copy_reduce_f32 (dgl.function.sum / dgl.function.mean) */
+enum {
+  KGAT_REDUCE_SUM = 0,
+  KGAT_REDUCE_MEAN = 1
+};
+
+/* activation of kgat_sage_dense_f32 */
+enum {
+  KGAT_ACT_NONE = 0,
+  KGAT_ACT_RELU = 1
 };
 
 typedef void* kgat_stream_t; /* hipStream_t */
@@ -460,6 +472,63 @@ int kgat_sum_partials_f32(int n_sets, const float* const* partials_host, float* 
 /* ab = a * b and ac = a * c elementwise in one pass (n a multiple of 4). */
 int kgat_mul2_f32(int64_t n, const float* a, const float* b, const float* c, float* ab, float* ac,
                   kgat_stream_t stream);
+
+/* ---------------------------------------------------------------- GraphSAGE layer (gnn_model = "graphsage")
+ * The kernels behind dgl.nn.pytorch.conv.SAGEConv(d_in, d_out, aggregator_type="mean", feat_drop, activation) of
+ * reference models.py:98-100,107-109 (DGL 0.4.x SAGEConv.forward on a homogeneous graph):
+ *   hd = feat_drop(h);  h_neigh[v] = mean_{u->v} hd[u];  rst = act(fc_self(hd) + fc_neigh(h_neigh)).
+ *
+ * kgat_copy_reduce_f32 replaces g.update_all(fn.copy_src('h','m'), fn.sum('m','h') | fn.mean('m','h')) (DGL
+ * copy_reduce(sum | mean, SRC)):
+ *   out[v - row0, :] = reduce_{p in [indptr[v], indptr[v+1])} X[col[p], :]
+ * over rows v in [row0, row0 + n_rows) whose CSR positions are [e_begin, e_end), as kgat_spmm_umule_sum_f32 - but no
+ * per-edge weight is read.  reduce = KGAT_REDUCE_SUM, or KGAT_REDUCE_MEAN: the fp32 sum divided (true division) by
+ * the row's number of positions (multi-edges count); rows without in-edges are written as 0.  A fixed order of
+ * additions, no float atomics: bitwise reproducible.  D in {16, 32, 64, 128}: the merge-path kernel (row_of
+ * required, X and out 16-byte aligned); any other D: one wavefront per row (row_of not read).
+ * workspace: kgat_spmm_workspace_bytes(e_end - e_begin, D).  The backward of the mean w.r.t. X is this call with
+ * KGAT_REDUCE_SUM on the CSR of the reversed graph over the rows kgat_sage_bwd_input_f32 writes to grad_agg. */
+int kgat_copy_reduce_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_t e_end, int D, const int32_t* indptr,
+                         const int32_t* col, const int32_t* row_of, const float* X, float* out, int reduce,
+                         void* workspace, size_t workspace_bytes, kgat_stream_t stream);
+
+/* The dense part of SAGEConv (fc_self(hd) + fc_neigh(h_neigh), then the activation; reference models.py:99,108) and,
+ * on the no-grad readout path, the F.normalize of models.py:165:
+ *   Z = act(H W_self^T + HN W_neigh^T + b_self + b_neigh),  act = KGAT_ACT_NONE | KGAT_ACT_RELU
+ * H = hd, HN = h_neigh (n_rows x d_in), W_self / W_neigh = fc_self.weight / fc_neigh.weight (d_out x d_in), b_self /
+ * b_neigh (d_out, either may be NULL).  h_out (n_rows x d_out, may be NULL) receives Z; norm_out (may be NULL) Z /
+ * max(||Z_row||_2, 1e-12) with row stride norm_stride floats; self_out (may be NULL) a copy of H with row stride
+ * self_stride (the ego block [h0 | ...] of Model.gnn's readout, models.py:159,168).  Strides multiples of 4 floats,
+ * every buffer 16-byte aligned.  fp32 MFMA (v_mfma_f32_16x16x4_f32); widths (kgat_sage_dense_supported): d_in, d_out
+ * in {16, 32, 64, 128}, others return KGAT_E_UNSUPPORTED. */
+int kgat_sage_dense_supported(int d_in, int d_out);
+int kgat_sage_dense_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W_self,
+                        const float* W_neigh, const float* b_self, const float* b_neigh, int act, float* h_out,
+                        float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
+                        kgat_stream_t stream);
+
+/* SAGEConv's feat_drop (nn.Dropout of reference models.py:99,108 on the layer input) with the counter hash of
+ * kgat_bi_interaction_train_f32: out = (x + x2) * keep / (1 - drop_p) over n_rows x d elements (x2 may be NULL),
+ * keep <=> hash(seed, row * d + column) >= drop_p * 2^32.  Forward: the dropped input, materialised once.  Backward:
+ * the same call on the gradient (x, x2 = the gradient's two paths: through fc_self and through the aggregation). */
+int kgat_dropout_rows_f32(int64_t n_rows, int d, const float* x, const float* x2, float drop_p, uint64_t seed,
+                          float* out, kgat_stream_t stream);
+
+/* Backward of kgat_sage_dense_f32 towards its inputs (reference models.py:99,108 under autograd), from grad_pre =
+ * the gradient at the pre-activation (kgat_bi_interaction_bwd_pre_f32 with slope 0 for ReLU, 1 for none, drop_p 0):
+ *   grad_self = grad_pre W_self,  grad_agg[v] = (grad_pre W_neigh)[v] / max(indptr[v+1] - indptr[v], 1)
+ * (n_rows x d_in each; grad_agg is what kgat_copy_reduce_f32 (sum) then aggregates over the reversed CSR: the
+ * gradient through the mean).  indptr: the forward CSR's row offsets.  Widths as kgat_sage_dense_f32. */
+int kgat_sage_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* grad_pre, const float* W_self,
+                            const float* W_neigh, const int32_t* indptr, float* grad_self, float* grad_agg,
+                            kgat_stream_t stream);
+/* The four parameter gradients as per-workgroup partials: part_self[b] / part_neigh[b] (d_out x d_in) = grad_pre^T H /
+ * grad_pre^T HN over the 64-row slabs b, b + n_partials, ...; part_bias[b] (d_out) = the column sums of grad_pre over
+ * the same rows (the gradient of b_self and of b_neigh).  n_partials = kgat_bi_interaction_bwd_weight_partials(n_rows);
+ * the caller adds the partials (kgat_sum_partials_f32).  Widths as kgat_sage_dense_f32. */
+int kgat_sage_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_pre, const float* H,
+                             const float* HN, float* part_self, float* part_neigh, float* part_bias, int64_t n_partials,
+                             kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- TransR KG step
  * Loss and gradients of reference models.py:114-133 (transR; bmm_maybe_select :13-47,

@@ -5,6 +5,7 @@ path or of bench.py's contract).  Interleaved rounds in one process, HIP events 
   python scripts/kbench.py att   [--algos mfma,mfma_chunk,generic] [--dim 64]
   python scripts/kbench.py spmm  [--algos merge,rows,rows_ordered] [--dim 64]
   python scripts/kbench.py softmax
+  python scripts/kbench.py sage    (GraphSAGE layer launches beside the KGAT layer's, and the CF step of both models)
 """
 import argparse
 import os
@@ -36,7 +37,7 @@ def timeit(fns, rounds, warm=3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("kernel", choices=["att", "spmm", "softmax", "train", "kg"])
+    ap.add_argument("kernel", choices=["att", "spmm", "softmax", "train", "kg", "sage"])
     ap.add_argument("--algos", default=None)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=20)
@@ -154,6 +155,88 @@ def main():
         tc = np.array([x.elapsed_time(y) for x, y in cold])
         print("spmm %-13s cold caches: median %.4f ms  min %.4f ms -> %.0f GB/s algorithmic (%.1f%% of 8 TB/s)"
               % (algos[0], np.median(tc), tc.min(), b / np.median(tc) / 1e6, b / np.median(tc) / 1e6 / 80))
+    elif args.kernel == "sage":
+        # GraphSAGE (mean) layer of gnn_model="graphsage": every launch of its forward and backward at the reference's
+        # widths, interleaved with the KGAT layer's spmm + bi_interaction_mul and a torch composition of the same layer
+        import time
+        import torch.nn.functional as F
+        import dgl_kgat_amd as K
+        rev = ops.csr_from_coo(n, dst, src)
+        w = torch.rand(E, device=dev)
+        src_l, dst_l = src.long(), dst.long()
+        inv_deg = 1.0 / torch.bincount(dst_l, minlength=n).clamp(min=1).float()[:, None]
+        print("sage: N = %d, E = %d, median of %d interleaved rounds (ms)" % (n, E, args.rounds))
+        for di, do in ((64, 64), (64, 32), (32, 16)):
+            torch.manual_seed(0)
+            X = torch.randn(n, di, device=dev)
+            Ws, Wn = torch.randn(do, di, device=dev) * 0.1, torch.randn(do, di, device=dev) * 0.1
+            bs, bn = torch.randn(do, device=dev), torch.randn(do, device=dev)
+            W2 = torch.randn(do, di, device=dev) * 0.1
+            norm = torch.empty(n, do, device=dev)
+            HN = ops.copy_reduce(indptr, col, row_of, X, "mean")
+            Z = ops.sage_dense(X, HN, Ws, Wn, bs, bn, "relu")
+            GZ = torch.randn(n, do, device=dev)
+            GP = ops.bi_interaction_bwd_pre(Z, GZ, None, None, 0.0, 0.0, 0)
+            GA = ops.sage_bwd_input(GP, Ws, Wn, indptr)[1]
+            ws = ops.spmm_workspace(E, di, dev)
+            fns = {
+                "sage.copy_mean": lambda: ops.copy_reduce(indptr, col, row_of, X, "mean", workspace=ws),
+                "sage.dense": lambda: ops.sage_dense(X, HN, Ws, Wn, bs, bn, "relu", want_h=True, norm_out=norm),
+                "sage.fwd(agg+dense)": lambda: ops.sage_dense(X, ops.copy_reduce(indptr, col, row_of, X, "mean", workspace=ws),
+                                                              Ws, Wn, bs, bn, "relu", norm_out=norm),
+                "kgat.spmm": lambda: ops.spmm(indptr, col, row_of, X, w, workspace=ws),
+                "kgat.bi_mul": lambda: ops.bi_interaction_mul(X, HN, W2, 0.01, norm_out=norm),
+                "kgat.fwd(spmm+bi_mul)": lambda: ops.bi_interaction_mul(X, ops.spmm(indptr, col, row_of, X, w, workspace=ws),
+                                                                        W2, 0.01, norm_out=norm),
+                "torch.fwd": lambda: torch.relu(F.linear(X, Ws, bs) + F.linear(
+                    torch.zeros(n, di, device=dev).index_add_(0, dst_l, X[src_l]) * inv_deg, Wn, bn)),
+                "sage.bwd_pre": lambda: ops.bi_interaction_bwd_pre(Z, GZ, None, None, 0.0, 0.0, 0),
+                "sage.bwd_input": lambda: ops.sage_bwd_input(GP, Ws, Wn, indptr),
+                "sage.bwd_copy_sum(rev)": lambda: ops.copy_reduce(rev[0], rev[1], rev[3], GA, "sum", workspace=ws),
+                "sage.bwd_weight(+sum)": lambda: ops.sage_bwd_weight(GP, X, HN),
+                "sage.dropout_rows": lambda: ops.dropout_rows(X, 0.1, 1234),
+            }
+            t = timeit(fns, args.rounds)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print("%d -> %d" % (di, do))
+            for k, v in med.items():
+                print("   %-24s %.4f" % (k, v))
+            print("   ratio sage.fwd / kgat.fwd = %.3f; sage.copy_mean / kgat.spmm = %.3f; torch.fwd / sage.fwd = %.2f"
+                  % (med["sage.fwd(agg+dense)"] / med["kgat.fwd(spmm+bi_mul)"], med["sage.copy_mean"] / med["kgat.spmm"],
+                     med["torch.fwd"] / med["sage.fwd(agg+dense)"]))
+        # the CF step of kgat.py:146-168 (gnn over all layers -> BPR loss -> backward -> Adam), both models, alternating
+        B = 10240
+        u = torch.randint(0, 70679, (B,), device=dev).int()
+        pi = torch.randint(70679, 95594, (B,), device=dev).int()
+        ni = torch.randint(70679, 95594, (B,), device=dev).int()
+        graph = synth.build_graph(n, trip, dev)
+        steps = {}
+        for gm in ("kgat", "graphsage"):
+            torch.manual_seed(0)
+            model = K.KGATPropagation(n, R, D, D, 3, D, dropout=0.1, gnn_model=gm).to(dev)
+            opt = K.FusedAdam(model.parameters(), lr=0.01)
+            with torch.no_grad():
+                graph.edata["w"] = model.compute_attention(graph)
+
+            def step(model=model, opt=opt):
+                loss = model.get_loss(model.gnn(graph), u, pi, ni)
+                loss.backward()
+                opt.step()
+                opt.zero_grad()
+            steps[gm] = step
+        res = {gm: [] for gm in steps}
+        for _ in range(3):
+            for f in steps.values():
+                f()
+        for _ in range(args.rounds):
+            for gm, f in steps.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                res[gm].append(time.perf_counter() - t0)
+        for gm, v in res.items():
+            print("CF step (fwd+bwd+Adam, 3 layers, batch %d) gnn_model=%-9s median %.3f ms" % (B, gm, 1e3 * float(np.median(v))))
     elif args.kernel == "train":
         # the CF step of kgat.py:146-168: gnn (all layers, full graph) -> BPR loss -> backward -> Adam
         import time
