@@ -125,6 +125,15 @@ SIGNATURES = {
     "kgat_dropout_rows_f32": (_i32, [_i64, _i32, _p, _p, C.c_float, C.c_uint64, _p, _p]),
     "kgat_sage_bwd_input_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "kgat_sage_bwd_weight_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "kgat_aggregator_supported": (_i32, [_i32, _i32, _i32]),
+    "kgat_aggregator_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, C.c_float, _p, _p, _i64, _p, _i64, _p]),
+    "kgat_aggregator_deferred_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, C.c_float, _p, _p, _i64, _p, _i64, _p,
+                                            _i64, _i64, _p, _i32, _p]),
+    "kgat_aggregator_train_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, C.c_float, C.c_float, C.c_uint64, _i64, _p,
+                                         _p, _i64, _p, _i64, _p]),
+    "kgat_aggregator_bwd_supported": (_i32, [_i32, _i32, _i32]),
+    "kgat_aggregator_bwd_input_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "kgat_aggregator_bwd_weight_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _p]),
     "kgat_eval_recall_ndcg_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p,
                                          _p, _p, _p]),
 }
@@ -145,7 +154,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 def source_hash():

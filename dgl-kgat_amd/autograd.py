@@ -213,10 +213,12 @@ class _GNNTrain(torch.autograd.Function):
     (h * h_N) W2^T + LeakyReLU + dropout + the normalised copy written into its slice of the
     readout; backward per layer one kernel for the normalise / dropout / LeakyReLU gradients, two
     dense GEMMs, one two-product pass and the SpMM on the reversed CSR.  Gradients: the input
-    embeddings and every W2; the edge weights are constants (kgat.py:139-145)."""
+    embeddings and every W2; the edge weights are constants (kgat.py:139-145).
+    `forms`: each layer's aggregator (ops.FORMS: the product of Bi, the sum of GCN, the concatenation of GraphSage -
+    KGATConv's res_type); the backward is routed by it, its structure is the same for all three."""
 
     @staticmethod
-    def forward(ctx, g, slope, drop_p, seed, h0, *weights):
+    def forward(ctx, g, slope, drop_p, seed, forms, h0, *weights):
         st = g._st
         dev = h0.device
         h = h0.detach().contiguous()
@@ -234,12 +236,12 @@ class _GNNTrain(torch.autograd.Function):
         hs, hns = [h], []
         for li, w in enumerate(weights):
             hn = ops.spmm(csr.indptr, csr.col, csr.row_of, hs[-1], w_csr)
-            hs.append(ops.bi_interaction_train(hs[-1], hn, w.detach().contiguous(), slope, drop_p, seed + li,
-                                               norm_out=out[:, off:off + widths[li + 1]],
-                                               self_out=out[:, :widths[0]] if (li == 0 and ego_in_kernel) else None))
+            hs.append(ops.aggregator_train(forms[li], hs[-1], hn, w.detach().contiguous(), slope, drop_p, seed + li,
+                                           norm_out=out[:, off:off + widths[li + 1]],
+                                           self_out=out[:, :widths[0]] if (li == 0 and ego_in_kernel) else None))
             hns.append(hn)
             off += widths[li + 1]
-        ctx.g, ctx.slope, ctx.drop_p, ctx.seed, ctx.widths, ctx.ew = g, slope, drop_p, seed, widths, ew
+        ctx.g, ctx.slope, ctx.drop_p, ctx.seed, ctx.widths, ctx.ew, ctx.forms = g, slope, drop_p, seed, widths, ew, forms
         ctx.save_for_backward(*hs, *hns, *weights)
         return out
 
@@ -262,31 +264,49 @@ class _GNNTrain(torch.autograd.Function):
         for li in range(n_l - 1, -1, -1):
             gz = ops.bi_interaction_bwd_pre(hs[li + 1], g_a, g_b, grad_out[:, offs[li + 1]:offs[li + 2]], ctx.slope,
                                             ctx.drop_p, ctx.seed + li)
-            if ctx.needs_input_grad[5 + li]:
-                if ops.bi_interaction_bwd_input_supported(hs[li].shape[1], gz.shape[1]):
-                    # grad_z^T (h * h_N) as per-workgroup partials; every layer's set is summed by ONE launch at the end
-                    pending.append((li, ops.bi_interaction_bwd_weight(gz, hs[li], hns[li], want_partials=True)))
+            form, d_in = ctx.forms[li], hs[li].shape[1]
+            kernels = ops.aggregator_bwd_supported(form, d_in, gz.shape[1])
+            if ctx.needs_input_grad[6 + li]:
+                if kernels:
+                    # grad_z^T (h * h_N) (h + h_N, [h | h_N]) as per-workgroup partials; every layer's set is summed by
+                    # ONE launch at the end
+                    pending.append((li, ops.aggregator_bwd_weight(form, gz, hs[li], hns[li], want_partials=True)))
                 else:
-                    grad_w[li] = tall_weight_grad(gz, hs[li] * hns[li])
+                    grad_w[li] = tall_weight_grad(gz, _combine(form, hs[li], hns[li]))
             w_l = weights[li].detach().contiguous()
-            if ops.bi_interaction_bwd_input_supported(w_l.shape[1], w_l.shape[0]):
-                # grad_P = grad_z W2 formed per tile and multiplied on the way: grad_P * h (to be aggregated), grad_P * h_N
-                t, g_b = ops.bi_interaction_bwd_input(gz, w_l, hs[li], hns[li])
-            else:
+            if kernels:
+                # grad_P = grad_z W formed per tile: the part to be aggregated (grad_P * h for Bi) and the part that goes to
+                # h directly (grad_P * h_N)
+                t, g_b = ops.aggregator_bwd_input(form, gz, w_l, hs[li], hns[li])
+            elif form == ops.FORMS["Bi"]:
                 t, g_b = ops.mul2(gz @ w_l, hs[li], hns[li])
+            elif form == ops.FORMS["GCN"]:
+                t = g_b = gz @ w_l
+            else:
+                gp = gz @ w_l
+                t, g_b = gp[:, d_in:].contiguous(), gp[:, :d_in].contiguous()
             g_a = ops.spmm(rev.indptr, rev.col, rev.row_of, t, w_rev)
         if pending:
             for (li, _), summed in zip(pending, ops.sum_partials([p_ for _, p_ in pending])):
                 grad_w[li] = summed
         grad_h0 = None
-        if ctx.needs_input_grad[4]:
+        if ctx.needs_input_grad[5]:
             g0 = grad_out[:, :ctx.widths[0]]
             if g_a is not None and ctx.widths[0] % 4 == 0 and grad_out.shape[1] % 4 == 0 and g0.data_ptr() % 16 == 0:
                 grad_h0 = ops.add3_rows(g0, g_a, g_b)      # one pass: (g0 + g_a) + g_b, the same additions
             else:
                 grad_h0 = g0 + g_a
                 grad_h0 += g_b
-        return (None, None, None, None, grad_h0, *grad_w)
+        return (None, None, None, None, None, grad_h0, *grad_w)
+
+
+def _combine(form, h, hn):
+    """The A operand of a layer's dense part: h * h_N (Bi), h + h_N (GCN), [h | h_N] (GraphSage)."""
+    if form == ops.FORMS["GCN"]:
+        return h + hn
+    if form == ops.FORMS["GraphSage"]:
+        return torch.cat([h, hn], 1)
+    return h * hn
 
 
 def tall_weight_grad(grad, x, slabs=128):
@@ -303,6 +323,10 @@ def tall_weight_grad(grad, x, slabs=128):
     return gw
 
 
-def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0):
-    """Differentiable fused propagation stack; returns the (N, sum of widths) readout."""
-    return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), h0, *weights)
+def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0, forms=None):
+    """Differentiable fused propagation stack; returns the (N, sum of widths) readout.  `forms`: one ops.FORMS value per
+    layer (default: Bi everywhere); a GraphSage layer's weight is (d_out, 2 d_in)."""
+    forms = tuple(int(f) for f in forms) if forms is not None else (ops.FORMS["Bi"],) * len(weights)
+    if len(forms) != len(weights):
+        raise ValueError("gnn_train: %d forms for %d layers" % (len(forms), len(weights)))
+    return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), forms, h0, *weights)

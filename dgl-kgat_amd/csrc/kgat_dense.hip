@@ -84,7 +84,12 @@ struct DeferredRows {
   int32_t te_shift;       // log2(edges per tile)
 };
 constexpr int kDeferLongChain = 8;  // = spmm_finish_kernel's kLongChain
-template <int DI, int DO, int MODE, bool VEC_NORM, bool DEFER = false>
+// COMB: how the layer's two inputs form the A operand (KGAT paper, "Information Aggregation"; the res_type of reference
+// models.py:50-58).  0 = Bi-Interaction, h * h_N (res_fc_2, d_out x d_in).  1 = GCN, h + h_N (res_fc, d_out x d_in).
+// 2 = GraphSage, [h | h_N] along K (res_fc, d_out x 2 d_in): the first KS steps of the contraction take W's columns
+// [0, d_in) on the rows of h, the next KS its columns [d_in, 2 d_in) on the rows of h_N - nothing is formed.
+enum { kCombMul = 0, kCombSum = 1, kCombCat = 2 };
+template <int DI, int DO, int MODE, bool VEC_NORM, bool DEFER = false, int COMB = kCombMul>
 __global__ __launch_bounds__(256) void bi_interaction_kernel(
     int32_t n_rows, const float* __restrict__ P, const float* __restrict__ HN, const float* __restrict__ W2,
     float slope, uint32_t drop_threshold, float keep_scale, uint32_t seed, uint32_t index0,
@@ -92,14 +97,16 @@ __global__ __launch_bounds__(256) void bi_interaction_kernel(
     const DeferredRows df) {
   constexpr bool TRAIN = MODE == 2;
   static_assert(!DEFER || (MODE == 1 && !kBiMulAtLoad), "the deferred rows go with the late product");
+  static_assert(COMB == kCombMul || (MODE >= 1 && !kBiMulAtLoad), "the sum and the concatenation need H and HN apart");
   constexpr int KS = DI / 4, KT = DO / 16;
+  constexpr int DIW = COMB == kCombCat ? 2 * DI : DI, KSW = DIW / 4;  // W's columns, its k-steps
   // W2 is staged once per workgroup through LDS (coalesced 16-byte reads of the whole matrix),
   // laid out in B-fragment order so that every wave then pulls its fragments with
   // conflict-free ds_read_b32: s_w[(s*KT + c)*64 + q*16 + i] = W2[16c + i][16*(s>>2) + 4q + (s&3)]
-  __shared__ float s_w[KS * KT * kWave];
-  for (int idx = threadIdx.x * 4; idx < DO * DI; idx += 256 * 4) {
+  __shared__ float s_w[KSW * KT * kWave];
+  for (int idx = threadIdx.x * 4; idx < DO * DIW; idx += 256 * 4) {
     const float4 v = *reinterpret_cast<const float4*>(W2 + idx);
-    const int j = idx / DI, k0 = idx % DI;  // four consecutive k of output column j
+    const int j = idx / DIW, k0 = idx % DIW;  // four consecutive k of output column j
     const int c = j >> 4, i = j & 15;
     const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -126,11 +133,13 @@ __global__ __launch_bounds__(256) void bi_interaction_kernel(
   // need 256 VGPRs: there every MFMA takes its fragment from the LDS copy (one conflict-free
   // ds_read_b32 each)
 constexpr int kBiWLdsAbove = 128;  // (A/B builds: 0 = fragments always from LDS, fewer registers, more wavefronts per SIMD)
-  constexpr bool W_IN_LDS = KS * KT > kBiWLdsAbove;
-  float wreg[W_IN_LDS ? 1 : KS][W_IN_LDS ? 1 : KT];
+  // (the concatenation's W is twice as large: its fragments always come from LDS - held in registers they cost it
+  // occupancy against the product at every width, and spill at 128 -> 128; kernel-resource-usage)
+  constexpr bool W_IN_LDS = COMB == kCombCat || KS * KT > kBiWLdsAbove;
+  float wreg[W_IN_LDS ? 1 : KSW][W_IN_LDS ? 1 : KT];
   if (!W_IN_LDS) {
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
+    for (int s = 0; s < KSW; ++s)
 #pragma unroll
       for (int c = 0; c < KT; ++c) wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c] = s_w[(s * KT + c) * kWave + lane];
   }
@@ -270,12 +279,22 @@ constexpr int kBiPrefetch = 2;
 #pragma unroll
         for (int m = 0; m < DI / 16; ++m) st_final4(pe + m * 4, make_float4(a[4 * m + 0], a[4 * m + 1], a[4 * m + 2], a[4 * m + 3]));
       }
+      if constexpr (COMB == kCombMul) {
 #pragma unroll
-      for (int s = 0; s < KS; ++s) a[s] *= b[s];
+        for (int s = 0; s < KS; ++s) a[s] *= b[s];
+      } else if constexpr (COMB == kCombSum) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) a[s] += b[s];
+      }
     }
     floatx4_d acc[KT];
 #pragma unroll
     for (int c = 0; c < KT; ++c) acc[c] = (floatx4_d){0.f, 0.f, 0.f, 0.f};
+    // (the concatenation's fragments from LDS through an index the compiler cannot prove loop-invariant, so they are
+    // read per tile - left to itself it hoists the reads out of the tile loop into registers, up to 512 values per lane
+    // at 128 -> 128, and spills)
+    int wl = lane;
+    if constexpr (COMB == kCombCat && W_IN_LDS) asm volatile("" : "+v"(wl));
     // operands swapped (A = W2 fragment, B = the tile's rows): the accumulators hold Z^T, i.e.
     // acc[c][j] = Z[row0 + i][16c + 4q + j] - four consecutive columns per lane, so the results
     // leave as 16-byte stores (a quarter of the store instructions of the row-major result)
@@ -284,7 +303,16 @@ constexpr int kBiPrefetch = 2;
 #pragma unroll
       for (int c = 0; c < KT; ++c)
         acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            W_IN_LDS ? s_w[(s * KT + c) * kWave + lane] : wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c], a[s], acc[c], 0, 0, 0);
+            W_IN_LDS ? s_w[(s * KT + c) * kWave + wl] : wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c], a[s], acc[c], 0, 0, 0);
+    if constexpr (COMB == kCombCat) {  // the h_N half of K: W's k-steps KS .. 2 KS - 1 on the rows of HN
+#pragma unroll
+      for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int c = 0; c < KT; ++c)
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              W_IN_LDS ? s_w[((KS + s) * KT + c) * kWave + wl] : wreg[W_IN_LDS ? 0 : KS + s][W_IN_LDS ? 0 : c], b[s],
+              acc[c], 0, 0, 0);
+    }
     const int32_t row = row0 + i;
     // row norm: per 16-column tile the sum of squares over the row's four lanes (i, q = 0..3), then the tiles'
     // partials in tile order - the order of the fused aggregation + dense launch (kgat_spmm_impl.h: tile_ssq),
@@ -490,7 +518,7 @@ static DropArgs drop_args(float p, uint64_t seed, int64_t row0, int d_out) {
   return a;
 }
 
-template <int DI, int DO>
+template <int DI, int DO, int COMB = kCombMul>
 static int launch_bi(int64_t n_rows, const float* P, const float* HN, const float* W2, float slope,
                      const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride, hipStream_t st,
                      int mode, const EgoCopy ego, const DeferredRows* defer = nullptr) {
@@ -503,23 +531,23 @@ constexpr int kBiMaxBlocks = 512;
                    ((reinterpret_cast<uintptr_t>(norm_out) & 15u) == 0 && norm_stride % 4 == 0);
   const DeferredRows no_defer{nullptr, nullptr, 0, 0, 0};
 #define KGAT_BI_LAUNCH(MD, VEC)                                                                                     \
-  hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, MD, VEC>), dim3((unsigned)blocks), dim3(256), 0, st,            \
+  hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, MD, VEC, false, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,\
                      (int32_t)n_rows, P, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,     \
                      norm_out, norm_stride, ego, no_defer)
   if (mode == 1 && defer != nullptr) {
     if (vec)
-      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, 1, true, true>), dim3((unsigned)blocks), dim3(256), 0, st,
+      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, 1, true, true, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,
                          (int32_t)n_rows, P, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,
                          norm_out, norm_stride, ego, *defer);
     else
-      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, 1, false, true>), dim3((unsigned)blocks), dim3(256), 0, st,
+      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, 1, false, true, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,
                          (int32_t)n_rows, P, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,
                          norm_out, norm_stride, ego, *defer);
   } else if (mode == 2) {
     if (vec) KGAT_BI_LAUNCH(2, true); else KGAT_BI_LAUNCH(2, false);
   } else if (mode == 1) {
     if (vec) KGAT_BI_LAUNCH(1, true); else KGAT_BI_LAUNCH(1, false);
-  } else {
+  } else if constexpr (COMB == kCombMul) {  // (MODE 0 - P formed elsewhere - exists for the product only)
     if (vec) KGAT_BI_LAUNCH(0, true); else KGAT_BI_LAUNCH(0, false);
   }
 #undef KGAT_BI_LAUNCH
@@ -592,16 +620,20 @@ __global__ __launch_bounds__(256) void bi_bwd_pre_kernel(int64_t n_rows, int d, 
 // B fragments s_w[(s*KT + c)*64 + q*16 + i] = W2[k][16c + i], k = 16 (s >> 2) + 4q + (s & 3) the contraction index (a
 // column of grad_z), 16c + i the output column; a lane ends with four consecutive columns of one row, where it also
 // holds H and HN (requested with the grad_z rows).
-template <int DK, int DN>
+// COMB (see bi_interaction_kernel): kCombSum - grad_P is the gradient through h_N and through h alike, written once to
+// T (GB unused, H and HN not read); kCombCat - W is d_out x 2 d_in, grad_P's columns [0, d_in) (the h half) go to GB
+// and [d_in, 2 d_in) (the h_N half, to be aggregated) to T.
+template <int DK, int DN, int COMB = kCombMul>
 __global__ __launch_bounds__(256) void bi_bwd_input_kernel(int32_t n_rows, const float* __restrict__ GZ,
                                                           const float* __restrict__ W2, const float* __restrict__ H,
                                                           const float* __restrict__ HN, float* __restrict__ T,
                                                           float* __restrict__ GB) {
-  constexpr int KS = DK / 4, KT = DN / 16;
+  constexpr int DNW = COMB == kCombCat ? 2 * DN : DN;  // W's columns = grad_P's
+  constexpr int KS = DK / 4, KT = DNW / 16;
   __shared__ float s_w[KS * KT * kWave];
-  for (int idx = threadIdx.x * 4; idx < DK * DN; idx += 256 * 4) {
+  for (int idx = threadIdx.x * 4; idx < DK * DNW; idx += 256 * 4) {
     const float4 v = *reinterpret_cast<const float4*>(W2 + idx);  // W2[k][j0 .. j0 + 3]
-    const int k = idx / DN, j0 = idx % DN;
+    const int k = idx / DNW, j0 = idx % DNW;
     const int s = (k >> 4) * 4 + (k & 3), q = (k >> 2) & 3;
     const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -619,7 +651,7 @@ __global__ __launch_bounds__(256) void bi_bwd_input_kernel(int32_t n_rows, const
   const int32_t t_begin = (int32_t)((int64_t)n_tiles * wv / n_waves);
   const int32_t t_end = (int32_t)((int64_t)n_tiles * (wv + 1) / n_waves);
   if (t_begin >= t_end) return;
-  constexpr bool W_IN_LDS = KS * KT > 128;
+  constexpr bool W_IN_LDS = COMB == kCombCat || KS * KT > 128;  // (as in bi_interaction_kernel)
   float wreg[W_IN_LDS ? 1 : KS][W_IN_LDS ? 1 : KT];
   if (!W_IN_LDS) {
 #pragma unroll
@@ -627,7 +659,8 @@ __global__ __launch_bounds__(256) void bi_bwd_input_kernel(int32_t n_rows, const
 #pragma unroll
       for (int c = 0; c < KT; ++c) wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c] = s_w[(s * KT + c) * kWave + lane];
   }
-  struct Rows { float g[KS]; float4 h[KT], hn[KT]; };
+  constexpr int KTH = COMB == kCombMul ? KT : 1;
+  struct Rows { float g[KS]; float4 h[KTH], hn[KTH]; };
   auto load_rows = [&](int32_t t, Rows& r) {
     int32_t ra = (t << 4) + i;
     ra = ra < n_rows ? ra : n_rows - 1;
@@ -637,33 +670,45 @@ __global__ __launch_bounds__(256) void bi_bwd_input_kernel(int32_t n_rows, const
       const float4 v = pg[m * 4];
       r.g[4 * m + 0] = v.x; r.g[4 * m + 1] = v.y; r.g[4 * m + 2] = v.z; r.g[4 * m + 3] = v.w;
     }
-    const float4* ph = reinterpret_cast<const float4*>(H + (size_t)ra * DN) + q;
-    const float4* pn = reinterpret_cast<const float4*>(HN + (size_t)ra * DN) + q;
+    if constexpr (COMB == kCombMul) {
+      const float4* ph = reinterpret_cast<const float4*>(H + (size_t)ra * DN) + q;
+      const float4* pn = reinterpret_cast<const float4*>(HN + (size_t)ra * DN) + q;
 #pragma unroll
-    for (int c = 0; c < KT; ++c) {
-      r.h[c] = ph[c * 4];
-      r.hn[c] = pn[c * 4];
+      for (int c = 0; c < KT; ++c) {
+        r.h[c] = ph[c * 4];
+        r.hn[c] = pn[c * 4];
+      }
     }
   };
   auto tile = [&](int32_t t, const Rows& r) {
     floatx4_d acc[KT];
 #pragma unroll
     for (int c = 0; c < KT; ++c) acc[c] = (floatx4_d){0.f, 0.f, 0.f, 0.f};
+    int wl = lane;  // (as in bi_interaction_kernel: the concatenation's fragments read per tile, not hoisted)
+    if constexpr (COMB == kCombCat && W_IN_LDS) asm volatile("" : "+v"(wl));
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
       for (int c = 0; c < KT; ++c)
         acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            W_IN_LDS ? s_w[(s * KT + c) * kWave + lane] : wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c], r.g[s], acc[c], 0, 0, 0);
+            W_IN_LDS ? s_w[(s * KT + c) * kWave + wl] : wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c], r.g[s], acc[c], 0, 0, 0);
     const int32_t row = (t << 4) + i;
     if (row < n_rows) {
 #pragma unroll
       for (int c = 0; c < KT; ++c) {
-        const size_t off = (size_t)row * DN + 16 * c + 4 * q;
-        *reinterpret_cast<float4*>(T + off) =
-            make_float4(acc[c][0] * r.h[c].x, acc[c][1] * r.h[c].y, acc[c][2] * r.h[c].z, acc[c][3] * r.h[c].w);
-        *reinterpret_cast<float4*>(GB + off) =
-            make_float4(acc[c][0] * r.hn[c].x, acc[c][1] * r.hn[c].y, acc[c][2] * r.hn[c].z, acc[c][3] * r.hn[c].w);
+        if constexpr (COMB == kCombMul) {
+          const size_t off = (size_t)row * DN + 16 * c + 4 * q;
+          *reinterpret_cast<float4*>(T + off) =
+              make_float4(acc[c][0] * r.h[c].x, acc[c][1] * r.h[c].y, acc[c][2] * r.h[c].z, acc[c][3] * r.h[c].w);
+          *reinterpret_cast<float4*>(GB + off) =
+              make_float4(acc[c][0] * r.hn[c].x, acc[c][1] * r.hn[c].y, acc[c][2] * r.hn[c].z, acc[c][3] * r.hn[c].w);
+        } else {
+          // (sum: every tile to T; concatenation: the first KT / 2 column tiles are the h half -> GB, the rest -> T)
+          const bool self_half = COMB == kCombCat && c < KT / 2;
+          const int cc = COMB == kCombCat && !self_half ? c - KT / 2 : c;
+          *reinterpret_cast<float4*>((self_half ? GB : T) + (size_t)row * DN + 16 * cc + 4 * q) =
+              make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
+        }
       }
     }
   };
@@ -685,13 +730,15 @@ __global__ __launch_bounds__(256) void bi_bwd_input_kernel(int32_t n_rows, const
 // w, w + 4, ... (at 64 x 64: one column tile, all four row tiles - one B read per four MFMAs); the contraction index
 // of v_mfma_f32_16x16x4_f32 is the ROW: A[m][k] = grad_z[r0 + k][16 cm + m], B[k][n] = P[r0 + k][16 cn + n].  Every
 // workgroup writes its partial (d_out x d_in); the caller sums the partials (fixed order: reproducible).
-template <int DO, int DI>
+// COMB (see bi_interaction_kernel): the B operand staged in LDS is H * HN, H + HN, or [H | HN] (a d_out x 2 d_in result).
+template <int DO, int DI, int COMB = kCombMul>
 __global__ __launch_bounds__(256) void bi_bwd_weight_kernel(int32_t n_rows, const float* __restrict__ GZ,
                                                            const float* __restrict__ H, const float* __restrict__ HN,
                                                            float* __restrict__ partial) {
   constexpr int SLAB = 64;
-  constexpr int LG = DO == 16 ? 16 : DO + 16, LP = DI == 16 ? 16 : DI + 16;
-  constexpr int TM = DO / 16, TN = DI / 16, TT = TM * TN;
+  constexpr int DIW = COMB == kCombCat ? 2 * DI : DI;  // the staged rows' width = the result's columns
+  constexpr int LG = DO == 16 ? 16 : DO + 16, LP = DIW == 16 ? 16 : DIW + 16;
+  constexpr int TM = DO / 16, TN = DIW / 16, TT = TM * TN;
   constexpr int TPW = (TT + 3) / 4;                 // output tiles per wavefront
   constexpr int G4 = SLAB * DO / 4 / 256 > 0 ? SLAB * DO / 4 / 256 : 1;  // float4 of grad_z per thread per slab
   constexpr int P4 = SLAB * DI / 4 / 256 > 0 ? SLAB * DI / 4 / 256 : 1;
@@ -734,9 +781,18 @@ __global__ __launch_bounds__(256) void bi_bwd_weight_kernel(int32_t n_rows, cons
 #pragma unroll
     for (int u = 0; u < P4; ++u) {
       const int e = (u * 256 + tid) * 4;
-      if (e < SLAB * DI)
-        *reinterpret_cast<float4*>(&s_p[(e / DI) * LP + e % DI]) =
-            make_float4(hh[u].x * hn[u].x, hh[u].y * hn[u].y, hh[u].z * hn[u].z, hh[u].w * hn[u].w);
+      if (e < SLAB * DI) {
+        if constexpr (COMB == kCombMul)
+          *reinterpret_cast<float4*>(&s_p[(e / DI) * LP + e % DI]) =
+              make_float4(hh[u].x * hn[u].x, hh[u].y * hn[u].y, hh[u].z * hn[u].z, hh[u].w * hn[u].w);
+        else if constexpr (COMB == kCombSum)
+          *reinterpret_cast<float4*>(&s_p[(e / DI) * LP + e % DI]) =
+              make_float4(hh[u].x + hn[u].x, hh[u].y + hn[u].y, hh[u].z + hn[u].z, hh[u].w + hn[u].w);
+        else {
+          *reinterpret_cast<float4*>(&s_p[(e / DI) * LP + e % DI]) = hh[u];
+          *reinterpret_cast<float4*>(&s_p[(e / DI) * LP + DI + e % DI]) = hn[u];
+        }
+      }
     }
     __syncthreads();
     if (slab + (int32_t)gridDim.x < n_slabs) request(slab + gridDim.x);  // in flight while this slab is multiplied
@@ -757,14 +813,14 @@ __global__ __launch_bounds__(256) void bi_bwd_weight_kernel(int32_t n_rows, cons
     }
   }
   // C[m = 4q + j][n = i] of tile (cm, cn) -> partial[block][16 cm + 4q + j][16 cn + i]
-  float* out = partial + (size_t)blockIdx.x * DO * DI;
+  float* out = partial + (size_t)blockIdx.x * DO * DIW;
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     const int tile = w + 4 * t;
     if (tile < TT) {
       const int cm = tile / TN, cn = tile % TN;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) out[(size_t)(16 * cm + 4 * q + j) * DI + 16 * cn + i] = acc[t][j];
+      for (int j = 0; j < 4; ++j) out[(size_t)(16 * cm + 4 * q + j) * DIW + 16 * cn + i] = acc[t][j];
     }
   }
 }
@@ -777,6 +833,64 @@ __global__ __launch_bounds__(256) void mul2_kernel(int64_t n4, const float4* __r
     AB[i] = make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
     AC[i] = make_float4(a.x * c.x, a.y * c.y, a.z * c.z, a.w * c.w);
   }
+}
+
+// The sum and the concatenation: the MFMA kernel's widths only (others are the caller's, in torch)
+template <int COMB>
+static int comb_dispatch(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W,
+                         float negative_slope, const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride,
+                         hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer) {
+#define KGAT_COMB_CASE(DI, DO) \
+  if (d_in == DI && d_out == DO) \
+    return launch_bi<DI, DO, COMB>(n_rows, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st, mode, ego, defer);
+  KGAT_COMB_CASE(16, 16) KGAT_COMB_CASE(16, 32) KGAT_COMB_CASE(16, 64) KGAT_COMB_CASE(16, 128)
+  KGAT_COMB_CASE(32, 16) KGAT_COMB_CASE(32, 32) KGAT_COMB_CASE(32, 64) KGAT_COMB_CASE(32, 128)
+  KGAT_COMB_CASE(64, 16) KGAT_COMB_CASE(64, 32) KGAT_COMB_CASE(64, 64) KGAT_COMB_CASE(64, 128)
+  KGAT_COMB_CASE(128, 16) KGAT_COMB_CASE(128, 32) KGAT_COMB_CASE(128, 64) KGAT_COMB_CASE(128, 128)
+#undef KGAT_COMB_CASE
+  set_error("aggregator: unsupported widths %d -> %d", d_in, d_out);
+  return KGAT_E_UNSUPPORTED;
+}
+
+template <int COMB>
+static int launch_bwd_input(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W, const float* H,
+                            const float* HN, float* t, float* gb, hipStream_t st) {
+  const int64_t tiles = (n_rows + 15) / 16;
+  int64_t blocks = (tiles + 3) / 4;
+  if (blocks > 512) blocks = 512;
+#define KGAT_BWD_CASE(DK, DN)                                                                                         \
+  if (d_out == DK && d_in == DN) {                                                                                    \
+    hipLaunchKernelGGL((bi_bwd_input_kernel<DK, DN, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,                 \
+                       (int32_t)n_rows, grad_z, W, H, HN, t, gb);                                                     \
+    KGAT_CHECK_LAUNCH("bi_bwd_input");                                                                                \
+    return KGAT_OK;                                                                                                   \
+  }
+  KGAT_BWD_CASE(16, 16) KGAT_BWD_CASE(16, 32) KGAT_BWD_CASE(16, 64) KGAT_BWD_CASE(16, 128)
+  KGAT_BWD_CASE(32, 16) KGAT_BWD_CASE(32, 32) KGAT_BWD_CASE(32, 64) KGAT_BWD_CASE(32, 128)
+  KGAT_BWD_CASE(64, 16) KGAT_BWD_CASE(64, 32) KGAT_BWD_CASE(64, 64) KGAT_BWD_CASE(64, 128)
+  KGAT_BWD_CASE(128, 16) KGAT_BWD_CASE(128, 32) KGAT_BWD_CASE(128, 64) KGAT_BWD_CASE(128, 128)
+#undef KGAT_BWD_CASE
+  set_error("bi_interaction_bwd_input: unsupported widths %d -> %d", d_in, d_out);
+  return KGAT_E_UNSUPPORTED;
+}
+
+template <int COMB>
+static int launch_bwd_weight(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H, const float* HN,
+                             float* partials, int64_t n_partials, hipStream_t st) {
+#define KGAT_BWW_CASE(DO_, DI_)                                                                                        \
+  if (d_out == DO_ && d_in == DI_) {                                                                                  \
+    hipLaunchKernelGGL((bi_bwd_weight_kernel<DO_, DI_, COMB>), dim3((unsigned)n_partials), dim3(256), 0, st,          \
+                       (int32_t)n_rows, grad_z, H, HN, partials);                                                     \
+    KGAT_CHECK_LAUNCH("bi_bwd_weight");                                                                               \
+    return KGAT_OK;                                                                                                   \
+  }
+  KGAT_BWW_CASE(16, 16) KGAT_BWW_CASE(16, 32) KGAT_BWW_CASE(16, 64) KGAT_BWW_CASE(16, 128)
+  KGAT_BWW_CASE(32, 16) KGAT_BWW_CASE(32, 32) KGAT_BWW_CASE(32, 64) KGAT_BWW_CASE(32, 128)
+  KGAT_BWW_CASE(64, 16) KGAT_BWW_CASE(64, 32) KGAT_BWW_CASE(64, 64) KGAT_BWW_CASE(64, 128)
+  KGAT_BWW_CASE(128, 16) KGAT_BWW_CASE(128, 32) KGAT_BWW_CASE(128, 64) KGAT_BWW_CASE(128, 128)
+#undef KGAT_BWW_CASE
+  set_error("bi_interaction_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
+  return KGAT_E_UNSUPPORTED;
 }
 
 }  // namespace kgat
@@ -857,6 +971,25 @@ static int bi_dispatch(int64_t n_rows, int d_in, int d_out, const float* P, cons
   return KGAT_E_UNSUPPORTED;
 }
 
+// form (KGAT_FORM_*) -> the kernels: KGAT_FORM_BI is bi_dispatch itself
+static int form_dispatch(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W,
+                         float negative_slope, const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride,
+                         hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer = nullptr) {
+  if (form == KGAT_FORM_GCN)
+    return comb_dispatch<kCombSum>(n_rows, d_in, d_out, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st,
+                                   mode, ego, defer);
+  if (form == KGAT_FORM_GRAPHSAGE)
+    return comb_dispatch<kCombCat>(n_rows, d_in, d_out, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st,
+                                   mode, ego, defer);
+  return bi_dispatch(n_rows, d_in, d_out, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st, mode, ego, defer);
+}
+
+int kgat_aggregator_supported(int form, int d_in, int d_out) {
+  auto ok = [](int d) { return d == 16 || d == 32 || d == 64 || d == 128; };
+  if (form == KGAT_FORM_BI) return kgat_bi_interaction_supported(d_in, d_out);
+  return (form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) && ok(d_in) && ok(d_out);
+}
+
 int kgat_bi_interaction_f32(int64_t n_rows, int d_in, int d_out, const float* P, const float* W2,
                             float negative_slope, float* h_out, float* norm_out,
                             int64_t norm_stride, kgat_stream_t stream) {
@@ -875,6 +1008,13 @@ int kgat_bi_interaction_f32(int64_t n_rows, int d_in, int d_out, const float* P,
 int kgat_bi_interaction_mul_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W2,
                                 float negative_slope, float* h_out, float* norm_out, int64_t norm_stride,
                                 float* self_out, int64_t self_stride, kgat_stream_t stream) {
+  return kgat_aggregator_f32(KGAT_FORM_BI, n_rows, d_in, d_out, H, HN, W2, negative_slope, h_out, norm_out, norm_stride,
+                             self_out, self_stride, stream);
+}
+
+int kgat_aggregator_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W2,
+                        float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
+                        int64_t self_stride, kgat_stream_t stream) {
   KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_mul: bad row count");
   if (n_rows == 0) return KGAT_OK;
   KGAT_CHECK_ARG(H && HN && W2 && (h_out || norm_out), "bi_interaction_mul: null pointer");
@@ -882,12 +1022,12 @@ int kgat_bi_interaction_mul_f32(int64_t n_rows, int d_in, int d_out, const float
   KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
                                          (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
                  "bi_interaction_mul: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
-  if (!kgat_bi_interaction_supported(d_in, d_out)) {
-    set_error("bi_interaction_mul: unsupported widths %d -> %d", d_in, d_out);
+  if (!kgat_aggregator_supported(form, d_in, d_out)) {
+    set_error("bi_interaction_mul: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
     return KGAT_E_UNSUPPORTED;
   }
-  return bi_dispatch(n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
-                     as_stream(stream), 1, EgoCopy{self_out, self_stride});
+  return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
+                       as_stream(stream), 1, EgoCopy{self_out, self_stride});
 }
 
 int kgat_bi_interaction_mul_deferred_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
@@ -895,6 +1035,18 @@ int kgat_bi_interaction_mul_deferred_f32(int64_t n_rows, int d_in, int d_out, co
                                          int64_t norm_stride, float* self_out, int64_t self_stride,
                                          const int32_t* indptr_rows, int64_t e_begin, int64_t e_end,
                                          const void* spmm_workspace, int tile_edges, kgat_stream_t stream) {
+  return kgat_aggregator_deferred_f32(KGAT_FORM_BI, n_rows, d_in, d_out, H, HN, W2, negative_slope, h_out, norm_out,
+                                      norm_stride, self_out, self_stride, indptr_rows, e_begin, e_end, spmm_workspace,
+                                      tile_edges, stream);
+}
+
+int kgat_aggregator_deferred_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
+                                 const float* W2, float negative_slope, float* h_out, float* norm_out,
+                                 int64_t norm_stride, float* self_out, int64_t self_stride, const int32_t* indptr_rows,
+                                 int64_t e_begin, int64_t e_end, const void* spmm_workspace, int tile_edges,
+                                 kgat_stream_t stream) {
+  KGAT_CHECK_ARG(form == KGAT_FORM_BI || form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE,
+                 "bi_interaction_mul_deferred: unknown form %d", form);
   KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_mul_deferred: bad row count");
   if (n_rows == 0) return KGAT_OK;
   KGAT_CHECK_ARG(H && HN && W2 && (h_out || norm_out) && indptr_rows, "bi_interaction_mul_deferred: null pointer");
@@ -909,14 +1061,22 @@ int kgat_bi_interaction_mul_deferred_f32(int64_t n_rows, int d_in, int d_out, co
   int shift = 0;
   while ((1 << shift) < tile_edges) ++shift;
   const DeferredRows df{indptr_rows, static_cast<const float4*>(spmm_workspace), (int32_t)e_begin, (int32_t)e_end, shift};
-  return bi_dispatch(n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
-                     as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
+  return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
+                       as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
 }
 
 int kgat_bi_interaction_train_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
                                   const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0,
                                   float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
                                   int64_t self_stride, kgat_stream_t stream) {
+  return kgat_aggregator_train_f32(KGAT_FORM_BI, n_rows, d_in, d_out, H, HN, W2, negative_slope, drop_p, seed, row0,
+                                   h_out, norm_out, norm_stride, self_out, self_stride, stream);
+}
+
+int kgat_aggregator_train_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
+                              const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0,
+                              float* h_out, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
+                              kgat_stream_t stream) {
   KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX && row0 >= 0 &&
                      (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32),
                  "bi_interaction_train: bad row count");
@@ -924,15 +1084,15 @@ int kgat_bi_interaction_train_f32(int64_t n_rows, int d_in, int d_out, const flo
   if (n_rows == 0) return KGAT_OK;
   KGAT_CHECK_ARG(H && HN && W2 && h_out, "bi_interaction_train: null pointer");
   KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "bi_interaction_train: bad norm_stride");
-  if (!kgat_bi_interaction_supported(d_in, d_out)) {
-    set_error("bi_interaction_train: unsupported widths %d -> %d", d_in, d_out);
+  if (!kgat_aggregator_supported(form, d_in, d_out)) {
+    set_error("bi_interaction_train: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
     return KGAT_E_UNSUPPORTED;
   }
   KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
                                          (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
                  "bi_interaction_train: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
-  return bi_dispatch(n_rows, d_in, d_out, H, HN, W2, negative_slope, drop_args(drop_p, seed, row0, d_out), h_out,
-                     norm_out, norm_stride, as_stream(stream), 2, EgoCopy{self_out, self_stride});
+  return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, drop_args(drop_p, seed, row0, d_out), h_out,
+                       norm_out, norm_stride, as_stream(stream), 2, EgoCopy{self_out, self_stride});
 }
 
 // out = a + b + c over n_rows x d (a: rows of a_stride floats - a column slice of a wider matrix; b, c, out contiguous)
@@ -996,27 +1156,32 @@ int kgat_bi_interaction_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const
   KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_bwd_input: bad row count");
   if (n_rows == 0) return KGAT_OK;
   KGAT_CHECK_ARG(grad_z && W2 && H && HN && grad_hn_times_h && grad_h_direct, "bi_interaction_bwd_input: null pointer");
-  if (!kgat_bi_interaction_bwd_input_supported(d_in, d_out)) {
-    set_error("bi_interaction_bwd_input: unsupported widths %d -> %d", d_in, d_out);
+  return kgat_aggregator_bwd_input_f32(KGAT_FORM_BI, n_rows, d_in, d_out, grad_z, W2, H, HN, grad_hn_times_h,
+                                       grad_h_direct, stream);
+}
+
+int kgat_aggregator_bwd_supported(int form, int d_in, int d_out) {
+  return (form == KGAT_FORM_BI || form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) &&
+         kgat_bi_interaction_bwd_input_supported(d_in, d_out);
+}
+
+int kgat_aggregator_bwd_input_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W,
+                                  const float* H, const float* HN, float* grad_agg, float* grad_self,
+                                  kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "aggregator_bwd_input: bad row count");
+  if (n_rows == 0) return KGAT_OK;
+  if (!kgat_aggregator_bwd_supported(form, d_in, d_out)) {
+    set_error("bi_interaction_bwd_input: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
     return KGAT_E_UNSUPPORTED;
   }
-  const int64_t tiles = (n_rows + 15) / 16;
-  int64_t blocks = (tiles + 3) / 4;
-  if (blocks > 512) blocks = 512;
-#define KGAT_BWD_CASE(DK, DN)                                                                                         \
-  if (d_out == DK && d_in == DN) {                                                                                    \
-    hipLaunchKernelGGL((bi_bwd_input_kernel<DK, DN>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),        \
-                       (int32_t)n_rows, grad_z, W2, H, HN, grad_hn_times_h, grad_h_direct);                           \
-    KGAT_CHECK_LAUNCH("bi_bwd_input");                                                                                \
-    return KGAT_OK;                                                                                                   \
-  }
-  KGAT_BWD_CASE(16, 16) KGAT_BWD_CASE(16, 32) KGAT_BWD_CASE(16, 64) KGAT_BWD_CASE(16, 128)
-  KGAT_BWD_CASE(32, 16) KGAT_BWD_CASE(32, 32) KGAT_BWD_CASE(32, 64) KGAT_BWD_CASE(32, 128)
-  KGAT_BWD_CASE(64, 16) KGAT_BWD_CASE(64, 32) KGAT_BWD_CASE(64, 64) KGAT_BWD_CASE(64, 128)
-  KGAT_BWD_CASE(128, 16) KGAT_BWD_CASE(128, 32) KGAT_BWD_CASE(128, 64) KGAT_BWD_CASE(128, 128)
-#undef KGAT_BWD_CASE
-  set_error("bi_interaction_bwd_input: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  KGAT_CHECK_ARG(grad_z && W && grad_agg && (form == KGAT_FORM_GCN || grad_self) && (form != KGAT_FORM_BI || (H && HN)),
+                 "aggregator_bwd_input: null pointer");
+  if (form == KGAT_FORM_GCN)
+    return launch_bwd_input<kCombSum>(n_rows, d_in, d_out, grad_z, W, nullptr, nullptr, grad_agg, nullptr, as_stream(stream));
+  if (form == KGAT_FORM_GRAPHSAGE)
+    return launch_bwd_input<kCombCat>(n_rows, d_in, d_out, grad_z, W, nullptr, nullptr, grad_agg, grad_self,
+                                      as_stream(stream));
+  return launch_bwd_input<kCombMul>(n_rows, d_in, d_out, grad_z, W, H, HN, grad_agg, grad_self, as_stream(stream));
 }
 
 int64_t kgat_bi_interaction_bwd_weight_partials(int64_t n_rows) {
@@ -1027,28 +1192,24 @@ int64_t kgat_bi_interaction_bwd_weight_partials(int64_t n_rows) {
 
 int kgat_bi_interaction_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
                                        const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream) {
+  return kgat_aggregator_bwd_weight_f32(KGAT_FORM_BI, n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, stream);
+}
+
+int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
+                                   const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream) {
   KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_bwd_weight: bad row count");
   KGAT_CHECK_ARG(n_partials == kgat_bi_interaction_bwd_weight_partials(n_rows),
                  "bi_interaction_bwd_weight: n_partials must be kgat_bi_interaction_bwd_weight_partials(n_rows)");
   KGAT_CHECK_ARG(partials != nullptr && (n_rows == 0 || (grad_z && H && HN)), "bi_interaction_bwd_weight: null pointer");
-  if (!kgat_bi_interaction_bwd_input_supported(d_in, d_out)) {
-    set_error("bi_interaction_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
+  if (!kgat_aggregator_bwd_supported(form, d_in, d_out)) {
+    set_error("bi_interaction_bwd_weight: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
     return KGAT_E_UNSUPPORTED;
   }
-#define KGAT_BWW_CASE(DO_, DI_)                                                                                        \
-  if (d_out == DO_ && d_in == DI_) {                                                                                  \
-    hipLaunchKernelGGL((bi_bwd_weight_kernel<DO_, DI_>), dim3((unsigned)n_partials), dim3(256), 0, as_stream(stream), \
-                       (int32_t)n_rows, grad_z, H, HN, partials);                                                     \
-    KGAT_CHECK_LAUNCH("bi_bwd_weight");                                                                               \
-    return KGAT_OK;                                                                                                   \
-  }
-  KGAT_BWW_CASE(16, 16) KGAT_BWW_CASE(16, 32) KGAT_BWW_CASE(16, 64) KGAT_BWW_CASE(16, 128)
-  KGAT_BWW_CASE(32, 16) KGAT_BWW_CASE(32, 32) KGAT_BWW_CASE(32, 64) KGAT_BWW_CASE(32, 128)
-  KGAT_BWW_CASE(64, 16) KGAT_BWW_CASE(64, 32) KGAT_BWW_CASE(64, 64) KGAT_BWW_CASE(64, 128)
-  KGAT_BWW_CASE(128, 16) KGAT_BWW_CASE(128, 32) KGAT_BWW_CASE(128, 64) KGAT_BWW_CASE(128, 128)
-#undef KGAT_BWW_CASE
-  set_error("bi_interaction_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  if (form == KGAT_FORM_GCN)
+    return launch_bwd_weight<kCombSum>(n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, as_stream(stream));
+  if (form == KGAT_FORM_GRAPHSAGE)
+    return launch_bwd_weight<kCombCat>(n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, as_stream(stream));
+  return launch_bwd_weight<kCombMul>(n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, as_stream(stream));
 }
 
 // out[s][e] = sum over the partials of set s, for up to four sets in ONE launch (the weight gradients of a stack's

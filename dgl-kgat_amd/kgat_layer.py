@@ -21,8 +21,19 @@ import torch.nn.functional as F
 
 from . import function as fn
 from .autograd import edge_softmax, u_mul_e_sum
+from .ops import FORMS
 from .options import options
 from .sage_layer import SAGEConv, draw_seed
+
+
+def _layer_dense(layer):
+    """(form, weight, d_in, d_out) of a KGAT layer's dense part: ops.FORMS[res_type] and res_fc_2 / res_fc (a
+    reference-shaped layer routed here by compat.accelerate has res_fc_2: Bi)."""
+    if hasattr(layer, "res_fc_2"):
+        lin = layer.res_fc_2
+        return FORMS["Bi"], lin.weight, lin.in_features, lin.out_features
+    form, lin = FORMS[layer._res_type], layer.res_fc
+    return form, lin.weight, lin.in_features // (2 if form == FORMS["GraphSage"] else 1), lin.out_features
 
 
 def ops_transr_supported(model, h):
@@ -58,22 +69,45 @@ class _TallLinear(torch.autograd.Function):
 
 
 class KGATConv(nn.Module):
-    """Bi-interaction propagation layer: LeakyReLU_{0.01}(W2 (h * h_N)), dropout
-    (reference models.py:49-70; only the ``Bi`` branch with ``res_fc_2`` exists there)."""
+    """KGAT propagation layer (reference models.py:49-70), then dropout, with one of the KGAT paper's three aggregators
+    ("Information Aggregation"; the reference implements only ``Bi`` and keeps ``res_type`` as the hook):
+      * ``"Bi"``        LeakyReLU_{0.01}(res_fc_2(h * h_N))       res_fc_2.weight (out, in)
+      * ``"GCN"``       LeakyReLU_{0.01}(res_fc(h + h_N))         res_fc.weight (out, in)
+      * ``"GraphSage"`` LeakyReLU_{0.01}(res_fc([h | h_N]))       res_fc.weight (out, 2 in): columns [:in] act on h."""
 
     def __init__(self, entity_in_feats, out_feats, dropout, res_type="Bi"):
         super().__init__()
-        if res_type != "Bi":
+        if res_type not in FORMS:
             raise NotImplementedError(res_type)
         self.mess_drop = nn.Dropout(dropout)
         self._res_type = res_type
-        self.res_fc_2 = nn.Linear(entity_in_feats, out_feats, bias=False)
+        if res_type == "Bi":
+            self.res_fc_2 = nn.Linear(entity_in_feats, out_feats, bias=False)
+        else:
+            k = 2 * entity_in_feats if res_type == "GraphSage" else entity_in_feats
+            self.res_fc = nn.Linear(k, out_feats, bias=False)
+
+    def _dense(self, h, h_neighbor, fused):
+        """The GCN / GraphSage dense part: LeakyReLU(res_fc(h + h_N | [h | h_N])).  fused and nothing to differentiate:
+        the aggregator kernel (kgat_aggregator_f32) where it covers the widths; otherwise library GEMMs."""
+        from . import ops
+        form, w = FORMS[self._res_type], self.res_fc.weight
+        d_in = h.shape[1]
+        if (fused and h.is_cuda and h.dtype == torch.float32 and ops.aggregator_supported(form, d_in, w.shape[0]) and
+                not (torch.is_grad_enabled() and (h.requires_grad or h_neighbor.requires_grad or w.requires_grad))):
+            return ops.aggregator(form, h.contiguous(), h_neighbor.contiguous(), w.detach().contiguous(), 0.01)
+        x = h + h_neighbor if form == FORMS["GCN"] else torch.cat([h, h_neighbor], 1)
+        return F.leaky_relu(_TallLinear.apply(x, w))
 
     def forward(self, g, nfeat, fused=None, seed=None):
         part = g.partition
         if fused is None:
             fused = not (torch.is_grad_enabled() and nfeat.requires_grad)
         if part is not None:
+            if self._res_type != "Bi":
+                from .graph import DGLError
+                raise DGLError("KGATConv(res_type=%r) on a partitioned graph: sharded models run the Bi aggregator only"
+                               % (self._res_type,))
             if torch.is_grad_enabled() and (nfeat.requires_grad or self.res_fc_2.weight.requires_grad):
                 # differentiable shard layer (partition._ShardConv): local backward + all-reduce of the
                 # gradients of the replicated operands; dropout is its hash mask, drawn on global rows
@@ -95,6 +129,8 @@ class KGATConv(nn.Module):
                     seed = int(torch.empty((), dtype=torch.int64).random_()) if p > 0 else 0
                 return shard_conv(part, g, nfeat, self.res_fc_2.weight, 0.01, p, seed)
             out = part.propagate(g, nfeat, self.res_fc_2.weight)
+        elif fused and self._res_type != "Bi":
+            out = self._dense(nfeat, u_mul_e_sum(g, nfeat, g.edata["w"]), fused=True)
         elif fused:
             # h * h_N formed in the SpMM epilogue (models.py:63 + the th.mul of :66)
             prod = u_mul_e_sum(g, nfeat, g.edata["w"], mul_self=True)
@@ -104,7 +140,10 @@ class KGATConv(nn.Module):
             g.ndata["h"] = nfeat
             g.update_all(fn.u_mul_e("h", "w", "m"), fn.sum("m", "h_neighbor"))
             h_neighbor = g.ndata["h_neighbor"]
-            out = F.leaky_relu(_TallLinear.apply(torch.mul(g.ndata["h"], h_neighbor), self.res_fc_2.weight))
+            if self._res_type != "Bi":
+                out = self._dense(g.ndata["h"], h_neighbor, fused=False)
+            else:
+                out = F.leaky_relu(_TallLinear.apply(torch.mul(g.ndata["h"], h_neighbor), self.res_fc_2.weight))
         return self.mess_drop(out)
 
 
@@ -115,11 +154,17 @@ class KGATPropagation(nn.Module):
     training-step test needs a scalar to differentiate."""
 
     def __init__(self, n_entities, n_relations, input_node_dim=64, relation_dim=64, num_gnn_layers=3,
-                 n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01, gnn_model="kgat"):
+                 n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01, gnn_model="kgat", res_type="Bi"):
         super().__init__()
         if gnn_model not in ("kgat", "graphsage"):
             raise NotImplementedError("gnn_model must be 'kgat' or 'graphsage', got %r" % (gnn_model,))
+        if res_type not in FORMS:
+            raise NotImplementedError("res_type must be one of %s, got %r" % (", ".join(sorted(FORMS)), res_type))
+        if gnn_model == "graphsage" and res_type != "Bi":
+            raise ValueError("res_type selects the aggregator of gnn_model='kgat'; gnn_model='graphsage' takes none "
+                             "(got res_type=%r)" % (res_type,))
         self._gnn_model = gnn_model
+        self._res_type = res_type
         self._n_entities, self._n_relations = n_entities, n_relations
         self._reg_lambda_gnn = reg_lambda_gnn
         self.entity_embed = nn.Embedding(n_entities, input_node_dim)
@@ -134,7 +179,7 @@ class KGATPropagation(nn.Module):
                 self.layers.append(SAGEConv(d_in, n_hidden // int(math.pow(2, i)), aggregator_type="mean",
                                             feat_drop=dropout, activation=act))
             else:
-                self.layers.append(KGATConv(d_in, n_hidden // int(math.pow(2, i)), dropout))
+                self.layers.append(KGATConv(d_in, n_hidden // int(math.pow(2, i)), dropout, res_type))
 
     # -- attention (models.py:135-154)
     def _att_score(self, edges):
@@ -164,6 +209,10 @@ class KGATPropagation(nn.Module):
     def gnn(self, g, x=None, fused=None):
         if self._sage_stack():
             return self._gnn_sage(g, fused)
+        if g.partition is not None and any(_layer_dense(layer)[0] != FORMS["Bi"] for layer in self.layers):
+            from .graph import DGLError
+            raise DGLError("res_type %r on a partitioned graph: sharded models run the Bi aggregator only"
+                           % (self._res_type,))
         auto = fused is None
         if auto:
             fused = not torch.is_grad_enabled()
@@ -175,8 +224,9 @@ class KGATPropagation(nn.Module):
             from .autograd import gnn_train
             p = self.layers[0].mess_drop.p if self.training else 0.0
             seed = int(torch.empty((), dtype=torch.int64).random_()) if p > 0 else 0
-            return gnn_train(g, self._node_embeddings(g), [layer.res_fc_2.weight for layer in self.layers],
-                             0.01, p, seed)
+            dense = [_layer_dense(layer) for layer in self.layers]
+            return gnn_train(g, self._node_embeddings(g), [d[1] for d in dense], 0.01, p, seed,
+                             forms=[d[0] for d in dense])
         if auto and g.partition is not None and torch.is_grad_enabled() and self._can_fuse_training(g, sharded=True):
             return self._gnn_train_sharded(g)
         g = g.local_var()
@@ -213,10 +263,13 @@ class KGATPropagation(nn.Module):
         if not all(isinstance(layer, KGATConv) or hasattr(layer, "res_fc_2") for layer in self.layers):
             return False
         w = self.entity_embed.weight
+        dense = [_layer_dense(layer) for layer in self.layers]
+        if sharded and any(d[0] != FORMS["Bi"] for d in dense):
+            return False
         return ((g.partition is None) != sharded and w.is_cuda and w.dtype == torch.float32 and "w" in g.edata and
                 not g.edata["w"].requires_grad and
-                all(ops.bi_interaction_supported(layer.res_fc_2.in_features, layer.res_fc_2.out_features) and
-                    layer.mess_drop.p < 1.0 for layer in self.layers))
+                all(ops.aggregator_supported(form, d_in, d_out) and layer.mess_drop.p < 1.0
+                    for layer, (form, _, d_in, d_out) in zip(self.layers, dense)))
 
     def _node_embeddings(self, g):
         """entity_embed(g.ndata['id']) (models.py:159); the reference's ids are arange(N)
@@ -236,15 +289,16 @@ class KGATPropagation(nn.Module):
         if not all(isinstance(layer, KGATConv) or hasattr(layer, "res_fc_2") for layer in self.layers):
             return False
         drop_off = all((not layer.training) or layer.mess_drop.p == 0 for layer in self.layers)
-        return drop_off and all(ops.bi_interaction_supported(layer.res_fc_2.in_features, layer.res_fc_2.out_features)
-                                for layer in self.layers)
+        return drop_off and all(ops.aggregator_supported(form, d_in, d_out)
+                                for form, _, d_in, d_out in map(_layer_dense, self.layers))
 
     def _gnn_fused(self, g):
         """No-grad fast path: aggregation with the h*h_N epilogue, then one kernel per layer for
         Linear + LeakyReLU + the L2-normalised copy written into its slice of the output."""
         from . import ops
         h = self._node_embeddings(g).detach()
-        widths = [h.shape[1]] + [layer.res_fc_2.out_features for layer in self.layers]
+        dense = [_layer_dense(layer) for layer in self.layers]
+        widths = [h.shape[1]] + [d[3] for d in dense]
         out = torch.empty((h.shape[0], sum(widths)), dtype=torch.float32, device=h.device)
         h0 = h
         off = widths[0]
@@ -264,23 +318,25 @@ class KGATPropagation(nn.Module):
         fuse_bi = options.fuse_bi
         # KGAT_GNN_MUL_IN_SPMM=1: rounds 1-3's split - h * h_N in the aggregation's epilogue (A/B)
         mul_in_spmm = options.gnn_mul_in_spmm
+        # (both compute the product: a GCN / GraphSage layer skips them and takes the aggregator kernel below)
         defer = options.gnn_defer_finish
         st = g._st
         scratch = None
-        for li, layer in enumerate(self.layers):
+        for li, (form, W, _, _) in enumerate(dense):
             last = li + 1 == len(self.layers)
             norm_out = out[:, off:off + widths[li + 1]]
-            if (fuse_bi and ops.spmm_bi_fused_supported(widths[li], widths[li + 1]) and off % 4 == 0 and
+            bi = form == FORMS["Bi"]
+            if (bi and fuse_bi and ops.spmm_bi_fused_supported(widths[li], widths[li + 1]) and off % 4 == 0 and
                     out.shape[1] % 4 == 0 and h.shape[0] > 0):
                 csr = st.csr(h.device)
                 if scratch is None or scratch.shape[1] != widths[li]:
                     scratch = torch.empty((h.shape[0], widths[li]), dtype=torch.float32, device=h.device)
                 h = ops.spmm_bi_fused(csr.indptr, csr.col, csr.row_of, h.contiguous(), st.csr_weights(w),
-                                      layer.res_fc_2.weight.detach(), 0.01, norm_out=norm_out, want_h=not last,
+                                      W.detach(), 0.01, norm_out=norm_out, want_h=not last,
                                       scratch=scratch, self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
                 off += widths[li + 1]
                 continue
-            if not mul_in_spmm:
+            if not (bi and mul_in_spmm):
                 # the plain aggregation, and h * h_N formed by the dense kernel while it loads its rows (+ the ego
                 # block of the readout from the rows of layer 0's input): round 4 - the aggregation's h * h_N
                 # epilogue is a dependent X[v] load per finished row inside its edge loop, 91 vs 78 us per launch
@@ -292,15 +348,13 @@ class KGATPropagation(nn.Module):
                     csr = st.csr(h.device)
                     hc = h.contiguous()
                     hn, rows_left = ops.spmm(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), defer_finish=True)
-                    h = ops.bi_interaction_mul(hc, hn, layer.res_fc_2.weight.detach(), 0.01, norm_out=norm_out,
-                                               want_h=not last, deferred=rows_left,
-                                               self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
+                    h = ops.aggregator(form, hc, hn, W.detach(), 0.01, norm_out=norm_out, want_h=not last,
+                                       deferred=rows_left, self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
                     off += widths[li + 1]
                     continue
                 hn = u_mul_e_sum(g, h, w)
-                h = ops.bi_interaction_mul(h.contiguous(), hn, layer.res_fc_2.weight.detach(), 0.01, norm_out=norm_out,
-                                           want_h=not last,
-                                           self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
+                h = ops.aggregator(form, h.contiguous(), hn, W.detach(), 0.01, norm_out=norm_out, want_h=not last,
+                                   self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
                 off += widths[li + 1]
                 continue
             if li == 0 and copy_self:
@@ -309,7 +363,7 @@ class KGATPropagation(nn.Module):
                                 self_out=out[:, :widths[0]])
             else:
                 prod = u_mul_e_sum(g, h, w, mul_self=True)
-            h = ops.bi_interaction(prod, layer.res_fc_2.weight.detach(), 0.01, norm_out=norm_out, want_h=not last)
+            h = ops.bi_interaction(prod, W.detach(), 0.01, norm_out=norm_out, want_h=not last)
             off += widths[li + 1]
         # the ego-embedding block last: the pass ends having just touched the embedding table, which
         # is what the next attention refresh gathers from (a step's working set is about the size

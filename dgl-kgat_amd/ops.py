@@ -976,6 +976,120 @@ def bi_interaction_bwd_weight(grad_z, H, HN, want_partials=False):
     return partials if want_partials else partials.sum(0)
 
 
+# The KGAT layer's aggregators (KGATConv res_type; include/kgat_hip.h KGAT_FORM_*): Bi-Interaction LeakyReLU(W (h * h_N)),
+# GCN LeakyReLU(W (h + h_N)), GraphSage LeakyReLU(W [h | h_N]) - W is d_out x 2 d_in for GraphSage.
+FORMS = {"Bi": 0, "GCN": 1, "GraphSage": 2}
+
+
+def aggregator_supported(form, d_in, d_out):
+    """The widths the form's forward kernels cover (kgat_aggregator_supported)."""
+    return bool(_lib.load().kgat_aggregator_supported(int(form), int(d_in), int(d_out)))
+
+
+def aggregator_bwd_supported(form, d_in, d_out):
+    """The widths the form's backward kernels cover (kgat_aggregator_bwd_supported)."""
+    return bool(_lib.load().kgat_aggregator_bwd_supported(int(form), int(d_in), int(d_out)))
+
+
+def _form_weight(form, W, d_in):
+    W = _need(W, torch.float32, "W")
+    k = 2 * d_in if form == FORMS["GraphSage"] else d_in
+    if W.dim() != 2 or W.shape[1] != k:
+        raise ValueError("W has shape %s, expected (*, %d) for form %d" % (tuple(W.shape), k, form))
+    return W, W.shape[0]
+
+
+def _agg_timed(form, n, d_in, d_out):
+    # (Bi under the name and key of its own entries: KernelTimer summaries read the same with either call path)
+    return _timed("bi_interaction", (n, d_in, d_out)) if form == FORMS["Bi"] else _timed("aggregator", (form, n, d_in, d_out))
+
+
+def aggregator(form, H, HN, W, negative_slope=0.01, h_out=None, norm_out=None, want_h=True, self_out=None,
+               deferred=None):
+    """Z = leaky_relu(combine(H, HN) @ W^T) with combine = H * HN (form 0, the bits of bi_interaction_mul), H + HN (1) or
+    [H | HN] (2) (kgat_aggregator_f32 / kgat_aggregator_deferred_f32); arguments as bi_interaction_mul."""
+    H = _need(H, torch.float32, "H")
+    HN = _need(HN, torch.float32, "HN", H.shape)
+    n, d_in = H.shape
+    W, d_out = _form_weight(form, W, d_in)
+    if want_h and h_out is None:
+        h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
+    if h_out is not None:
+        h_out = _need(h_out, torch.float32, "h_out", (n, d_out))
+    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
+    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    with _agg_timed(form, n, d_in, d_out):
+        if deferred is not None:
+            if deferred.n_rows != n or deferred.D != d_in:
+                raise ValueError("deferred rows of a (%d, %d) aggregation with a (%d, %d) input" % (deferred.n_rows, deferred.D, n, d_in))
+            check(_lib.load().kgat_aggregator_deferred_f32(
+                int(form), n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W), float(negative_slope), _ptr(h_out), _ptr(norm_out),
+                stride, _ptr(self_out), self_stride, _ptr(deferred.indptr_rows), deferred.e_range[0], deferred.e_range[1],
+                _ptr(deferred.workspace), deferred.tile_edges, _stream(H)), "kgat_aggregator_deferred_f32")
+        else:
+            check(_lib.load().kgat_aggregator_f32(int(form), n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W),
+                                                  float(negative_slope), _ptr(h_out), _ptr(norm_out), stride,
+                                                  _ptr(self_out), self_stride, _stream(H)), "kgat_aggregator_f32")
+    return h_out
+
+
+def aggregator_train(form, H, HN, W, negative_slope, drop_p, seed, norm_out=None, row0=0, self_out=None):
+    """Training form of `aggregator` (kgat_aggregator_train_f32): as bi_interaction_train for any form."""
+    H = _need(H, torch.float32, "H")
+    HN = _need(HN, torch.float32, "HN", H.shape)
+    n, d_in = H.shape
+    W, d_out = _form_weight(form, W, d_in)
+    h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
+    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
+    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    with _agg_timed(form, n, d_in, d_out):
+        check(_lib.load().kgat_aggregator_train_f32(int(form), n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W),
+                                                    float(negative_slope), float(drop_p), int(seed) & (2 ** 64 - 1),
+                                                    int(row0), _ptr(h_out), _ptr(norm_out), stride, _ptr(self_out),
+                                                    self_stride, _stream(H)), "kgat_aggregator_train_f32")
+    return h_out
+
+
+def aggregator_bwd_input(form, grad_z, W, H, HN):
+    """(grad_agg, grad_self) of the form's dense part (kgat_aggregator_bwd_input_f32): what the reversed-CSR aggregation
+    sums and what goes to h directly - (grad_P * H, grad_P * HN) for Bi, (grad_P, grad_P) - one tensor - for GCN,
+    (grad_P[:, d_in:], grad_P[:, :d_in]) for GraphSage, grad_P = grad_z @ W."""
+    grad_z = _need(grad_z, torch.float32, "grad_z")
+    n, d_out = grad_z.shape
+    H = _need(H, torch.float32, "H")
+    d_in = H.shape[1]
+    W, _ = _form_weight(form, W, d_in)
+    if W.shape[0] != d_out:
+        raise ValueError("W has shape %s, expected (%d, *)" % (tuple(W.shape), d_out))
+    H = _need(H, torch.float32, "H", (n, d_in))
+    HN = _need(HN, torch.float32, "HN", (n, d_in))
+    t = torch.empty_like(H)
+    gb = t if form == FORMS["GCN"] else torch.empty_like(H)
+    check(_lib.load().kgat_aggregator_bwd_input_f32(int(form), n, d_in, d_out, _ptr(grad_z), _ptr(W), _ptr(H), _ptr(HN),
+                                                    _ptr(t), _ptr(None if gb is t else gb), _stream(H)),
+          "kgat_aggregator_bwd_input_f32")
+    return t, gb
+
+
+def aggregator_bwd_weight(form, grad_z, H, HN, want_partials=False):
+    """grad_W of the form's dense part (kgat_aggregator_bwd_weight_f32's partials, d_out x 2 d_in for GraphSage; summed
+    here in index order - or, want_partials=True, handed back for sum_partials)."""
+    grad_z = _need(grad_z, torch.float32, "grad_z")
+    n, d_out = grad_z.shape
+    H = _need(H, torch.float32, "H")
+    d_in = H.shape[1]
+    if H.shape[0] != n:
+        raise ValueError("H has %d rows, grad_z %d" % (H.shape[0], n))
+    HN = _need(HN, torch.float32, "HN", (n, d_in))
+    lib = _lib.load()
+    nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
+    k = 2 * d_in if form == FORMS["GraphSage"] else d_in
+    partials = torch.empty((nb, d_out, k), dtype=torch.float32, device=H.device)
+    check(lib.kgat_aggregator_bwd_weight_f32(int(form), n, d_in, d_out, _ptr(grad_z), _ptr(H), _ptr(HN), _ptr(partials),
+                                             nb, _stream(H)), "kgat_aggregator_bwd_weight_f32")
+    return partials if want_partials else partials.sum(0)
+
+
 def mul2(a, b, c):
     """(a * b, a * c) in one pass."""
     a = _need(a, torch.float32, "a")
@@ -1065,6 +1179,8 @@ def sddmm_dot(src, dst, X, G):
 __all__ = ["csr_from_coo", "group_by_relation", "invert_permutation", "row_order_by_degree", "gather",
            "att_score", "att_score_split", "att_score_split_supported", "att_score_folded_supported", "att_score_fused", "att_pack_records", "att_score_fused_supported", "fold_tiles", "fold_tile_cost", "bi_interaction_train", "add3_rows", "bi_interaction_bwd_pre", "bi_interaction_bwd_input", "bi_interaction_bwd_input_supported", "bi_interaction_bwd_weight", "sum_partials", "mul2", "dropout_keep_mask", "transr_loss_grad", "transr_supported", "transr_presort", "transr_adam_step", "TransRAdamState", "head_groups", "edge_softmax", "edge_softmax_bwd", "spmm", "spmm_workspace", "sddmm_dot",
            "bi_interaction", "bi_interaction_supported", "l2_normalize_rows", "readout_concat",
+           "FORMS", "aggregator", "aggregator_supported", "aggregator_bwd_supported", "aggregator_train",
+           "aggregator_bwd_input", "aggregator_bwd_weight",
            "KGATLibraryError"]
 
 

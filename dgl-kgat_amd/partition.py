@@ -362,6 +362,10 @@ class GraphedForward:
                 attention(state)
                 state["out"] = model.gnn(g)
             return [(whole, None)]
+        if not all(hasattr(layer, "res_fc_2") for layer in layers):
+            from .graph import DGLError
+            raise DGLError("a partitioned graph runs the Bi aggregator only (res_type %r)"
+                           % (getattr(model, "_res_type", None),))
         widths = [model.entity_embed.weight.shape[1]] + [layer.res_fc_2.out_features for layer in layers]
         stretches = []
         for li, layer in enumerate(layers):

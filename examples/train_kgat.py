@@ -121,7 +121,7 @@ def user_dict(pairs, item_offset):
     return {int(u): p[s:e, 1] - item_offset for u, s, e in zip(users, start, list(start[1:]) + [len(p)])}
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_dir", default=None)
     ap.add_argument("--synthetic", type=float, default=0.01, help="scale of the synthetic amazon-book-shaped CKG")
@@ -133,6 +133,9 @@ def main(argv=None):
     ap.add_argument("--gnn_hidden_size", type=int, default=64)
     ap.add_argument("--gnn_model", choices=("kgat", "graphsage"), default="kgat",
                     help="propagation layers (reference kgat.py:23): bi-interaction KGATConv or SAGEConv (mean)")
+    ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage"), default="Bi",
+                    help="aggregator of the kgat layers (KGATConv res_type, reference models.py:50-58): Bi-Interaction "
+                         "(the reference's), GCN or GraphSage")
     ap.add_argument("--dropout_rate", type=float, default=0.1)
     ap.add_argument("--lr", type=float, default=0.0001)
     ap.add_argument("--batch_size", type=int, default=10240)
@@ -145,6 +148,16 @@ def main(argv=None):
     ap.add_argument("--grad_digest", action="store_true",
                     help="print |grad| sums of the first CF step (to compare an N-GPU run with the one-GPU run)")
     args = ap.parse_args(argv)
+    # (before --gpus starts its ranks: a refused combination fails once, here)
+    if args.res_type != "Bi" and args.gnn_model != "kgat":
+        ap.error("--res_type %s selects the aggregator of --gnn_model kgat; graphsage takes none" % args.res_type)
+    if args.res_type != "Bi" and args.gpus > 1:
+        ap.error("--res_type %s runs on one GPU: sharded models run the Bi aggregator only" % args.res_type)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import socket
         import subprocess
@@ -174,7 +187,7 @@ def main(argv=None):
         ds.n_users, ds.n_items, ds.n_KG_entity, ds.n_KG_relation, len(ds.train_KG_triplet)))
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
-                              gnn_model=args.gnn_model).to(dev)
+                              gnn_model=args.gnn_model, res_type=args.res_type).to(dev)
     K.enable_lazy_edge_weights()   # the attention refresh hands back its edge-id-ordered copy unwritten (nothing here reads it)
 
     def replicas_agree(tag):

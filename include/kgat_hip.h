@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define KGAT_ABI_VERSION 11
+#define KGAT_ABI_VERSION 12
 
 enum {
   KGAT_OK = 0,
@@ -83,6 +83,14 @@ enum {
 enum {
   KGAT_REDUCE_SUM = 0,
   KGAT_REDUCE_MEAN = 1
+};
+
+/* the aggregator of a KGAT layer (res_type of KGATConv, reference models.py:50-58; the KGAT paper's "Information
+ * Aggregation": Bi-Interaction, GCN, GraphSage) - the `form` argument of the kgat_aggregator_* entries */
+enum {
+  KGAT_FORM_BI = 0,        /* LeakyReLU(W (h * h_N)), W = res_fc_2.weight (d_out x d_in) */
+  KGAT_FORM_GCN = 1,       /* LeakyReLU(W (h + h_N)), W = res_fc.weight (d_out x d_in) */
+  KGAT_FORM_GRAPHSAGE = 2  /* LeakyReLU(W [h | h_N]), W = res_fc.weight (d_out x 2 d_in): columns [0, d_in) act on h */
 };
 
 /* activation of kgat_sage_dense_f32 */
@@ -472,6 +480,50 @@ int kgat_sum_partials_f32(int n_sets, const float* const* partials_host, float* 
 /* ab = a * b and ac = a * c elementwise in one pass (n a multiple of 4). */
 int kgat_mul2_f32(int64_t n, const float* a, const float* b, const float* c, float* ab, float* ac,
                   kgat_stream_t stream);
+
+/* ---------------------------------------------------------------- the KGAT layer's three aggregators
+ * The entries above for any `form` (KGAT_FORM_*), i.e. the dense part of KGATConv with res_type "Bi", "GCN" or
+ * "GraphSage" - the KGAT paper's three aggregators (Wang et al. 2019, "Information Aggregation", eqs. 6-8), whose hook
+ * the reference keeps in KGATConv.__init__ (models.py:50-58: res_type, the commented-out res_fc of :55):
+ *   GCN:        Z = LeakyReLU_slope((H + HN) W^T),      W = res_fc.weight   (d_out x d_in)
+ *   GraphSage:  Z = LeakyReLU_slope([H | HN] W^T),      W = res_fc.weight   (d_out x 2 d_in; columns [0, d_in) act on H)
+ *   Bi:         Z = LeakyReLU_slope((H * HN) W^T),      W = res_fc_2.weight (d_out x d_in)
+ * HN = update_all(u_mul_e('h','w','m'), sum('m','h_neighbor')) as for Bi (models.py:63).  KGAT_FORM_BI runs the very
+ * kernels of the kgat_bi_interaction_* entries (same bits, same launches).  Widths (kgat_aggregator_supported): Bi as
+ * kgat_bi_interaction_supported; GCN and GraphSage d_in, d_out in {16, 32, 64, 128} (others: KGAT_E_UNSUPPORTED - a
+ * caller forms those in a library GEMM).
+ * kgat_aggregator_f32 / _deferred_f32 / _train_f32: the arguments, outputs and bits of kgat_bi_interaction_mul_f32 /
+ * _mul_deferred_f32 / _train_f32 with W in W2's place (the no-grad layer, the same with the aggregation's second
+ * launch left to it, the training form with LeakyReLU, hash dropout, normalised slice and ego block). */
+int kgat_aggregator_supported(int form, int d_in, int d_out);
+int kgat_aggregator_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W,
+                        float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
+                        int64_t self_stride, kgat_stream_t stream);
+int kgat_aggregator_deferred_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
+                                 const float* W, float negative_slope, float* h_out, float* norm_out,
+                                 int64_t norm_stride, float* self_out, int64_t self_stride, const int32_t* indptr_rows,
+                                 int64_t e_begin, int64_t e_end, const void* spmm_workspace, int tile_edges,
+                                 kgat_stream_t stream);
+int kgat_aggregator_train_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
+                              const float* W, float negative_slope, float drop_p, uint64_t seed, int64_t row0,
+                              float* h_out, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
+                              kgat_stream_t stream);
+/* Backward of the dense part towards its inputs (the layer under autograd), from grad_z (n_rows x d_out,
+ * kgat_bi_interaction_bwd_pre_f32); grad_P = grad_z W is formed per 16-row tile and
+ *   Bi:        grad_agg = grad_P * H, grad_self = grad_P * HN     (= kgat_bi_interaction_bwd_input_f32)
+ *   GCN:       grad_agg = grad_P (the gradient through h_N and through h alike; grad_self unused, may be NULL)
+ *   GraphSage: grad_agg = grad_P[:, d_in:2 d_in] (the h_N half), grad_self = grad_P[:, 0:d_in] (the h half)
+ * grad_agg is what the reversed-CSR aggregation then sums; grad_self goes to h directly (both n_rows x d_in).  H and
+ * HN are read for Bi only.  Widths (kgat_aggregator_bwd_supported): d_in, d_out in {16, 32, 64, 128}. */
+int kgat_aggregator_bwd_supported(int form, int d_in, int d_out);
+int kgat_aggregator_bwd_input_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W,
+                                  const float* H, const float* HN, float* grad_agg, float* grad_self,
+                                  kgat_stream_t stream);
+/* grad_W = grad_z^T (H * HN) (Bi), grad_z^T (H + HN) (GCN), grad_z^T [H | HN] (GraphSage: d_out x 2 d_in) as per-workgroup
+ * partials, as kgat_bi_interaction_bwd_weight_f32: partials[b] is d_out x d_in (d_out x 2 d_in for GraphSage),
+ * n_partials = kgat_bi_interaction_bwd_weight_partials(n_rows), the caller adds them (kgat_sum_partials_f32). */
+int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
+                                   const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- GraphSAGE layer (gnn_model = "graphsage")
  * The kernels behind dgl.nn.pytorch.conv.SAGEConv(d_in, d_out, aggregator_type="mean", feat_drop, activation) of

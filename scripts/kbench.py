@@ -6,6 +6,8 @@ path or of bench.py's contract).  Interleaved rounds in one process, HIP events 
   python scripts/kbench.py spmm  [--algos merge,rows,rows_ordered] [--dim 64]
   python scripts/kbench.py softmax
   python scripts/kbench.py sage    (GraphSAGE layer launches beside the KGAT layer's, and the CF step of both models)
+  python scripts/kbench.py agg     (the KGAT layer per res_type - Bi, GCN, GraphSage - interleaved: no-grad layer,
+                                    backward launches, CF step)
 """
 import argparse
 import os
@@ -37,7 +39,7 @@ def timeit(fns, rounds, warm=3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("kernel", choices=["att", "spmm", "softmax", "train", "kg", "sage"])
+    ap.add_argument("kernel", choices=["att", "spmm", "softmax", "train", "kg", "sage", "agg"])
     ap.add_argument("--algos", default=None)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=20)
@@ -237,6 +239,69 @@ def main():
                 res[gm].append(time.perf_counter() - t0)
         for gm, v in res.items():
             print("CF step (fwd+bwd+Adam, 3 layers, batch %d) gnn_model=%-9s median %.3f ms" % (B, gm, 1e3 * float(np.median(v))))
+    elif args.kernel == "agg":
+        # KGATConv's three aggregators (res_type): per form the no-grad layer (aggregation + dense kernel with the
+        # normalised slice), its dense kernel alone, and the dense part's backward launches (bwd_input + bwd_weight),
+        # interleaved with Bi's; then the CF step of the three models, alternating
+        import time
+        import dgl_kgat_amd as K
+        forms = ops.FORMS
+        w = torch.rand(E, device=dev)
+        print("agg: N = %d, E = %d, median of %d interleaved rounds (ms)" % (n, E, args.rounds))
+        for di, do in ((64, 64), (64, 32), (32, 16)):
+            torch.manual_seed(0)
+            X = torch.randn(n, di, device=dev)
+            HN = ops.spmm(indptr, col, row_of, X, w)
+            GZ = torch.randn(n, do, device=dev)
+            norm = torch.empty(n, do, device=dev)
+            ws = ops.spmm_workspace(E, di, dev)
+            fns = {}
+            for name, f in forms.items():
+                W = torch.randn(do, di * (2 if name == "GraphSage" else 1), device=dev) * 0.1
+                fns[name + ".layer"] = (lambda f=f, W=W: ops.aggregator(
+                    f, X, ops.spmm(indptr, col, row_of, X, w, workspace=ws), W, 0.01, norm_out=norm))
+                fns[name + ".dense"] = lambda f=f, W=W: ops.aggregator(f, X, HN, W, 0.01, norm_out=norm)
+                fns[name + ".bwd_input"] = lambda f=f, W=W: ops.aggregator_bwd_input(f, GZ, W, X, HN)
+                fns[name + ".bwd_weight"] = lambda f=f: ops.aggregator_bwd_weight(f, GZ, X, HN, want_partials=True)
+            t = timeit(fns, args.rounds)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print("%d -> %d" % (di, do))
+            for k, v in med.items():
+                print("   %-22s %.4f   (x %.3f of Bi)" % (k, v, v / med["Bi." + k.split(".", 1)[1]]))
+        B = 10240
+        u = torch.randint(0, 70679, (B,), device=dev).int()
+        pi = torch.randint(70679, 95594, (B,), device=dev).int()
+        ni = torch.randint(70679, 95594, (B,), device=dev).int()
+        graph = synth.build_graph(n, trip, dev)
+        steps = {}
+        for rt in forms:
+            torch.manual_seed(0)
+            model = K.KGATPropagation(n, R, D, D, 3, D, dropout=0.1, res_type=rt).to(dev)
+            opt = K.FusedAdam(model.parameters(), lr=0.01)
+            with torch.no_grad():
+                graph.edata["w"] = model.compute_attention(graph)
+
+            def step(model=model, opt=opt):
+                loss = model.get_loss(model.gnn(graph), u, pi, ni)
+                loss.backward()
+                opt.step()
+                opt.zero_grad()
+            steps[rt] = step
+        res = {rt: [] for rt in steps}
+        for _ in range(3):
+            for f in steps.values():
+                f()
+        for _ in range(args.rounds):
+            for rt, f in steps.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                res[rt].append(time.perf_counter() - t0)
+        med = {rt: 1e3 * float(np.median(v)) for rt, v in res.items()}
+        for rt, v in med.items():
+            print("CF step (fwd+bwd+Adam, 3 layers, batch %d) res_type=%-9s median %.3f ms  (x %.3f of Bi)"
+                  % (B, rt, v, v / med["Bi"]))
     elif args.kernel == "train":
         # the CF step of kgat.py:146-168: gnn (all layers, full graph) -> BPR loss -> backward -> Adam
         import time
