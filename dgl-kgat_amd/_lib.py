@@ -134,6 +134,17 @@ SIGNATURES = {
     "kgat_aggregator_bwd_supported": (_i32, [_i32, _i32, _i32]),
     "kgat_aggregator_bwd_input_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "kgat_aggregator_bwd_weight_f32": (_i32, [_i32, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _p]),
+    "kgat_bi2_supported": (_i32, [_i32, _i32]),
+    "kgat_bi2_bwd_supported": (_i32, [_i32, _i32]),
+    "kgat_bi2_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, C.c_float, _p, _p, _i64, _p, _i64, _p]),
+    "kgat_bi2_deferred_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, C.c_float, _p, _p, _i64, _p, _i64, _p, _i64, _i64,
+                                     _p, _i32, _p]),
+    "kgat_bi2_train_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, C.c_float, C.c_float, C.c_uint64, _i64, _p, _p, _p,
+                                  _i64, _p, _i64, _p]),
+    "kgat_bi2_bwd_pre_f32": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_uint64, _i64, _p, _p,
+                                    _p]),
+    "kgat_bi2_bwd_input_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "kgat_bi2_bwd_weight_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "kgat_eval_recall_ndcg_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p,
                                          _p, _p, _p]),
 }
@@ -154,7 +165,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def source_hash():

@@ -215,7 +215,10 @@ class _GNNTrain(torch.autograd.Function):
     dense GEMMs, one two-product pass and the SpMM on the reversed CSR.  Gradients: the input
     embeddings and every W2; the edge weights are constants (kgat.py:139-145).
     `forms`: each layer's aggregator (ops.FORMS: the product of Bi, the sum of GCN, the concatenation of GraphSage -
-    KGATConv's res_type); the backward is routed by it, its structure is the same for all three."""
+    KGATConv's res_type); the backward is routed by it, its structure is the same for all three.  ops.BI2_FORM: the
+    paper's two-term Bi-Interaction - such a layer has TWO weights in `weights` (W1 on h + h_N, then W2 on h * h_N), its
+    forward also saves the sign record, its backward head writes two gradients, and its backward towards the inputs
+    still ends in ONE reversed aggregation."""
 
     @staticmethod
     def forward(ctx, g, slope, drop_p, seed, forms, h0, *weights):
@@ -225,31 +228,43 @@ class _GNNTrain(torch.autograd.Function):
         csr = st.csr(dev)
         ew = g.edata["w"]
         w_csr = st.csr_weights(ew)
-        widths = [h.shape[1]] + [w.shape[0] for w in weights]
+        first = [0]  # layer li's weights: weights[first[li]:first[li + 1]]
+        for f in forms:
+            first.append(first[-1] + (2 if f == ops.BI2_FORM else 1))
+        widths = [h.shape[1]] + [weights[first[li]].shape[0] for li in range(len(forms))]
         out = torch.empty((h.shape[0], sum(widths)), dtype=torch.float32, device=dev)
         # the ego block (out[:, :d] = h0, models.py:159,168) is written by layer 0's dense kernel from the rows it loads
         # anyway (self_out) where the slice allows 16-byte stores; otherwise by a copy here
-        ego_in_kernel = len(weights) > 0 and widths[0] % 4 == 0 and out.shape[1] % 4 == 0 and h.shape[0] > 0
+        ego_in_kernel = len(forms) > 0 and widths[0] % 4 == 0 and out.shape[1] % 4 == 0 and h.shape[0] > 0
         if not ego_in_kernel:
             out[:, :widths[0]] = h
         off = widths[0]
-        hs, hns = [h], []
-        for li, w in enumerate(weights):
+        hs, hns, signs = [h], [], []
+        for li, form in enumerate(forms):
             hn = ops.spmm(csr.indptr, csr.col, csr.row_of, hs[-1], w_csr)
-            hs.append(ops.aggregator_train(forms[li], hs[-1], hn, w.detach().contiguous(), slope, drop_p, seed + li,
-                                           norm_out=out[:, off:off + widths[li + 1]],
-                                           self_out=out[:, :widths[0]] if (li == 0 and ego_in_kernel) else None))
+            lw = [w.detach().contiguous() for w in weights[first[li]:first[li + 1]]]
+            kw = dict(norm_out=out[:, off:off + widths[li + 1]],
+                      self_out=out[:, :widths[0]] if (li == 0 and ego_in_kernel) else None)
+            if form == ops.BI2_FORM:
+                y, sg = ops.bi2_train(hs[-1], hn, lw[0], lw[1], slope, drop_p, seed + li, **kw)
+                signs.append(sg)
+            else:
+                y = ops.aggregator_train(form, hs[-1], hn, lw[0], slope, drop_p, seed + li, **kw)
+            hs.append(y)
             hns.append(hn)
             off += widths[li + 1]
         ctx.g, ctx.slope, ctx.drop_p, ctx.seed, ctx.widths, ctx.ew, ctx.forms = g, slope, drop_p, seed, widths, ew, forms
-        ctx.save_for_backward(*hs, *hns, *weights)
+        ctx.first = first
+        ctx.save_for_backward(*hs, *hns, *weights, *signs)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         n_l = len(ctx.widths) - 1
         saved = ctx.saved_tensors
-        hs, hns, weights = saved[:n_l + 1], saved[n_l + 1:2 * n_l + 1], saved[2 * n_l + 1:]
+        first = ctx.first
+        hs, hns, weights = saved[:n_l + 1], saved[n_l + 1:2 * n_l + 1], saved[2 * n_l + 1:2 * n_l + 1 + first[-1]]
+        signs = list(saved[2 * n_l + 1 + first[-1]:])  # the two-term layers' sign records, in layer order
         st = ctx.g._st
         dev = grad_out.device
         rev = st.csr_rev(dev)
@@ -259,21 +274,42 @@ class _GNNTrain(torch.autograd.Function):
         for wd in ctx.widths:
             offs.append(offs[-1] + wd)
         g_a = g_b = None  # the two addends of the gradient arriving at hs[li + 1] from the layer above
-        grad_w = [None] * n_l
-        pending = []
+        grad_w = [None] * first[-1]
+        pending = []  # (index into weights, that weight gradient's per-workgroup partials)
         for li in range(n_l - 1, -1, -1):
+            if ctx.forms[li] == ops.BI2_FORM:
+                wi = first[li]
+                gz1, gz2 = ops.bi2_bwd_pre(hs[li + 1], signs.pop(), g_a, g_b, grad_out[:, offs[li + 1]:offs[li + 2]],
+                                           ctx.slope, ctx.drop_p, ctx.seed + li)
+                kernels = ops.bi2_bwd_supported(hs[li].shape[1], gz1.shape[1])
+                w1, w2 = weights[wi].detach().contiguous(), weights[wi + 1].detach().contiguous()
+                if ctx.needs_input_grad[6 + wi] or ctx.needs_input_grad[7 + wi]:
+                    if kernels:
+                        p1, p2 = ops.bi2_bwd_weight(gz1, gz2, hs[li], hns[li], want_partials=True)
+                        pending += [(wi, p1), (wi + 1, p2)]
+                    else:
+                        grad_w[wi] = tall_weight_grad(gz1, hs[li] + hns[li])
+                        grad_w[wi + 1] = tall_weight_grad(gz2, hs[li] * hns[li])
+                if kernels:
+                    # P1 + P2 * h (to be aggregated) and P1 + P2 * h_N (to h directly), P1 = gz1 W1, P2 = gz2 W2 per tile
+                    t, g_b = ops.bi2_bwd_input(gz1, gz2, w1, w2, hs[li], hns[li])
+                else:
+                    p1, p2 = gz1 @ w1, gz2 @ w2
+                    t, g_b = p1 + p2 * hs[li], p1 + p2 * hns[li]
+                g_a = ops.spmm(rev.indptr, rev.col, rev.row_of, t, w_rev)
+                continue
             gz = ops.bi_interaction_bwd_pre(hs[li + 1], g_a, g_b, grad_out[:, offs[li + 1]:offs[li + 2]], ctx.slope,
                                             ctx.drop_p, ctx.seed + li)
             form, d_in = ctx.forms[li], hs[li].shape[1]
             kernels = ops.aggregator_bwd_supported(form, d_in, gz.shape[1])
-            if ctx.needs_input_grad[6 + li]:
+            if ctx.needs_input_grad[6 + first[li]]:
                 if kernels:
                     # grad_z^T (h * h_N) (h + h_N, [h | h_N]) as per-workgroup partials; every layer's set is summed by
                     # ONE launch at the end
-                    pending.append((li, ops.aggregator_bwd_weight(form, gz, hs[li], hns[li], want_partials=True)))
+                    pending.append((first[li], ops.aggregator_bwd_weight(form, gz, hs[li], hns[li], want_partials=True)))
                 else:
-                    grad_w[li] = tall_weight_grad(gz, _combine(form, hs[li], hns[li]))
-            w_l = weights[li].detach().contiguous()
+                    grad_w[first[li]] = tall_weight_grad(gz, _combine(form, hs[li], hns[li]))
+            w_l = weights[first[li]].detach().contiguous()
             if kernels:
                 # grad_P = grad_z W formed per tile: the part to be aggregated (grad_P * h for Bi) and the part that goes to
                 # h directly (grad_P * h_N)
@@ -287,8 +323,8 @@ class _GNNTrain(torch.autograd.Function):
                 t, g_b = gp[:, d_in:].contiguous(), gp[:, :d_in].contiguous()
             g_a = ops.spmm(rev.indptr, rev.col, rev.row_of, t, w_rev)
         if pending:
-            for (li, _), summed in zip(pending, ops.sum_partials([p_ for _, p_ in pending])):
-                grad_w[li] = summed
+            for (wi, _), summed in zip(pending, ops.sum_partials([p_ for _, p_ in pending])):
+                grad_w[wi] = summed
         grad_h0 = None
         if ctx.needs_input_grad[5]:
             g0 = grad_out[:, :ctx.widths[0]]
@@ -325,8 +361,17 @@ def tall_weight_grad(grad, x, slabs=128):
 
 def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0, forms=None):
     """Differentiable fused propagation stack; returns the (N, sum of widths) readout.  `forms`: one ops.FORMS value per
-    layer (default: Bi everywhere); a GraphSage layer's weight is (d_out, 2 d_in)."""
+    layer (default: Bi everywhere); a GraphSage layer's weight is (d_out, 2 d_in).  A two-term layer (ops.BI2_FORM) gives
+    its entry of `weights` as the pair (W1, W2) = (res_fc.weight, res_fc_2.weight)."""
     forms = tuple(int(f) for f in forms) if forms is not None else (ops.FORMS["Bi"],) * len(weights)
     if len(forms) != len(weights):
         raise ValueError("gnn_train: %d forms for %d layers" % (len(forms), len(weights)))
-    return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), forms, h0, *weights)
+    flat = []
+    for f, w in zip(forms, weights):
+        if f == ops.BI2_FORM:
+            if not (isinstance(w, (tuple, list)) and len(w) == 2):
+                raise ValueError("gnn_train: a two-term layer takes the pair (W1, W2)")
+            flat += list(w)
+        else:
+            flat.append(w)
+    return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), forms, h0, *flat)

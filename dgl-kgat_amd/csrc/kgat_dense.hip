@@ -88,297 +88,36 @@ constexpr int kDeferLongChain = 8;  // = spmm_finish_kernel's kLongChain
 // models.py:50-58).  0 = Bi-Interaction, h * h_N (res_fc_2, d_out x d_in).  1 = GCN, h + h_N (res_fc, d_out x d_in).
 // 2 = GraphSage, [h | h_N] along K (res_fc, d_out x 2 d_in): the first KS steps of the contraction take W's columns
 // [0, d_in) on the rows of h, the next KS its columns [d_in, 2 d_in) on the rows of h_N - nothing is formed.
-enum { kCombMul = 0, kCombSum = 1, kCombCat = 2 };
+// 3 = the paper's two-term Bi-Interaction ("Bi2", eq. 8): LeakyReLU((h + h_N) W1^T) + LeakyReLU((h * h_N) W2^T).  The
+// activation sits between the contraction and the sum, so the two products have accumulators of their own; both weights
+// are staged like the concatenation's W (k-steps [0, KS): W1 = res_fc on the sum, [KS, 2 KS): W2 = res_fc_2 on the
+// product); the sum and the product are formed in the registers of the two row sets.  The training form also writes
+// the SIGN RECORD the backward needs (the sign of the saved output no longer tells the two LeakyReLU' apart): one byte
+// per output element, bit 0 = (z1 > 0), bit 1 = (z2 > 0).
+// The kernel body (kgat_dense_body.h) is shared by two entry points: bi_interaction_kernel (the three one-weight forms,
+// signature and code as they were) and bi2_kernel (two weights and the sign record).
+enum { kCombMul = 0, kCombSum = 1, kCombCat = 2, kCombBi2 = 3 };
 template <int DI, int DO, int MODE, bool VEC_NORM, bool DEFER = false, int COMB = kCombMul>
 __global__ __launch_bounds__(256) void bi_interaction_kernel(
     int32_t n_rows, const float* __restrict__ P, const float* __restrict__ HN, const float* __restrict__ W2,
     float slope, uint32_t drop_threshold, float keep_scale, uint32_t seed, uint32_t index0,
     float* __restrict__ h_out, float* __restrict__ norm_out, int64_t norm_stride, const EgoCopy ego,
     const DeferredRows df) {
-  constexpr bool TRAIN = MODE == 2;
-  static_assert(!DEFER || (MODE == 1 && !kBiMulAtLoad), "the deferred rows go with the late product");
-  static_assert(COMB == kCombMul || (MODE >= 1 && !kBiMulAtLoad), "the sum and the concatenation need H and HN apart");
-  constexpr int KS = DI / 4, KT = DO / 16;
-  constexpr int DIW = COMB == kCombCat ? 2 * DI : DI, KSW = DIW / 4;  // W's columns, its k-steps
-  // W2 is staged once per workgroup through LDS (coalesced 16-byte reads of the whole matrix),
-  // laid out in B-fragment order so that every wave then pulls its fragments with
-  // conflict-free ds_read_b32: s_w[(s*KT + c)*64 + q*16 + i] = W2[16c + i][16*(s>>2) + 4q + (s&3)]
-  __shared__ float s_w[KSW * KT * kWave];
-  for (int idx = threadIdx.x * 4; idx < DO * DIW; idx += 256 * 4) {
-    const float4 v = *reinterpret_cast<const float4*>(W2 + idx);
-    const int j = idx / DIW, k0 = idx % DIW;  // four consecutive k of output column j
-    const int c = j >> 4, i = j & 15;
-    const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int k = k0 + t;
-      const int s = (k >> 4) * 4 + (k & 3), q = (k >> 2) & 3;
-      s_w[(s * KT + c) * kWave + q * 16 + i] = vv[t];
-    }
-  }
-  __syncthreads();
+  static_assert(COMB != kCombBi2, "the two-term form has its own entry point");
+  constexpr const float* W1 = nullptr;  // (the two-term form's)
+  constexpr uint8_t* signs = nullptr;
+#include "kgat_dense_body.h"
+}
 
-  const int lane = threadIdx.x % kWave;
-  const int i = lane & 15, q = lane >> 4;
-  const int64_t n_waves = (int64_t)gridDim.x * (256 / kWave);
-  // (the wavefront's index through readfirstlane: its tile range is then held in SGPRs and the tile loop's branches
-  // are scalar - as a per-lane value the loop was compiled as divergent control flow, exec-masked block by block)
-  const int64_t wv = (int64_t)blockIdx.x * (256 / kWave) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-  const int32_t n_tiles = (n_rows + 15) >> 4;
-  const int32_t t_begin = (int32_t)((int64_t)n_tiles * wv / n_waves);
-  const int32_t t_end = (int32_t)((int64_t)n_tiles * (wv + 1) / n_waves);
-  if (t_begin >= t_end) return;
-
-  // W2's fragments live in registers for the whole launch - except at 128 x 128, where they would
-  // need 256 VGPRs: there every MFMA takes its fragment from the LDS copy (one conflict-free
-  // ds_read_b32 each)
-constexpr int kBiWLdsAbove = 128;  // (A/B builds: 0 = fragments always from LDS, fewer registers, more wavefronts per SIMD)
-  // (the concatenation's W is twice as large: its fragments always come from LDS - held in registers they cost it
-  // occupancy against the product at every width, and spill at 128 -> 128; kernel-resource-usage)
-  constexpr bool W_IN_LDS = COMB == kCombCat || KS * KT > kBiWLdsAbove;
-  float wreg[W_IN_LDS ? 1 : KSW][W_IN_LDS ? 1 : KT];
-  if (!W_IN_LDS) {
-#pragma unroll
-    for (int s = 0; s < KSW; ++s)
-#pragma unroll
-      for (int c = 0; c < KT; ++c) wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c] = s_w[(s * KT + c) * kWave + lane];
-  }
-
-  // MODE >= 1: the rows of H and of HN are REQUESTED here and multiplied when the tile is computed (round 4, second
-  // form).  The first form multiplied here, which put the waits for both row sets - one after the other, the ego
-  // copy in between - into the load step: two exposed memory round trips per tile with nothing else of the
-  // wavefront in flight, and no overlap with the previous tile's matrix work whatever kBiPrefetch said
-  // (kBiMulAtLoad = true restores that form.)
-  constexpr bool LATE_MUL = MODE >= 1 && !kBiMulAtLoad;
-constexpr int kBiPrefetch = 2;
-  constexpr int PF = KS * kBiPrefetch <= 64 ? kBiPrefetch : (64 / KS >= 2 ? 64 / KS : 2);  // <= 64 VGPRs of rows in flight (x 2 with HN)
-  // DEFER: per stage, the offsets of the row this lane loads NEXT (requested one load step ahead), and what the load
-  // step found out for the tile step: nf = followers of the row's chain of tile partials (-1: a row without in-edges,
-  // 0: an ordinary row or a one-partial chain), bh = the chain's head tile
-  constexpr int LPR = DI / 4;
-  struct Defer { int32_t rb, re, nf, bh, slot; };
-  auto row_offsets = [&](int32_t t, Defer& d) {
-    int32_t ra = (t << 4) + i;
-    ra = ra < n_rows ? ra : n_rows - 1;
-    d.rb = df.indptr[ra];
-    d.re = df.indptr[ra + 1];
-  };
-  auto load_a = [&](int32_t t, float (&a)[KS], float (&b)[LATE_MUL ? KS : 1], Defer& d) {
-    int32_t ra = (t << 4) + i;
-    ra = ra < n_rows ? ra : n_rows - 1;
-    const float4* pa = reinterpret_cast<const float4*>(P + (size_t)ra * DI) + q;
-#pragma unroll
-    for (int m = 0; m < DI / 16; ++m) {
-      const float4 v = ld_row4<(kBiNtLoads & 1) != 0>(pa + m * 4);
-      a[4 * m + 0] = v.x; a[4 * m + 1] = v.y; a[4 * m + 2] = v.z; a[4 * m + 3] = v.w;
-    }
-    if constexpr (LATE_MUL) {
-      const float4* pb = reinterpret_cast<const float4*>(HN + (size_t)ra * DI) + q;
-      if constexpr (DEFER) {
-        // a row the aggregation's tiles left as partials: the head partial has an HN row's layout - it is requested
-        // in the row's place, the followers when the tile is computed
-        const int32_t rb = d.rb - df.e0, re = d.re - df.e0;
-        const int32_t te_mask = (1 << df.te_shift) - 1;
-        const int32_t bh = rb >> df.te_shift, bl = (re - 1) >> df.te_shift;
-        const bool empty = rb == re;
-        const bool lo_al = (rb & te_mask) == 0;
-        const bool partial = !empty && (bh != bl || lo_al || (re & te_mask) == 0 || d.re == df.e1);
-        if (partial) pb = df.bpart + ((size_t)bh * 2 + (lo_al ? 0 : 1)) * LPR + q;
-        d.nf = empty ? -1 : (partial ? bl - bh : 0);
-        d.bh = bh;
-        d.slot = lo_al ? 0 : 1;
-      }
-#pragma unroll
-      for (int m = 0; m < DI / 16; ++m) {
-        const float4 v = ld_row4<(kBiNtLoads & 2) != 0>(pb + m * 4);
-        b[4 * m + 0] = v.x; b[4 * m + 1] = v.y; b[4 * m + 2] = v.z; b[4 * m + 3] = v.w;
-      }
-      if constexpr (DEFER) row_offsets(t + PF, d);  // (clamped to the last row past the end)
-    } else if (MODE >= 1) {
-      if (MODE >= 1 && ego.out != nullptr && (t << 4) + i < n_rows) {
-        float4* pe = reinterpret_cast<float4*>(ego.out + (size_t)ra * ego.stride) + q;
-#pragma unroll
-        for (int m = 0; m < DI / 16; ++m) st_final4(pe + m * 4, make_float4(a[4 * m + 0], a[4 * m + 1], a[4 * m + 2], a[4 * m + 3]));
-      }
-      const float4* pb = reinterpret_cast<const float4*>(HN + (size_t)ra * DI) + q;
-#pragma unroll
-      for (int m = 0; m < DI / 16; ++m) {
-        const float4 v = ld_row4<(kBiNtLoads & 2) != 0>(pb + m * 4);
-        a[4 * m + 0] *= v.x; a[4 * m + 1] *= v.y; a[4 * m + 2] *= v.z; a[4 * m + 3] *= v.w;
-      }
-    }
-  };
-  auto tile = [&](int32_t t, float (&a)[KS], float (&b)[LATE_MUL ? KS : 1], const int32_t nf, const int32_t bh, const int32_t slot) {
-    const int32_t row0 = t << 4;
-    if constexpr (DEFER) {
-      if (__builtin_amdgcn_ballot_w64(nf != 0) != 0ull) {  // (uniform: about a third of the 16-row tiles)
-        const bool is_long = nf >= kDeferLongChain;
-        if (nf < 0) {
-#pragma unroll
-          for (int s = 0; s < KS; ++s) b[s] = 0.f;
-        } else if (nf > 0 && !is_long) {
-          // acc = head partial; acc += the followers' first-row partials, in tile order (spmm_finish_kernel)
-          const float4* pf = df.bpart + ((size_t)(bh + 1) * 2) * LPR + q;
-          for (int32_t k = 0; k < nf; ++k, pf += 2 * LPR) {
-#pragma unroll
-            for (int m = 0; m < DI / 16; ++m) {
-              const float4 v = pf[m * 4];
-              b[4 * m + 0] += v.x; b[4 * m + 1] += v.y; b[4 * m + 2] += v.z; b[4 * m + 3] += v.w;
-            }
-          }
-        }
-        // hub rows (a chain of more than kDeferLongChain tiles): the whole wavefront sums one row, as the finish
-        // launch does - lane group g = lane / LPR takes the tiles head + g, head + g + SPW, ..., a fixed shuffle
-        // tree adds the groups' sums - and hands the row to its four lanes
-        unsigned long long todo = __builtin_amdgcn_ballot_w64(is_long && q == 0);
-        if (todo) {
-          constexpr int SPW = kWave / LPR;
-          const int g = lane / LPR, sl = lane % LPR;
-          while (todo) {
-            const int src = __ffsll((long long)todo) - 1;  // (q == 0: the lane index is the row's i)
-            todo &= todo - 1;
-            const int32_t bo = __shfl(bh, src, kWave);
-            const int32_t bl = bo + __shfl(nf, src, kWave);
-            const int so = __shfl(slot, src, kWave);
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            int32_t bb = bo + g;
-            constexpr int U = 8;
-            for (; bb + (U - 1) * SPW <= bl; bb += U * SPW) {
-              float4 v[U];
-#pragma unroll
-              for (int u = 0; u < U; ++u) {
-                const int32_t tt = bb + u * SPW;
-                v[u] = df.bpart[((size_t)tt * 2 + ((tt == bo) ? so : 0)) * LPR + sl];
-              }
-#pragma unroll
-              for (int u = 0; u < U; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
-            }
-            for (; bb <= bl; bb += SPW) {
-              const float4 v = df.bpart[((size_t)bb * 2 + ((bb == bo) ? so : 0)) * LPR + sl];
-              acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-#pragma unroll
-            for (int off = LPR; off < kWave; off <<= 1) {
-              acc.x += __shfl_xor(acc.x, off, kWave); acc.y += __shfl_xor(acc.y, off, kWave);
-              acc.z += __shfl_xor(acc.z, off, kWave); acc.w += __shfl_xor(acc.w, off, kWave);
-            }
-            // every lane group now holds the row (lane sl: columns 4 sl .. 4 sl + 3); lane (i, q) takes 4 (4m + q)..
-#pragma unroll
-            for (int m = 0; m < DI / 16; ++m) {
-              const float x = __shfl(acc.x, 4 * m + q, kWave), y = __shfl(acc.y, 4 * m + q, kWave);
-              const float z = __shfl(acc.z, 4 * m + q, kWave), w = __shfl(acc.w, 4 * m + q, kWave);
-              if (i == src) { b[4 * m + 0] = x; b[4 * m + 1] = y; b[4 * m + 2] = z; b[4 * m + 3] = w; }
-            }
-          }
-        }
-      }
-    }
-    if constexpr (LATE_MUL) {
-      if (MODE >= 1 && ego.out != nullptr && row0 + i < n_rows) {
-        float4* pe = reinterpret_cast<float4*>(ego.out + (size_t)(row0 + i) * ego.stride) + q;
-#pragma unroll
-        for (int m = 0; m < DI / 16; ++m) st_final4(pe + m * 4, make_float4(a[4 * m + 0], a[4 * m + 1], a[4 * m + 2], a[4 * m + 3]));
-      }
-      if constexpr (COMB == kCombMul) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s) a[s] *= b[s];
-      } else if constexpr (COMB == kCombSum) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s) a[s] += b[s];
-      }
-    }
-    floatx4_d acc[KT];
-#pragma unroll
-    for (int c = 0; c < KT; ++c) acc[c] = (floatx4_d){0.f, 0.f, 0.f, 0.f};
-    // (the concatenation's fragments from LDS through an index the compiler cannot prove loop-invariant, so they are
-    // read per tile - left to itself it hoists the reads out of the tile loop into registers, up to 512 values per lane
-    // at 128 -> 128, and spills)
-    int wl = lane;
-    if constexpr (COMB == kCombCat && W_IN_LDS) asm volatile("" : "+v"(wl));
-    // operands swapped (A = W2 fragment, B = the tile's rows): the accumulators hold Z^T, i.e.
-    // acc[c][j] = Z[row0 + i][16c + 4q + j] - four consecutive columns per lane, so the results
-    // leave as 16-byte stores (a quarter of the store instructions of the row-major result)
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int c = 0; c < KT; ++c)
-        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-            W_IN_LDS ? s_w[(s * KT + c) * kWave + wl] : wreg[W_IN_LDS ? 0 : s][W_IN_LDS ? 0 : c], a[s], acc[c], 0, 0, 0);
-    if constexpr (COMB == kCombCat) {  // the h_N half of K: W's k-steps KS .. 2 KS - 1 on the rows of HN
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int c = 0; c < KT; ++c)
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-              W_IN_LDS ? s_w[((KS + s) * KT + c) * kWave + wl] : wreg[W_IN_LDS ? 0 : KS + s][W_IN_LDS ? 0 : c], b[s],
-              acc[c], 0, 0, 0);
-    }
-    const int32_t row = row0 + i;
-    // row norm: per 16-column tile the sum of squares over the row's four lanes (i, q = 0..3), then the tiles'
-    // partials in tile order - the order of the fused aggregation + dense launch (kgat_spmm_impl.h: tile_ssq),
-    // whose wavefronts each own one column tile, so the two paths give the same bits
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < KT; ++c) {
-      float part = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float z = acc[c][j];
-        z = z >= 0.f ? z : z * slope;
-        if (TRAIN)
-          z = drop_keep(seed, index0 + (uint32_t)row * (uint32_t)DO + (uint32_t)(16 * c + 4 * q + j), drop_threshold)
-                  ? z * keep_scale : 0.f;
-        acc[c][j] = z;
-        part = j == 0 ? z * z : fmaf(z, z, part);
-      }
-      part += __shfl_xor(part, 16, kWave);
-      part += __shfl_xor(part, 32, kWave);
-      ss = c == 0 ? part : ss + part;
-    }
-    const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);  // one division per row; the 4 x KT values are scaled by it
-    if (row < n_rows) {
-#pragma unroll
-      for (int c = 0; c < KT; ++c) {
-        const float z0 = acc[c][0], z1 = acc[c][1], z2 = acc[c][2], z3 = acc[c][3];
-        if (h_out) *reinterpret_cast<float4*>(h_out + (size_t)row * DO + 16 * c + 4 * q) = make_float4(z0, z1, z2, z3);
-        if (norm_out) {
-          float* dst = norm_out + (size_t)row * norm_stride + 16 * c + 4 * q;
-          if (VEC_NORM) {
-            st_final4(reinterpret_cast<float4*>(dst), make_float4(z0 * inv, z1 * inv, z2 * inv, z3 * inv));
-          } else {
-            dst[0] = z0 * inv; dst[1] = z1 * inv; dst[2] = z2 * inv; dst[3] = z3 * inv;
-          }
-        }
-      }
-    }
-  };
-
-  // Ring of PF stages: the rows of tile t + PF are requested once tile t is computed.  (Round 4 measured an explicit
-  // two-buffer loop, load t + 1 / compute t, with unconditional load steps against it: stand-alone faster at 64 -> 64
-  // (37.2 vs 38.9 us), slower at 32 -> 16 (14.8 vs 14.0); inside the step the ring wins, 0.4374 vs 0.4395 ms:
-  // profiles/r04_bi_late_mul_ab.txt; that form is in the history, commit c6eba96 and before.  Round 4 had
-  // also tried PF = 4, W2's fragments from LDS with 4 and 8 workgroups per CU and a 1,024-block grid:
-  // profiles/r04_bi_probe.txt - the launch runs at the rate of a device copy of its bytes.)
-  float a[PF][KS], b[PF][LATE_MUL ? KS : 1];
-  Defer d[PF];
-#pragma unroll
-  for (int p = 0; p < PF; ++p) {
-    d[p] = Defer{0, 0, 0, 0, 0};
-    if (DEFER) row_offsets(t_begin + p, d[p]);
-  }
-#pragma unroll
-  for (int p = 0; p < PF; ++p)
-    if (t_begin + p < t_end) load_a(t_begin + p, a[p], b[p], d[p]);
-  for (int32_t t = t_begin; t < t_end; t += PF) {
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-      if (t + p < t_end) {
-        // (nf / bh by value: the load step below overwrites the stage's record)
-        tile(t + p, a[p], b[p], d[p].nf, d[p].bh, d[p].slot);
-        if (t + p + PF < t_end) load_a(t + p + PF, a[p], b[p], d[p]);
-      }
-    }
-  }
+// The two-term Bi-Interaction (kCombBi2): W1 on h + h_N, W2 on h * h_N; MODE 2 writes the sign record.
+template <int DI, int DO, int MODE, bool VEC_NORM, bool DEFER = false>
+__global__ __launch_bounds__(256) void bi2_kernel(
+    int32_t n_rows, const float* __restrict__ P, const float* __restrict__ HN, const float* __restrict__ W1,
+    const float* __restrict__ W2, float slope, uint32_t drop_threshold, float keep_scale, uint32_t seed, uint32_t index0,
+    float* __restrict__ h_out, uint8_t* __restrict__ signs, float* __restrict__ norm_out, int64_t norm_stride,
+    const EgoCopy ego, const DeferredRows df) {
+  constexpr int COMB = kCombBi2;
+#include "kgat_dense_body.h"
 }
 
 // F.normalize(x, p=2, dim=1, eps=1e-12) of contiguous rows into a strided destination (a column
@@ -555,6 +294,33 @@ constexpr int kBiMaxBlocks = 512;
   return KGAT_OK;
 }
 
+// The two-term form: mode 1 (no-grad, optionally with the deferred rows) or 2 (training, with the sign record)
+template <int DI, int DO>
+static int launch_bi2(int64_t n_rows, const float* H, const float* HN, const float* W1, const float* W2, float slope,
+                      const DropArgs& dr, float* h_out, uint8_t* signs, float* norm_out, int64_t norm_stride,
+                      hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer) {
+  const int64_t tiles = (n_rows + 15) / 16;
+  int64_t blocks = (tiles + 3) / 4;
+  if (blocks > 512) blocks = 512;  // (as launch_bi)
+  const bool vec = norm_out == nullptr ||
+                   ((reinterpret_cast<uintptr_t>(norm_out) & 15u) == 0 && norm_stride % 4 == 0);
+  const DeferredRows no_defer{nullptr, nullptr, 0, 0, 0};
+#define KGAT_BI2_LAUNCH(MD, VEC, DEF, DFV)                                                                            \
+  hipLaunchKernelGGL((bi2_kernel<DI, DO, MD, VEC, DEF>), dim3((unsigned)blocks), dim3(256), 0, st, (int32_t)n_rows, H, \
+                     HN, W1, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out, signs, norm_out,      \
+                     norm_stride, ego, DFV)
+  if (mode == 2) {
+    if (vec) KGAT_BI2_LAUNCH(2, true, false, no_defer); else KGAT_BI2_LAUNCH(2, false, false, no_defer);
+  } else if (defer != nullptr) {
+    if (vec) KGAT_BI2_LAUNCH(1, true, true, *defer); else KGAT_BI2_LAUNCH(1, false, true, *defer);
+  } else {
+    if (vec) KGAT_BI2_LAUNCH(1, true, false, no_defer); else KGAT_BI2_LAUNCH(1, false, false, no_defer);
+  }
+#undef KGAT_BI2_LAUNCH
+  KGAT_CHECK_LAUNCH("bi2");
+  return KGAT_OK;
+}
+
 template <int DI, int DO>
 static int launch_bi_small(int64_t n_rows, const float* P, const float* HN, const float* W2, float slope,
                            const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride, hipStream_t st,
@@ -610,6 +376,150 @@ __global__ __launch_bounds__(256) void bi_bwd_pre_kernel(int64_t n_rows, int d, 
         dZ[(size_t)row * d + i] = keep ? g * keep_scale * (yv[c] > 0.f ? 1.f : slope) : 0.f;
       }
     }
+  }
+}
+
+// Backward head of the two-term layer: bi_bwd_pre_kernel's arithmetic up to the LeakyReLU' factor - g = [gA + gB +
+// normalize_bwd(g_norm; y)] * keep/(1-p) - then the two slopes from the forward's sign record.  It WRITES BOTH
+// gz1 = g * LeakyReLU'(z1) and gz2 = g * LeakyReLU'(z2): the dense backward kernels then read plain gradients.
+__global__ __launch_bounds__(256) void bi2_bwd_pre_kernel(int64_t n_rows, int d, const float* __restrict__ y,
+                                                          const uint8_t* __restrict__ signs,
+                                                          const float* __restrict__ gA, const float* __restrict__ gB,
+                                                          const float* __restrict__ g_norm, int64_t g_norm_stride,
+                                                          float slope, uint32_t drop_threshold, float keep_scale,
+                                                          uint32_t seed, uint32_t index0, float* __restrict__ dZ1,
+                                                          float* __restrict__ dZ2) {
+  const int sub = threadIdx.x >> 4, sl = threadIdx.x & 15;
+  for (int64_t row = (int64_t)blockIdx.x * 16 + sub; row < n_rows; row += (int64_t)gridDim.x * 16) {
+    const float* yr = y + (size_t)row * d;
+    float yv[8], gn[8];
+    float ss = 0.f, dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int i = sl + 16 * c;
+      yv[c] = i < d ? yr[i] : 0.f;
+      gn[c] = (g_norm && i < d) ? g_norm[(size_t)row * g_norm_stride + i] : 0.f;
+      ss = fmaf(yv[c], yv[c], ss);
+      dot = fmaf(yv[c], gn[c], dot);
+    }
+    ss = row16_sum_d(ss);
+    dot = row16_sum_d(dot);
+    const float nrm = sqrtf(ss);
+    const bool clamped = nrm < 1e-12f;  // F.normalize: x / max(|x|, eps)
+    const float inv = 1.f / fmaxf(nrm, 1e-12f);
+    const float proj = clamped ? 0.f : dot * inv * inv;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int i = sl + 16 * c;
+      if (i < d) {
+        float g = (gn[c] - yv[c] * proj) * inv;
+        if (gA) g += gA[(size_t)row * d + i];
+        if (gB) g += gB[(size_t)row * d + i];
+        const bool keep = drop_keep(seed, index0 + (uint32_t)row * (uint32_t)d + (uint32_t)i, drop_threshold);
+        const uint32_t sb = signs[(size_t)row * d + i];
+        g = keep ? g * keep_scale : 0.f;
+        dZ1[(size_t)row * d + i] = g * ((sb & 1u) ? 1.f : slope);
+        dZ2[(size_t)row * d + i] = g * ((sb & 2u) ? 1.f : slope);
+      }
+    }
+  }
+}
+
+// Backward of the two-term layer towards its inputs: P1 = gz1 W1 and P2 = gz2 W2 per 16-row tile (never written), then
+//   T = P1 + P2 * H (what the reversed-CSR aggregation sums: the gradient through h_N)   GB = P1 + P2 * HN (through h)
+// in one pass.  bi_bwd_input_kernel's structure with two weights (both in LDS, transposed fragment order, W2 behind
+// W1), two gradient row sets and two accumulator sets; the rows of H and HN are requested when the tile is computed,
+// ahead of its MFMA chains, so only the gradient rows are double-buffered.
+template <int DK, int DN>
+__global__ __launch_bounds__(256) void bi2_bwd_input_kernel(int32_t n_rows, const float* __restrict__ GZ1,
+                                                            const float* __restrict__ GZ2, const float* __restrict__ W1,
+                                                            const float* __restrict__ W2, const float* __restrict__ H,
+                                                            const float* __restrict__ HN, float* __restrict__ T,
+                                                            float* __restrict__ GB) {
+  constexpr int KS = DK / 4, KT = DN / 16;
+  __shared__ float s_w[2 * KS * KT * kWave];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const float* W = m == 0 ? W1 : W2;
+    for (int idx = threadIdx.x * 4; idx < DK * DN; idx += 256 * 4) {
+      const float4 v = *reinterpret_cast<const float4*>(W + idx);  // W[k][j0 .. j0 + 3]
+      const int k = idx / DN, j0 = idx % DN;
+      const int s = m * KS + (k >> 4) * 4 + (k & 3), q = (k >> 2) & 3;
+      const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int j = j0 + t;
+        s_w[(s * KT + (j >> 4)) * kWave + q * 16 + (j & 15)] = vv[t];
+      }
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x % kWave;
+  const int i = lane & 15, q = lane >> 4;
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / kWave);
+  const int64_t wv = (int64_t)blockIdx.x * (256 / kWave) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+  const int32_t n_tiles = (n_rows + 15) >> 4;
+  const int32_t t_begin = (int32_t)((int64_t)n_tiles * wv / n_waves);
+  const int32_t t_end = (int32_t)((int64_t)n_tiles * (wv + 1) / n_waves);
+  if (t_begin >= t_end) return;
+  struct Rows { float g1[KS], g2[KS]; };
+  auto load_rows = [&](int32_t t, Rows& r) {
+    int32_t ra = (t << 4) + i;
+    ra = ra < n_rows ? ra : n_rows - 1;
+    const float4* p1 = reinterpret_cast<const float4*>(GZ1 + (size_t)ra * DK) + q;
+    const float4* p2 = reinterpret_cast<const float4*>(GZ2 + (size_t)ra * DK) + q;
+#pragma unroll
+    for (int m = 0; m < DK / 16; ++m) {
+      const float4 v = p1[m * 4], u = p2[m * 4];
+      r.g1[4 * m + 0] = v.x; r.g1[4 * m + 1] = v.y; r.g1[4 * m + 2] = v.z; r.g1[4 * m + 3] = v.w;
+      r.g2[4 * m + 0] = u.x; r.g2[4 * m + 1] = u.y; r.g2[4 * m + 2] = u.z; r.g2[4 * m + 3] = u.w;
+    }
+  };
+  auto tile = [&](int32_t t, const Rows& r) {
+    int32_t ra = (t << 4) + i;
+    ra = ra < n_rows ? ra : n_rows - 1;
+    const float4* ph = reinterpret_cast<const float4*>(H + (size_t)ra * DN) + q;
+    const float4* pn = reinterpret_cast<const float4*>(HN + (size_t)ra * DN) + q;
+    float4 h[KT], hn[KT];
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+      h[c] = ph[c * 4];
+      hn[c] = pn[c * 4];
+    }
+    floatx4_d acc1[KT], acc2[KT];
+#pragma unroll
+    for (int c = 0; c < KT; ++c) acc1[c] = acc2[c] = (floatx4_d){0.f, 0.f, 0.f, 0.f};
+    int wl = lane;  // (as in bi_interaction_kernel: the fragments are read per tile, not hoisted into registers)
+    asm volatile("" : "+v"(wl));
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int c = 0; c < KT; ++c) {
+        acc1[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_w[(s * KT + c) * kWave + wl], r.g1[s], acc1[c], 0, 0, 0);
+        acc2[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_w[((KS + s) * KT + c) * kWave + wl], r.g2[s], acc2[c], 0, 0, 0);
+      }
+    const int32_t row = (t << 4) + i;
+    if (row < n_rows) {
+#pragma unroll
+      for (int c = 0; c < KT; ++c) {
+        const size_t off = (size_t)row * DN + 16 * c + 4 * q;
+        *reinterpret_cast<float4*>(T + off) =
+            make_float4(fmaf(acc2[c][0], h[c].x, acc1[c][0]), fmaf(acc2[c][1], h[c].y, acc1[c][1]),
+                        fmaf(acc2[c][2], h[c].z, acc1[c][2]), fmaf(acc2[c][3], h[c].w, acc1[c][3]));
+        *reinterpret_cast<float4*>(GB + off) =
+            make_float4(fmaf(acc2[c][0], hn[c].x, acc1[c][0]), fmaf(acc2[c][1], hn[c].y, acc1[c][1]),
+                        fmaf(acc2[c][2], hn[c].z, acc1[c][2]), fmaf(acc2[c][3], hn[c].w, acc1[c][3]));
+      }
+    }
+  };
+  Rows r0, r1;
+  load_rows(t_begin, r0);
+  for (int32_t t = t_begin; t < t_end; t += 2) {
+    if (t + 1 < t_end) load_rows(t + 1, r1);
+    tile(t, r0);
+    if (t + 1 >= t_end) break;
+    if (t + 2 < t_end) load_rows(t + 2, r0);
+    tile(t + 1, r1);
   }
 }
 
@@ -825,6 +735,109 @@ __global__ __launch_bounds__(256) void bi_bwd_weight_kernel(int32_t n_rows, cons
   }
 }
 
+// Both weight gradients of the two-term layer in one pass: grad_W1 = gz1^T (H + HN), grad_W2 = gz2^T (H * HN).
+// bi_bwd_weight_kernel's slab scheme with two gradient blocks and two operand blocks in LDS and two accumulator sets
+// per output tile - the rows of H and HN are read once for both (run back to back on gz1 and gz2, the sum- and the
+// product-form kernels read them twice: 0.057 against this kernel's time at 64 -> 64).  Partials and
+// their order of additions as there.
+template <int DO, int DI>
+__global__ __launch_bounds__(256) void bi2_bwd_weight_kernel(int32_t n_rows, const float* __restrict__ GZ1,
+                                                             const float* __restrict__ GZ2, const float* __restrict__ H,
+                                                             const float* __restrict__ HN, float* __restrict__ partial1,
+                                                             float* __restrict__ partial2) {
+  constexpr int SLAB = 64;
+  constexpr int LG = DO == 16 ? 16 : DO + 16, LP = DI == 16 ? 16 : DI + 16;
+  constexpr int TM = DO / 16, TN = DI / 16, TT = TM * TN;
+  constexpr int TPW = (TT + 3) / 4;                 // output tiles per wavefront
+  constexpr int G4 = SLAB * DO / 4 / 256 > 0 ? SLAB * DO / 4 / 256 : 1;  // float4 of each gradient per thread per slab
+  constexpr int P4 = SLAB * DI / 4 / 256 > 0 ? SLAB * DI / 4 / 256 : 1;
+  __shared__ float s_g1[SLAB * LG];
+  __shared__ float s_g2[SLAB * LG];
+  __shared__ float s_ps[SLAB * LP];  // H + HN
+  __shared__ float s_pp[SLAB * LP];  // H * HN
+  const int tid = threadIdx.x, lane = tid % kWave, w = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int i = lane & 15, q = lane >> 4;
+  const int32_t n_slabs = (n_rows + SLAB - 1) / SLAB;
+  floatx4_d acc1[TPW], acc2[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) acc1[t] = acc2[t] = (floatx4_d){0.f, 0.f, 0.f, 0.f};
+  float4 g1[G4], g2[G4], hh[P4], hn[P4];
+  auto request = [&](int32_t slab) {  // the slab's rows into registers (rows past the end: zeros)
+    const int32_t r0 = slab * SLAB;
+#pragma unroll
+    for (int u = 0; u < G4; ++u) {
+      const int e = (u * 256 + tid) * 4;            // element index inside the SLAB x DO block
+      const int32_t r = r0 + e / DO;
+      const bool in = e < SLAB * DO && r < n_rows;
+      g1[u] = in ? *reinterpret_cast<const float4*>(GZ1 + (size_t)r * DO + e % DO) : make_float4(0.f, 0.f, 0.f, 0.f);
+      g2[u] = in ? *reinterpret_cast<const float4*>(GZ2 + (size_t)r * DO + e % DO) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < P4; ++u) {
+      const int e = (u * 256 + tid) * 4;
+      const int32_t r = r0 + e / DI;
+      const bool in = e < SLAB * DI && r < n_rows;
+      hh[u] = in ? *reinterpret_cast<const float4*>(H + (size_t)r * DI + e % DI) : make_float4(0.f, 0.f, 0.f, 0.f);
+      hn[u] = in ? *reinterpret_cast<const float4*>(HN + (size_t)r * DI + e % DI) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  int32_t slab = blockIdx.x;
+  if (slab < n_slabs) request(slab);
+  for (; slab < n_slabs; slab += gridDim.x) {
+    __syncthreads();  // the previous slab's fragments have been read
+#pragma unroll
+    for (int u = 0; u < G4; ++u) {
+      const int e = (u * 256 + tid) * 4;
+      if (e < SLAB * DO) {
+        *reinterpret_cast<float4*>(&s_g1[(e / DO) * LG + e % DO]) = g1[u];
+        *reinterpret_cast<float4*>(&s_g2[(e / DO) * LG + e % DO]) = g2[u];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < P4; ++u) {
+      const int e = (u * 256 + tid) * 4;
+      if (e < SLAB * DI) {
+        *reinterpret_cast<float4*>(&s_ps[(e / DI) * LP + e % DI]) =
+            make_float4(hh[u].x + hn[u].x, hh[u].y + hn[u].y, hh[u].z + hn[u].z, hh[u].w + hn[u].w);
+        *reinterpret_cast<float4*>(&s_pp[(e / DI) * LP + e % DI]) =
+            make_float4(hh[u].x * hn[u].x, hh[u].y * hn[u].y, hh[u].z * hn[u].z, hh[u].w * hn[u].w);
+      }
+    }
+    __syncthreads();
+    if (slab + (int32_t)gridDim.x < n_slabs) request(slab + gridDim.x);  // in flight while this slab is multiplied
+    if (w < TT) {  // (narrow results have fewer tiles than wavefronts)
+#pragma unroll 4
+      for (int r0 = 0; r0 < SLAB; r0 += 4) {
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+          const int tile = w + 4 * t;
+          if (tile < TT) {
+            const int cm = tile / TN, cn = tile % TN;
+            const int ga = (r0 + q) * LG + 16 * cm + i, pa = (r0 + q) * LP + 16 * cn + i;
+            acc1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_g1[ga], s_ps[pa], acc1[t], 0, 0, 0);
+            acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_g2[ga], s_pp[pa], acc2[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  // C[m = 4q + j][n = i] of tile (cm, cn) -> partial[block][16 cm + 4q + j][16 cn + i]
+  float* out1 = partial1 + (size_t)blockIdx.x * DO * DI;
+  float* out2 = partial2 + (size_t)blockIdx.x * DO * DI;
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    const int tile = w + 4 * t;
+    if (tile < TT) {
+      const int cm = tile / TN, cn = tile % TN;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        out1[(size_t)(16 * cm + 4 * q + j) * DI + 16 * cn + i] = acc1[t][j];
+        out2[(size_t)(16 * cm + 4 * q + j) * DI + 16 * cn + i] = acc2[t][j];
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void mul2_kernel(int64_t n4, const float4* __restrict__ A, const float4* __restrict__ B,
                                                    const float4* __restrict__ C, float4* __restrict__ AB,
                                                    float4* __restrict__ AC) {
@@ -871,6 +884,45 @@ static int launch_bwd_input(int64_t n_rows, int d_in, int d_out, const float* gr
   KGAT_BWD_CASE(128, 16) KGAT_BWD_CASE(128, 32) KGAT_BWD_CASE(128, 64) KGAT_BWD_CASE(128, 128)
 #undef KGAT_BWD_CASE
   set_error("bi_interaction_bwd_input: unsupported widths %d -> %d", d_in, d_out);
+  return KGAT_E_UNSUPPORTED;
+}
+
+static int launch_bi2_bwd_input(int64_t n_rows, int d_in, int d_out, const float* gz1, const float* gz2, const float* W1,
+                                const float* W2, const float* H, const float* HN, float* t, float* gb, hipStream_t st) {
+  const int64_t tiles = (n_rows + 15) / 16;
+  int64_t blocks = (tiles + 3) / 4;
+  if (blocks > 512) blocks = 512;
+#define KGAT_BI2_BWD_CASE(DK, DN)                                                                                      \
+  if (d_out == DK && d_in == DN) {                                                                                    \
+    hipLaunchKernelGGL((bi2_bwd_input_kernel<DK, DN>), dim3((unsigned)blocks), dim3(256), 0, st, (int32_t)n_rows, gz1, \
+                       gz2, W1, W2, H, HN, t, gb);                                                                    \
+    KGAT_CHECK_LAUNCH("bi2_bwd_input");                                                                               \
+    return KGAT_OK;                                                                                                   \
+  }
+  KGAT_BI2_BWD_CASE(16, 16) KGAT_BI2_BWD_CASE(16, 32) KGAT_BI2_BWD_CASE(16, 64) KGAT_BI2_BWD_CASE(16, 128)
+  KGAT_BI2_BWD_CASE(32, 16) KGAT_BI2_BWD_CASE(32, 32) KGAT_BI2_BWD_CASE(32, 64) KGAT_BI2_BWD_CASE(32, 128)
+  KGAT_BI2_BWD_CASE(64, 16) KGAT_BI2_BWD_CASE(64, 32) KGAT_BI2_BWD_CASE(64, 64) KGAT_BI2_BWD_CASE(64, 128)
+  KGAT_BI2_BWD_CASE(128, 16) KGAT_BI2_BWD_CASE(128, 32) KGAT_BI2_BWD_CASE(128, 64) KGAT_BI2_BWD_CASE(128, 128)
+#undef KGAT_BI2_BWD_CASE
+  set_error("bi2_bwd_input: unsupported widths %d -> %d", d_in, d_out);
+  return KGAT_E_UNSUPPORTED;
+}
+
+static int launch_bi2_bwd_weight(int64_t n_rows, int d_in, int d_out, const float* gz1, const float* gz2, const float* H,
+                                 const float* HN, float* partials1, float* partials2, int64_t n_partials, hipStream_t st) {
+#define KGAT_BI2_BWW_CASE(DO_, DI_)                                                                                    \
+  if (d_out == DO_ && d_in == DI_) {                                                                                  \
+    hipLaunchKernelGGL((bi2_bwd_weight_kernel<DO_, DI_>), dim3((unsigned)n_partials), dim3(256), 0, st,               \
+                       (int32_t)n_rows, gz1, gz2, H, HN, partials1, partials2);                                       \
+    KGAT_CHECK_LAUNCH("bi2_bwd_weight");                                                                              \
+    return KGAT_OK;                                                                                                   \
+  }
+  KGAT_BI2_BWW_CASE(16, 16) KGAT_BI2_BWW_CASE(16, 32) KGAT_BI2_BWW_CASE(16, 64) KGAT_BI2_BWW_CASE(16, 128)
+  KGAT_BI2_BWW_CASE(32, 16) KGAT_BI2_BWW_CASE(32, 32) KGAT_BI2_BWW_CASE(32, 64) KGAT_BI2_BWW_CASE(32, 128)
+  KGAT_BI2_BWW_CASE(64, 16) KGAT_BI2_BWW_CASE(64, 32) KGAT_BI2_BWW_CASE(64, 64) KGAT_BI2_BWW_CASE(64, 128)
+  KGAT_BI2_BWW_CASE(128, 16) KGAT_BI2_BWW_CASE(128, 32) KGAT_BI2_BWW_CASE(128, 64) KGAT_BI2_BWW_CASE(128, 128)
+#undef KGAT_BI2_BWW_CASE
+  set_error("bi2_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
   return KGAT_E_UNSUPPORTED;
 }
 
@@ -1093,6 +1145,144 @@ int kgat_aggregator_train_f32(int form, int64_t n_rows, int d_in, int d_out, con
                  "bi_interaction_train: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
   return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, drop_args(drop_p, seed, row0, d_out), h_out,
                        norm_out, norm_stride, as_stream(stream), 2, EgoCopy{self_out, self_stride});
+}
+
+// ---- the two-term Bi-Interaction ("Bi2"): entries of their own (two weights, the sign record)
+int kgat_bi2_supported(int d_in, int d_out) {
+  auto ok = [](int d) { return d == 16 || d == 32 || d == 64 || d == 128; };
+  return ok(d_in) && ok(d_out);
+}
+
+int kgat_bi2_bwd_supported(int d_in, int d_out) { return kgat_bi2_supported(d_in, d_out); }
+
+static int bi2_dispatch(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
+                        const float* W2, float negative_slope, const DropArgs& dr, float* h_out, uint8_t* signs,
+                        float* norm_out, int64_t norm_stride, hipStream_t st, int mode, const EgoCopy ego,
+                        const DeferredRows* defer) {
+#define KGAT_BI2_CASE(DI, DO) \
+  if (d_in == DI && d_out == DO) \
+    return launch_bi2<DI, DO>(n_rows, H, HN, W1, W2, negative_slope, dr, h_out, signs, norm_out, norm_stride, st, mode, ego, defer);
+  KGAT_BI2_CASE(16, 16) KGAT_BI2_CASE(16, 32) KGAT_BI2_CASE(16, 64) KGAT_BI2_CASE(16, 128)
+  KGAT_BI2_CASE(32, 16) KGAT_BI2_CASE(32, 32) KGAT_BI2_CASE(32, 64) KGAT_BI2_CASE(32, 128)
+  KGAT_BI2_CASE(64, 16) KGAT_BI2_CASE(64, 32) KGAT_BI2_CASE(64, 64) KGAT_BI2_CASE(64, 128)
+  KGAT_BI2_CASE(128, 16) KGAT_BI2_CASE(128, 32) KGAT_BI2_CASE(128, 64) KGAT_BI2_CASE(128, 128)
+#undef KGAT_BI2_CASE
+  set_error("bi2: unsupported widths %d -> %d", d_in, d_out);
+  return KGAT_E_UNSUPPORTED;
+}
+
+// the checks the three forward entries share; 1 = nothing to do (no rows)
+static int bi2_check_forward(const char* what, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
+                             const float* W1, const float* W2, const float* h_out, const float* norm_out,
+                             int64_t norm_stride, const float* self_out, int64_t self_stride, bool need_h_out) {
+  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "%s: bad row count", what);
+  if (n_rows == 0) return 1;
+  KGAT_CHECK_ARG(H && HN && W1 && W2 && (h_out || (norm_out && !need_h_out)), "%s: null pointer", what);
+  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "%s: bad norm_stride", what);
+  KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
+                                         (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
+                 "%s: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in", what);
+  if (!kgat_bi2_supported(d_in, d_out)) {
+    set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
+    return KGAT_E_UNSUPPORTED;
+  }
+  return KGAT_OK;
+}
+
+int kgat_bi2_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1, const float* W2,
+                 float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
+                 int64_t self_stride, kgat_stream_t stream) {
+  const int rc = bi2_check_forward("bi2", n_rows, d_in, d_out, H, HN, W1, W2, h_out, norm_out, norm_stride, self_out,
+                                   self_stride, false);
+  if (rc != KGAT_OK) return rc > 0 ? KGAT_OK : rc;
+  return bi2_dispatch(n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, DropArgs(), h_out, nullptr, norm_out,
+                      norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride}, nullptr);
+}
+
+int kgat_bi2_deferred_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
+                          const float* W2, float negative_slope, float* h_out, float* norm_out, int64_t norm_stride,
+                          float* self_out, int64_t self_stride, const int32_t* indptr_rows, int64_t e_begin,
+                          int64_t e_end, const void* spmm_workspace, int tile_edges, kgat_stream_t stream) {
+  const int rc = bi2_check_forward("bi2_deferred", n_rows, d_in, d_out, H, HN, W1, W2, h_out, norm_out, norm_stride,
+                                   self_out, self_stride, false);
+  if (rc != KGAT_OK) return rc > 0 ? KGAT_OK : rc;
+  KGAT_CHECK_ARG(indptr_rows != nullptr, "bi2_deferred: null pointer");
+  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "bi2_deferred: bad edge range");
+  KGAT_CHECK_ARG(e_end == e_begin || spmm_workspace != nullptr, "bi2_deferred: null workspace");
+  KGAT_CHECK_ARG(tile_edges > 0 && (tile_edges & (tile_edges - 1)) == 0,
+                 "bi2_deferred: tile_edges must be kgat_spmm_tile_edges() of the aggregation (a power of two)");
+  int shift = 0;
+  while ((1 << shift) < tile_edges) ++shift;
+  const DeferredRows df{indptr_rows, static_cast<const float4*>(spmm_workspace), (int32_t)e_begin, (int32_t)e_end, shift};
+  return bi2_dispatch(n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, DropArgs(), h_out, nullptr, norm_out,
+                      norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
+}
+
+int kgat_bi2_train_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
+                       const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* h_out,
+                       uint8_t* signs, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
+                       kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_rows >= 0 && row0 >= 0 && d_out > 0 && (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32),
+                 "bi2_train: bad row count");
+  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "bi2_train: dropout probability outside [0, 1)");
+  const int rc = bi2_check_forward("bi2_train", n_rows, d_in, d_out, H, HN, W1, W2, h_out, norm_out, norm_stride,
+                                   self_out, self_stride, true);
+  if (rc != KGAT_OK) return rc > 0 ? KGAT_OK : rc;
+  KGAT_CHECK_ARG(signs != nullptr && (reinterpret_cast<uintptr_t>(signs) & 3u) == 0,
+                 "bi2_train: the sign record must be a 4-byte aligned buffer of n_rows * d_out bytes");
+  return bi2_dispatch(n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, drop_args(drop_p, seed, row0, d_out), h_out,
+                      signs, norm_out, norm_stride, as_stream(stream), 2, EgoCopy{self_out, self_stride}, nullptr);
+}
+
+int kgat_bi2_bwd_pre_f32(int64_t n_rows, int d_out, const float* h_out, const uint8_t* signs, const float* grad_a,
+                         const float* grad_b, const float* grad_norm, int64_t grad_norm_stride, float negative_slope,
+                         float drop_p, uint64_t seed, int64_t row0, float* grad_z1, float* grad_z2,
+                         kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_rows >= 0 && d_out > 0 && d_out <= 128 && row0 >= 0 &&
+                     (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32), "bi2_bwd_pre: bad size");
+  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "bi2_bwd_pre: dropout probability outside [0, 1)");
+  if (n_rows == 0) return KGAT_OK;
+  KGAT_CHECK_ARG(h_out && signs && grad_z1 && grad_z2 && grad_z1 != grad_z2, "bi2_bwd_pre: null pointer");
+  KGAT_CHECK_ARG(grad_norm == nullptr || grad_norm_stride >= d_out, "bi2_bwd_pre: bad stride");
+  const DropArgs dr = drop_args(drop_p, seed, row0, d_out);
+  int64_t blocks = (n_rows + 15) / 16;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(bi2_bwd_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), n_rows, d_out, h_out,
+                     signs, grad_a, grad_b, grad_norm, grad_norm_stride, negative_slope, dr.threshold, dr.keep_scale,
+                     dr.seed, dr.index0, grad_z1, grad_z2);
+  KGAT_CHECK_LAUNCH("bi2_bwd_pre");
+  return KGAT_OK;
+}
+
+int kgat_bi2_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z1, const float* grad_z2,
+                           const float* W1, const float* W2, const float* H, const float* HN, float* grad_agg,
+                           float* grad_self, kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi2_bwd_input: bad row count");
+  if (n_rows == 0) return KGAT_OK;
+  if (!kgat_bi2_bwd_supported(d_in, d_out)) {
+    set_error("bi2_bwd_input: unsupported widths %d -> %d", d_in, d_out);
+    return KGAT_E_UNSUPPORTED;
+  }
+  KGAT_CHECK_ARG(grad_z1 && grad_z2 && W1 && W2 && H && HN && grad_agg && grad_self && grad_agg != grad_self,
+                 "bi2_bwd_input: null pointer");
+  return launch_bi2_bwd_input(n_rows, d_in, d_out, grad_z1, grad_z2, W1, W2, H, HN, grad_agg, grad_self,
+                              as_stream(stream));
+}
+
+int kgat_bi2_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z1, const float* grad_z2,
+                            const float* H, const float* HN, float* partials_w1, float* partials_w2, int64_t n_partials,
+                            kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi2_bwd_weight: bad row count");
+  KGAT_CHECK_ARG(n_partials == kgat_bi_interaction_bwd_weight_partials(n_rows),
+                 "bi2_bwd_weight: n_partials must be kgat_bi_interaction_bwd_weight_partials(n_rows)");
+  KGAT_CHECK_ARG(partials_w1 && partials_w2 && partials_w1 != partials_w2 &&
+                     (n_rows == 0 || (grad_z1 && grad_z2 && H && HN)), "bi2_bwd_weight: null pointer");
+  if (!kgat_bi2_bwd_supported(d_in, d_out)) {
+    set_error("bi2_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
+    return KGAT_E_UNSUPPORTED;
+  }
+  return launch_bi2_bwd_weight(n_rows, d_in, d_out, grad_z1, grad_z2, H, HN, partials_w1, partials_w2, n_partials,
+                               as_stream(stream));
 }
 
 // out = a + b + c over n_rows x d (a: rows of a_stride floats - a column slice of a wider matrix; b, c, out contiguous)

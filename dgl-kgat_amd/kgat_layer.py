@@ -21,19 +21,42 @@ import torch.nn.functional as F
 
 from . import function as fn
 from .autograd import edge_softmax, u_mul_e_sum
-from .ops import FORMS
+from .ops import BI2_FORM, FORMS
 from .options import options
 from .sage_layer import SAGEConv, draw_seed
 
 
+# what KGATConv's res_type may be -> the layer code's tag: the ops.FORMS values and the two-term Bi-Interaction, which is
+# no form of the kgat_aggregator_* entries (two weights, kgat_bi2_*)
+RES_TYPES = dict(FORMS, Bi2=BI2_FORM)
+
+
 def _layer_dense(layer):
-    """(form, weight, d_in, d_out) of a KGAT layer's dense part: ops.FORMS[res_type] and res_fc_2 / res_fc (a
-    reference-shaped layer routed here by compat.accelerate has res_fc_2: Bi)."""
+    """(form, weight, d_in, d_out) of a KGAT layer's dense part: RES_TYPES[res_type] and res_fc_2 / res_fc (a
+    reference-shaped layer routed here by compat.accelerate has res_fc_2 and no _res_type: Bi).  A two-term layer
+    ("Bi2") has both linears: its weight is the pair (res_fc.weight, res_fc_2.weight)."""
+    if getattr(layer, "_res_type", None) == "Bi2":
+        lin = layer.res_fc
+        return BI2_FORM, (lin.weight, layer.res_fc_2.weight), lin.in_features, lin.out_features
     if hasattr(layer, "res_fc_2"):
         lin = layer.res_fc_2
         return FORMS["Bi"], lin.weight, lin.in_features, lin.out_features
     form, lin = FORMS[layer._res_type], layer.res_fc
     return form, lin.weight, lin.in_features // (2 if form == FORMS["GraphSage"] else 1), lin.out_features
+
+
+def _dense_supported(form, d_in, d_out):
+    """The forward kernels cover the layer's widths (every kernel form's backward covers the same MFMA widths)."""
+    from . import ops
+    return ops.bi2_supported(d_in, d_out) if form == BI2_FORM else ops.aggregator_supported(form, d_in, d_out)
+
+
+def _dense_no_grad(form, h, hn, W, **kw):
+    """The no-grad dense kernel of a layer (ops.aggregator, or ops.bi2 with the layer's pair of weights)."""
+    from . import ops
+    if form == BI2_FORM:
+        return ops.bi2(h, hn, W[0].detach(), W[1].detach(), 0.01, **kw)
+    return ops.aggregator(form, h, hn, W.detach(), 0.01, **kw)
 
 
 def ops_transr_supported(model, h):
@@ -69,28 +92,42 @@ class _TallLinear(torch.autograd.Function):
 
 
 class KGATConv(nn.Module):
-    """KGAT propagation layer (reference models.py:49-70), then dropout, with one of the KGAT paper's three aggregators
+    """KGAT propagation layer (reference models.py:49-70), then dropout, with one of the KGAT paper's aggregators
     ("Information Aggregation"; the reference implements only ``Bi`` and keeps ``res_type`` as the hook):
       * ``"Bi"``        LeakyReLU_{0.01}(res_fc_2(h * h_N))       res_fc_2.weight (out, in)
       * ``"GCN"``       LeakyReLU_{0.01}(res_fc(h + h_N))         res_fc.weight (out, in)
-      * ``"GraphSage"`` LeakyReLU_{0.01}(res_fc([h | h_N]))       res_fc.weight (out, 2 in): columns [:in] act on h."""
+      * ``"GraphSage"`` LeakyReLU_{0.01}(res_fc([h | h_N]))       res_fc.weight (out, 2 in): columns [:in] act on h
+      * ``"Bi2"``       LeakyReLU_{0.01}(res_fc(h + h_N)) + LeakyReLU_{0.01}(res_fc_2(h * h_N)): the paper's two-term
+                        Bi-Interaction (eq. 8), both weights (out, in); the reference's ``Bi`` is its second term."""
 
     def __init__(self, entity_in_feats, out_feats, dropout, res_type="Bi"):
         super().__init__()
-        if res_type not in FORMS:
+        if res_type not in RES_TYPES:
             raise NotImplementedError(res_type)
         self.mess_drop = nn.Dropout(dropout)
         self._res_type = res_type
-        if res_type == "Bi":
+        if res_type == "Bi2":  # (the reference's own names: res_fc on the sum - models.py:55 - res_fc_2 on the product)
+            self.res_fc = nn.Linear(entity_in_feats, out_feats, bias=False)
+            self.res_fc_2 = nn.Linear(entity_in_feats, out_feats, bias=False)
+        elif res_type == "Bi":
             self.res_fc_2 = nn.Linear(entity_in_feats, out_feats, bias=False)
         else:
             k = 2 * entity_in_feats if res_type == "GraphSage" else entity_in_feats
             self.res_fc = nn.Linear(k, out_feats, bias=False)
 
     def _dense(self, h, h_neighbor, fused):
-        """The GCN / GraphSage dense part: LeakyReLU(res_fc(h + h_N | [h | h_N])).  fused and nothing to differentiate:
-        the aggregator kernel (kgat_aggregator_f32) where it covers the widths; otherwise library GEMMs."""
+        """The GCN / GraphSage / Bi2 dense part: LeakyReLU(res_fc(h + h_N | [h | h_N])), for Bi2 plus
+        LeakyReLU(res_fc_2(h * h_N)).  fused and nothing to differentiate: the aggregator kernel (kgat_aggregator_f32,
+        kgat_bi2_f32) where it covers the widths; otherwise library GEMMs."""
         from . import ops
+        if self._res_type == "Bi2":
+            w1, w2 = self.res_fc.weight, self.res_fc_2.weight
+            if (fused and h.is_cuda and h.dtype == torch.float32 and ops.bi2_supported(h.shape[1], w1.shape[0]) and
+                    not (torch.is_grad_enabled() and (h.requires_grad or h_neighbor.requires_grad or w1.requires_grad or
+                                                      w2.requires_grad))):
+                return ops.bi2(h.contiguous(), h_neighbor.contiguous(), w1.detach().contiguous(), w2.detach().contiguous(), 0.01)
+            return (F.leaky_relu(_TallLinear.apply(h + h_neighbor, w1)) +
+                    F.leaky_relu(_TallLinear.apply(h * h_neighbor, w2)))
         form, w = FORMS[self._res_type], self.res_fc.weight
         d_in = h.shape[1]
         if (fused and h.is_cuda and h.dtype == torch.float32 and ops.aggregator_supported(form, d_in, w.shape[0]) and
@@ -158,8 +195,8 @@ class KGATPropagation(nn.Module):
         super().__init__()
         if gnn_model not in ("kgat", "graphsage"):
             raise NotImplementedError("gnn_model must be 'kgat' or 'graphsage', got %r" % (gnn_model,))
-        if res_type not in FORMS:
-            raise NotImplementedError("res_type must be one of %s, got %r" % (", ".join(sorted(FORMS)), res_type))
+        if res_type not in RES_TYPES:
+            raise NotImplementedError("res_type must be one of %s, got %r" % (", ".join(sorted(RES_TYPES)), res_type))
         if gnn_model == "graphsage" and res_type != "Bi":
             raise ValueError("res_type selects the aggregator of gnn_model='kgat'; gnn_model='graphsage' takes none "
                              "(got res_type=%r)" % (res_type,))
@@ -225,6 +262,7 @@ class KGATPropagation(nn.Module):
             p = self.layers[0].mess_drop.p if self.training else 0.0
             seed = int(torch.empty((), dtype=torch.int64).random_()) if p > 0 else 0
             dense = [_layer_dense(layer) for layer in self.layers]
+            # (a two-term layer's d[1] is its pair of weights)
             return gnn_train(g, self._node_embeddings(g), [d[1] for d in dense], 0.01, p, seed,
                              forms=[d[0] for d in dense])
         if auto and g.partition is not None and torch.is_grad_enabled() and self._can_fuse_training(g, sharded=True):
@@ -268,7 +306,7 @@ class KGATPropagation(nn.Module):
             return False
         return ((g.partition is None) != sharded and w.is_cuda and w.dtype == torch.float32 and "w" in g.edata and
                 not g.edata["w"].requires_grad and
-                all(ops.aggregator_supported(form, d_in, d_out) and layer.mess_drop.p < 1.0
+                all(_dense_supported(form, d_in, d_out) and layer.mess_drop.p < 1.0
                     for layer, (form, _, d_in, d_out) in zip(self.layers, dense)))
 
     def _node_embeddings(self, g):
@@ -289,7 +327,7 @@ class KGATPropagation(nn.Module):
         if not all(isinstance(layer, KGATConv) or hasattr(layer, "res_fc_2") for layer in self.layers):
             return False
         drop_off = all((not layer.training) or layer.mess_drop.p == 0 for layer in self.layers)
-        return drop_off and all(ops.aggregator_supported(form, d_in, d_out)
+        return drop_off and all(_dense_supported(form, d_in, d_out)
                                 for form, _, d_in, d_out in map(_layer_dense, self.layers))
 
     def _gnn_fused(self, g):
@@ -318,7 +356,7 @@ class KGATPropagation(nn.Module):
         fuse_bi = options.fuse_bi
         # KGAT_GNN_MUL_IN_SPMM=1: rounds 1-3's split - h * h_N in the aggregation's epilogue (A/B)
         mul_in_spmm = options.gnn_mul_in_spmm
-        # (both compute the product: a GCN / GraphSage layer skips them and takes the aggregator kernel below)
+        # (both compute the product alone: a GCN / GraphSage / Bi2 layer skips them and takes its dense kernel below)
         defer = options.gnn_defer_finish
         st = g._st
         scratch = None
@@ -348,12 +386,12 @@ class KGATPropagation(nn.Module):
                     csr = st.csr(h.device)
                     hc = h.contiguous()
                     hn, rows_left = ops.spmm(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), defer_finish=True)
-                    h = ops.aggregator(form, hc, hn, W.detach(), 0.01, norm_out=norm_out, want_h=not last,
+                    h = _dense_no_grad(form, hc, hn, W, norm_out=norm_out, want_h=not last,
                                        deferred=rows_left, self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
                     off += widths[li + 1]
                     continue
                 hn = u_mul_e_sum(g, h, w)
-                h = ops.aggregator(form, h.contiguous(), hn, W.detach(), 0.01, norm_out=norm_out, want_h=not last,
+                h = _dense_no_grad(form, h.contiguous(), hn, W, norm_out=norm_out, want_h=not last,
                                    self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
                 off += widths[li + 1]
                 continue

@@ -1090,6 +1090,131 @@ def aggregator_bwd_weight(form, grad_z, H, HN, want_partials=False):
     return partials if want_partials else partials.sum(0)
 
 
+# The KGAT paper's two-term Bi-Interaction (KGATConv res_type "Bi2"; include/kgat_hip.h kgat_bi2_*):
+# LeakyReLU(W1 (h + h_N)) + LeakyReLU(W2 (h * h_N)), W1 = res_fc.weight, W2 = res_fc_2.weight.  Two weights and a sign
+# record: entries of their own, not a FORMS value.
+BI2_FORM = 3  # the layer code's tag for such a layer beside the FORMS values (autograd.gnn_train, kgat_layer)
+
+
+def bi2_supported(d_in, d_out):
+    """The widths the two-term forward kernels cover (kgat_bi2_supported)."""
+    return bool(_lib.load().kgat_bi2_supported(int(d_in), int(d_out)))
+
+
+def bi2_bwd_supported(d_in, d_out):
+    """The widths the two-term backward kernels cover (kgat_bi2_bwd_supported)."""
+    return bool(_lib.load().kgat_bi2_bwd_supported(int(d_in), int(d_out)))
+
+
+def _bi2_weights(W1, W2, d_in):
+    W1 = _need(W1, torch.float32, "W1")
+    if W1.dim() != 2 or W1.shape[1] != d_in:
+        raise ValueError("W1 has shape %s, expected (*, %d)" % (tuple(W1.shape), d_in))
+    W2 = _need(W2, torch.float32, "W2", W1.shape)
+    return W1, W2, W1.shape[0]
+
+
+def bi2(H, HN, W1, W2, negative_slope=0.01, h_out=None, norm_out=None, want_h=True, self_out=None, deferred=None):
+    """Z = leaky_relu((H + HN) @ W1^T) + leaky_relu((H * HN) @ W2^T) (kgat_bi2_f32 / kgat_bi2_deferred_f32); the other
+    arguments as bi_interaction_mul."""
+    H = _need(H, torch.float32, "H")
+    HN = _need(HN, torch.float32, "HN", H.shape)
+    n, d_in = H.shape
+    W1, W2, d_out = _bi2_weights(W1, W2, d_in)
+    if want_h and h_out is None:
+        h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
+    if h_out is not None:
+        h_out = _need(h_out, torch.float32, "h_out", (n, d_out))
+    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
+    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    with _timed("bi2", (n, d_in, d_out)):
+        if deferred is not None:
+            if deferred.n_rows != n or deferred.D != d_in:
+                raise ValueError("deferred rows of a (%d, %d) aggregation with a (%d, %d) input" % (deferred.n_rows, deferred.D, n, d_in))
+            check(_lib.load().kgat_bi2_deferred_f32(
+                n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W1), _ptr(W2), float(negative_slope), _ptr(h_out), _ptr(norm_out),
+                stride, _ptr(self_out), self_stride, _ptr(deferred.indptr_rows), deferred.e_range[0], deferred.e_range[1],
+                _ptr(deferred.workspace), deferred.tile_edges, _stream(H)), "kgat_bi2_deferred_f32")
+        else:
+            check(_lib.load().kgat_bi2_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W1), _ptr(W2), float(negative_slope),
+                                           _ptr(h_out), _ptr(norm_out), stride, _ptr(self_out), self_stride, _stream(H)),
+                  "kgat_bi2_f32")
+    return h_out
+
+
+def bi2_train(H, HN, W1, W2, negative_slope, drop_p, seed, norm_out=None, row0=0, self_out=None):
+    """Training form of `bi2` (kgat_bi2_train_f32): returns (h_out, signs) - the dropped sum of the two terms and the
+    (n, d_out) uint8 sign record, bit 0 = (z1 > 0), bit 1 = (z2 > 0), that bi2_bwd_pre reads."""
+    H = _need(H, torch.float32, "H")
+    HN = _need(HN, torch.float32, "HN", H.shape)
+    n, d_in = H.shape
+    W1, W2, d_out = _bi2_weights(W1, W2, d_in)
+    h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
+    signs = torch.empty((n, d_out), dtype=torch.uint8, device=H.device)
+    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
+    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    with _timed("bi2", (n, d_in, d_out)):
+        check(_lib.load().kgat_bi2_train_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W1), _ptr(W2), float(negative_slope),
+                                             float(drop_p), int(seed) & (2 ** 64 - 1), int(row0), _ptr(h_out), _ptr(signs),
+                                             _ptr(norm_out), stride, _ptr(self_out), self_stride, _stream(H)),
+              "kgat_bi2_train_f32")
+    return h_out, signs
+
+
+def bi2_bwd_pre(h_out, signs, grad_a, grad_b, grad_norm, negative_slope, drop_p, seed, row0=0):
+    """(grad_z1, grad_z2) of the two-term training layer (kgat_bi2_bwd_pre_f32): bi_interaction_bwd_pre's gradient
+    times LeakyReLU'(z1) and times LeakyReLU'(z2), the slopes from bi2_train's sign record."""
+    h_out = _need(h_out, torch.float32, "h_out")
+    n, d = h_out.shape
+    signs = _need(signs, torch.uint8, "signs", (n, d))
+    for name, t in (("grad_a", grad_a), ("grad_b", grad_b)):
+        if t is not None:
+            _need(t, torch.float32, name, (n, d))
+    stride = _strided_rows(grad_norm, n, d, "grad_norm") if grad_norm is not None else 0
+    gz1, gz2 = torch.empty_like(h_out), torch.empty_like(h_out)
+    check(_lib.load().kgat_bi2_bwd_pre_f32(n, d, _ptr(h_out), _ptr(signs), _ptr(grad_a), _ptr(grad_b), _ptr(grad_norm),
+                                           stride, float(negative_slope), float(drop_p), int(seed) & (2 ** 64 - 1),
+                                           int(row0), _ptr(gz1), _ptr(gz2), _stream(h_out)), "kgat_bi2_bwd_pre_f32")
+    return gz1, gz2
+
+
+def _bi2_bwd_operands(grad_z1, grad_z2, H, HN):
+    grad_z1 = _need(grad_z1, torch.float32, "grad_z1")
+    grad_z2 = _need(grad_z2, torch.float32, "grad_z2", grad_z1.shape)
+    n, d_out = grad_z1.shape
+    H = _need(H, torch.float32, "H")
+    if H.shape[0] != n:
+        raise ValueError("H has %d rows, grad_z1 %d" % (H.shape[0], n))
+    HN = _need(HN, torch.float32, "HN", H.shape)
+    return grad_z1, grad_z2, H, HN, n, H.shape[1], d_out
+
+
+def bi2_bwd_input(grad_z1, grad_z2, W1, W2, H, HN):
+    """(grad_agg, grad_self) = (P1 + P2 * H, P1 + P2 * HN) with P1 = grad_z1 @ W1, P2 = grad_z2 @ W2 in one pass
+    (kgat_bi2_bwd_input_f32): what the reversed-CSR aggregation sums and what goes to h directly."""
+    grad_z1, grad_z2, H, HN, n, d_in, d_out = _bi2_bwd_operands(grad_z1, grad_z2, H, HN)
+    W1, W2, wd = _bi2_weights(W1, W2, d_in)
+    if wd != d_out:
+        raise ValueError("W1 has shape %s, expected (%d, *)" % (tuple(W1.shape), d_out))
+    t, gb = torch.empty_like(H), torch.empty_like(H)
+    check(_lib.load().kgat_bi2_bwd_input_f32(n, d_in, d_out, _ptr(grad_z1), _ptr(grad_z2), _ptr(W1), _ptr(W2), _ptr(H),
+                                             _ptr(HN), _ptr(t), _ptr(gb), _stream(H)), "kgat_bi2_bwd_input_f32")
+    return t, gb
+
+
+def bi2_bwd_weight(grad_z1, grad_z2, H, HN, want_partials=False):
+    """(grad_W1, grad_W2) = (grad_z1^T (H + HN), grad_z2^T (H * HN)) (kgat_bi2_bwd_weight_f32's partials, summed here
+    in index order - or, want_partials=True, handed back for sum_partials)."""
+    grad_z1, grad_z2, H, HN, n, d_in, d_out = _bi2_bwd_operands(grad_z1, grad_z2, H, HN)
+    lib = _lib.load()
+    nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
+    p1 = torch.empty((nb, d_out, d_in), dtype=torch.float32, device=H.device)
+    p2 = torch.empty_like(p1)
+    check(lib.kgat_bi2_bwd_weight_f32(n, d_in, d_out, _ptr(grad_z1), _ptr(grad_z2), _ptr(H), _ptr(HN), _ptr(p1), _ptr(p2),
+                                      nb, _stream(H)), "kgat_bi2_bwd_weight_f32")
+    return (p1, p2) if want_partials else (p1.sum(0), p2.sum(0))
+
+
 def mul2(a, b, c):
     """(a * b, a * c) in one pass."""
     a = _need(a, torch.float32, "a")

@@ -362,7 +362,7 @@ class GraphedForward:
                 attention(state)
                 state["out"] = model.gnn(g)
             return [(whole, None)]
-        if not all(hasattr(layer, "res_fc_2") for layer in layers):
+        if not all(hasattr(layer, "res_fc_2") and getattr(layer, "_res_type", "Bi") == "Bi" for layer in layers):
             from .graph import DGLError
             raise DGLError("a partitioned graph runs the Bi aggregator only (res_type %r)"
                            % (getattr(model, "_res_type", None),))

@@ -133,9 +133,10 @@ def parse_args(argv=None):
     ap.add_argument("--gnn_hidden_size", type=int, default=64)
     ap.add_argument("--gnn_model", choices=("kgat", "graphsage"), default="kgat",
                     help="propagation layers (reference kgat.py:23): bi-interaction KGATConv or SAGEConv (mean)")
-    ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage"), default="Bi",
+    ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage", "Bi2"), default="Bi",
                     help="aggregator of the kgat layers (KGATConv res_type, reference models.py:50-58): Bi-Interaction "
-                         "(the reference's), GCN or GraphSage")
+                         "(the reference's one-term form), GCN, GraphSage, or Bi2, the KGAT paper's two-term "
+                         "Bi-Interaction (eq. 8)")
     ap.add_argument("--dropout_rate", type=float, default=0.1)
     ap.add_argument("--lr", type=float, default=0.0001)
     ap.add_argument("--batch_size", type=int, default=10240)

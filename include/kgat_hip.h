@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define KGAT_ABI_VERSION 12
+#define KGAT_ABI_VERSION 13
 
 enum {
   KGAT_OK = 0,
@@ -524,6 +524,63 @@ int kgat_aggregator_bwd_input_f32(int form, int64_t n_rows, int d_in, int d_out,
  * n_partials = kgat_bi_interaction_bwd_weight_partials(n_rows), the caller adds them (kgat_sum_partials_f32). */
 int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
                                    const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream);
+
+/* ---------------------------------------------------------------- the two-term Bi-Interaction aggregator ("Bi2")
+ * (ABI 13) The Bi-Interaction aggregator as the KGAT paper states it (Wang et al. 2019, eq. 8, and the authors' code):
+ *   z1 = (H + HN) W1^T   W1 = res_fc.weight   (d_out x d_in; the line the reference keeps commented out, models.py:55)
+ *   z2 = (H * HN) W2^T   W2 = res_fc_2.weight (d_out x d_in; the reference's own term, models.py:66)
+ *   Z  = LeakyReLU_slope(z1) + LeakyReLU_slope(z2),   out = mess_drop(Z) (one mask on the sum, models.py:70)
+ * i.e. KGATConv with res_type "Bi2".  No bias; HN = update_all(u_mul_e('h','w','m'), sum('m','h_neighbor')) (models.py:63).
+ * The activation sits between the contractions and the sum: the kernels keep two accumulator sets per 16-row tile and
+ * stage both weights in LDS.  Not a `form` of the kgat_aggregator_* entries (two weights, and the backward needs a
+ * record those do not have).  Widths (kgat_bi2_supported / kgat_bi2_bwd_supported): d_in, d_out in {16, 32, 64, 128};
+ * others: KGAT_E_UNSUPPORTED (a caller forms those in library GEMMs).  All entries are bitwise reproducible from call
+ * to call (no atomics) and check their arguments before any device work.
+ *
+ * kgat_bi2_f32 / kgat_bi2_deferred_f32: the no-grad layer, with the arguments and outputs of kgat_aggregator_f32 /
+ * kgat_aggregator_deferred_f32 and W1, W2 in W's place - h_out (n_rows x d_out, may be NULL if norm_out is given), the
+ * L2-normalised rows into norm_out (row stride norm_stride: a column slice of the readout), the rows of H into
+ * self_out (the ego block).  The deferred entry forms the rows the aggregation's KGAT_SPMM_DEFER_FINISH launch left as
+ * tile partials and gives the plain entry's bits.
+ * kgat_bi2_train_f32: the training form - hash dropout (drop_p, seed, row0 as kgat_bi_interaction_train_f32) on the sum
+ * of the two terms; h_out is required.  It also writes the SIGN RECORD `signs`, n_rows x d_out bytes (4-byte aligned):
+ * bit 0 = (z1 > 0), bit 1 = (z2 > 0) of that element before dropout - the sign of the saved output no longer tells
+ * LeakyReLU'(z1) and LeakyReLU'(z2) apart (LeakyReLU'(0) = slope, as in kgat_bi_interaction_bwd_pre_f32). */
+int kgat_bi2_supported(int d_in, int d_out);
+int kgat_bi2_bwd_supported(int d_in, int d_out);
+int kgat_bi2_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1, const float* W2,
+                 float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
+                 int64_t self_stride, kgat_stream_t stream);
+int kgat_bi2_deferred_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
+                          const float* W2, float negative_slope, float* h_out, float* norm_out, int64_t norm_stride,
+                          float* self_out, int64_t self_stride, const int32_t* indptr_rows, int64_t e_begin,
+                          int64_t e_end, const void* spmm_workspace, int tile_edges, kgat_stream_t stream);
+int kgat_bi2_train_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
+                       const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* h_out,
+                       uint8_t* signs, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
+                       kgat_stream_t stream);
+/* Backward head of the two-term layer (the autograd of F.normalize, mess_drop and the two LeakyReLU): with
+ *   g = [grad_a + grad_b + normalize_bwd(grad_norm; h_out)] * keep / (1 - p)
+ * exactly as kgat_bi_interaction_bwd_pre_f32 forms it before its last factor, it writes BOTH
+ *   grad_z1 = g * LeakyReLU'(z1)   and   grad_z2 = g * LeakyReLU'(z2)      (n_rows x d_out each)
+ * with the two slopes read from the training forward's sign record, so that the dense backward kernels read plain
+ * gradients.  grad_a / grad_b / grad_norm may be NULL. */
+int kgat_bi2_bwd_pre_f32(int64_t n_rows, int d_out, const float* h_out, const uint8_t* signs, const float* grad_a,
+                         const float* grad_b, const float* grad_norm, int64_t grad_norm_stride, float negative_slope,
+                         float drop_p, uint64_t seed, int64_t row0, float* grad_z1, float* grad_z2,
+                         kgat_stream_t stream);
+/* Backward towards the inputs: P1 = grad_z1 W1 and P2 = grad_z2 W2 per 16-row tile (never written), and in one pass
+ *   grad_agg  = P1 + P2 * H    (what the reversed-CSR aggregation then sums: ONE aggregation per layer)
+ *   grad_self = P1 + P2 * HN   (goes to h directly)                        (both n_rows x d_in) */
+int kgat_bi2_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z1, const float* grad_z2,
+                           const float* W1, const float* W2, const float* H, const float* HN, float* grad_agg,
+                           float* grad_self, kgat_stream_t stream);
+/* grad_W1 = grad_z1^T (H + HN) and grad_W2 = grad_z2^T (H * HN) as per-workgroup partials, in ONE launch that reads the
+ * rows of H and HN once (the slab scheme of kgat_aggregator_bwd_weight_f32): partials_w1[b], partials_w2[b] are d_out x d_in,
+ * n_partials = kgat_bi_interaction_bwd_weight_partials of n_rows, the caller adds them (kgat_sum_partials_f32). */
+int kgat_bi2_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z1, const float* grad_z2,
+                            const float* H, const float* HN, float* partials_w1, float* partials_w2, int64_t n_partials,
+                            kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- GraphSAGE layer (gnn_model = "graphsage")
  * The kernels behind dgl.nn.pytorch.conv.SAGEConv(d_in, d_out, aggregator_type="mean", feat_drop, activation) of

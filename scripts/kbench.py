@@ -6,7 +6,7 @@ path or of bench.py's contract).  Interleaved rounds in one process, HIP events 
   python scripts/kbench.py spmm  [--algos merge,rows,rows_ordered] [--dim 64]
   python scripts/kbench.py softmax
   python scripts/kbench.py sage    (GraphSAGE layer launches beside the KGAT layer's, and the CF step of both models)
-  python scripts/kbench.py agg     (the KGAT layer per res_type - Bi, GCN, GraphSage - interleaved: no-grad layer,
+  python scripts/kbench.py agg     (the KGAT layer per res_type - Bi, GCN, GraphSage, Bi2 - interleaved: no-grad layer,
                                     backward launches, CF step)
 """
 import argparse
@@ -240,7 +240,7 @@ def main():
         for gm, v in res.items():
             print("CF step (fwd+bwd+Adam, 3 layers, batch %d) gnn_model=%-9s median %.3f ms" % (B, gm, 1e3 * float(np.median(v))))
     elif args.kernel == "agg":
-        # KGATConv's three aggregators (res_type): per form the no-grad layer (aggregation + dense kernel with the
+        # KGATConv's aggregators (res_type; Bi2, the two-term Bi-Interaction, has entries of its own: added explicitly): per form the no-grad layer (aggregation + dense kernel with the
         # normalised slice), its dense kernel alone, and the dense part's backward launches (bwd_input + bwd_weight),
         # interleaved with Bi's; then the CF step of the three models, alternating
         import time
@@ -263,6 +263,13 @@ def main():
                 fns[name + ".dense"] = lambda f=f, W=W: ops.aggregator(f, X, HN, W, 0.01, norm_out=norm)
                 fns[name + ".bwd_input"] = lambda f=f, W=W: ops.aggregator_bwd_input(f, GZ, W, X, HN)
                 fns[name + ".bwd_weight"] = lambda f=f: ops.aggregator_bwd_weight(f, GZ, X, HN, want_partials=True)
+            W1, W2 = torch.randn(do, di, device=dev) * 0.1, torch.randn(do, di, device=dev) * 0.1
+            GZ2 = torch.randn(n, do, device=dev)
+            fns["Bi2.layer"] = lambda W1=W1, W2=W2: ops.bi2(
+                X, ops.spmm(indptr, col, row_of, X, w, workspace=ws), W1, W2, 0.01, norm_out=norm)
+            fns["Bi2.dense"] = lambda W1=W1, W2=W2: ops.bi2(X, HN, W1, W2, 0.01, norm_out=norm)
+            fns["Bi2.bwd_input"] = lambda W1=W1, W2=W2: ops.bi2_bwd_input(GZ, GZ2, W1, W2, X, HN)
+            fns["Bi2.bwd_weight"] = lambda: ops.bi2_bwd_weight(GZ, GZ2, X, HN, want_partials=True)
             t = timeit(fns, args.rounds)
             med = {k: float(np.median(v)) for k, v in t.items()}
             print("%d -> %d" % (di, do))
@@ -274,7 +281,7 @@ def main():
         ni = torch.randint(70679, 95594, (B,), device=dev).int()
         graph = synth.build_graph(n, trip, dev)
         steps = {}
-        for rt in forms:
+        for rt in list(forms) + ["Bi2"]:
             torch.manual_seed(0)
             model = K.KGATPropagation(n, R, D, D, 3, D, dropout=0.1, res_type=rt).to(dev)
             opt = K.FusedAdam(model.parameters(), lr=0.01)
