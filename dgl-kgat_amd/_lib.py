@@ -23,6 +23,7 @@ SOURCES = {
     "kgat_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_transr.hip": [],
     "kgat_eval.hip": [],
+    "kgat_eval_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_optim.hip": [],
     "kgat_bpr.hip": [],
     "kgat_sage.hip": [],
@@ -147,6 +148,10 @@ SIGNATURES = {
     "kgat_bi2_bwd_weight_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "kgat_eval_recall_ndcg_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p,
                                          _p, _p, _p]),
+    "kgat_eval_topk_supported": (_i32, [_i32, _i32]),
+    "kgat_eval_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "kgat_eval_topk_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _sz, _p, _p, _p]),
+    "kgat_eval_metrics_at_ks": (_i32, [_i64, _i32, _p, _p, _p, _i32, _p, _p, _p, _p]),
 }
 
 _lib = None
@@ -165,7 +170,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def source_hash():

@@ -10,6 +10,11 @@ no (users x items) score matrix, no sort of 24,915 scores per user.  Equal score
 position (what the reference's stable CPU ``th.sort`` gives: among the masked zeros the lower
 index first).  ``calc_recall_ndcg_sorted`` is the batched matmul + full stable sort of rounds
 1-4, kept as an independent check of the kernel (tests); nothing dispatches to it.
+
+``calc_metrics`` gives the KGAT paper's table - recall, ndcg, precision and hit ratio at several
+cut-offs up to 128 - from one sweep at the largest cut-off (``kgat_eval_topk_f32`` +
+``kgat_eval_metrics_at_ks``, csrc/kgat_eval_topk.hip); ``recommend`` returns the K best unseen
+items of a list of users with their scores.
 """
 import numpy as np
 import torch
@@ -81,7 +86,7 @@ def calc_recall_ndcg(embedding, train_user_dict, test_user_dict, all_item_id_ran
     (``KGATLibraryError`` otherwise), K <= 32; a float64 embedding is ranked in float32 - the kernel's
     arithmetic, and what the reference's fp32 model produces - so near-ties of a float64 input can rank
     differently than a float64 sort would rank them.  ``calc_recall_ndcg_sorted`` (torch operators) takes any K,
-    dtype and device."""
+    dtype and device.  K up to 128, several cut-offs at once, precision and hit ratio: ``calc_metrics``."""
     from . import ops
     if plan is None:
         plan = EvalPlan(train_user_dict, test_user_dict, all_item_id_range, embedding.device)
@@ -102,6 +107,79 @@ def calc_recall_ndcg(embedding, train_user_dict, test_user_dict, all_item_id_ran
     if return_per_user:
         return recall, ndcg
     return float(recall.sum()) / plan.n_users, float(ndcg.sum()) / plan.n_users
+
+
+def _device_rows(embedding, what):
+    from .ops import KGATLibraryError
+    if not embedding.is_cuda:
+        raise KGATLibraryError("%s: the embedding is on %s: the evaluation only runs on a HIP device (no CPU "
+                               "implementation exists in this package)" % (what, embedding.device))
+    emb = embedding.detach()
+    if emb.dtype != torch.float32:
+        emb = emb.float()
+    if emb.stride(1) != 1:
+        emb = emb.contiguous()
+    return emb
+
+
+METRIC_NAMES = ("recall", "ndcg", "precision", "hit_ratio")
+
+
+def calc_metrics(embedding, train_user_dict, test_user_dict, all_item_id_range, Ks=(20, 40, 60, 80, 100), plan=None,
+                 return_per_user=False):
+    """recall, ndcg, precision and hit ratio at every cut-off of ``Ks`` (ascending, distinct, at most 8, each <= 128 -
+    the KGAT paper's table is ``(20, 40, 60, 80, 100)``): one item layout pass, one sweep at ``max(Ks)`` and one
+    metrics launch.  Inputs, masking rule (``metric.py:50``), checks and exceptions as ``calc_recall_ndcg``; recall and
+    ndcg are the reference's (``metric.py:5-7, 23-34``) applied to the first k ranks, precision = hits / k, hit ratio =
+    1 if any hit.  Returns a dict ``{"recall", "ndcg", "precision", "hit_ratio"}`` of float64 numpy arrays of
+    ``len(Ks)`` - means over the test users - or, with ``return_per_user``, of ``(n_users, len(Ks))`` tensors."""
+    from . import ops
+    Ks = [int(k) for k in Ks]
+    if not 1 <= len(Ks) <= 8:
+        raise ValueError("calc_metrics: 1 to 8 cut-offs, got %d" % len(Ks))
+    if Ks[0] < 1 or any(b <= a for a, b in zip(Ks, Ks[1:])):
+        raise ValueError("calc_metrics: the cut-offs must be positive, ascending and distinct: %r" % (Ks,))
+    if Ks[-1] > 128:
+        raise ops.KGATLibraryError("calc_metrics: cut-off %d is beyond the kernel's 128" % Ks[-1])
+    emb = _device_rows(embedding, "calc_metrics")
+    if plan is None:
+        plan = EvalPlan(train_user_dict, test_user_dict, all_item_id_range, embedding.device)
+    if plan.n_users == 0:
+        raise ZeroDivisionError("no test users")   # (metric.py:65 divides by len(test_user_dict))
+    if plan.max_node_id >= embedding.shape[0]:
+        raise IndexError("user / item node id %d outside the embedding's %d rows" % (plan.max_node_id,
+                                                                                    embedding.shape[0]))
+    with torch.no_grad():
+        topk = ops.eval_topk(emb, plan.user_ids, plan.item_ids, plan.train_ptr, plan.train_items, Ks[-1],
+                             want_scores=False)
+        out = ops.eval_metrics_at_ks(topk, plan.test_ptr, plan.test_items, Ks)
+    if return_per_user:
+        return {name: out[:, :, m] for m, name in enumerate(METRIC_NAMES)}
+    mean = (out.sum(0) / plan.n_users).cpu().numpy()
+    return {name: mean[:, m].copy() for m, name in enumerate(METRIC_NAMES)}
+
+
+def recommend(embedding, user_ids, all_item_id_range, K, seen=None):
+    """The K best items of every user of ``user_ids`` (node ids) that the user has not seen: ``(items, scores)`` -
+    int64 item NODE ids ``(len(user_ids), K)`` in rank order (score descending, equal scores in the order of
+    ``all_item_id_range``) and their float32 scores; a user with fewer than K unseen items gets ``-1`` / ``-inf`` at
+    the end.  ``seen`` maps a user id to the items to leave out, as positions in ``all_item_id_range`` (a dict like
+    ``train_user_dict``; None: nothing is left out).  1 <= K <= 128; HIP tensors only."""
+    from . import ops
+    emb = _device_rows(embedding, "recommend")
+    users = [int(u) for u in np.asarray(user_ids).reshape(-1)]
+    plan = EvalPlan(seen if seen is not None else {}, dict.fromkeys(users, _EMPTY), all_item_id_range, embedding.device)
+    if len(plan.user_ids) != len(users):
+        raise ValueError("recommend: a user is listed twice")
+    if plan.n_users and plan.max_node_id >= embedding.shape[0]:
+        raise IndexError("user / item node id %d outside the embedding's %d rows" % (plan.max_node_id,
+                                                                                    embedding.shape[0]))
+    with torch.no_grad():
+        topk, scores = ops.eval_topk(emb, plan.user_ids, plan.item_ids, plan.train_ptr, plan.train_items, K,
+                                     drop_train=True)
+        pos = topk.long()
+        items = torch.where(pos >= 0, plan.item_ids.long()[pos.clamp(min=0)], pos) if plan.n_items else pos
+    return items, scores
 
 
 def calc_recall_ndcg_sorted(embedding, train_user_dict, test_user_dict, all_item_id_range, K=20, batch_users=2048):

@@ -1353,6 +1353,73 @@ def eval_recall_ndcg(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, 
     return (recall, ndcg, topk) if want_topk else (recall, ndcg)
 
 
+def eval_topk_supported(F, K):
+    return bool(_lib.load().kgat_eval_topk_supported(int(F), int(K)))
+
+
+def eval_topk(emb, user_ids, item_ids, train_ptr, train_items, K, drop_train=False, want_scores=True):
+    """The K best items of every user in rank order (reference metric.py:48-51), 1 <= K <= 128, on the device:
+    kgat_eval_items_kmajor_f32 + kgat_eval_topk_f32.  Arguments as eval_recall_ndcg.  drop_train=False is the
+    reference's rule (a training item scores 0.0 and can rank; needs n_items >= K); drop_train=True never lists a
+    training item and pads a short list.  Returns (topk[, scores]) - int32 item POSITIONS (n_users, K), -1 padding,
+    and float32 scores, -inf padding."""
+    if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
+        raise KGATLibraryError("eval_topk: `emb` must be a float32 HIP matrix with unit column stride")
+    F, stride = emb.shape[1], emb.stride(0)
+    user_ids = _need(user_ids, torch.int32, "user_ids")
+    item_ids = _need(item_ids, torch.int32, "item_ids")
+    n_users, n_items = user_ids.numel(), item_ids.numel()
+    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
+    train_items = _need(train_items, torch.int32, "train_items")
+    K = int(K)
+    lib = _lib.load()
+    if not lib.kgat_eval_topk_supported(F, K):
+        raise KGATLibraryError("eval_topk: K = %d / F = %d outside the kernel's range" % (K, F))
+    dev = emb.device
+    topk = torch.empty((n_users, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((n_users, K), dtype=torch.float32, device=dev) if want_scores else None
+    if n_users == 0:
+        return (topk, scores) if want_scores else topk
+    itemT = torch.empty(max(int(lib.kgat_eval_items_elems(n_items, F)), 1), dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.kgat_eval_topk_workspace_bytes(n_users, n_items, F, K), dtype=torch.uint8, device=dev)
+    with _timed("eval_items_kmajor", (n_items, F)):
+        check(lib.kgat_eval_items_kmajor_f32(n_items, F, _ptr(emb), stride, _ptr(item_ids), _ptr(itemT), _stream(emb)),
+              "kgat_eval_items_kmajor_f32")
+    with _timed("eval_topk", (n_users, n_items, F, K)):
+        check(lib.kgat_eval_topk_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
+                                     _ptr(train_ptr), _ptr(train_items), K, 1 if drop_train else 0, _ptr(ws),
+                                     ws.numel(), _ptr(topk), _ptr(scores) if want_scores else None, _stream(emb)),
+              "kgat_eval_topk_f32")
+    return (topk, scores) if want_scores else topk
+
+
+def eval_metrics_at_ks(topk, test_ptr, test_items, ks):
+    """recall / ndcg / precision / hit ratio of ranked lists at the ascending cut-offs `ks` (at most 8, each <= the
+    lists' width; reference metric.py:52-63 per cut-off) - kgat_eval_metrics_at_ks.  `topk` int32 (n_users, K) item
+    positions (-1 never hits), the test lists as in eval_recall_ndcg.  Returns float64 (n_users, len(ks), 4)."""
+    if topk.dtype != torch.int32 or not topk.is_cuda or topk.dim() != 2 or not topk.is_contiguous():
+        raise KGATLibraryError("eval_metrics_at_ks: `topk` must be a contiguous int32 HIP matrix")
+    n_users, K = topk.shape
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 8:
+        raise ValueError("eval_metrics_at_ks: 1 to 8 cut-offs, got %d" % len(ks))
+    if any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1 or ks[-1] > K:
+        raise ValueError("eval_metrics_at_ks: the cut-offs must ascend within 1..%d: %r" % (K, ks))
+    test_ptr = _need(test_ptr, torch.int32, "test_ptr", (n_users + 1,))
+    test_items = _need(test_items, torch.int32, "test_items")
+    import ctypes
+    import numpy as np
+    dev = topk.device
+    disc = torch.as_tensor(1.0 / np.log2(np.arange(2, K + 2)), dtype=torch.float64, device=dev)
+    out = torch.zeros((n_users, len(ks), 4), dtype=torch.float64, device=dev)
+    ks_host = (ctypes.c_int32 * len(ks))(*ks)
+    with _timed("eval_metrics_at_ks", (n_users, K, len(ks))):
+        check(_lib.load().kgat_eval_metrics_at_ks(n_users, K, _ptr(topk), _ptr(test_ptr), _ptr(test_items), len(ks),
+                                                  ctypes.cast(ks_host, ctypes.c_void_p), _ptr(disc), _ptr(out),
+                                                  _stream(topk)), "kgat_eval_metrics_at_ks")
+    return out
+
+
 def bpr_loss(emb, u, p, n, reg_lambda):
     """BPR loss of reference models.py:170-178 on the readout (kgat_bpr_loss_f32).  Returns (loss (0-dim), coef (B,),
     workspace) - the last two feed bpr_grad."""

@@ -121,6 +121,16 @@ def user_dict(pairs, item_offset):
     return {int(u): p[s:e, 1] - item_offset for u, s, e in zip(users, start, list(start[1:]) + [len(p)])}
 
 
+def _cutoffs(text):
+    try:
+        ks = [int(x) for x in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("a comma-separated list of integers, e.g. 20,40,60,80,100")
+    if not 1 <= len(ks) <= 8 or ks[0] < 1 or ks[-1] > 128 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise argparse.ArgumentTypeError("1 to 8 ascending, distinct cut-offs in 1..128")
+    return ks
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_dir", default=None)
@@ -146,6 +156,10 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--eval_before", action="store_true", help="evaluate the untrained model first (epoch 0)")
     ap.add_argument("--log_json", default=None, help="write the per-epoch records (phase wall-clock, losses, metrics) here")
+    ap.add_argument("--Ks", type=_cutoffs, default=[20], metavar="K[,K...]",
+                    help="evaluation cut-offs, ascending (the KGAT paper's table: 20,40,60,80,100; at most 8, each <= "
+                         "128).  The default keeps recall@20 / ndcg@20; a longer list logs recall, ndcg, precision and "
+                         "hit ratio at every cut-off (metrics.calc_metrics)")
     ap.add_argument("--grad_digest", action="store_true",
                     help="print |grad| sums of the first CF step (to compare an N-GPU run with the one-GPU run)")
     args = ap.parse_args(argv)
@@ -240,9 +254,17 @@ def main(argv=None):
             for name, g, seen, held in (("valid", train_g, train_dict, valid_dict), ("test", test_g, train_valid_dict, test_dict)):
                 g.edata["w"] = model.compute_attention(g)
                 emb = model.gnn(g, g.ndata["id"])
-                rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
-                    emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
-                say("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+                if args.Ks == [20]:
+                    rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
+                        emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
+                    say("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+                    continue
+                m = metrics.calc_metrics(emb, seen, held, ds.item_id_range, Ks=args.Ks, plan=plans[name])
+                for j, k in enumerate(args.Ks):
+                    for metric in metrics.METRIC_NAMES:
+                        rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                    say("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
+                        name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
         rec["eval_s"] = clock() - t0
         say("           | eval %.4fs" % rec["eval_s"])
 

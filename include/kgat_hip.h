@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define KGAT_ABI_VERSION 13
+#define KGAT_ABI_VERSION 14
 
 enum {
   KGAT_OK = 0,
@@ -718,7 +718,8 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
  * kgat_eval_items_kmajor_f32 first lays the item rows out as MFMA fragments (itemT: kgat_eval_items_elems floats).
  * disc[K] = 1 / log2(k + 2) in fp64 (host-computed, so the device divides by the very values numpy uses).
  * recall_out / ndcg_out: n_users doubles; topk_out (optional, n_users x K): the ranked item positions.
- * Needs 1 <= K <= 32, n_items >= K, F <= ~1100 (kgat_eval_supported).  Bitwise reproducible. */
+ * Needs 1 <= K <= 32, n_items >= K, F <= ~1100 (kgat_eval_supported).  Bitwise reproducible.
+ * (Ranked lists with scores, K up to 128 and further metrics: kgat_eval_topk_f32 / kgat_eval_metrics_at_ks below.) */
 int kgat_eval_supported(int F, int K);
 int64_t kgat_eval_items_elems(int64_t n_items, int F);
 int kgat_eval_items_kmajor_f32(int64_t n_items, int F, const float* emb, int64_t emb_stride, const int32_t* item_ids,
@@ -729,6 +730,35 @@ int kgat_eval_recall_ndcg_f32(int64_t n_users, const int32_t* user_ids, int64_t 
                               const int32_t* train_items, const int32_t* test_ptr, const int32_t* test_items, int K,
                               const double* disc, void* workspace, size_t workspace_bytes, double* recall_out,
                               double* ndcg_out, int32_t* topk_out, kgat_stream_t stream);
+
+/* (ABI 14) The ranked list itself, for 1 <= K <= 128, and the metrics of the KGAT paper's table at several cut-offs.
+ * kgat_eval_topk_f32 replaces metric.py:48-51 (score, mask, sort - the K first of the descending sort, for every user
+ * of user_ids): same inputs and the same total order as kgat_eval_recall_ndcg_f32 (itemT from
+ * kgat_eval_items_kmajor_f32); for K <= 32 it launches that entry's sweep, beyond it a sweep over a candidate buffer of
+ * 128 (K <= 64) or 156 entries per user (four wavefronts' buffers in a CU's LDS).  topk_items (n_users x K, int32):
+ * item POSITIONS in rank order, padded with -1; topk_scores (optional, n_users x K, fp32): their scores, padding -inf.
+ *   drop_train == 0 ("mask", metric.py:50): a training item scores 0.0 and can rank; needs n_items >= K.
+ *   drop_train != 0 ("drop"): training items are never listed - the list a recommender shows; a user with fewer than K
+ *     other items gets padding at the end; any n_items >= 1.
+ * kgat_eval_topk_supported: 1 <= K <= 128 and an F whose rows fit beside the buffer (F <= 352 in registers; in LDS
+ * F <= ~1100 for K <= 32, ~1000 for K <= 64, ~950 beyond).  Errors before any device work: bad sizes / null pointers
+ * KGAT_E_BADARG, K or F outside the range KGAT_E_UNSUPPORTED, workspace_bytes < kgat_eval_topk_workspace_bytes
+ * KGAT_E_WORKSPACE (the segments' partial lists: n_users x n_lists x K x 8 bytes).  Bitwise reproducible.
+ * kgat_eval_metrics_at_ks replaces metric.py:52-63 for n_ks <= 8 cut-offs ks[j] (a HOST array, ascending, 1 <= ks[j]
+ * <= K) over ranked lists topk_items (n_users x K, -1 never hits) and the test lists (CSR, ascending):
+ *   out[u][j] = { recall (one_recall_at_k :5-7; 0 for an empty test list), ndcg (one_ndcg_at_k :23-34: the DCG of the
+ *   first ks[j] ranks over the DCG of the user's own sorted hit list within them), precision = hits / ks[j],
+ *   hit ratio = 1 if any hit else 0 }  - n_users x n_ks x 4 doubles; disc[K] as above, summed in ascending rank order:
+ *   for ks[j] <= 32 recall and ndcg equal kgat_eval_recall_ndcg_f32's at K = ks[j] bit for bit. */
+int kgat_eval_topk_supported(int F, int K);
+size_t kgat_eval_topk_workspace_bytes(int64_t n_users, int64_t n_items, int F, int K);
+int kgat_eval_topk_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
+                       int64_t emb_stride, const float* itemT, const int32_t* train_ptr, const int32_t* train_items,
+                       int K, int drop_train, void* workspace, size_t workspace_bytes, int32_t* topk_items,
+                       float* topk_scores, kgat_stream_t stream);
+int kgat_eval_metrics_at_ks(int64_t n_users, int K, const int32_t* topk_items, const int32_t* test_ptr,
+                            const int32_t* test_items, int n_ks, const int32_t* ks, const double* disc, double* out,
+                            kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- optimiser of the training loop (8f #1, #3)
  * One step of torch.optim.Adam (reference kgat.py:85: optim.Adam(model.parameters(), lr); amsgrad off, no weight
