@@ -551,6 +551,8 @@ def edge_softmax_bwd(indptr, eid, a, grad_a, row_range=None):
         eid = _need(eid, torch.int32, "eid", a.shape)
     row0, n_rows = (0, indptr.numel() - 1) if row_range is None else row_range
     out = torch.zeros_like(a)
+    if a.numel() == 0:  # rows without a single edge: nothing to write, and empty tensors have no storage to point at
+        return out
     check(_lib.load().kgat_edge_softmax_bwd_f32(n_rows, row0, _ptr(indptr), _ptr(eid), _ptr(a),
                                                 _ptr(grad_a), _ptr(out), _stream(a)),
           "kgat_edge_softmax_bwd_f32")

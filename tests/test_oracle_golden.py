@@ -144,6 +144,45 @@ def test_edge_softmax_backward_fd():
         assert abs(fd - gs[i]) < 1e-7
 
 
+def test_sddmm_dot_matches_dense(golden):
+    """orc.sddmm_dot (the reference of the GPU tests' weight gradients) against the dense product it samples."""
+    g = golden
+    rng = np.random.default_rng(6)
+    X = g["entity_embed"].astype(np.float64)
+    G = rng.standard_normal(X.shape)
+    got = orc.sddmm_dot(g["src"], g["dst"], X, G)
+    assert got.shape == (len(g["src"]),)
+    assert rel_err(got, (G @ X.T)[g["dst"], g["src"]]) < 1e-12
+
+
+def test_spmm_backward_fd():
+    """Central differences of sum(spmm_u_mul_e_sum(X, w) * G) - bilinear, so exact up to rounding - against
+    orc.sddmm_dot (w.r.t. the weights) and orc.spmm_backward_x (w.r.t. the features); self-loops and parallel
+    edges included."""
+    rng = np.random.default_rng(7)
+    n, e, d = 6, 20, 3
+    src, dst = rng.integers(0, n, e), rng.integers(0, n, e)
+    dst[0] = src[0]
+    src[1:4], dst[1:4] = src[4], dst[4]
+    X = rng.standard_normal((n, d))
+    w = rng.standard_normal(e)
+    G = rng.standard_normal((n, d))
+    gw = orc.sddmm_dot(src, dst, X, G)
+    gx = orc.spmm_backward_x(n, src, dst, G, w)
+
+    def f(X_, w_):
+        return float(np.sum(orc.spmm_u_mul_e_sum(n, src, dst, X_, w_) * G))
+    eps = 1e-6
+    for i in range(e):
+        wp = w.copy(); wp[i] += eps
+        wm = w.copy(); wm[i] -= eps
+        assert abs((f(X, wp) - f(X, wm)) / (2 * eps) - gw[i]) < 1e-7
+    for u, c in [(0, 0), (1, 2), (int(src[4]), 1), (int(dst[4]), 0), (5, 2)]:
+        Xp = X.copy(); Xp[u, c] += eps
+        Xm = X.copy(); Xm[u, c] -= eps
+        assert abs((f(Xp, w) - f(Xm, w)) / (2 * eps) - gx[u, c]) < 1e-7
+
+
 def test_c1_config_cpu_anchor():
     """BASELINE configs[0] - the reference's own CPU-runnable case (last-fm CKG, 1 propagation
     layer, embed_dim = 8) - on a 5 % last-fm-shaped graph: the two independently written CPU
