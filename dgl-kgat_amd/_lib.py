@@ -27,6 +27,7 @@ SOURCES = {
     "kgat_optim.hip": [],
     "kgat_bpr.hip": [],
     "kgat_sage.hip": [],
+    "kgat_edge_weights.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -152,6 +153,8 @@ SIGNATURES = {
     "kgat_eval_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "kgat_eval_topk_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _sz, _p, _p, _p]),
     "kgat_eval_metrics_at_ks": (_i32, [_i64, _i32, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "kgat_edge_norm_f32": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p]),
+    "kgat_edge_dropout_f32": (_i32, [_i64, _p, _p, C.c_float, C.c_uint64, _p, _p]),
 }
 
 _lib = None
@@ -170,7 +173,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def source_hash():

@@ -218,16 +218,22 @@ class _GNNTrain(torch.autograd.Function):
     KGATConv's res_type); the backward is routed by it, its structure is the same for all three.  ops.BI2_FORM: the
     paper's two-term Bi-Interaction - such a layer has TWO weights in `weights` (W1 on h + h_N, then W2 on h * h_N), its
     forward also saves the sign record, its backward head writes two gradients, and its backward towards the inputs
-    still ends in ONE reversed aggregation."""
+    still ends in ONE reversed aggregation.
+    `edge` = (edge_p, edge_seed): node dropout - with edge_p > 0 every layer aggregates over ONE dropped adjacency, the
+    forward stream ops.edge_dropout(w_csr, csr.eid, ...) formed here, the reversed stream ops.edge_dropout(w_rev,
+    csr_rev.eid, ...) formed in backward: keyed by edge id, both hold the same surviving edges.  The edge-id-ordered
+    dropped weights are never formed, and the graph's cached copies of the undropped weights are read, not replaced."""
 
     @staticmethod
-    def forward(ctx, g, slope, drop_p, seed, forms, h0, *weights):
+    def forward(ctx, g, slope, drop_p, seed, forms, edge, h0, *weights):
         st = g._st
         dev = h0.device
         h = h0.detach().contiguous()
         csr = st.csr(dev)
         ew = g.edata["w"]
         w_csr = st.csr_weights(ew)
+        if edge[0] > 0:
+            w_csr = ops.edge_dropout(w_csr, csr.eid, edge[0], edge[1])
         first = [0]  # layer li's weights: weights[first[li]:first[li + 1]]
         for f in forms:
             first.append(first[-1] + (2 if f == ops.BI2_FORM else 1))
@@ -254,7 +260,7 @@ class _GNNTrain(torch.autograd.Function):
             hns.append(hn)
             off += widths[li + 1]
         ctx.g, ctx.slope, ctx.drop_p, ctx.seed, ctx.widths, ctx.ew, ctx.forms = g, slope, drop_p, seed, widths, ew, forms
-        ctx.first = first
+        ctx.first, ctx.edge = first, edge
         ctx.save_for_backward(*hs, *hns, *weights, *signs)
         return out
 
@@ -269,6 +275,8 @@ class _GNNTrain(torch.autograd.Function):
         dev = grad_out.device
         rev = st.csr_rev(dev)
         w_rev = st.rev_weights(ctx.ew)
+        if ctx.edge[0] > 0:
+            w_rev = ops.edge_dropout(w_rev, rev.eid, ctx.edge[0], ctx.edge[1])
         grad_out = grad_out.contiguous()
         offs = [0]
         for wd in ctx.widths:
@@ -283,7 +291,7 @@ class _GNNTrain(torch.autograd.Function):
                                            ctx.slope, ctx.drop_p, ctx.seed + li)
                 kernels = ops.bi2_bwd_supported(hs[li].shape[1], gz1.shape[1])
                 w1, w2 = weights[wi].detach().contiguous(), weights[wi + 1].detach().contiguous()
-                if ctx.needs_input_grad[6 + wi] or ctx.needs_input_grad[7 + wi]:
+                if ctx.needs_input_grad[7 + wi] or ctx.needs_input_grad[8 + wi]:
                     if kernels:
                         p1, p2 = ops.bi2_bwd_weight(gz1, gz2, hs[li], hns[li], want_partials=True)
                         pending += [(wi, p1), (wi + 1, p2)]
@@ -302,7 +310,7 @@ class _GNNTrain(torch.autograd.Function):
                                             ctx.drop_p, ctx.seed + li)
             form, d_in = ctx.forms[li], hs[li].shape[1]
             kernels = ops.aggregator_bwd_supported(form, d_in, gz.shape[1])
-            if ctx.needs_input_grad[6 + first[li]]:
+            if ctx.needs_input_grad[7 + first[li]]:
                 if kernels:
                     # grad_z^T (h * h_N) (h + h_N, [h | h_N]) as per-workgroup partials; every layer's set is summed by
                     # ONE launch at the end
@@ -326,14 +334,14 @@ class _GNNTrain(torch.autograd.Function):
             for (wi, _), summed in zip(pending, ops.sum_partials([p_ for _, p_ in pending])):
                 grad_w[wi] = summed
         grad_h0 = None
-        if ctx.needs_input_grad[5]:
+        if ctx.needs_input_grad[6]:
             g0 = grad_out[:, :ctx.widths[0]]
             if g_a is not None and ctx.widths[0] % 4 == 0 and grad_out.shape[1] % 4 == 0 and g0.data_ptr() % 16 == 0:
                 grad_h0 = ops.add3_rows(g0, g_a, g_b)      # one pass: (g0 + g_a) + g_b, the same additions
             else:
                 grad_h0 = g0 + g_a
                 grad_h0 += g_b
-        return (None, None, None, None, None, grad_h0, *grad_w)
+        return (None, None, None, None, None, None, grad_h0, *grad_w)
 
 
 def _combine(form, h, hn):
@@ -359,13 +367,16 @@ def tall_weight_grad(grad, x, slabs=128):
     return gw
 
 
-def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0, forms=None):
+def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0, forms=None, edge_drop_p=0.0, edge_seed=0):
     """Differentiable fused propagation stack; returns the (N, sum of widths) readout.  `forms`: one ops.FORMS value per
     layer (default: Bi everywhere); a GraphSage layer's weight is (d_out, 2 d_in).  A two-term layer (ops.BI2_FORM) gives
-    its entry of `weights` as the pair (W1, W2) = (res_fc.weight, res_fc_2.weight)."""
+    its entry of `weights` as the pair (W1, W2) = (res_fc.weight, res_fc_2.weight).  `edge_drop_p` > 0: node dropout
+    - the stack, forward and backward, runs over the adjacency dropped with ops.edge_keep_mask(edge_seed, E, edge_drop_p)."""
     forms = tuple(int(f) for f in forms) if forms is not None else (ops.FORMS["Bi"],) * len(weights)
     if len(forms) != len(weights):
         raise ValueError("gnn_train: %d forms for %d layers" % (len(forms), len(weights)))
+    if not 0.0 <= float(edge_drop_p) < 1.0:
+        raise ValueError("gnn_train: edge_drop_p must be in [0, 1), got %r" % (edge_drop_p,))
     flat = []
     for f, w in zip(forms, weights):
         if f == ops.BI2_FORM:
@@ -374,4 +385,5 @@ def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0, forms=None):
             flat += list(w)
         else:
             flat.append(w)
-    return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), forms, h0, *flat)
+    return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), forms, (float(edge_drop_p), int(edge_seed)), h0,
+                           *flat)

@@ -297,14 +297,24 @@ class _Structure:
         hit = pending_csr_weights(w, self)
         if hit is not None:
             return hit
-        return self.weight_in_csr_order(self._flat(w).detach().contiguous())
+        flat = self._flat(w).detach().contiguous()
+        hit = self._dropped(flat)
+        if hit is not None:
+            return hit[1]
+        return self.weight_in_csr_order(flat)
 
     def rev_weights(self, w):
         """The same weights in the reversed graph's CSR order (SpMM backward); a pending
         LazyEdgeWeights is served from its CSR copy through the composed position map."""
         w_csr = pending_csr_weights(w, self)
         if w_csr is None:
-            return self.weight_in_rev_order(self._flat(w).detach().contiguous())
+            flat = self._flat(w).detach().contiguous()
+            hit = self._dropped(flat)
+            if hit is not None:
+                if hit[2][0] is None:  # the reversed stream of the same surviving edges, formed on first use
+                    hit[2][0] = hit[3]()
+                return hit[2][0]
+            return self.weight_in_rev_order(flat)
         c = self._cache(w_csr.device)
         hit = c.get("w_rev_of_csr")
         if hit is None or hit[0] is not w_csr:
@@ -316,6 +326,17 @@ class _Structure:
     def remember_weight(self, w_flat, w_csr):
         self._cache(w_flat.device)["w_csr"] = ((w_flat.data_ptr(), w_flat._version, w_flat.numel()),
                                                w_csr, w_flat)
+
+    def remember_dropped(self, w_flat, w_csr, make_rev):
+        """A node-dropped copy of the edge weights (edge-id order, one training step's) with its CSR-order stream and
+        the call that forms its reversed stream: served by csr_weights / rev_weights from a slot of its own, so the
+        step neither permutes it nor evicts the cached copies of the undropped weights."""
+        self._cache(w_flat.device)["w_dropped"] = ((w_flat.data_ptr(), w_flat._version, w_flat.numel()),
+                                                   w_csr, [None], make_rev, w_flat)
+
+    def _dropped(self, w_flat):
+        hit = self._cache(w_flat.device).get("w_dropped")
+        return hit if hit is not None and hit[0] == (w_flat.data_ptr(), w_flat._version, w_flat.numel()) else None
 
 
 def _f32_products():
@@ -634,6 +655,59 @@ class DGLGraph:
         if 2 * groups.n_groups <= st.n_edges and ops.att_score_split_supported(st.n_nodes, d, k, n_rel):
             return "split"
         return "one"
+
+    # ---- edge weights without attention (not part of the DGL surface)
+    def laplacian_weights(self, adj_type="si"):
+        """The Laplacian edge weights that stand in for the attention when it is off (reference kgat.py:27,139-145 with
+        --use_attention False; --adj_type of kgat.py:19): "si" 1 / indeg(dst) (D^-1 A), "bi" 1 / sqrt(outdeg(src) *
+        indeg(dst)) (D^-1/2 A D^-1/2 on a symmetric graph), degrees from the device CSR (kgat_edge_norm_f32) - so it
+        runs on a read-only graph whose host edge list is gone.  Returns the (E,1) weights in edge-id order; the graph
+        keeps their CSR-ordered copy, so a following ``edata['w'] = result`` + ``update_all`` streams them without a
+        permutation pass (the contract of ``kgat_attention``, including the lazy opt-in: a `lazy.LazyEdgeWeights` then).
+        The graph is static: cached per device and adj_type.  The graph's feature device is the one of ndata / edata
+        if any is set, else the edge list's, else the current HIP device."""
+        if adj_type not in ops.NORM_MODES:
+            raise ValueError("adj_type must be 'si' or 'bi', got %r" % (adj_type,))
+        if self.partition is not None and adj_type == "bi":
+            raise DGLError("laplacian_weights('bi') on a partitioned graph: a shard holds only part of a source's "
+                           "out-edges; use 'si' or the unsharded graph")
+        st = self._st
+        dev = self._feature_device()
+        c = st._cache(dev)
+        hit = c.get(("laplacian", adj_type))
+        if hit is not None and hit[0]._version == hit[2]:
+            a, w_csr = hit[0], hit[1]
+            if pending_csr_weights(a, st) is None:  # (a pending lazy tensor is answered from w_csr as it is)
+                st.remember_weight(a.view(-1), w_csr)
+            return a
+        from . import lazy as lazy_mod
+        lazy = lazy_mod.enabled()
+        csr = st.csr(dev)
+        out_indptr = st.csr_rev(dev).indptr if adj_type == "bi" else None
+        w_csr, w_eid = ops.edge_norm(csr, out_indptr, adj_type, want_eid=not lazy)
+        if not lazy:
+            a = w_eid.view(-1, 1)
+            st.remember_weight(w_eid, w_csr)
+        else:
+            store = torch.empty((st.n_edges, 1), dtype=torch.float32, device=dev)
+            flat = store.view(-1)
+
+            def fill():
+                ops.gather(st.csr_pos(dev), w_csr, out=flat)
+                st.remember_weight(flat, w_csr)
+            a = LazyEdgeWeights(store, fill, st, w_csr)
+        c[("laplacian", adj_type)] = (a, w_csr, a._version)
+        return a
+
+    def _feature_device(self):
+        for frame in (self._edge_frame, self._node_frame):
+            for t in frame._cols.values():  # (not frame[key]: looking is not handing the column out)
+                if t.is_cuda:
+                    return t.device
+        dev = self._st.edge_device()
+        if dev is not None:
+            return dev
+        return torch.device("cuda", torch.cuda.current_device())
 
     # ---- fused fast path (not part of the DGL surface)
     def kgat_attention(self, ent, W_R, rel, etype=None, algo="auto", lazy=None):

@@ -188,10 +188,23 @@ class KGATPropagation(nn.Module):
     """The hot-path part of the reference's ``Model`` (models.py:72-111,135-168): embeddings,
     W_R, the KGATConv stack, ``compute_attention`` and ``gnn``.  The TransR / BPR losses of the
     reference (models.py:114-133,170-178) are outside this path; ``get_loss`` is kept because the
-    training-step test needs a scalar to differentiate."""
+    training-step test needs a scalar to differentiate.
+
+    ``use_attention=False`` (reference kgat.py:27, models.py:73; the paper's "w/o Att"): ``compute_attention`` returns
+    the Laplacian weights ``g.laplacian_weights(adj_type)`` (kgat.py:19: "si" D^-1 A, "bi" D^-1/2 A D^-1/2) instead of
+    the attention - the epoch loop needs no other change.  ``node_dropout`` (the paper's second regulariser): in
+    training mode with gradients enabled every ``gnn`` call drops each edge with that probability and scales the
+    survivors by 1 / (1 - p); one dropped adjacency per call, shared by all layers and by the backward.  The three
+    add no parameter or buffer.
+
+    Draw order of a ``gnn`` call (torch's CPU generator, so ``torch.manual_seed`` reproduces a run): first the
+    message-dropout seed - one ``torch.empty((), dtype=torch.int64).random_()``, drawn only by the fused training unit
+    and only when the layers' dropout is > 0 -, then the node-dropout seed - one more such draw, only when node dropout
+    applies.  The edges kept are ``ops.edge_keep_mask(seed, E, node_dropout)``, by edge id."""
 
     def __init__(self, n_entities, n_relations, input_node_dim=64, relation_dim=64, num_gnn_layers=3,
-                 n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01, gnn_model="kgat", res_type="Bi"):
+                 n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01, gnn_model="kgat", res_type="Bi", use_attention=True,
+                 adj_type="si", node_dropout=0.0):
         super().__init__()
         if gnn_model not in ("kgat", "graphsage"):
             raise NotImplementedError("gnn_model must be 'kgat' or 'graphsage', got %r" % (gnn_model,))
@@ -200,8 +213,16 @@ class KGATPropagation(nn.Module):
         if gnn_model == "graphsage" and res_type != "Bi":
             raise ValueError("res_type selects the aggregator of gnn_model='kgat'; gnn_model='graphsage' takes none "
                              "(got res_type=%r)" % (res_type,))
+        if adj_type not in ("si", "bi"):
+            raise ValueError("adj_type must be 'si' or 'bi', got %r" % (adj_type,))
+        if not 0.0 <= float(node_dropout) < 1.0:
+            raise ValueError("node_dropout must be in [0, 1), got %r" % (node_dropout,))
+        if gnn_model == "graphsage" and node_dropout > 0:
+            raise ValueError("node_dropout scales the edge weights; gnn_model='graphsage' aggregates without weights "
+                             "(got node_dropout=%r)" % (node_dropout,))
         self._gnn_model = gnn_model
         self._res_type = res_type
+        self._use_attention, self._adj_type, self._node_dropout = bool(use_attention), adj_type, float(node_dropout)
         self._n_entities, self._n_relations = n_entities, n_relations
         self._reg_lambda_gnn = reg_lambda_gnn
         self.entity_embed = nn.Embedding(n_entities, input_node_dim)
@@ -239,7 +260,10 @@ class KGATPropagation(nn.Module):
     def compute_attention(self, g, algo="auto"):
         """Fused: one attention-logit launch over relation-grouped edges + destination softmax.
         The kernels index the table by node position; `_node_embeddings` is the table itself when
-        ndata['id'] is arange(N) (dataset.py:118) and entity_embed(ids) otherwise (models.py:140-141)."""
+        ndata['id'] is arange(N) (dataset.py:118) and entity_embed(ids) otherwise (models.py:140-141).
+        use_attention=False: the Laplacian weights of adj_type (graph-static, cached with the graph)."""
+        if not getattr(self, "_use_attention", True):
+            return g.laplacian_weights(self._adj_type)
         return g.kgat_attention(self._node_embeddings(g), self.W_R, self.relation_embed.weight, algo=algo)
 
     # -- propagation (models.py:156-168)
@@ -253,7 +277,16 @@ class KGATPropagation(nn.Module):
         auto = fused is None
         if auto:
             fused = not torch.is_grad_enabled()
-        if fused and self._can_fuse_readout():
+        # node dropout: training mode under autograd only (a reference-shaped model routed here has none)
+        edge_p = getattr(self, "_node_dropout", 0.0) if (self.training and torch.is_grad_enabled()) else 0.0
+        if edge_p > 0:
+            from .graph import DGLError
+            if g.partition is not None:
+                raise DGLError("node_dropout on a partitioned graph is not supported: it runs on one GPU")
+            if g.edata["w"].requires_grad:
+                raise DGLError("node_dropout treats the edge weights as constants (kgat.py:139-145 computes them "
+                               "under no_grad): g.edata['w'].requires_grad is True")
+        if edge_p == 0 and fused and self._can_fuse_readout():
             return self._gnn_fused(g) if g.partition is None else self._gnn_fused_sharded(g)
         if auto and self._can_fuse_training(g):
             # training mode (kgat.py:146-168): the whole stack as one autograd unit; the dropout mask
@@ -261,13 +294,16 @@ class KGATPropagation(nn.Module):
             from .autograd import gnn_train
             p = self.layers[0].mess_drop.p if self.training else 0.0
             seed = int(torch.empty((), dtype=torch.int64).random_()) if p > 0 else 0
+            edge_seed = int(torch.empty((), dtype=torch.int64).random_()) if edge_p > 0 else 0
             dense = [_layer_dense(layer) for layer in self.layers]
             # (a two-term layer's d[1] is its pair of weights)
             return gnn_train(g, self._node_embeddings(g), [d[1] for d in dense], 0.01, p, seed,
-                             forms=[d[0] for d in dense])
+                             forms=[d[0] for d in dense], edge_drop_p=edge_p, edge_seed=edge_seed)
         if auto and g.partition is not None and torch.is_grad_enabled() and self._can_fuse_training(g, sharded=True):
             return self._gnn_train_sharded(g)
         g = g.local_var()
+        if edge_p > 0:
+            g.edata["w"] = self._dropped_edge_weights(g, edge_p, int(torch.empty((), dtype=torch.int64).random_()))
         h = self._node_embeddings(g)
         node_embed_cache = [h]
         for layer in self.layers:
@@ -275,6 +311,25 @@ class KGATPropagation(nn.Module):
             h = layer(g, h, fused=fused) if isinstance(layer, KGATConv) else layer(g, h)
             node_embed_cache.append(F.normalize(h, p=2, dim=1))
         return torch.cat(node_embed_cache, 1)
+
+    @staticmethod
+    def _dropped_edge_weights(g, p, seed):
+        """The per-layer path's node dropout: the dropped weights in edge-id order for the local_var graph's
+        edata['w'], with their CSR-order stream (and, on first use in backward, the reversed one) kept beside them in
+        the structure's slot for dropped weights - the layers' aggregations take those, permute nothing and leave the
+        cached copies of the undropped weights alone."""
+        from . import ops
+        st = g._st
+        w = g.edata["w"]
+        flat = st._flat(w).detach().contiguous()
+        csr = st.csr(flat.device)
+        w_csr = ops.edge_dropout(st.csr_weights(w), csr.eid, p, seed)
+        dropped = ops.edge_dropout(flat, None, p, seed)
+
+        def make_rev():
+            return ops.edge_dropout(st.rev_weights(w), st.csr_rev(flat.device).eid, p, seed)
+        st.remember_dropped(dropped, w_csr, make_rev)
+        return dropped.reshape(w.shape)
 
     def _gnn_train_sharded(self, g):
         """Training mode on a destination-range shard (kgat.py:146-168 on N GPUs): every layer is a

@@ -1243,6 +1243,58 @@ def dropout_keep_mask(seed, n_rows, d, drop_p, row0=0):
     return (x >= np.uint32(t)).reshape(n_rows, d)
 
 
+NORM_MODES = {"si": 0, "bi": 1}  # include/kgat_hip.h: KGAT_NORM_SI, KGAT_NORM_BI
+
+
+def edge_norm(csr, out_indptr, mode, want_eid=True):
+    """Laplacian edge weights from the device CSR (kgat_edge_norm_f32): (w_csr, w_eid), both (E,); w_eid (edge-id order)
+    is None unless asked for.  `csr`: the destination-major (indptr, col, eid, row_of); `mode` "si": 1 / indeg(dst);
+    "bi": 1 / sqrt(outdeg(src) * indeg(dst)) with `out_indptr` the reversed CSR's indptr (None for "si")."""
+    if mode not in NORM_MODES:
+        raise ValueError("edge_norm: mode must be 'si' or 'bi', got %r" % (mode,))
+    indptr = _need(csr.indptr, torch.int32, "indptr")
+    n, e = indptr.numel() - 1, csr.row_of.numel()
+    row_of = _need(csr.row_of, torch.int32, "row_of")
+    col = _need(csr.col, torch.int32, "col", (e,))
+    eid = _need(csr.eid, torch.int32, "eid", (e,))
+    if mode == "bi":
+        if out_indptr is None:
+            raise ValueError("edge_norm: mode 'bi' needs the reversed CSR's indptr")
+        out_indptr = _need(out_indptr, torch.int32, "out_indptr", (n + 1,))
+    else:
+        out_indptr = None
+    w_csr = torch.empty(e, dtype=torch.float32, device=indptr.device)
+    w_eid = torch.empty(e, dtype=torch.float32, device=indptr.device) if want_eid else None
+    with _timed("edge_norm", (e, mode)):
+        check(_lib.load().kgat_edge_norm_f32(n, e, _ptr(indptr), _ptr(row_of), _ptr(col), _ptr(eid), _ptr(out_indptr),
+                                             NORM_MODES[mode], _ptr(w_csr), _ptr(w_eid), _stream(indptr)),
+              "kgat_edge_norm_f32")
+    return w_csr, w_eid
+
+
+def edge_dropout(w, key, p, seed):
+    """Node dropout's dropped copy of a weight stream (kgat_edge_dropout_f32): w * keep / (1 - p) with
+    keep = edge_keep_mask(seed, E, p)[key].  `key`: the edge id at every position of `w` - csr.eid of the CSR `w` is
+    ordered by - or None for a stream in edge-id order.  `w` (E,) or (E,1), any 4-byte aligned start."""
+    w = _need(w, torch.float32, "w")
+    e = w.numel()
+    if key is not None:
+        key = _need(key, torch.int32, "key", (e,))
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("edge_dropout: p must be in [0, 1), got %r" % (p,))
+    out = torch.empty_like(w)
+    with _timed("edge_dropout", (e,)):
+        check(_lib.load().kgat_edge_dropout_f32(e, _ptr(w), _ptr(key), float(p), int(seed) & (2 ** 64 - 1), _ptr(out),
+                                                _stream(w)), "kgat_edge_dropout_f32")
+    return out
+
+
+def edge_keep_mask(seed, n_edges, p):
+    """The edges node dropout keeps, by edge id, restated in numpy (tests): dropout_keep_mask over (row = edge id,
+    d = 1, column 0)."""
+    return dropout_keep_mask(seed, n_edges, 1, p).reshape(-1)
+
+
 def l2_normalize_rows(x, out):
     """out[:, :] = x / max(||x_row||, 1e-12); `out` may be a column slice of a wider buffer."""
     x = _need(x, torch.float32, "x")

@@ -148,6 +148,14 @@ def parse_args(argv=None):
                          "(the reference's one-term form), GCN, GraphSage, or Bi2, the KGAT paper's two-term "
                          "Bi-Interaction (eq. 8)")
     ap.add_argument("--dropout_rate", type=float, default=0.1)
+    ap.add_argument("--use_attention", type=int, choices=(0, 1), default=1,
+                    help="0: the attention ablation (reference kgat.py:27) - the edge weights are the Laplacian of "
+                         "--adj_type instead of the attention")
+    ap.add_argument("--adj_type", choices=("si", "bi"), default="si",
+                    help="Laplacian of --use_attention 0 (reference kgat.py:19): si = D^-1 A, bi = D^-1/2 A D^-1/2")
+    ap.add_argument("--node_dropout", type=float, default=0.0,
+                    help="node dropout of the CF phase: every step drops each edge with this probability and scales "
+                         "the survivors by 1 / (1 - p)")
     ap.add_argument("--lr", type=float, default=0.0001)
     ap.add_argument("--batch_size", type=int, default=10240)
     ap.add_argument("--batch_size_kg", type=int, default=2048)
@@ -168,6 +176,14 @@ def parse_args(argv=None):
         ap.error("--res_type %s selects the aggregator of --gnn_model kgat; graphsage takes none" % args.res_type)
     if args.res_type != "Bi" and args.gpus > 1:
         ap.error("--res_type %s runs on one GPU: sharded models run the Bi aggregator only" % args.res_type)
+    if not 0.0 <= args.node_dropout < 1.0:
+        ap.error("--node_dropout must be in [0, 1)")
+    if args.node_dropout > 0 and args.gnn_model == "graphsage":
+        ap.error("--node_dropout scales the edge weights; --gnn_model graphsage aggregates without weights")
+    if args.node_dropout > 0 and args.gpus > 1:
+        ap.error("--node_dropout runs on one GPU")
+    if not args.use_attention and args.adj_type == "bi" and args.gpus > 1:
+        ap.error("--adj_type bi runs on one GPU: a shard holds only part of a source's out-edges")
     return args
 
 
@@ -202,7 +218,8 @@ def main(argv=None):
         ds.n_users, ds.n_items, ds.n_KG_entity, ds.n_KG_relation, len(ds.train_KG_triplet)))
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
-                              gnn_model=args.gnn_model, res_type=args.res_type).to(dev)
+                              gnn_model=args.gnn_model, res_type=args.res_type, use_attention=bool(args.use_attention),
+                              adj_type=args.adj_type, node_dropout=args.node_dropout).to(dev)
     K.enable_lazy_edge_weights()   # the attention refresh hands back its edge-id-ordered copy unwritten (nothing here reads it)
 
     def replicas_agree(tag):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define KGAT_ABI_VERSION 14
+#define KGAT_ABI_VERSION 15
 
 enum {
   KGAT_OK = 0,
@@ -83,6 +83,12 @@ enum {
 enum {
   KGAT_REDUCE_SUM = 0,
   KGAT_REDUCE_MEAN = 1
+};
+
+/* mode of kgat_edge_norm_f32 (the commented-out --adj_type of reference kgat.py:19: "si" / "bi") */
+enum {
+  KGAT_NORM_SI = 0,  /* random-walk Laplacian D^-1 A: 1 / in-degree of the destination */
+  KGAT_NORM_BI = 1   /* symmetric Laplacian D^-1/2 A D^-1/2: 1 / sqrt(out-degree of the source * in-degree of the destination) */
 };
 
 /* the aggregator of a KGAT layer (res_type of KGATConv, reference models.py:50-58; the KGAT paper's "Information
@@ -759,6 +765,36 @@ int kgat_eval_topk_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items
 int kgat_eval_metrics_at_ks(int64_t n_users, int K, const int32_t* topk_items, const int32_t* test_ptr,
                             const int32_t* test_items, int n_ks, const int32_t* ks, const double* disc, double* out,
                             kgat_stream_t stream);
+
+/* ---------------------------------------------------------------- edge weights without attention, node dropout (ABI 15)
+ * kgat_edge_norm_f32: the weights g.edata['w'] that reference models.py:63 multiplies by when kgat.py:27,139-145 runs
+ * with --use_attention False (there nothing ever writes them; the adjacency meant is the Laplacian the commented-out
+ * --adj_type of kgat.py:19 names), from the device CSR alone.  For position p of the destination-major CSR (indptr,
+ * row_of, col, eid of kgat_csr_from_coo) with destination v = row_of[p] and source u = col[p], in fp32:
+ *   KGAT_NORM_SI:  w = 1.f / (float)(indptr[v + 1] - indptr[v])
+ *   KGAT_NORM_BI:  w = 1.f / sqrtf((float)(out_indptr[u + 1] - out_indptr[u]) * (float)(indptr[v + 1] - indptr[v]))
+ * (IEEE division and square root, no contraction) - out_indptr [n_nodes + 1] is the indptr of the REVERSED graph's CSR
+ * (rows = sources; NULL for SI, which reads neither it nor col).  Every edge counts in both of its endpoints' degrees
+ * (multi-edges and self-loops as often as they occur), so no weight is infinite or zero.  One Laplacian over all
+ * relations: the per-relation normalisation of the original TensorFlow KGAT is not formed.  w_csr [n_edges]: CSR
+ * order, coalesced; w_eid (optional, may be NULL; needs eid): w_eid[eid[p]] = w_csr[p].  A node id outside
+ * [0, n_nodes) gives NaN and is never used as an index.  One launch; n_edges == 0 launches nothing. */
+int kgat_edge_norm_f32(int64_t n_nodes, int64_t n_edges, const int32_t* indptr, const int32_t* row_of,
+                       const int32_t* col, const int32_t* eid, const int32_t* out_indptr, int mode, float* w_csr,
+                       float* w_eid, kgat_stream_t stream);
+
+/* Node dropout (the KGAT paper's second regulariser beside the message dropout of reference models.py:54,69: entries of
+ * the adjacency dropped with probability drop_p, survivors scaled by 1 / (1 - drop_p)) as the dropped copy of one
+ * weight stream:
+ *   w_out[p] = keep(seed, key[p]) ? w_in[p] * keep_scale : 0,   keep_scale = 1.f / (1.f - drop_p)  (fp32)
+ * keep is the counter hash of kgat_bi_interaction_train_f32 over (row = edge id, d = 1, column 0): keep <=>
+ * hash(seed, key[p]) >= drop_p * 2^32.  key [n_edges] holds the edge id at every position of the stream - `eid` of the
+ * CSR the stream is ordered by (kgat_csr_from_coo's, or the reversed graph's for the backward stream); NULL: the stream
+ * is in edge-id order (key[p] = p).  Keyed by edge id, the calls on the forward and on the reversed stream describe
+ * the same surviving edge set.  drop_p in [0, 1); drop_p == 0 copies the bits.  16-byte accesses where key / w_out
+ * (and, separately, w_in) are 16-byte aligned; any 4-byte alignment works.  One launch; n_edges == 0 launches nothing. */
+int kgat_edge_dropout_f32(int64_t n_edges, const float* w_in, const int32_t* key, float drop_p, uint64_t seed,
+                          float* w_out, kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- optimiser of the training loop (8f #1, #3)
  * One step of torch.optim.Adam (reference kgat.py:85: optim.Adam(model.parameters(), lr); amsgrad off, no weight
