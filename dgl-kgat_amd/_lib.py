@@ -28,6 +28,7 @@ SOURCES = {
     "kgat_bpr.hip": [],
     "kgat_sage.hip": [],
     "kgat_edge_weights.hip": [],
+    "kgat_att_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -66,6 +67,11 @@ SIGNATURES = {
                                         _p, _p, _p, _p, _p, _p, _i32, _p]),
     "kgat_att_score_fused_timed_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32,
                                               _p, _p, _p, _p, _p, _p, _i32, _p, _p]),
+    # backward of the attention logits: reference models.py:135-154 under autograd (ABI 15, additive)
+    "kgat_att_score_bwd_supported": (_i32, [_i64, _i32, _i32, _i32]),
+    "kgat_att_score_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
+    "kgat_att_score_bwd_f32": (_i32, [_i64, _i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                      _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_edge_softmax_workspace_bytes": (_sz, [_i64, _i64]),
     "kgat_edge_softmax_f32": (_i32, [_i64, _i64, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     "kgat_edge_softmax_3pass_workspace_bytes": (_sz, [_i64]),

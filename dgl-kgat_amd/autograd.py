@@ -7,8 +7,11 @@
 * ``edge_softmax`` - reference models.py:153; backward as DGL 0.4.x EdgeSoftmax.backward.
 * ``copy_reduce`` - update_all(copy_src, sum | mean), the aggregation of DGL's SAGEConv (gnn_model
   "graphsage"); backward over the reversed graph's CSR.
+* ``kgat_attention`` - the fused attention (logits + destination softmax, models.py:135-154) as one unit that
+  differentiates towards the entity table, W_R and the relation embeddings.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -144,6 +147,72 @@ def edge_softmax(graph, logits, eids=None):
     if logits.shape[0] != graph.number_of_edges():
         raise ValueError("logits has %d rows, graph has %d edges" % (logits.shape[0], graph.number_of_edges()))
     return _EdgeSoftmax.apply(logits, graph)
+
+
+class _KGATAttention(torch.autograd.Function):
+    """DGLGraph.kgat_attention under autograd: forward is the default (detached) pipeline - logits of the chosen form,
+    kgat_edge_softmax_f32, weights in edge-id order - so the values are its bits; the weights are saved.  Backward:
+    kgat_edge_softmax_bwd_f32, one gather of the logit gradients into grouped order, kgat_att_score_bwd_f32 (widths
+    outside its range: a torch restatement over the relation-grouped edges)."""
+
+    @staticmethod
+    def forward(ctx, ent, W_R, rel, g, etype, algo):
+        a = g.kgat_attention(ent, W_R, rel, etype, algo=algo, lazy=False)
+        ctx.g, ctx.etype = g, etype
+        ctx.save_for_backward(a, ent, W_R, rel)
+        return a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_a):
+        from .graph import att_bwd_statics
+        a, ent, W_R, rel = ctx.saved_tensors
+        st = ctx.g._st
+        dev = a.device
+        need = ctx.needs_input_grad
+        ent_c, W_c, rel_c = ent.detach().contiguous(), W_R.detach().contiguous(), rel.detach().contiguous()
+        n_rel, d, k = W_c.shape
+        csr = st.csr(dev)
+        groups = st.rel_groups(ctx.etype, n_rel, dev)
+        gs = ops.edge_softmax_bwd(csr.indptr, csr.eid, a.detach().reshape(-1),
+                                  grad_a.detach().reshape(-1).contiguous())
+        if ops.att_score_bwd_supported(st.n_nodes, d, k, n_rel):
+            s = att_bwd_statics(groups, st.n_nodes)
+            g_ent, g_w, g_rel = ops.att_score_bwd(st.n_nodes, s.n_scored, groups.n_groups, groups.perm, groups.src_g, groups.gid,
+                                                  s.gstart, groups.gptr, groups.g_node, s.node_ptr, s.node_col,
+                                                  s.node_row, s.node_wsrc, ent_c, W_c, rel_c, gs)  # (gathers gs into grouped order)
+        else:
+            g_ent, g_w, g_rel = _att_score_bwd_torch(groups, ent_c, W_c, rel_c, ops.gather(groups.perm, gs))
+        return (g_ent if need[0] else None, g_w if need[1] else None, g_rel if need[2] else None, None, None, None)
+
+
+def _att_score_bwd_torch(groups, ent, W_R, rel, gamma_g):
+    """The logits' backward restated in torch over the relation-grouped edges (one round per relation), for widths
+    outside kgat_att_score_bwd_supported: the same gradients to rounding."""
+    bounds = groups.rel_ptr.tolist()
+    with torch.enable_grad():
+        e, w, r = (t.detach().clone().requires_grad_(True) for t in (ent, W_R, rel))
+        total = e.sum() * 0 + w.sum() * 0 + r.sum() * 0
+        for i in range(w.shape[0]):
+            p0, p1 = bounds[i], bounds[i + 1]
+            if p1 > p0:
+                t_r = e[groups.src_g[p0:p1].long()] @ w[i]
+                h_r = e[groups.dst_g[p0:p1].long()] @ w[i]
+                total = total + ((t_r * torch.tanh(h_r + r[i])).sum(-1) * gamma_g[p0:p1]).sum()
+        return torch.autograd.grad(total, (e, w, r))
+
+
+def kgat_attention(g, ent, W_R, rel, etype=None, algo="auto"):
+    """Differentiable fused attention: the (E,1) weights of ``g.kgat_attention`` in edge-id order, bit for bit, as a
+    plain tensor whose grad_fn (when gradients are enabled and `ent`, `W_R` or `rel` requires one) reaches the three
+    parameters - what the reference's compute_attention gives without its ``with th.no_grad()`` (models.py:135-154)."""
+    if g.partition is not None:
+        from .graph import DGLError
+        raise DGLError("kgat_attention under autograd on a partitioned graph: a shard holds only part of a tail's "
+                       "out-edges; use the unsharded graph")
+    if etype is None:
+        etype = g.edata["type"]
+    return _KGATAttention.apply(ent, W_R, rel, g, etype, algo)
 
 
 class _TransRLoss(torch.autograd.Function):

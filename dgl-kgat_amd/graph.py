@@ -381,6 +381,29 @@ def _fused_tiles(groups, d, gpt=16):
     return tiles
 
 
+AttBwdStatics = namedtuple("AttBwdStatics", "n_scored gstart node_ptr node_col node_row node_wsrc")
+
+
+def att_bwd_statics(groups, n_nodes):
+    """The graph-static index arrays of the attention backward (kgat_att_score_bwd_f32), kept with the relation
+    grouping: the scored position count rel_ptr[R] (one host read), every group's first grouped position, and the
+    node-major CSR over { out-edge positions of a node } + { groups the node heads } whose columns index the backward's
+    [V ; H] table and whose weight indices point into [logit gradients ; 1.0]."""
+    hit = groups.g_tab.get("att_bwd")
+    if hit is None:
+        dev = groups.gid.device
+        n_scored, ng = int(groups.rel_ptr[-1].item()), groups.n_groups
+        gid = groups.gid[:n_scored]
+        i32 = dict(dtype=torch.int32, device=dev)
+        gstart = torch.searchsorted(gid, torch.arange(ng + 1, **i32)).to(torch.int32)  # (gid ascends by position)
+        node = torch.cat([groups.src_g[:n_scored], groups.g_node[:ng]])
+        col = torch.cat([gid, torch.arange(ng, 2 * ng, **i32)])
+        node_ptr, node_col, eid, node_row = ops.csr_from_coo(n_nodes, col, node)
+        hit = groups.g_tab["att_bwd"] = AttBwdStatics(n_scored, gstart, node_ptr, node_col, node_row,
+                                                      eid.clamp(max=n_scored))
+    return hit
+
+
 class EdgeBatch:
     """What a UDF passed to filter_edges / apply_edges sees: lazily gathered src / dst /
     edge features of the selected edges (reference models.py:140-143)."""
@@ -710,14 +733,20 @@ class DGLGraph:
         return torch.device("cuda", torch.cuda.current_device())
 
     # ---- fused fast path (not part of the DGL surface)
-    def kgat_attention(self, ent, W_R, rel, etype=None, algo="auto", lazy=None):
+    def kgat_attention(self, ent, W_R, rel, etype=None, algo="auto", lazy=None, differentiable=False):
         """compute_attention (models.py:146-154): relation-grouped attention logits + destination
         softmax.  Returns the (E,1) weights in edge-id order; the graph keeps their CSR-ordered
         copy, so a following ``edata['w'] = result`` + ``update_all`` streams them without a
         permutation pass.  With ``lazy=True``, or ``lazy=None`` after the process opted in
         (``dgl_kgat_amd.enable_lazy_edge_weights()`` / ``KGAT_LAZY_EDGE_WEIGHTS=1``; see lazy.py),
         the result is a `lazy.LazyEdgeWeights`: real storage whose edge-id-ordered values are
-        written by the first operation that looks at them - nothing on the path does."""
+        written by the first operation that looks at them - nothing on the path does.
+        The default treats `ent`, `W_R` and `rel` as constants (kgat.py:142-144 runs it under no_grad) whatever the
+        caller's autograd state.  ``differentiable=True``: the same values as a plain tensor (never lazy) that carries
+        the gradient towards the three parameters (autograd.kgat_attention: models.py:135-154 under autograd)."""
+        if differentiable:
+            from .autograd import kgat_attention   # (refuses a partitioned graph)
+            return kgat_attention(self, ent, W_R, rel, etype, algo=algo)
         if etype is None:
             etype = self._edge_frame["type"]
         st = self._st

@@ -257,14 +257,21 @@ class KGATPropagation(nn.Module):
             g.apply_edges(self._att_score, e_idxs)
         return edge_softmax(g, g.edata.pop("att_w"))
 
-    def compute_attention(self, g, algo="auto"):
+    def compute_attention(self, g, algo="auto", differentiable=False):
         """Fused: one attention-logit launch over relation-grouped edges + destination softmax.
         The kernels index the table by node position; `_node_embeddings` is the table itself when
         ndata['id'] is arange(N) (dataset.py:118) and entity_embed(ids) otherwise (models.py:140-141).
-        use_attention=False: the Laplacian weights of adj_type (graph-static, cached with the graph)."""
+        use_attention=False: the Laplacian weights of adj_type (graph-static, cached with the graph).
+        The result is a constant whatever the autograd state (kgat.py:142-144).  differentiable=True: the same values
+        as a plain tensor that carries the gradient to entity_embed, W_R and relation_embed (DGLGraph.kgat_attention);
+        ``gnn`` then runs its per-layer path, whose aggregation returns the weight gradient."""
         if not getattr(self, "_use_attention", True):
+            if differentiable:
+                raise ValueError("compute_attention(differentiable=True) with use_attention=False: the Laplacian "
+                                 "weights have no parameter to differentiate towards")
             return g.laplacian_weights(self._adj_type)
-        return g.kgat_attention(self._node_embeddings(g), self.W_R, self.relation_embed.weight, algo=algo)
+        return g.kgat_attention(self._node_embeddings(g), self.W_R, self.relation_embed.weight, algo=algo,
+                                differentiable=differentiable)
 
     # -- propagation (models.py:156-168)
     def gnn(self, g, x=None, fused=None):

@@ -384,6 +384,51 @@ def att_score_fused(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, til
     return (logits, logits_csr, logits_g) if want_grouped else (logits, logits_csr)
 
 
+def att_score_bwd_supported(n_nodes, d, k, n_rel):
+    return bool(_lib.load().kgat_att_score_bwd_supported(int(n_nodes), int(d), int(k), int(n_rel)))
+
+
+def att_score_bwd(n_nodes, n_scored, n_groups, perm, src_g, gid, gstart, gptr, g_node, node_ptr, node_col, node_row,
+                  node_wsrc, ent, W_R, rel, grad_logits):
+    """Gradients (grad_ent (N,d), grad_W_R (R,d,k), grad_rel (R,k)) of the attention logits w.r.t. their three
+    parameters, given the logits' gradient `grad_logits` (E,) in EDGE-ID order (kgat_att_score_bwd_f32; the index arrays
+    are the graph-static ones its header comment names, `perm` the edge id of every grouped position).  All three are
+    fully written by the call.  The one gather into grouped order happens here, into a buffer of this call's own with
+    the float of room the entry writes its 1.0 to: no tensor of the caller is written."""
+    ent = _need(ent, torch.float32, "ent")
+    W_R = _need(W_R, torch.float32, "W_R")
+    n_rel, d, k = W_R.shape
+    rel = _need(rel, torch.float32, "rel", (n_rel, k))
+    if ent.shape != (n_nodes, d):
+        raise ValueError("ent has shape %s, expected %s" % (tuple(ent.shape), (n_nodes, d)))
+    n_scored, n_groups = int(n_scored), int(n_groups)
+    perm = _need(perm, torch.int32, "perm")
+    grad_logits = _need(grad_logits, torch.float32, "grad_logits", perm.shape)
+    if perm.numel() < n_scored:
+        raise ValueError("perm holds %d positions, needs %d" % (perm.numel(), n_scored))
+    grad_logits_g = torch.empty(n_scored + 1, dtype=torch.float32, device=ent.device)
+    gather(perm[:n_scored], grad_logits, out=grad_logits_g[:n_scored])
+    for name, t, n in (("src_g", src_g, n_scored), ("gid", gid, n_scored), ("gstart", gstart, n_groups + 1),
+                       ("gptr", gptr, n_rel + 1), ("g_node", g_node, n_groups), ("node_ptr", node_ptr, n_nodes + 1),
+                       ("node_col", node_col, n_scored + n_groups), ("node_row", node_row, n_scored + n_groups),
+                       ("node_wsrc", node_wsrc, n_scored + n_groups)):
+        if _need(t, torch.int32, name).numel() < n:
+            raise ValueError("%s holds %d entries, needs %d" % (name, t.numel(), n))
+    lib = _lib.load()
+    dev = ent.device
+    grad_ent = torch.empty((n_nodes, d), dtype=torch.float32, device=dev)
+    grad_W = torch.empty((n_rel, d, k), dtype=torch.float32, device=dev)
+    grad_rel = torch.empty((n_rel, k), dtype=torch.float32, device=dev)
+    ws = _workspace(lib.kgat_att_score_bwd_workspace_bytes(n_nodes, n_scored, n_groups, d, k, n_rel), dev)
+    with _timed("att_score_bwd", (n_scored, n_groups, d, k)):
+        check(lib.kgat_att_score_bwd_f32(n_nodes, n_scored, n_groups, d, k, n_rel, _ptr(src_g), _ptr(gid), _ptr(gstart),
+                                         _ptr(gptr), _ptr(g_node), _ptr(node_ptr), _ptr(node_col), _ptr(node_row),
+                                         _ptr(node_wsrc), _ptr(ent), _ptr(W_R), _ptr(rel), _ptr(grad_logits_g),
+                                         _ptr(grad_ent), _ptr(grad_W), _ptr(grad_rel), _ptr(ws), ws.numel(), _stream(ent)),
+              "kgat_att_score_bwd_f32")
+    return grad_ent, grad_W, grad_rel
+
+
 def transr_supported(n_nodes, d, k, n_rel, batch):
     return bool(_lib.load().kgat_transr_supported(int(n_nodes), int(d), int(k), int(n_rel), int(batch)))
 

@@ -156,6 +156,11 @@ def parse_args(argv=None):
     ap.add_argument("--node_dropout", type=float, default=0.0,
                     help="node dropout of the CF phase: every step drops each edge with this probability and scales "
                          "the survivors by 1 / (1 - p)")
+    ap.add_argument("--attention_grad", type=int, choices=(0, 1), default=0,
+                    help="1: train the attention end to end through the CF loss - every CF step recomputes the weights "
+                         "with compute_attention(differentiable=True), so W_R, the relation embeddings and the entity "
+                         "table also receive the BPR gradient through them (the reference computes them once per "
+                         "epoch under no_grad, kgat.py:139-145)")
     ap.add_argument("--lr", type=float, default=0.0001)
     ap.add_argument("--batch_size", type=int, default=10240)
     ap.add_argument("--batch_size_kg", type=int, default=2048)
@@ -184,11 +189,30 @@ def parse_args(argv=None):
         ap.error("--node_dropout runs on one GPU")
     if not args.use_attention and args.adj_type == "bi" and args.gpus > 1:
         ap.error("--adj_type bi runs on one GPU: a shard holds only part of a source's out-edges")
+    if args.attention_grad:
+        if not args.use_attention:
+            ap.error("--attention_grad 1 needs the attention: --use_attention 0 has no parameter to differentiate towards")
+        if args.node_dropout > 0:
+            ap.error("--attention_grad 1 with --node_dropout: node dropout treats the edge weights as constants")
+        if args.gpus > 1:
+            ap.error("--attention_grad 1 runs on one GPU: a shard holds only part of a tail's out-edges")
+        if args.gnn_model == "graphsage":
+            ap.error("--attention_grad 1 needs --gnn_model kgat: graphsage aggregates without edge weights")
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
+    # the attention refresh hands back its edge-id-ordered copy unwritten (nothing here reads it)
+    lazy_before = K.enable_lazy_edge_weights()
+    try:
+        return _run(args, argv)
+    finally:
+        if args.attention_grad:   # leave the process-wide lazy setting as this call found it
+            K.enable_lazy_edge_weights(lazy_before)
+
+
+def _run(args, argv):
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import socket
         import subprocess
@@ -220,7 +244,6 @@ def main(argv=None):
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
                               gnn_model=args.gnn_model, res_type=args.res_type, use_attention=bool(args.use_attention),
                               adj_type=args.adj_type, node_dropout=args.node_dropout).to(dev)
-    K.enable_lazy_edge_weights()   # the attention refresh hands back its edge-id-ordered copy unwritten (nothing here reads it)
 
     def replicas_agree(tag):
         """Every rank holds a replica of the parameters and runs the same optimiser on the same gradients
@@ -312,8 +335,9 @@ def main(argv=None):
         del idx, h_all, r_all, t_all, neg_all
         # ---- attention refresh (kgat.py:139-145)
         t0 = clock()
-        with torch.no_grad():
-            train_g.edata["w"] = model.compute_attention(train_g)
+        if not args.attention_grad:   # (--attention_grad 1: every CF step computes its own, differentiable weights)
+            with torch.no_grad():
+                train_g.edata["w"] = model.compute_attention(train_g)
         rec["attention_s"] = clock() - t0
         say("           | attention %.4fs" % rec["attention_s"])
         # ---- CF phase (kgat.py:146-168): full-graph gnn for every batch
@@ -323,7 +347,10 @@ def main(argv=None):
         u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
         n_all = torch.randint(off, off + ds.n_items, (n_it, bs), device=dev, dtype=torch.int32)
         total = torch.zeros((), dtype=torch.float32, device=dev)
+        w_r_before = model.W_R.detach().clone()
         for i in range(n_it):
+            if args.attention_grad:
+                train_g.edata["w"] = model.compute_attention(train_g, differentiable=True)
             emb = model.gnn(train_g, train_g.ndata["id"])
             loss = model.get_loss(emb, u_all[i], p_all[i], n_all[i])
             loss.backward()
@@ -336,6 +363,7 @@ def main(argv=None):
             total += loss.detach()
         rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
         rec["cf_loss"] = float(total) / n_it
+        rec["cf_W_R_change"] = float((model.W_R.detach() - w_r_before).abs().max())   # 0 unless --attention_grad 1
         say("           | GNN %.4fs (%d it, %.4f ms/it) loss %.4f" % (rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it, rec["cf_loss"]))
         del idx, u_all, p_all, n_all
         replicas_agree("epoch %d" % epoch)

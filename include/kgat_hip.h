@@ -29,6 +29,8 @@ extern "C" {
 #endif
 
 #define KGAT_ABI_VERSION 15
+/* Added at 15 without a bump (additive: no existing entry changed): kgat_att_score_bwd_supported,
+ * kgat_att_score_bwd_workspace_bytes, kgat_att_score_bwd_f32. */
 
 enum {
   KGAT_OK = 0,
@@ -271,6 +273,47 @@ int kgat_att_score_fused_timed_f32(int64_t n_nodes, int64_t n_edges, int d, int 
                                    const float* ent, const float* W_R, const float* rel, float* logits,
                                    float* logits_csr, float* logits_g, int flags, long long* part_clocks,
                                    kgat_stream_t stream);
+
+/* ---------------------------------------------------------------- attention score, backward
+ * Gradient of the logits above w.r.t. ent, W_R and rel: what autograd computes through the apply_edges loop of
+ * reference models.py:135-154 when the caller drops the `with th.no_grad()` around compute_attention.  With
+ *   T = tanh(ent[h] W_r + rel[r]),  V = W_r T  (the folded forward's per-group vectors),  g_p = grad of the logit of
+ * grouped position p, the sums factorise over the (head, relation) groups G of kgat_head_groups:
+ *   A_G = sum_{p in G} g_p ent[src_g[p]]    dP_G = (A_G W_r) * (1 - T_G^2)
+ *   grad_ent[src_g[p]] += g_p V_G           grad_ent[h] += dP_G W_r^T
+ *   grad_rel[r] += dP_G                     grad_W_R[r] += A_G^T (x) T_G + ent[h]^T (x) dP_G
+ * Positions past n_scored = rel_ptr[R] (types outside [0,R): constant logit 0) take no part.  A self-loop gives its
+ * node both terms, parallel edges count once each.  T and V are recomputed from ent (the forward saves nothing).
+ * Inputs, all graph-static except the last four:
+ *   src_g[n_scored], gid[n_scored], gptr[R+1], g_node[n_groups]   as for kgat_att_score_folded_f32
+ *   gstart[n_groups+1]   first grouped position of each group; gstart[n_groups] = n_scored
+ *   node_ptr[N+1], node_col / node_row / node_wsrc [n_scored + n_groups]   a node-major CSR (kgat_csr_from_coo) of the
+ *       entries { node src_g[p], column gid[p], weight index p } for every scored position and
+ *       { node g_node[G], column n_groups + G, weight index n_scored } for every group: node_row = node per entry
+ *   ent (N,d), W_R (R,d,k), rel (R,k)
+ *   grad_logits_g[n_scored + 1]: the logit gradients in grouped order (position p of kgat_group_by_relation) and one
+ *       float of room after them, to which the call writes 1.0 (the weight of the per-group entries of the node CSR,
+ *       read through node_wsrc) - a buffer of E + 1 floats gathered into serves; what follows element n_scored is not read
+ * Outputs, fully written (rows and relations without a contribution are exact zeros; nothing is pre-zeroed by the
+ * caller): grad_ent (N,d), grad_W_R (R,d,k), grad_rel (R,k).
+ * Launches: kgat_spmm_umule_sum_f32 for A_G (rows = groups); one v_mfma_f32_16x16x4_f32 kernel over tiles of at most 16
+ * consecutive groups of one relation that forms T, V, dP, dP W_r^T and the tile's grad W_r / grad rel terms - a
+ * workgroup owns a contiguous tile range, accumulates across its tiles of one relation and flushes one partial per
+ * relation change (at most n_workgroups + R partials); a fixed-order sum of those partials; kgat_spmm_umule_sum_f32
+ * over the node-major CSR for grad_ent (columns index the [V ; dP W_r^T] table).  No float atomics, fixed summation
+ * order: bitwise reproducible (on one device model: the workgroup count, and with it the order in which the weight-
+ * gradient partials are summed, follows the sizes and the number of compute units).  Widths: d == k in {16,32,64,128}, 0 < R <= 4096, n_nodes * d * 4 < 4 GiB (the bound of
+ * the forward's group forms); others return KGAT_E_UNSUPPORTED.  ent, W_R, grad_ent and the workspace 16-byte aligned.
+ * Workspace: the three tables (3 n_groups d floats), the partials ((n_workgroups + R) (d k + k) floats) and the
+ * aggregation's scratch. */
+int kgat_att_score_bwd_supported(int64_t n_nodes, int d, int k, int n_rel);
+size_t kgat_att_score_bwd_workspace_bytes(int64_t n_nodes, int64_t n_scored, int64_t n_groups, int d, int k, int n_rel);
+int kgat_att_score_bwd_f32(int64_t n_nodes, int64_t n_scored, int64_t n_groups, int d, int k, int n_rel,
+                           const int32_t* src_g, const int32_t* gid, const int32_t* gstart, const int32_t* gptr,
+                           const int32_t* g_node, const int32_t* node_ptr, const int32_t* node_col,
+                           const int32_t* node_row, const int32_t* node_wsrc, const float* ent, const float* W_R,
+                           const float* rel, float* grad_logits_g, float* grad_ent, float* grad_W_R,
+                           float* grad_rel, void* workspace, size_t workspace_bytes, kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- edge softmax (A3)
  * Replaces dgl.nn.pytorch.softmax.edge_softmax (call site reference models.py:153):

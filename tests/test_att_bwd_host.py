@@ -1,0 +1,100 @@
+"""The differentiable attention without a GPU: the three C-ABI entries of the logits' backward are declared (at
+version 15, no bump) and bound, the Python switches exist, and the refusals fire - at the model, at the graph and in the
+example's parser."""
+import importlib.util
+import inspect
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import dgl_kgat_amd as K  # noqa: E402
+from dgl_kgat_amd import _lib, autograd, ops  # noqa: E402
+from dgl_kgat_amd.graph import DGLError, DGLGraph  # noqa: E402
+
+ENTRIES = ("kgat_att_score_bwd_supported", "kgat_att_score_bwd_workspace_bytes", "kgat_att_score_bwd_f32")
+
+
+def test_header_declares_the_three_entries_without_a_version_bump():
+    header = open(os.path.join(ROOT, "include", "kgat_hip.h")).read()
+    declared = set(re.findall(r"\b(kgat_[a-z0-9_]+)\s*\(", header))
+    for name in ENTRIES:
+        assert name in declared and name in _lib.SIGNATURES
+    assert "#define KGAT_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15
+    assert "kgat_att_bwd.hip" in _lib.SOURCES
+    assert os.path.exists(os.path.join(_lib.CSRC, "kgat_att_bwd.hip"))
+    assert "models.py:135-154" in header[header.index("attention score, backward"):header.index(ENTRIES[0] + "(")]
+    # every declared function is bound and every bound one declared (the loader's own contract)
+    assert declared == set(_lib.SIGNATURES)
+    lib = _lib.load()
+    assert lib.kgat_version() == 15
+
+
+def test_supported_widths_and_the_32_bit_bound():
+    for d in (16, 32, 64, 128):
+        assert ops.att_score_bwd_supported(1000, d, d, 41)
+        assert ops.att_score_bwd_supported(1000, d, d, 4096)
+    assert not ops.att_score_bwd_supported(1000, 64, 32, 41)
+    assert not ops.att_score_bwd_supported(1000, 8, 8, 41)
+    assert not ops.att_score_bwd_supported(1000, 64, 64, 0)
+    # n_nodes * d * 4 must stay below 4 GiB, as for the forward's group forms
+    assert ops.att_score_bwd_supported((1 << 24) - 1, 64, 64, 41)
+    assert not ops.att_score_bwd_supported(1 << 24, 64, 64, 41)
+    assert ops.att_score_bwd_supported((1 << 24), 64, 64, 41) == ops.att_score_folded_supported((1 << 24), 64, 64, 41)
+
+
+def test_switches_exist():
+    assert inspect.signature(K.KGATPropagation.compute_attention).parameters["differentiable"].default is False
+    assert inspect.signature(DGLGraph.kgat_attention).parameters["differentiable"].default is False
+    assert list(inspect.signature(autograd.kgat_attention).parameters)[:5] == ["g", "ent", "W_R", "rel", "etype"]
+    assert callable(ops.att_score_bwd) and callable(ops.att_score_bwd_supported)
+
+
+def test_differentiable_without_attention_is_a_value_error():
+    model = K.KGATPropagation(20, 3, input_node_dim=16, relation_dim=16, num_gnn_layers=1, n_hidden=16, dropout=0.0,
+                              use_attention=False)
+    with pytest.raises(ValueError):
+        model.compute_attention(None, differentiable=True)
+
+
+def test_differentiable_on_a_partitioned_graph_is_a_dgl_error():
+    g = DGLGraph()
+    g.add_nodes(4)
+    g.add_edges([0, 1, 2], [1, 2, 3])
+    g.edata["type"] = torch.zeros(3, dtype=torch.long)
+    g.partition = object()
+    ent, W, rel = torch.zeros(4, 16), torch.zeros(2, 16, 16), torch.zeros(2, 16)
+    with pytest.raises(DGLError):
+        g.kgat_attention(ent, W, rel, differentiable=True)
+    with pytest.raises(DGLError):
+        autograd.kgat_attention(g, ent, W, rel)
+    model = K.KGATPropagation(4, 2, input_node_dim=16, relation_dim=16, num_gnn_layers=1, n_hidden=16, dropout=0.0)
+    g.ndata["id"] = torch.arange(4)
+    with pytest.raises(DGLError):
+        model.compute_attention(g, differentiable=True)
+
+
+def _train_kgat():
+    spec = importlib.util.spec_from_file_location("_train_kgat_parser_att_bwd", os.path.join(ROOT, "examples", "train_kgat.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_example_parser():
+    tk = _train_kgat()
+    assert tk.parse_args([]).attention_grad == 0
+    assert tk.parse_args(["--attention_grad", "1"]).attention_grad == 1
+    assert tk.parse_args(["--attention_grad", "1", "--res_type", "GCN"]).attention_grad == 1
+    for bad in (["--use_attention", "0"], ["--node_dropout", "0.1"], ["--gpus", "2"], ["--gnn_model", "graphsage"]):
+        with pytest.raises(SystemExit):
+            tk.parse_args(["--attention_grad", "1"] + bad)
+        tk.parse_args(["--attention_grad", "0"] + bad)   # each is fine without the switch
+    with pytest.raises(SystemExit):
+        tk.parse_args(["--attention_grad", "2"])
