@@ -58,11 +58,11 @@ SIGNATURES = {
                                          _p, _p, _p, _p, _i32, _p]),
     "kgat_fold_tiles_max": (_i64, [_i64, _i64, _i32, _i32]),
     "kgat_fold_tiles_workspace_bytes": (_sz, [_i64, _i32]),
-    "kgat_fold_tiles": (_i32, [_i64, _i32, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "kgat_fold_tiles": (_i32, [_i64, _i32, _i64, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     "kgat_att_score_fused_supported": (_i32, [_i64, _i32, _i32, _i32]),
     "kgat_fold_tile_parts_workspace_bytes": (_sz, [_i64]),
     "kgat_fold_tile_parts": (_i32, [_i64, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
-    "kgat_att_pack_records": (_i32, [_i64, _i32, _p, _p, _p, _p, _i32, _p, _p]),
+    "kgat_att_pack_records": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _p]),
     "kgat_att_score_fused_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32,
                                         _p, _p, _p, _p, _p, _p, _i32, _p]),
     "kgat_att_score_fused_timed_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32,
@@ -84,17 +84,13 @@ SIGNATURES = {
     "kgat_spmm_bi_fused_supported": (_i32, [_i32, _i32]),
     "kgat_spmm_bi_fused_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p,
                                       _i64, _p, _p, _sz, _p, _i64, _p]),
-    "kgat_bi_interaction_train_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, C.c_float, C.c_float, C.c_uint64, _i64, _p,
-                                             _p, _i64, _p, _i64, _p]),
     "kgat_add3_rows_f32": (_i32, [_i64, _i32, _p, _i64, _p, _p, _p, _p]),
     "kgat_sum_partials_f32": (_i32, [_i32, _p, _p, _p, _p, _p]),
     "kgat_bi_interaction_bwd_pre_f32": (_i32, [_i64, _i32, _p, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_uint64, _i64,
                                                _p, _p]),
     "kgat_mul2_f32": (_i32, [_i64, _p, _p, _p, _p, _p, _p]),
     "kgat_bi_interaction_bwd_input_supported": (_i32, [_i32, _i32]),
-    "kgat_bi_interaction_bwd_input_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "kgat_bi_interaction_bwd_weight_partials": (_i64, [_i64]),
-    "kgat_bi_interaction_bwd_weight_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _i64, _p]),
     "kgat_transr_supported": (_i32, [_i64, _i32, _i32, _i32, _i64]),
     "kgat_transr_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "kgat_transr_loss_grad_f32": (_i32, [_i64, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p,
@@ -102,9 +98,6 @@ SIGNATURES = {
     "kgat_transr_forward_f32": (_i32, [_i64, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p, _sz, _p]),
     "kgat_transr_backward_f32": (_i32, [_i64, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_bi_interaction_f32": (_i32, [_i64, _i32, _i32, _p, _p, C.c_float, _p, _p, _i64, _p]),
-    "kgat_bi_interaction_mul_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, C.c_float, _p, _p, _i64, _p, _i64, _p]),
-    "kgat_bi_interaction_mul_deferred_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, C.c_float, _p, _p, _i64, _p, _i64,
-                                                    _p, _i64, _i64, _p, _i32, _p]),
     "kgat_spmm_tile_edges": (_i32, [_i64, _i32]),
     "kgat_l2_normalize_rows_f32": (_i32, [_i64, _i32, _p, _p, _i64, _p]),
     "kgat_readout_concat_f32": (_i32, [_i64, _i32, _p, _p, _p, _p, _i64, _p]),
@@ -179,7 +172,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def source_hash():

@@ -57,7 +57,7 @@ __device__ __forceinline__ bool drop_keep(uint32_t seed, uint32_t index, uint32_
   return x >= threshold;
 }
 
-// MODE 0: the A operand is P as given.  MODE 1 (kgat_bi_interaction_mul_f32): A = H * HN formed while loading
+// MODE 0: the A operand is P as given.  MODE 1 (kgat_aggregator_f32): A = H * HN formed while loading
 // (P = H, second factor HN) - the th.mul of reference models.py:66, which the aggregation used to form in its
 // epilogue at the price of a dependent X[v] load inside its edge loop (91 vs 78 us, profiles/
 // r04_spmm_epilogue_probe.txt) and which costs this kernel one more coalesced stream; the rows of H can also be
@@ -68,7 +68,7 @@ struct EgoCopy {
   float* out;      // nullptr: off
   int64_t stride;  // row stride in floats
 };
-// DEFER (MODE 1, kgat_bi_interaction_mul_deferred_f32): HN comes from an aggregation launched with
+// DEFER (MODE 1, kgat_aggregator_deferred_f32): HN comes from an aggregation launched with
 // KGAT_SPMM_DEFER_FINISH - its second launch (kgat_spmm_impl.h: spmm_finish_kernel) did not run, so the rows that
 // are the first or the last row of one of its edge tiles, and the rows without in-edges, are not in HN: this
 // kernel forms them on the way, from the row offsets and the tiles' boundary partials in the aggregation's
@@ -1057,13 +1057,6 @@ int kgat_bi_interaction_f32(int64_t n_rows, int d_in, int d_out, const float* P,
                      as_stream(stream), 0);
 }
 
-int kgat_bi_interaction_mul_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W2,
-                                float negative_slope, float* h_out, float* norm_out, int64_t norm_stride,
-                                float* self_out, int64_t self_stride, kgat_stream_t stream) {
-  return kgat_aggregator_f32(KGAT_FORM_BI, n_rows, d_in, d_out, H, HN, W2, negative_slope, h_out, norm_out, norm_stride,
-                             self_out, self_stride, stream);
-}
-
 int kgat_aggregator_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W2,
                         float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
                         int64_t self_stride, kgat_stream_t stream) {
@@ -1080,16 +1073,6 @@ int kgat_aggregator_f32(int form, int64_t n_rows, int d_in, int d_out, const flo
   }
   return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
                        as_stream(stream), 1, EgoCopy{self_out, self_stride});
-}
-
-int kgat_bi_interaction_mul_deferred_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
-                                         const float* W2, float negative_slope, float* h_out, float* norm_out,
-                                         int64_t norm_stride, float* self_out, int64_t self_stride,
-                                         const int32_t* indptr_rows, int64_t e_begin, int64_t e_end,
-                                         const void* spmm_workspace, int tile_edges, kgat_stream_t stream) {
-  return kgat_aggregator_deferred_f32(KGAT_FORM_BI, n_rows, d_in, d_out, H, HN, W2, negative_slope, h_out, norm_out,
-                                      norm_stride, self_out, self_stride, indptr_rows, e_begin, e_end, spmm_workspace,
-                                      tile_edges, stream);
 }
 
 int kgat_aggregator_deferred_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
@@ -1115,14 +1098,6 @@ int kgat_aggregator_deferred_f32(int form, int64_t n_rows, int d_in, int d_out, 
   const DeferredRows df{indptr_rows, static_cast<const float4*>(spmm_workspace), (int32_t)e_begin, (int32_t)e_end, shift};
   return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
                        as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
-}
-
-int kgat_bi_interaction_train_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
-                                  const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0,
-                                  float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
-                                  int64_t self_stride, kgat_stream_t stream) {
-  return kgat_aggregator_train_f32(KGAT_FORM_BI, n_rows, d_in, d_out, H, HN, W2, negative_slope, drop_p, seed, row0,
-                                   h_out, norm_out, norm_stride, self_out, self_stride, stream);
 }
 
 int kgat_aggregator_train_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
@@ -1340,16 +1315,6 @@ int kgat_bi_interaction_bwd_input_supported(int d_in, int d_out) {
   return ok(d_in) && ok(d_out);
 }
 
-int kgat_bi_interaction_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W2,
-                                      const float* H, const float* HN, float* grad_hn_times_h, float* grad_h_direct,
-                                      kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_bwd_input: bad row count");
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(grad_z && W2 && H && HN && grad_hn_times_h && grad_h_direct, "bi_interaction_bwd_input: null pointer");
-  return kgat_aggregator_bwd_input_f32(KGAT_FORM_BI, n_rows, d_in, d_out, grad_z, W2, H, HN, grad_hn_times_h,
-                                       grad_h_direct, stream);
-}
-
 int kgat_aggregator_bwd_supported(int form, int d_in, int d_out) {
   return (form == KGAT_FORM_BI || form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) &&
          kgat_bi_interaction_bwd_input_supported(d_in, d_out);
@@ -1378,11 +1343,6 @@ int64_t kgat_bi_interaction_bwd_weight_partials(int64_t n_rows) {
   int64_t nb = (n_rows + 63) / 64;
   if (nb > 768) nb = 768;   // three workgroups per CU; each partial is d_out x d_in floats
   return nb < 1 ? 1 : nb;
-}
-
-int kgat_bi_interaction_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
-                                       const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream) {
-  return kgat_aggregator_bwd_weight_f32(KGAT_FORM_BI, n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, stream);
 }
 
 int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,

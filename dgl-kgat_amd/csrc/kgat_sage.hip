@@ -12,7 +12,7 @@
 //    over rows pre-scaled by 1 / max(deg, 1) of their destination (sage_bwd_input_kernel writes them so).
 //  * sage_dense: Z = act(H W_self^T + HN W_neigh^T + b_self + b_neigh) on v_mfma_f32_16x16x4_f32 (exact fp32): one
 //    wavefront per 16-row tile, both weights staged once per workgroup in MFMA fragment order in LDS; optional
-//    L2-normalised copy into a slice of the readout and the ego block (a copy of H) as kgat_bi_interaction_mul_f32.
+//    L2-normalised copy into a slice of the readout and the ego block (a copy of H) as kgat_aggregator_f32.
 //  * dropout_rows: out = (x [+ x2]) * keep / (1 - p) with the counter hash of the bi-interaction's dropout.
 //  * sage_bwd_input / sage_bwd_weight: grad_pre W_self, (grad_pre W_neigh) / max(deg, 1) and per-workgroup partials
 //    of grad_pre^T H, grad_pre^T HN and the column sums of grad_pre.

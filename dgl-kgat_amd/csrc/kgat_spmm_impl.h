@@ -366,7 +366,7 @@ constexpr int kSpmmXcdRemap = 0;
   // other lane groups and its gathers in flight wait for it (benchmark graph: 91.4 us with that epilogue against
   // 77.5 us for the plain operator, profiles/r04_spmm_epilogue_probe.txt).  A/B arm KGAT_SPMM_SELF_PREFETCH=1:
   // request it when the row OPENS instead.  The layer now forms h * h_N in the bi-interaction kernel
-  // (kgat_bi_interaction_mul_f32) and calls the plain operator.
+  // (kgat_aggregator_f32) and calls the plain operator.
 constexpr int kSpmmSelfPrefetch = 0;  // measured SLOWER (100.7 vs 91.4 us at D = 64): the conditional load makes every later wait of the loop conservative
   constexpr bool SELF_PF = MUL_SELF && !FUSED && kSpmmSelfPrefetch != 0;
   float4 xs = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -997,7 +997,7 @@ static int launch_merge_c(const SpmmArgs& a) {
   int64_t nz_blocks = (a.n_rows + kThreads - 1) / kThreads;  // one lane per row
   if (nz_blocks > 2048) nz_blocks = 2048;
   if (nz_blocks < 1) nz_blocks = 1;
-  // KGAT_SPMM_DEFER_FINISH: the consumer (kgat_bi_interaction_mul_deferred_f32) forms the tiles' first / last rows
+  // KGAT_SPMM_DEFER_FINISH: the consumer (kgat_aggregator_deferred_f32) forms the tiles' first / last rows
   // from the partials in the workspace, and the rows without in-edges, itself
   if (DO == 0 && (a.flags & KGAT_SPMM_DEFER_FINISH)) return KGAT_OK;
   hipLaunchKernelGGL((spmm_finish_kernel<LPR, C, MUL_SELF, COPY_SELF, DO>),

@@ -346,9 +346,8 @@ def _f32_products():
 
 
 def _fused_gpt(n_nodes, d):
-    """Head groups per work tile of the fused attention kernel: 32 at d = k = 64 with the piece products (the kernel on
-    v_mfma_f32_32x32x16_f16, KGAT_ATT_TILES32; node ids below 2^27), else 16."""
-    return 32 if (d == 64 and options.att_tiles32 and not _f32_products() and n_nodes < (1 << 27)) else 16
+    """Head groups per work tile of the fused attention kernel (bench.py counts the launch's FLOPs with it)."""
+    return 16
 
 
 def _gpos_csr(groups):
@@ -358,26 +357,23 @@ def _gpos_csr(groups):
     return groups.g_tab["gpos_csr"]
 
 
-def _fused_statics(groups, gpt=16):
-    """Packed records of the fused path for `gpt` groups per tile + the position map (graph-static)."""
-    rec = groups.g_tab.get(("rec_g", gpt))
+def _fused_statics(groups):
+    """Packed records of the fused path + the position map (graph-static)."""
+    rec = groups.g_tab.get("rec_g")
     if rec is None:
-        rec = groups.g_tab[("rec_g", gpt)] = ops.att_pack_records(groups.rel_ptr, groups.gptr, groups.gid, groups.src_g,
-                                                                  groups_per_tile=gpt)
+        rec = groups.g_tab["rec_g"] = ops.att_pack_records(groups.rel_ptr, groups.gptr, groups.gid, groups.src_g)
     return rec, _gpos_csr(groups)
 
 
-def _fused_tiles(groups, d, gpt=16):
+def _fused_tiles(groups, d):
     """Work tiles of the fused attention kernel and their split over the workgroups, kept with the
     relation grouping (graph-static); the split cost goes with the product form taken at width d."""
-    cost = ops.fold_tile_cost(d, _f32_products(), gpt)
-    key = (cost, gpt)
+    cost = ops.fold_tile_cost(d, _f32_products())
     tiles = groups.g_tab.get("tiles")
-    if tiles is None or groups.g_tab.get("tiles_cost") != key:
+    if tiles is None or groups.g_tab.get("tiles_cost") != cost:
         tiles = groups.g_tab["tiles"] = ops.fold_tiles(groups.rel_ptr, groups.gid, groups.gptr, groups.n_groups,
-                                                       cap=ops.FOLD_TILE_CAP32 if gpt == 32 else ops.FOLD_TILE_CAP,
-                                                       cost=cost, groups_per_tile=gpt)
-        groups.g_tab["tiles_cost"] = key
+                                                       cost=cost)
+        groups.g_tab["tiles_cost"] = cost
     return tiles
 
 
@@ -665,10 +661,8 @@ class DGLGraph:
                         best = (ms, f)
                 form = best[1]
             else:
-                gpt = _fused_gpt(st.n_nodes, d)
-                tiles = _fused_tiles(groups, d, gpt)
-                n_tiles = int(tiles[1][-1])
-                form = "fused" if n_tiles <= 2 * ((groups.n_groups + gpt - 1) // gpt) else "folded"
+                n_tiles = int(_fused_tiles(groups, d)[1][-1])
+                form = "fused" if n_tiles <= 2 * ((groups.n_groups + 15) // 16) else "folded"   # 16 groups per tile
             groups.g_tab.pop("tiles" if form == "folded" else d, None)  # the other form's scratch
             return form
         if fused_ok:
@@ -760,22 +754,18 @@ class DGLGraph:
         # do the whole relation-space product per group and a d-length dot per edge (one launch
         # with the per-group vectors in LDS / two launches with a table); "split" keeps the
         # reference's contraction order (bit-identical to "one")
-        grouped_out = not options.att_scatter_csr
 
         def run(form):
             if form == "fused":
-                gpt = _fused_gpt(st.n_nodes, d)
-                tiles = _fused_tiles(groups, d, gpt)  # graph-static work tiles of the fused kernel
-                rec, _ = _fused_statics(groups, gpt)
+                tiles = _fused_tiles(groups, d)  # graph-static work tiles of the fused kernel
+                rec, _ = _fused_statics(groups)
                 # the logits leave in grouped order (coalesced stores); the softmax reads them through
-                # the inverse position map.  KGAT_ATT_SCATTER_CSR=1: the round-2 form, a 4-byte
-                # scatter into CSR order (73 MB written for 14.6 MB of logits on the benchmark graph)
-                res = ops.att_score_fused(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.pos_g,
-                                          groups.gid, groups.gptr, groups.g_node, tiles[0], tiles[1],
-                                          ent_c, W_c, rel_c, want_eid=False, want_csr=not grouped_out,
-                                          want_grouped=grouped_out, part_tptr=tiles[2],
-                                          f32_products=_f32_products(), rec_g=rec, groups_per_tile=gpt)
-                return res[2] if grouped_out else res[1]
+                # the inverse position map (a 4-byte scatter into CSR order wrote 73 MB for 14.6 MB of
+                # logits on the benchmark graph)
+                return ops.att_score_fused(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.pos_g,
+                                           groups.gid, groups.gptr, groups.g_node, tiles[0], tiles[1],
+                                           ent_c, W_c, rel_c, want_eid=False, want_csr=False, want_grouped=True,
+                                           part_tptr=tiles[2], f32_products=_f32_products(), rec_g=rec)[2]
             if form in ("folded", "split"):
                 folded = form == "folded"
                 width = d if folded else k
@@ -801,7 +791,7 @@ class DGLGraph:
         if form not in ("fused", "folded", "split"):
             form = "one"
         st.last_att_form = (form, groups.n_groups)
-        if form == "fused" and grouped_out:
+        if form == "fused":
             # grouped-order logits: the sweep gathers logits[gpos_csr[q]] for CSR position q (the map
             # takes the place of `eid` on the input side; no edge-id-ordered output is asked for)
             _, a_csr = ops.edge_softmax(csr.indptr, csr.row_of, _gpos_csr(groups), logits,

@@ -354,7 +354,7 @@ class KGATPropagation(nn.Module):
             # (the gradient of a layer's input is needed in full only where that input is a replicated parameter -
             # the embedding table under layer 0; deeper layers reduce it to the rows' owners)
             h = shard_conv(g.partition, g, h, layer.res_fc_2.weight, 0.01, p, seed + li,
-                           owner_only_grad=li > 0 and not options.shard_grad_allreduce)
+                           owner_only_grad=li > 0)
             cache.append(F.normalize(h, p=2, dim=1))
         return torch.cat(cache, 1)
 
@@ -393,8 +393,8 @@ class KGATPropagation(nn.Module):
                                 for form, _, d_in, d_out in map(_layer_dense, self.layers))
 
     def _gnn_fused(self, g):
-        """No-grad fast path: aggregation with the h*h_N epilogue, then one kernel per layer for
-        Linear + LeakyReLU + the L2-normalised copy written into its slice of the output."""
+        """No-grad fast path: the plain aggregation, then one kernel per layer for h * h_N (or the layer's other
+        combination) + Linear + LeakyReLU + the L2-normalised copy written into its slice of the output."""
         from . import ops
         h = self._node_embeddings(g).detach()
         dense = [_layer_dense(layer) for layer in self.layers]
@@ -403,68 +403,47 @@ class KGATPropagation(nn.Module):
         h0 = h
         off = widths[0]
         w = g.edata["w"]
-        # the first aggregation also writes the ego block (kgat_spmm_umule_sum_f32's self_out: X[v] is in a
-        # register for the h * h_N product anyway) instead of an N x d copy pass at the end: step 0.491 ->
-        # 0.481 ms on the benchmark graph (the copy launch was 18 us; the aggregation grows by 3.5 us, and
-        # the attention launch of the next step by 3.5 us because the pass no longer ends on the embedding
-        # table).  KGAT_GNN_COPY_SELF=0 restores the separate copy.
-        copy_self = options.gnn_copy_self and widths[0] % 4 == 0
+        # the first layer's dense kernel also writes the ego block (self_out: the rows of its input are in registers
+        # anyway) instead of an N x d copy pass at the end: step 0.491 -> 0.481 ms on the benchmark graph
+        copy_self = widths[0] % 4 == 0
         # KGAT_FUSE_BI=1: aggregation and dense part of a layer in ONE launch where the widths allow
         # (kgat_spmm_bi_fused_f32: the rows h * h_N stay with the workgroup that completed them; same bits as the
         # two launches).  Off by default: measured 3-4 % SLOWER per layer than the two launches on the benchmark
         # graph (119.7 vs 116.4 us at 64 -> 64, profiles/r04_fused_bi_ab.txt) - the dense tail
         # keeps a workgroup's gather slots idle, which costs the latency-bound aggregation more than the 82 MB
         # round trip of h * h_N costs the separate launch.
+        # (it computes the product alone: a GCN / GraphSage / Bi2 layer skips it and takes its dense kernel below)
         fuse_bi = options.fuse_bi
-        # KGAT_GNN_MUL_IN_SPMM=1: rounds 1-3's split - h * h_N in the aggregation's epilogue (A/B)
-        mul_in_spmm = options.gnn_mul_in_spmm
-        # (both compute the product alone: a GCN / GraphSage / Bi2 layer skips them and takes its dense kernel below)
         defer = options.gnn_defer_finish
         st = g._st
         scratch = None
         for li, (form, W, _, _) in enumerate(dense):
             last = li + 1 == len(self.layers)
-            norm_out = out[:, off:off + widths[li + 1]]
-            bi = form == FORMS["Bi"]
-            if (bi and fuse_bi and ops.spmm_bi_fused_supported(widths[li], widths[li + 1]) and off % 4 == 0 and
-                    out.shape[1] % 4 == 0 and h.shape[0] > 0):
+            lo, off = off, off + widths[li + 1]
+            norm_out = out[:, lo:off]
+            self_out = out[:, :widths[0]] if (li == 0 and copy_self) else None
+            hc = h.contiguous()
+            if (form == FORMS["Bi"] and fuse_bi and ops.spmm_bi_fused_supported(widths[li], widths[li + 1]) and
+                    lo % 4 == 0 and out.shape[1] % 4 == 0 and h.shape[0] > 0):
                 csr = st.csr(h.device)
                 if scratch is None or scratch.shape[1] != widths[li]:
                     scratch = torch.empty((h.shape[0], widths[li]), dtype=torch.float32, device=h.device)
-                h = ops.spmm_bi_fused(csr.indptr, csr.col, csr.row_of, h.contiguous(), st.csr_weights(w),
-                                      W.detach(), 0.01, norm_out=norm_out, want_h=not last,
-                                      scratch=scratch, self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
-                off += widths[li + 1]
+                h = ops.spmm_bi_fused(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), W.detach(), 0.01,
+                                      norm_out=norm_out, want_h=not last, scratch=scratch, self_out=self_out)
                 continue
-            if not (bi and mul_in_spmm):
-                # the plain aggregation, and h * h_N formed by the dense kernel while it loads its rows (+ the ego
-                # block of the readout from the rows of layer 0's input): round 4 - the aggregation's h * h_N
-                # epilogue is a dependent X[v] load per finished row inside its edge loop, 91 vs 78 us per launch
-                # ... and the aggregation's second launch (the sums of the rows its edge tiles cut, the zero rows)
-                # left to that kernel too: the rows are formed there from the tiles' partials, in the same order of
-                # additions (KGAT_SPMM_DEFER_FINISH; same bits, one dependent launch less per layer: step 0.4415 ->
-                # 0.43 ms).  KGAT_GNN_DEFER_FINISH=0 restores the two launches.
-                if defer and ops.bi_interaction_deferral_supported(widths[li], widths[li + 1]) and h.shape[0] > 0:
-                    csr = st.csr(h.device)
-                    hc = h.contiguous()
-                    hn, rows_left = ops.spmm(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), defer_finish=True)
-                    h = _dense_no_grad(form, hc, hn, W, norm_out=norm_out, want_h=not last,
-                                       deferred=rows_left, self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
-                    off += widths[li + 1]
-                    continue
-                hn = u_mul_e_sum(g, h, w)
-                h = _dense_no_grad(form, h.contiguous(), hn, W, norm_out=norm_out, want_h=not last,
-                                   self_out=out[:, :widths[0]] if (li == 0 and copy_self) else None)
-                off += widths[li + 1]
-                continue
-            if li == 0 and copy_self:
+            # the plain aggregation; h * h_N is formed by the dense kernel while it loads its rows (as an epilogue of
+            # the aggregation it is a dependent X[v] load per finished row inside the edge loop: 91 vs 78 us per
+            # launch).  The aggregation's second launch (the sums of the rows its edge tiles cut, the zero rows) is
+            # left to the dense kernel too: it forms those rows from the tiles' partials in the same order of
+            # additions (KGAT_SPMM_DEFER_FINISH; same bits, one dependent launch less per layer: step 0.4415 ->
+            # 0.43 ms).  KGAT_GNN_DEFER_FINISH=0 restores the two launches.
+            if defer and ops.bi_interaction_deferral_supported(widths[li], widths[li + 1]) and h.shape[0] > 0:
                 csr = st.csr(h.device)
-                prod = ops.spmm(csr.indptr, csr.col, csr.row_of, h.contiguous(), st.csr_weights(w), mul_self=True,
-                                self_out=out[:, :widths[0]])
+                hn, rows_left = ops.spmm(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), defer_finish=True)
             else:
-                prod = u_mul_e_sum(g, h, w, mul_self=True)
-            h = ops.bi_interaction(prod, W.detach(), 0.01, norm_out=norm_out, want_h=not last)
-            off += widths[li + 1]
+                hn, rows_left = u_mul_e_sum(g, h, w), None
+            h = _dense_no_grad(form, hc, hn, W, norm_out=norm_out, want_h=not last, deferred=rows_left,
+                               self_out=self_out)
         # the ego-embedding block last: the pass ends having just touched the embedding table, which
         # is what the next attention refresh gathers from (a step's working set is about the size
         # of the 256 MiB Infinity Cache; written first, the table was the oldest resident by then:

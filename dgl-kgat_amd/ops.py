@@ -197,7 +197,6 @@ def head_groups(rel_ptr, dst_g):
 
 
 ATT_F32_PRODUCTS = 1  # include/kgat_hip.h: KGAT_ATT_F32_PRODUCTS
-ATT_TILES32 = 2       # include/kgat_hip.h: KGAT_ATT_TILES32
 
 
 def att_score_split_supported(n_nodes, d, k, n_rel):
@@ -249,7 +248,6 @@ def att_score_split(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, n_g
 # small part of its workgroup's time for the eight waves to balance.  Measured on MI355X with the
 # cost-balanced split (amazon-book-shaped CKG): 128: 0.2135 ms, 256: 0.2019.
 FOLD_TILE_CAP = 256
-FOLD_TILE_CAP32 = 512   # 32-group tiles (d = 64): the same positions per head group
 # per-tile cost model of the fused kernel (kgat_fold_tile_parts; from per-workgroup clock stamps,
 # scripts/micro/att_stamps.py): a tile, a chunk of 64 positions past the first 64, a relation
 # change inside a workgroup's range.  With the bf16-piece products (d % 32 == 0) the fit is 649
@@ -272,10 +270,7 @@ FOLD_TILE_COST_F32 = (64, 12, 466)
 FOLD_TILE_COST_128 = (64, 24, 700)
 
 
-FOLD_TILE_COST32 = (110, 38, 1051)   # 32-group tiles: a tile's MFMA phase serves twice the groups (round 5)
-
-
-def fold_tile_cost(d, f32_products=False, groups_per_tile=16):
+def fold_tile_cost(d, f32_products=False):
     """The split cost that goes with the product form att_score_fused takes at width d
     (``KGAT_FOLD_TILE_COST="tile,chunk,relation"`` overrides it: A/B runs of the whole step)."""
     from .options import options
@@ -283,12 +278,10 @@ def fold_tile_cost(d, f32_products=False, groups_per_tile=16):
         return options.fold_tile_cost
     if d == 128:
         return FOLD_TILE_COST_128
-    if groups_per_tile == 32:
-        return FOLD_TILE_COST32
     return FOLD_TILE_COST if (d % 32 == 0 and not f32_products) else FOLD_TILE_COST_F32
 
 
-def fold_tiles(rel_ptr, gid, gptr, n_groups, cap=FOLD_TILE_CAP, n_parts=None, cost=FOLD_TILE_COST, groups_per_tile=16):
+def fold_tiles(rel_ptr, gid, gptr, n_groups, cap=FOLD_TILE_CAP, n_parts=None, cost=FOLD_TILE_COST):
     """Work tiles of the fused attention kernel (kgat_fold_tiles) and their cost-balanced split
     over `n_parts` workgroups (kgat_fold_tile_parts; default: one per compute unit).  Returns
     (tiles (T_max, 4) int32, rel_tptr (R+1,) int32, part_tptr (n_parts+1,) int32); rel_tptr[-1]
@@ -305,8 +298,7 @@ def fold_tiles(rel_ptr, gid, gptr, n_groups, cap=FOLD_TILE_CAP, n_parts=None, co
     rel_tptr = torch.zeros(n_rel + 1, dtype=torch.int32, device=dev)
     ws = _workspace(lib.kgat_fold_tiles_workspace_bytes(int(n_groups), n_rel), dev)
     check(lib.kgat_fold_tiles(e, n_rel, int(n_groups), _ptr(rel_ptr), _ptr(gid), _ptr(gptr), int(cap),
-                              int(groups_per_tile), _ptr(tiles), _ptr(rel_tptr), _ptr(ws), ws.numel(), _stream(gid)),
-          "kgat_fold_tiles")
+                              _ptr(tiles), _ptr(rel_tptr), _ptr(ws), ws.numel(), _stream(gid)), "kgat_fold_tiles")
     if n_parts is None:
         n_parts = torch.cuda.get_device_properties(dev).multi_processor_count
     part_tptr = torch.zeros(int(n_parts) + 1, dtype=torch.int32, device=dev)
@@ -321,8 +313,8 @@ def att_score_fused_supported(n_nodes, d, k, n_rel):
     return bool(_lib.load().kgat_att_score_fused_supported(int(n_nodes), int(d), int(k), int(n_rel)))
 
 
-def att_pack_records(rel_ptr, gptr, gid, src_g, groups_per_tile=16):
-    """rec_g[p] = src_g[p] | (slot of p's head group in its 16-group block << 28; 32-group block << 27): the one
+def att_pack_records(rel_ptr, gptr, gid, src_g):
+    """rec_g[p] = src_g[p] | (slot of p's head group in its 16-group block << 28): the one
     index the fused attention kernel reads per grouped position (kgat_att_pack_records; graph-static)."""
     rel_ptr = _need(rel_ptr, torch.int32, "rel_ptr")
     gptr = _need(gptr, torch.int32, "gptr", rel_ptr.shape)
@@ -331,13 +323,13 @@ def att_pack_records(rel_ptr, gptr, gid, src_g, groups_per_tile=16):
     gid = _need(gid, torch.int32, "gid", (e,))
     rec = torch.empty(e, dtype=torch.int32, device=src_g.device)
     check(_lib.load().kgat_att_pack_records(e, rel_ptr.numel() - 1, _ptr(rel_ptr), _ptr(gptr), _ptr(gid), _ptr(src_g),
-                                            int(groups_per_tile), _ptr(rec), _stream(src_g)), "kgat_att_pack_records")
+                                            _ptr(rec), _stream(src_g)), "kgat_att_pack_records")
     return rec
 
 
 def att_score_fused(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, tiles, rel_tptr, ent, W_R, rel,
                     want_csr=True, want_eid=True, part_tptr=None, f32_products=False, rec_g=None, want_grouped=False,
-                    groups_per_tile=16, part_clocks=None):
+                    part_clocks=None):
     """Attention logits, fused folded form (kgat_att_score_fused_f32).  The kernel reads one packed
     record per grouped position (`rec_g`, att_pack_records; built here from `src_g` / `gid` when the
     caller does not keep one).  `part_tptr`: the tile range of every workgroup (fold_tiles); None:
@@ -353,7 +345,7 @@ def att_score_fused(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, til
     _need(rel_ptr, torch.int32, "rel_ptr", (n_rel + 1,))
     _need(gptr, torch.int32, "gptr", (n_rel + 1,))
     if rec_g is None:
-        rec_g = att_pack_records(rel_ptr, gptr, gid, src_g, groups_per_tile)
+        rec_g = att_pack_records(rel_ptr, gptr, gid, src_g)
     rec_g = _need(rec_g, torch.int32, "rec_g")
     e = rec_g.numel()
     if want_eid:
@@ -370,7 +362,7 @@ def att_score_fused(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, til
     logits = torch.empty(e, dtype=torch.float32, device=ent.device) if want_eid else None
     logits_csr = torch.empty(e, dtype=torch.float32, device=ent.device) if want_csr else None
     logits_g = torch.empty(e, dtype=torch.float32, device=ent.device) if want_grouped else None
-    flags = (ATT_F32_PRODUCTS if f32_products else 0) | (ATT_TILES32 if groups_per_tile == 32 else 0)
+    flags = ATT_F32_PRODUCTS if f32_products else 0
     args = (n_nodes, e, d, k, n_rel, _ptr(rel_ptr), _ptr(perm) if want_eid else None, _ptr(rec_g),
             _ptr(pos_g) if want_csr else None, _ptr(gptr), _ptr(g_node), _ptr(tiles), _ptr(rel_tptr), _ptr(part_tptr), n_parts,
             _ptr(ent), _ptr(W_R), _ptr(rel), _ptr(logits), _ptr(logits_csr), _ptr(logits_g), flags)
@@ -619,7 +611,7 @@ class DeferredRows:
 
 
 def bi_interaction_deferral_supported(d_in, d_out):
-    """The widths kgat_spmm_umule_sum_f32(KGAT_SPMM_DEFER_FINISH) + kgat_bi_interaction_mul_deferred_f32 cover."""
+    """The widths kgat_spmm_umule_sum_f32(KGAT_SPMM_DEFER_FINISH) + kgat_aggregator_deferred_f32 cover."""
     return int(d_in) in (16, 32, 64, 128) and int(d_out) in (16, 32, 64, 128)
 
 
@@ -871,37 +863,8 @@ def bi_interaction(P, W2, negative_slope=0.01, h_out=None, norm_out=None, want_h
 
 def bi_interaction_mul(H, HN, W2, negative_slope=0.01, h_out=None, norm_out=None, want_h=True, self_out=None,
                        deferred=None):
-    """Z = leaky_relu((H * HN) @ W2^T) (kgat_bi_interaction_mul_f32): the layer input H and the plain aggregation HN,
-    the product formed while the rows are loaded; `self_out`: an (n, d_in) column slice that also receives H (the
-    ego block of the readout).  Otherwise as bi_interaction.  `deferred`: the DeferredRows of the
-    spmm(defer_finish=True) call that produced HN (kgat_bi_interaction_mul_deferred_f32; same bits)."""
-    H = _need(H, torch.float32, "H")
-    HN = _need(HN, torch.float32, "HN", H.shape)
-    W2 = _need(W2, torch.float32, "W2")
-    n, d_in = H.shape
-    d_out = W2.shape[0]
-    if W2.shape[1] != d_in:
-        raise ValueError("W2 has shape %s, expected (*, %d)" % (tuple(W2.shape), d_in))
-    if want_h and h_out is None:
-        h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
-    if h_out is not None:
-        h_out = _need(h_out, torch.float32, "h_out", (n, d_out))
-    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
-    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
-    with _timed("bi_interaction", (n, d_in, d_out)):
-        if deferred is not None:
-            if deferred.n_rows != n or deferred.D != d_in:
-                raise ValueError("deferred rows of a (%d, %d) aggregation with a (%d, %d) input" % (deferred.n_rows, deferred.D, n, d_in))
-            check(_lib.load().kgat_bi_interaction_mul_deferred_f32(
-                n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W2), float(negative_slope), _ptr(h_out), _ptr(norm_out), stride,
-                _ptr(self_out), self_stride, _ptr(deferred.indptr_rows), deferred.e_range[0], deferred.e_range[1],
-                _ptr(deferred.workspace), deferred.tile_edges, _stream(H)), "kgat_bi_interaction_mul_deferred_f32")
-        else:
-            check(_lib.load().kgat_bi_interaction_mul_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W2), float(negative_slope),
-                                                          _ptr(h_out), _ptr(norm_out), stride, _ptr(self_out), self_stride,
-                                                          _stream(H)),
-                  "kgat_bi_interaction_mul_f32")
-    return h_out
+    """Z = leaky_relu((H * HN) @ W2^T): `aggregator` with the "Bi" form."""
+    return aggregator(FORMS["Bi"], H, HN, W2, negative_slope, h_out, norm_out, want_h, self_out, deferred)
 
 
 def _strided_rows(t, n, d, name):
@@ -911,27 +874,8 @@ def _strided_rows(t, n, d, name):
 
 
 def bi_interaction_train(H, HN, W2, negative_slope, drop_p, seed, norm_out=None, row0=0, self_out=None):
-    """Training form: h_out = dropout_p(leaky_relu((H * HN) @ W2^T)) and its normalised copy into
-    `norm_out` (kgat_bi_interaction_train_f32; the mask is a hash of (seed, element); `row0`: the
-    global index of row 0 when H holds a row range of a larger matrix, so that a destination shard
-    draws the mask the unsharded layer draws)."""
-    H = _need(H, torch.float32, "H")
-    HN = _need(HN, torch.float32, "HN", H.shape)
-    W2 = _need(W2, torch.float32, "W2")
-    n, d_in = H.shape
-    d_out = W2.shape[0]
-    if W2.shape[1] != d_in:
-        raise ValueError("W2 has shape %s, expected (*, %d)" % (tuple(W2.shape), d_in))
-    h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
-    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
-    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0   # the ego block (copy of H)
-    with _timed("bi_interaction", (n, d_in, d_out)):
-        check(_lib.load().kgat_bi_interaction_train_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W2),
-                                                        float(negative_slope), float(drop_p), int(seed) & (2 ** 64 - 1),
-                                                        int(row0), _ptr(h_out), _ptr(norm_out), stride, _ptr(self_out),
-                                                        self_stride, _stream(H)),
-              "kgat_bi_interaction_train_f32")
-    return h_out
+    """Training form of bi_interaction_mul: `aggregator_train` with the "Bi" form."""
+    return aggregator_train(FORMS["Bi"], H, HN, W2, negative_slope, drop_p, seed, norm_out, row0, self_out)
 
 
 def add3_rows(a, b, c):
@@ -948,7 +892,7 @@ def add3_rows(a, b, c):
 
 def bi_interaction_bwd_pre(h_out, grad_a, grad_b, grad_norm, negative_slope, drop_p, seed, row0=0):
     """grad_z of the training layer (kgat_bi_interaction_bwd_pre_f32); grad_a / grad_b / grad_norm may be
-    None; `row0` as in bi_interaction_train."""
+    None; `row0` as in aggregator_train."""
     h_out = _need(h_out, torch.float32, "h_out")
     n, d = h_out.shape
     for name, t in (("grad_a", grad_a), ("grad_b", grad_b)):
@@ -968,20 +912,8 @@ def bi_interaction_bwd_input_supported(d_in, d_out):
 
 
 def bi_interaction_bwd_input(grad_z, W2, H, HN):
-    """((grad_z @ W2) * H, (grad_z @ W2) * HN) in one pass (kgat_bi_interaction_bwd_input_f32): the gradient of the
-    layer's dense part towards h_N (times h: what the reversed-CSR aggregation then sums) and towards h itself."""
-    grad_z = _need(grad_z, torch.float32, "grad_z")
-    W2 = _need(W2, torch.float32, "W2")
-    n, d_out = grad_z.shape
-    d_in = W2.shape[1]
-    if W2.shape[0] != d_out:
-        raise ValueError("W2 has shape %s, expected (%d, *)" % (tuple(W2.shape), d_out))
-    H = _need(H, torch.float32, "H", (n, d_in))
-    HN = _need(HN, torch.float32, "HN", (n, d_in))
-    t, gb = torch.empty_like(H), torch.empty_like(H)
-    check(_lib.load().kgat_bi_interaction_bwd_input_f32(n, d_in, d_out, _ptr(grad_z), _ptr(W2), _ptr(H), _ptr(HN), _ptr(t),
-                                                        _ptr(gb), _stream(H)), "kgat_bi_interaction_bwd_input_f32")
-    return t, gb
+    """((grad_z @ W2) * H, (grad_z @ W2) * HN): `aggregator_bwd_input` with the "Bi" form."""
+    return aggregator_bwd_input(FORMS["Bi"], grad_z, W2, H, HN)
 
 
 def sum_partials(partial_sets):
@@ -1005,22 +937,8 @@ def sum_partials(partial_sets):
 
 
 def bi_interaction_bwd_weight(grad_z, H, HN, want_partials=False):
-    """grad_W2 = grad_z^T (H * HN) (kgat_bi_interaction_bwd_weight_f32: per-workgroup partials over 64-row slabs, the
-    product formed on the way; the partials are added here in index order - or, want_partials=True, handed back for
-    ops.sum_partials, which sums several layers' sets in one launch)."""
-    grad_z = _need(grad_z, torch.float32, "grad_z")
-    n, d_out = grad_z.shape
-    H = _need(H, torch.float32, "H")
-    d_in = H.shape[1]
-    HN = _need(HN, torch.float32, "HN", (n, d_in))
-    if H.shape[0] != n:
-        raise ValueError("H has %d rows, grad_z %d" % (H.shape[0], n))
-    lib = _lib.load()
-    nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
-    partials = torch.empty((nb, d_out, d_in), dtype=torch.float32, device=H.device)
-    check(lib.kgat_bi_interaction_bwd_weight_f32(n, d_in, d_out, _ptr(grad_z), _ptr(H), _ptr(HN), _ptr(partials), nb,
-                                                 _stream(H)), "kgat_bi_interaction_bwd_weight_f32")
-    return partials if want_partials else partials.sum(0)
+    """grad_W2 = grad_z^T (H * HN): `aggregator_bwd_weight` with the "Bi" form."""
+    return aggregator_bwd_weight(FORMS["Bi"], grad_z, H, HN, want_partials)
 
 
 # The KGAT layer's aggregators (KGATConv res_type; include/kgat_hip.h KGAT_FORM_*): Bi-Interaction LeakyReLU(W (h * h_N)),
@@ -1047,14 +965,17 @@ def _form_weight(form, W, d_in):
 
 
 def _agg_timed(form, n, d_in, d_out):
-    # (Bi under the name and key of its own entries: KernelTimer summaries read the same with either call path)
+    # (Bi under the name and key of ops.bi_interaction: the KernelTimer summaries of the benchmark read that name)
     return _timed("bi_interaction", (n, d_in, d_out)) if form == FORMS["Bi"] else _timed("aggregator", (form, n, d_in, d_out))
 
 
 def aggregator(form, H, HN, W, negative_slope=0.01, h_out=None, norm_out=None, want_h=True, self_out=None,
                deferred=None):
-    """Z = leaky_relu(combine(H, HN) @ W^T) with combine = H * HN (form 0, the bits of bi_interaction_mul), H + HN (1) or
-    [H | HN] (2) (kgat_aggregator_f32 / kgat_aggregator_deferred_f32); arguments as bi_interaction_mul."""
+    """Z = leaky_relu(combine(H, HN) @ W^T) with combine = H * HN (form 0), H + HN (1) or [H | HN] (2)
+    (kgat_aggregator_f32): the layer input H and the plain aggregation HN, combined while the rows are loaded;
+    `self_out`: an (n, d_in) column slice that also receives H (the ego block of the readout).  Otherwise as
+    bi_interaction.  `deferred`: the DeferredRows of the spmm(defer_finish=True) call that produced HN
+    (kgat_aggregator_deferred_f32; same bits)."""
     H = _need(H, torch.float32, "H")
     HN = _need(HN, torch.float32, "HN", H.shape)
     n, d_in = H.shape
@@ -1081,7 +1002,10 @@ def aggregator(form, H, HN, W, negative_slope=0.01, h_out=None, norm_out=None, w
 
 
 def aggregator_train(form, H, HN, W, negative_slope, drop_p, seed, norm_out=None, row0=0, self_out=None):
-    """Training form of `aggregator` (kgat_aggregator_train_f32): as bi_interaction_train for any form."""
+    """Training form of `aggregator`: h_out = dropout_p(leaky_relu(combine(H, HN) @ W^T)) and its normalised copy into
+    `norm_out` (kgat_aggregator_train_f32; the mask is a hash of (seed, element); `row0`: the global index of row 0
+    when H holds a row range of a larger matrix, so that a destination shard draws the mask the unsharded layer
+    draws)."""
     H = _need(H, torch.float32, "H")
     HN = _need(HN, torch.float32, "HN", H.shape)
     n, d_in = H.shape
@@ -1119,8 +1043,9 @@ def aggregator_bwd_input(form, grad_z, W, H, HN):
 
 
 def aggregator_bwd_weight(form, grad_z, H, HN, want_partials=False):
-    """grad_W of the form's dense part (kgat_aggregator_bwd_weight_f32's partials, d_out x 2 d_in for GraphSage; summed
-    here in index order - or, want_partials=True, handed back for sum_partials)."""
+    """grad_W of the form's dense part (kgat_aggregator_bwd_weight_f32: per-workgroup partials over 64-row slabs,
+    d_out x 2 d_in for GraphSage, the combination formed on the way; the partials are added here in index order - or,
+    want_partials=True, handed back for sum_partials, which sums several layers' sets in one launch)."""
     grad_z = _need(grad_z, torch.float32, "grad_z")
     n, d_out = grad_z.shape
     H = _need(H, torch.float32, "H")
@@ -1273,7 +1198,7 @@ def mul2(a, b, c):
 
 
 def dropout_keep_mask(seed, n_rows, d, drop_p, row0=0):
-    """The mask kgat_bi_interaction_train_f32 applies, restated in numpy (tests): element (row, col)
+    """The mask kgat_aggregator_train_f32 applies, restated in numpy (tests): element (row, col)
     is kept iff murmur3-finalised (((row0 + row)*d + col) * 0x9E3779B1 ^ seed32) >= p * 2^32."""
     import numpy as np
     seed = int(seed) & (2 ** 64 - 1)

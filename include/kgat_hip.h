@@ -28,9 +28,10 @@
 extern "C" {
 #endif
 
-#define KGAT_ABI_VERSION 15
-/* Added at 15 without a bump (additive: no existing entry changed): kgat_att_score_bwd_supported,
- * kgat_att_score_bwd_workspace_bytes, kgat_att_score_bwd_f32. */
+#define KGAT_ABI_VERSION 16
+/* 16: removed the five kgat_bi_interaction_{mul,mul_deferred,train,bwd_input,bwd_weight} entries (call the
+ * kgat_aggregator_* entry with KGAT_FORM_BI), flag value 2 of the fused attention (a kernel on 32-group tiles) and the
+ * groups-per-tile parameter of kgat_fold_tiles / kgat_att_pack_records. */
 
 enum {
   KGAT_OK = 0,
@@ -43,7 +44,7 @@ enum {
 /* flags for kgat_spmm_umule_sum_f32 */
 enum {
   KGAT_SPMM_MUL_SELF = 1, /* out[v,:] *= X[row0+v,:]  (the h * h_neighbor of models.py:66) */
-  KGAT_SPMM_DEFER_FINISH = 2 /* the second launch is left to kgat_bi_interaction_mul_deferred_f32 (see there) */
+  KGAT_SPMM_DEFER_FINISH = 2 /* the second launch is left to kgat_aggregator_deferred_f32 (see kgat_spmm_tile_edges) */
 };
 
 /* algorithm selectors (AUTO picks the tuned kernel; the others exist for A/B and tests) */
@@ -65,7 +66,7 @@ enum {
 
 /* flags for kgat_att_score_fused_f32 and kgat_att_score_folded_f32 */
 enum {
-  KGAT_ATT_F32_PRODUCTS = 1, /* both products as v_mfma_f32_16x16x4_f32 (the round-1 form) instead of
+  KGAT_ATT_F32_PRODUCTS = 1 /* both products as v_mfma_f32_16x16x4_f32 (the round-1 form) instead of
                              * the default where a kernel has it (fused: d % 32 == 0; folded: d = 128):
                              * every fp32 operand cut by round-to-nearest into three bf16 pieces that
                              * sum to it exactly (|m| <= 2^-8 |x|, |l| <= 2^-16 |x|), the six piece
@@ -73,12 +74,6 @@ enum {
                              * v_mfma_f32_16x16x32_bf16; the three dropped products are together
                              * < 2^-23 of |a*b| (one fp32 ulp), of either sign; error against fp64
                              * measured no larger than the fp32 form's */
-  KGAT_ATT_TILES32 = 2      /* kgat_att_score_fused_f32 at d = k = 64: `tiles` / `rec_g` were built with 32 groups per
-                             * tile (kgat_fold_tiles / kgat_att_pack_records, groups_per_tile = 32): the kernel on
-                             * v_mfma_f32_32x32x16_f16 with both products on fp16 pieces (W_r 2^shift three, the head
-                             * rows - scaled per row to [2^13, 2^14) - and the tanh values 2^14 two: five piece products
-                             * each).  Opt-in (KGAT_ATT_TILES32=1): 25 % fewer vector and 55 % fewer matrix instructions per launch at the
-                             * same run time as the 16-group kernel (profiles/r05_att32_experiments.txt). */
 };
 
 /* reduce of kgat_copy_reduce_f32 (dgl.function.sum / dgl.function.mean) */
@@ -219,8 +214,8 @@ int kgat_att_score_folded_f32(int64_t n_nodes, int64_t n_edges, int d, int k, in
 int64_t kgat_fold_tiles_max(int64_t n_edges, int64_t n_groups, int n_rel, int cap);
 size_t kgat_fold_tiles_workspace_bytes(int64_t n_groups, int n_rel);
 int kgat_fold_tiles(int64_t n_edges, int n_rel, int64_t n_groups, const int32_t* rel_ptr, const int32_t* gid,
-                    const int32_t* gptr, int cap, int groups_per_tile /* 16, or 32 for KGAT_ATT_TILES32 */,
-                    int32_t* tiles, int32_t* rel_tptr, void* workspace, size_t workspace_bytes, kgat_stream_t stream);
+                    const int32_t* gptr, int cap, int32_t* tiles, int32_t* rel_tptr, void* workspace,
+                    size_t workspace_bytes, kgat_stream_t stream);
 /* Split of the tiles over the n_parts workgroups of the fused kernel (graph-static, like the
  * tiles): part b owns the contiguous tile range [part_tptr[b], part_tptr[b+1]), chosen on the
  * prefix sum of a per-tile cost
@@ -244,8 +239,7 @@ int kgat_att_score_fused_supported(int64_t n_nodes, int d, int k, int n_rel);
  * (tiles are cut out of such blocks, whatever the cap).  Needs n_nodes <= 2^28.  Positions past
  * rel_ptr[R] (never scored) get their source node and slot 0. */
 int kgat_att_pack_records(int64_t n_edges, int n_rel, const int32_t* rel_ptr, const int32_t* gptr,
-                          const int32_t* gid, const int32_t* src_g, int groups_per_tile /* 16: slot << 28; 32: the
-                          slot of the 32-group block << 27, node ids below 2^27 */, int32_t* rec_g, kgat_stream_t stream);
+                          const int32_t* gid, const int32_t* src_g, int32_t* rec_g, kgat_stream_t stream);
 /* part_tptr / n_parts: the split above (one workgroup per part); NULL / 0: one workgroup per
  * compute unit, equal tile counts.  flags: 0 or KGAT_ATT_F32_PRODUCTS.
  * Outputs (any non-empty subset): logits_g[E] in grouped order (position p of the relation-grouped
@@ -260,11 +254,11 @@ int kgat_att_score_fused_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int
                              const float* ent, const float* W_R, const float* rel, float* logits,
                              float* logits_csr, float* logits_g, int flags, kgat_stream_t stream);
 /* Measurement aid: the same launch with every workgroup's start and end time written to part_clocks[2 b], [2 b + 1]
- * (100 MHz ticks of s_memrealtime; part b = workgroup b's tile range).  Same results; needs part_tptr; not with
- * KGAT_ATT_TILES32.  (What it showed, scripts/micro/att_rebalance_probe.py: the cost model of kgat_fold_tile_parts
- * leaves the workgroups' end times 8-9 % apart and the pattern repeats - correlation 0.98 run to run -, so ranges
- * re-cut from measured times take 7-9 % off the launch where the calibration and the use share their surroundings;
- * calibrated on the caller's first launches inside the benchmark step the gain was 1.5 %: not adopted.) */
+ * (100 MHz ticks of s_memrealtime; part b = workgroup b's tile range).  Same results; needs part_tptr.  (What it
+ * showed, scripts/micro/att_rebalance_probe.py: the cost model of kgat_fold_tile_parts leaves the workgroups' end
+ * times 8-9 % apart and the pattern repeats - correlation 0.98 run to run -, so ranges re-cut from measured times
+ * take 7-9 % off the launch where the calibration and the use share their surroundings; calibrated on the
+ * caller's first launches inside the benchmark step the gain was 1.5 %: not adopted.) */
 int kgat_att_score_fused_timed_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel,
                                    const int32_t* rel_ptr, const int32_t* perm, const int32_t* rec_g,
                                    const int32_t* pos_g, const int32_t* gptr,
@@ -409,33 +403,7 @@ int kgat_bi_interaction_f32(int64_t n_rows, int d_in, int d_out, const float* P,
                             float negative_slope, float* h_out, float* norm_out,
                             int64_t norm_stride, kgat_stream_t stream);
 
-/* The same with the product formed on the way (round 4): Z = LeakyReLU_slope((H * HN) @ W2^T) - reference
- * models.py:66's th.mul(g.ndata['h'], g.ndata['h_neighbor']) + res_fc_2 + LeakyReLU, and models.py:165's normalize -
- * from the layer input H and the plain aggregation HN = update_all(u_mul_e, sum) (both n_rows x d_in), so that the
- * aggregation needs no epilogue (its KGAT_SPMM_MUL_SELF form pays a dependent load per finished row inside the edge
- * loop: 91 vs 78 us on the benchmark graph).  self_out (may be NULL): the rows of H are also copied to
- * self_out[row * self_stride + 0..d_in) - the ego block [h0 | ...] of Model.gnn's readout (models.py:159,168);
- * 16-byte aligned, self_stride a multiple of 4 floats.  Same bits as KGAT_SPMM_MUL_SELF + kgat_bi_interaction_f32. */
-int kgat_bi_interaction_mul_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W2,
-                                float negative_slope, float* h_out, float* norm_out, int64_t norm_stride,
-                                float* self_out, int64_t self_stride, kgat_stream_t stream);
-
-/* The pair update_all(u_mul_e, sum) -> th.mul / res_fc_2 / LeakyReLU / normalize (reference models.py:63-66, :165) with
- * one launch less (round 4).  The aggregation's MERGE algorithm cuts the CSR positions into tiles of
- * kgat_spmm_tile_edges(e_end - e_begin, D) edges; a tile leaves its first and its last row as partial sums in the
- * workspace and a second, dependent launch adds them up and zero-fills the rows without in-edges.  With
- * KGAT_SPMM_DEFER_FINISH (plain operator, CSR-ordered weights, MERGE / AUTO, D in {16, 32, 64, 128}) that launch is
- * skipped: those rows of `out` are NOT written, and kgat_bi_interaction_mul_deferred_f32 - the same operator as
- * kgat_bi_interaction_mul_f32 - forms them on the way from `indptr_rows` (= indptr + row0: the row offsets of the
- * call's rows 0 .. n_rows), the edge range and the untouched workspace, in the second launch's order of additions:
- * bit-identical results.  d_in, d_out in {16, 32, 64, 128}; nothing else may use the workspace between the two calls.
- * (Benchmark graph: the three second launches cost 13 us of a 0.44 ms step; forming their rows costs the dense kernels 6.) */
-int kgat_spmm_tile_edges(int64_t n_edges, int D);  /* 0: D outside {16, 32, 64, 128} */
-int kgat_bi_interaction_mul_deferred_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
-                                         const float* W2, float negative_slope, float* h_out, float* norm_out,
-                                         int64_t norm_stride, float* self_out, int64_t self_stride,
-                                         const int32_t* indptr_rows, int64_t e_begin, int64_t e_end,
-                                         const void* spmm_workspace, int tile_edges, kgat_stream_t stream);
+/* (The same with the product formed on the way - what the layer runs - is kgat_aggregator_f32 with KGAT_FORM_BI.) */
 
 /* ---------------------------------------------------------------- one KGATConv forward in one pass (S1 + B1 + B2)
  * Replaces reference models.py:63-66 (update_all(u_mul_e, sum); th.mul; res_fc_2; LeakyReLU) and the
@@ -477,19 +445,7 @@ int kgat_gather_i32(int64_t n, const int32_t* index, const int32_t* in, int32_t*
                     kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- training form of the layer (8f #1)
- * Forward of one KGATConv under autograd (reference models.py:63-70 with mess_drop active):
- *   h_out = dropout_p(LeakyReLU((H * HN) W2^T)),  norm_out = F.normalize(h_out)
- * H * HN is formed while the rows are loaded.  The dropout mask is a counter-based hash of
- * (seed, (row0 + row) * d_out + column): keep <=> hash >= p * 2^32, kept values scaled by 1/(1-p);
- * the backward recomputes it from the same seed.  row0 = global index of the first row when H is a
- * row range of a larger matrix (a destination shard draws the mask of the unsharded layer; 0
- * otherwise).  Widths as kgat_bi_interaction_supported. */
-int kgat_bi_interaction_train_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
-                                  const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0,
-                                  float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
-                                  int64_t self_stride, kgat_stream_t stream);
-/* (self_out / self_stride as in kgat_bi_interaction_mul_f32: the rows of H copied into a column slice of the readout
- * on the way - the ego block of reference models.py:159,168, which the training stack wrote with a separate copy pass.)
+ * The forward of one KGATConv under autograd is kgat_aggregator_train_f32 (below); these are the pieces around it.
  * kgat_add3_rows_f32: out = (a + b) + c over n_rows x d, a being a column slice (rows of a_stride floats) of a wider
  * matrix: the gradient arriving at the embedding table through Model.gnn's three paths (the ego block of the readout's
  * gradient, the aggregated branch, the elementwise branch of layer 0) in one pass instead of two. */
@@ -505,24 +461,14 @@ int kgat_bi_interaction_bwd_pre_f32(int64_t n_rows, int d_out, const float* h_ou
                                     const float* grad_b, const float* grad_norm, int64_t grad_norm_stride,
                                     float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* grad_z,
                                     kgat_stream_t stream);
-/* The same two steps in one pass (round 4): grad_P = grad_z W2 formed per 16-row tile on the fp32 MFMA and never
- * written; grad_hn_times_h = grad_P * H (what the reversed-CSR SpMM then aggregates: the gradient through h_N, reference
- * models.py:63,66 under autograd) and grad_h_direct = grad_P * HN (the gradient through the row's own features), both
- * n_rows x d_in.  grad_z n_rows x d_out, W2 = res_fc_2.weight (d_out x d_in).  d_in, d_out in {16, 32, 64, 128}. */
+/* The same two steps in one pass (round 4) are kgat_aggregator_bwd_input_f32, the weight gradient
+ * kgat_aggregator_bwd_weight_f32 (below).  Their widths: d_in, d_out in {16, 32, 64, 128}; the number of per-workgroup
+ * partial sums the weight gradient leaves for n_rows rows: */
 int kgat_bi_interaction_bwd_input_supported(int d_in, int d_out);
-int kgat_bi_interaction_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W2,
-                                      const float* H, const float* HN, float* grad_hn_times_h, float* grad_h_direct,
-                                      kgat_stream_t stream);
-/* grad_W2 = grad_z^T (H * HN) (d_out x d_in; reference models.py:66's res_fc_2 under autograd) as per-workgroup
- * partial sums: partials[b] (b < n_partials = kgat_bi_interaction_bwd_weight_partials(n_rows), each d_out x d_in row-major)
- * is the product over the 64-row slabs b, b + n_partials, ...; the caller adds the partials up (any fixed order:
- * reproducible).  The product H * HN is formed on the way and never written.  Widths as kgat_bi_interaction_bwd_input. */
 int64_t kgat_bi_interaction_bwd_weight_partials(int64_t n_rows);
-int kgat_bi_interaction_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
-                                       const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream);
 /* out_s = the sum of set s's n_partials_s partials (each n_elems_s floats, a multiple of 4, back to back) for up to four
  * sets in ONE launch - the weight gradients of a propagation stack's layers, whose partials
- * kgat_bi_interaction_bwd_weight_f32 leaves to the caller.  HOST arrays of n_sets entries.  A fixed order of additions
+ * kgat_aggregator_bwd_weight_f32 leaves to the caller.  HOST arrays of n_sets entries.  A fixed order of additions
  * (sixteen strided lane sums, then a shuffle tree): bitwise reproducible; not the order of a sequential sum. */
 int kgat_sum_partials_f32(int n_sets, const float* const* partials_host, float* const* out_host,
                           const int64_t* n_partials_host, const int64_t* n_elems_host, kgat_stream_t stream);
@@ -531,19 +477,36 @@ int kgat_mul2_f32(int64_t n, const float* a, const float* b, const float* c, flo
                   kgat_stream_t stream);
 
 /* ---------------------------------------------------------------- the KGAT layer's three aggregators
- * The entries above for any `form` (KGAT_FORM_*), i.e. the dense part of KGATConv with res_type "Bi", "GCN" or
+ * The dense part of KGATConv for any `form` (KGAT_FORM_*), i.e. with res_type "Bi", "GCN" or
  * "GraphSage" - the KGAT paper's three aggregators (Wang et al. 2019, "Information Aggregation", eqs. 6-8), whose hook
  * the reference keeps in KGATConv.__init__ (models.py:50-58: res_type, the commented-out res_fc of :55):
  *   GCN:        Z = LeakyReLU_slope((H + HN) W^T),      W = res_fc.weight   (d_out x d_in)
  *   GraphSage:  Z = LeakyReLU_slope([H | HN] W^T),      W = res_fc.weight   (d_out x 2 d_in; columns [0, d_in) act on H)
  *   Bi:         Z = LeakyReLU_slope((H * HN) W^T),      W = res_fc_2.weight (d_out x d_in)
- * HN = update_all(u_mul_e('h','w','m'), sum('m','h_neighbor')) as for Bi (models.py:63).  KGAT_FORM_BI runs the very
- * kernels of the kgat_bi_interaction_* entries (same bits, same launches).  Widths (kgat_aggregator_supported): Bi as
- * kgat_bi_interaction_supported; GCN and GraphSage d_in, d_out in {16, 32, 64, 128} (others: KGAT_E_UNSUPPORTED - a
- * caller forms those in a library GEMM).
- * kgat_aggregator_f32 / _deferred_f32 / _train_f32: the arguments, outputs and bits of kgat_bi_interaction_mul_f32 /
- * _mul_deferred_f32 / _train_f32 with W in W2's place (the no-grad layer, the same with the aggregation's second
- * launch left to it, the training form with LeakyReLU, hash dropout, normalised slice and ego block). */
+ * HN = update_all(u_mul_e('h','w','m'), sum('m','h_neighbor')) (models.py:63), both H and HN n_rows x d_in.  Widths
+ * (kgat_aggregator_supported): Bi as kgat_bi_interaction_supported; GCN and GraphSage d_in, d_out in {16, 32, 64, 128}
+ * (others: KGAT_E_UNSUPPORTED - a caller forms those in a library GEMM).
+ * kgat_aggregator_f32: the no-grad layer.  The combination is formed while the rows are loaded (round 4), so that the
+ * aggregation needs no epilogue (its KGAT_SPMM_MUL_SELF form pays a dependent load per finished row inside the edge
+ * loop: 91 vs 78 us on the benchmark graph); h_out / norm_out / norm_stride as kgat_bi_interaction_f32.  self_out (may
+ * be NULL): the rows of H are also copied to self_out[row * self_stride + 0..d_in) - the ego block [h0 | ...] of
+ * Model.gnn's readout (models.py:159,168); 16-byte aligned, self_stride a multiple of 4 floats.  KGAT_FORM_BI: the same
+ * bits as KGAT_SPMM_MUL_SELF + kgat_bi_interaction_f32.
+ * kgat_aggregator_deferred_f32: the pair update_all(u_mul_e, sum) -> dense part with one launch less (round 4).  The
+ * aggregation's MERGE algorithm cuts the CSR positions into tiles of kgat_spmm_tile_edges(e_end - e_begin, D) edges; a
+ * tile leaves its first and its last row as partial sums in the workspace and a second, dependent launch adds them up
+ * and zero-fills the rows without in-edges.  With KGAT_SPMM_DEFER_FINISH (plain operator, CSR-ordered weights, MERGE /
+ * AUTO, D in {16, 32, 64, 128}) that launch is skipped: those rows of `out` are NOT written, and this entry - the same
+ * operator as kgat_aggregator_f32 - forms them on the way from `indptr_rows` (= indptr + row0: the row offsets of the
+ * call's rows 0 .. n_rows), the edge range and the untouched workspace, in the second launch's order of additions:
+ * bit-identical results.  d_in, d_out in {16, 32, 64, 128}; nothing else may use the workspace between the two calls.
+ * (Benchmark graph: the three second launches cost 13 us of a 0.44 ms step; forming their rows costs the dense kernels 6.)
+ * kgat_aggregator_train_f32: the forward of one KGATConv under autograd (reference models.py:63-70 with mess_drop
+ * active): h_out = dropout_p(LeakyReLU(combine(H, HN) W^T)), norm_out = F.normalize(h_out), self_out as above.  The
+ * dropout mask is a counter-based hash of (seed, (row0 + row) * d_out + column): keep <=> hash >= p * 2^32, kept
+ * values scaled by 1/(1-p); the backward recomputes it from the same seed.  row0 = global index of the first row when
+ * H is a row range of a larger matrix (a destination shard draws the mask of the unsharded layer; 0 otherwise). */
+int kgat_spmm_tile_edges(int64_t n_edges, int D);  /* 0: D outside {16, 32, 64, 128} */
 int kgat_aggregator_supported(int form, int d_in, int d_out);
 int kgat_aggregator_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W,
                         float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
@@ -558,8 +521,8 @@ int kgat_aggregator_train_f32(int form, int64_t n_rows, int d_in, int d_out, con
                               float* h_out, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
                               kgat_stream_t stream);
 /* Backward of the dense part towards its inputs (the layer under autograd), from grad_z (n_rows x d_out,
- * kgat_bi_interaction_bwd_pre_f32); grad_P = grad_z W is formed per 16-row tile and
- *   Bi:        grad_agg = grad_P * H, grad_self = grad_P * HN     (= kgat_bi_interaction_bwd_input_f32)
+ * kgat_bi_interaction_bwd_pre_f32); grad_P = grad_z W is formed per 16-row tile on the fp32 MFMA, never written, and
+ *   Bi:        grad_agg = grad_P * H, grad_self = grad_P * HN
  *   GCN:       grad_agg = grad_P (the gradient through h_N and through h alike; grad_self unused, may be NULL)
  *   GraphSage: grad_agg = grad_P[:, d_in:2 d_in] (the h_N half), grad_self = grad_P[:, 0:d_in] (the h half)
  * grad_agg is what the reversed-CSR aggregation then sums; grad_self goes to h directly (both n_rows x d_in).  H and
@@ -569,8 +532,9 @@ int kgat_aggregator_bwd_input_f32(int form, int64_t n_rows, int d_in, int d_out,
                                   const float* H, const float* HN, float* grad_agg, float* grad_self,
                                   kgat_stream_t stream);
 /* grad_W = grad_z^T (H * HN) (Bi), grad_z^T (H + HN) (GCN), grad_z^T [H | HN] (GraphSage: d_out x 2 d_in) as per-workgroup
- * partials, as kgat_bi_interaction_bwd_weight_f32: partials[b] is d_out x d_in (d_out x 2 d_in for GraphSage),
- * n_partials = kgat_bi_interaction_bwd_weight_partials(n_rows), the caller adds them (kgat_sum_partials_f32). */
+ * partial sums: partials[b] (d_out x d_in row-major, d_out x 2 d_in for GraphSage) is the product over the 64-row slabs
+ * b, b + n_partials, ... with n_partials = kgat_bi_interaction_bwd_weight_partials(n_rows); the combination is formed
+ * on the way and never written; the caller adds the partials up in any fixed order (kgat_sum_partials_f32). */
 int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
                                    const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream);
 
@@ -591,7 +555,7 @@ int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out
  * L2-normalised rows into norm_out (row stride norm_stride: a column slice of the readout), the rows of H into
  * self_out (the ego block).  The deferred entry forms the rows the aggregation's KGAT_SPMM_DEFER_FINISH launch left as
  * tile partials and gives the plain entry's bits.
- * kgat_bi2_train_f32: the training form - hash dropout (drop_p, seed, row0 as kgat_bi_interaction_train_f32) on the sum
+ * kgat_bi2_train_f32: the training form - hash dropout (drop_p, seed, row0 as kgat_aggregator_train_f32) on the sum
  * of the two terms; h_out is required.  It also writes the SIGN RECORD `signs`, n_rows x d_out bytes (4-byte aligned):
  * bit 0 = (z1 > 0), bit 1 = (z2 > 0) of that element before dropout - the sign of the saved output no longer tells
  * LeakyReLU'(z1) and LeakyReLU'(z2) apart (LeakyReLU'(0) = slope, as in kgat_bi_interaction_bwd_pre_f32). */
@@ -666,7 +630,7 @@ int kgat_sage_dense_f32(int64_t n_rows, int d_in, int d_out, const float* H, con
                         kgat_stream_t stream);
 
 /* SAGEConv's feat_drop (nn.Dropout of reference models.py:99,108 on the layer input) with the counter hash of
- * kgat_bi_interaction_train_f32: out = (x + x2) * keep / (1 - drop_p) over n_rows x d elements (x2 may be NULL),
+ * kgat_aggregator_train_f32: out = (x + x2) * keep / (1 - drop_p) over n_rows x d elements (x2 may be NULL),
  * keep <=> hash(seed, row * d + column) >= drop_p * 2^32.  Forward: the dropped input, materialised once.  Backward:
  * the same call on the gradient (x, x2 = the gradient's two paths: through fc_self and through the aggregation). */
 int kgat_dropout_rows_f32(int64_t n_rows, int d, const float* x, const float* x2, float drop_p, uint64_t seed,
@@ -830,7 +794,7 @@ int kgat_edge_norm_f32(int64_t n_nodes, int64_t n_edges, const int32_t* indptr, 
  * the adjacency dropped with probability drop_p, survivors scaled by 1 / (1 - drop_p)) as the dropped copy of one
  * weight stream:
  *   w_out[p] = keep(seed, key[p]) ? w_in[p] * keep_scale : 0,   keep_scale = 1.f / (1.f - drop_p)  (fp32)
- * keep is the counter hash of kgat_bi_interaction_train_f32 over (row = edge id, d = 1, column 0): keep <=>
+ * keep is the counter hash of kgat_aggregator_train_f32 over (row = edge id, d = 1, column 0): keep <=>
  * hash(seed, key[p]) >= drop_p * 2^32.  key [n_edges] holds the edge id at every position of the stream - `eid` of the
  * CSR the stream is ordered by (kgat_csr_from_coo's, or the reversed graph's for the backward stream); NULL: the stream
  * is in edge-id order (key[p] = p).  Keyed by edge id, the calls on the forward and on the reversed stream describe

@@ -13,8 +13,8 @@ n, trip, R = synth.amazon_book_ckg(seed=1234, scale=1.0)
 g = synth.build_graph(n, trip, dev)
 st = g._st
 groups = st.rel_groups(g.edata["type"], R, dev)
-tiles, rel_tptr, part_tptr = G._fused_tiles(groups, d, 16)
-rec_g, _ = G._fused_statics(groups, 16)
+tiles, rel_tptr, part_tptr = G._fused_tiles(groups, d)
+rec_g, _ = G._fused_statics(groups)
 torch.manual_seed(0)
 ent = torch.randn(n, d, device=dev) * 0.1
 W = (torch.rand(R, d, d, device=dev) - 0.5) * (2 / d ** 0.5)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: what forming the aggregation's left rows costs the dense kernel - kgat_bi_interaction_mul_f32 on a
-complete h_N against kgat_bi_interaction_mul_deferred_f32 on the h_N of a KGAT_SPMM_DEFER_FINISH aggregation (same
+"""Developer tool: what forming the aggregation's left rows costs the dense kernel - kgat_aggregator_f32 (Bi form) on a
+complete h_N against kgat_aggregator_deferred_f32 on the h_N of a KGAT_SPMM_DEFER_FINISH aggregation (same
 graph, same rows), launches alternated; and the aggregation with and without its second launch."""
 import os
 import sys

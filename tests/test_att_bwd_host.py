@@ -26,14 +26,14 @@ def test_header_declares_the_three_entries_without_a_version_bump():
     declared = set(re.findall(r"\b(kgat_[a-z0-9_]+)\s*\(", header))
     for name in ENTRIES:
         assert name in declared and name in _lib.SIGNATURES
-    assert "#define KGAT_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15
+    assert "#define KGAT_ABI_VERSION 16" in header and _lib.ABI_VERSION == 16
     assert "kgat_att_bwd.hip" in _lib.SOURCES
     assert os.path.exists(os.path.join(_lib.CSRC, "kgat_att_bwd.hip"))
     assert "models.py:135-154" in header[header.index("attention score, backward"):header.index(ENTRIES[0] + "(")]
     # every declared function is bound and every bound one declared (the loader's own contract)
     assert declared == set(_lib.SIGNATURES)
     lib = _lib.load()
-    assert lib.kgat_version() == 15
+    assert lib.kgat_version() == 16
 
 
 def test_supported_widths_and_the_32_bit_bound():

@@ -26,11 +26,11 @@ def test_header_declares_both_entries_at_version_15():
     declared = set(re.findall(r"\b(kgat_[a-z0-9_]+)\s*\(", header))
     for name in ("kgat_edge_norm_f32", "kgat_edge_dropout_f32"):
         assert name in declared and name in _lib.SIGNATURES
-    assert "#define KGAT_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15
+    assert "#define KGAT_ABI_VERSION 16" in header and _lib.ABI_VERSION == 16
     assert "KGAT_NORM_SI = 0" in header and "KGAT_NORM_BI = 1" in header
     assert ops.NORM_MODES == {"si": 0, "bi": 1}
     assert "kgat_edge_weights.hip" in _lib.SOURCES
-    assert _lib.load().kgat_version() == 15
+    assert _lib.load().kgat_version() == 16
 
 
 @pytest.mark.parametrize("seed", [0, 1234, 2 ** 63 + 12345])

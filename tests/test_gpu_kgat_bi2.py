@@ -1,6 +1,6 @@
 """The KGAT paper's two-term Bi-Interaction aggregator (KGATConv res_type "Bi2") on the MI355X: the kgat_bi2_* kernels at
 every width pair (no-grad, deferred, training form with its sign record, backward head and both backward kernels), the
-KGATPropagation stack (fused readout, surface path, the product-only switches, the whole-stack training unit's
+KGATPropagation stack (fused readout, surface path, the product-only switch, the whole-stack training unit's
 gradients, a width off the kernels) and an end-to-end training run.  References are float64 restatements inside this
 file of
     Z = LeakyReLU(W1 (h + h_N)) + LeakyReLU(W2 (h * h_N))        (Wang et al. 2019, eq. 8)
@@ -230,8 +230,6 @@ def test_stack_readout_fused_surface_and_switches(dev, capsys):
         surface = model.gnn(g, fused=False)
         with override(fuse_bi=True):
             out_fb = model.gnn(g)
-        with override(gnn_mul_in_spmm=True):
-            out_mis = model.gnn(g)
         with override(gnn_defer_finish=not options.gnn_defer_finish):
             out_df = model.gnn(g)
     ref = _readout_ref64(model, g, n, trip)
@@ -249,8 +247,8 @@ def test_stack_readout_fused_surface_and_switches(dev, capsys):
     for b, err in enumerate(errs):
         assert err <= readout_abs_bar(b), (b, err)
     assert torch.equal(out[:, :64], model.entity_embed.weight)
-    # the product-only switches are skipped for this form, never applied; the deferred finish gives the same bits
-    assert torch.equal(out_fb, out) and torch.equal(out_mis, out) and torch.equal(out_df, out)
+    # the product-only switch is skipped for this form, never applied; the deferred finish gives the same bits
+    assert torch.equal(out_fb, out) and torch.equal(out_df, out)
 
 
 def test_stack_training_unit_gradients(dev):
