@@ -5,7 +5,7 @@ The package holds only what the hot path needs: ``csrc/`` (HIP kernels + the C A
 reference's operator surface (``DGLGraph``, ``function``, ``edge_softmax``, ``KGATConv``, ``SAGEConv``).
 Import name: ``dgl_kgat_amd`` (a shim at the repository root maps it to this directory).
 """
-from . import function  # noqa: F401
+from . import explain, function  # noqa: F401
 from .graph import ALL, DGLError, DGLGraph  # noqa: F401
 from .softmax import edge_softmax  # noqa: F401
 from .kgat_layer import KGATConv, KGATPropagation  # noqa: F401
@@ -17,6 +17,6 @@ from .lazy import enable as enable_lazy_edge_weights  # noqa: F401
 from .partition import GraphedForward  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 
-__all__ = ["DGLGraph", "DGLError", "ALL", "function", "edge_softmax", "KGATConv", "KGATPropagation", "SAGEConv",
+__all__ = ["DGLGraph", "DGLError", "ALL", "function", "explain", "edge_softmax", "KGATConv", "KGATPropagation", "SAGEConv",
            "install_as_dgl", "accelerate", "KGATLibraryError", "CKGDataset", "enable_lazy_edge_weights", "GraphedForward",
            "FusedAdam"]

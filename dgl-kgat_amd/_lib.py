@@ -16,6 +16,7 @@ SO_PATH = os.path.join(_HERE, "libkgat_hip.so")
 SOURCES = {
     "kgat_graph.hip": [],
     "kgat_spmm.hip": [],
+    "kgat_spmm_max.hip": [],
     "kgat_spmm_bi.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_softmax.hip": [],
     "kgat_att.hip": [],
@@ -80,6 +81,9 @@ SIGNATURES = {
     "kgat_spmm_workspace_bytes": (_sz, [_i64, _i32]),
     "kgat_spmm_umule_sum_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p,
                                        _p, _sz, _u32, _i32, _p, _i64, _p]),
+    # DGL's fn.max reducer with argmax; the max-times product of explain.attention_paths (ABI 16, additive)
+    "kgat_spmm_max_workspace_bytes": (_sz, [_i64, _i32]),
+    "kgat_spmm_umule_max_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_bi_interaction_supported": (_i32, [_i32, _i32]),
     "kgat_spmm_bi_fused_supported": (_i32, [_i32, _i32]),
     "kgat_spmm_bi_fused_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p,

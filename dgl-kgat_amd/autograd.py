@@ -7,6 +7,8 @@
 * ``edge_softmax`` - reference models.py:153; backward as DGL 0.4.x EdgeSoftmax.backward.
 * ``copy_reduce`` - update_all(copy_src, sum | mean), the aggregation of DGL's SAGEConv (gnn_model
   "graphsage"); backward over the reversed graph's CSR.
+* ``max_reduce`` - update_all(u_mul_e | copy_src, max) (kgat_spmm_umule_max_f32).  Forward only: it lives here to refuse,
+  in one place, inputs that would need a backward.
 * ``kgat_attention`` - the fused attention (logits + destination softmax, models.py:135-154) as one unit that
   differentiates towards the entity table, W_R and the relation embeddings.
 """
@@ -110,6 +112,26 @@ def copy_reduce(g, x, reduce="sum"):
     if x.shape[0] != g.number_of_nodes():
         raise ValueError("node feature has %d rows, graph has %d nodes" % (x.shape[0], g.number_of_nodes()))
     return _CopyReduce.apply(x, g, reduce)
+
+
+def max_reduce(g, x, w=None):
+    """h[v] = max_{e:u->v} w[e] * x[u] (w=None: x[u]) - update_all(fn.u_mul_e | fn.copy_src, fn.max).  There is no
+    backward: inputs that would need one are refused, not detached."""
+    if x.shape[0] != g.number_of_nodes():
+        raise ValueError("node feature has %d rows, graph has %d nodes" % (x.shape[0], g.number_of_nodes()))
+    if w is not None and w.shape[0] != g.number_of_edges():
+        raise ValueError("edge weight has %d rows, graph has %d edges" % (w.shape[0], g.number_of_edges()))
+    if torch.is_grad_enabled() and (x.requires_grad or (w is not None and w.requires_grad)):
+        raise NotImplementedError("fn.max has no backward on the HIP kernels: call it under torch.no_grad() or on "
+                                  "detached inputs (the feature or the edge weight requires grad)")
+    st = g._st
+    x2 = (x if x.dim() == 2 else x.unsqueeze(1)).detach().contiguous()
+    if x2.dtype != torch.float32:
+        raise TypeError("node features must be float32, got %s" % x2.dtype)
+    csr = st.csr(x2.device)
+    w_csr = None if w is None else st.csr_weights(w)  # a pending lazy attention tensor is served from its CSR copy
+    out, _ = ops.spmm_max(csr.indptr, csr.col, csr.row_of, x2, w_csr, want_arg=False)
+    return out.squeeze(1) if x.dim() == 1 else out
 
 
 class _EdgeSoftmax(torch.autograd.Function):

@@ -1,6 +1,7 @@
 """Builtin message / reduce descriptors, the counterpart of ``dgl.function`` for the calls
 the reference makes (``fn.u_mul_e('h','w','m')``, ``fn.sum('m','h_neighbor')``,
-models.py:4,63; ``fn.copy_src`` / ``fn.mean`` of DGL's SAGEConv, the graphsage branch).  They are plain descriptors: ``DGLGraph.update_all`` maps the pair to the
+models.py:4,63; ``fn.copy_src`` / ``fn.mean`` of DGL's SAGEConv, the graphsage branch; ``fn.max``, the reducer behind
+``explain.attention_paths``).  They are plain descriptors: ``DGLGraph.update_all`` maps the pair to the
 HIP aggregation kernel."""
 
 
@@ -44,3 +45,9 @@ copy_u = copy_src  # DGL >= 0.4.2 name
 def mean(msg, out):
     """reduce = mean of the incoming messages of each destination (0 where there is none)."""
     return BuiltinReduce("mean", msg, out)
+
+
+def max(msg, out):  # noqa: A001 - mirrors dgl.function.max
+    """reduce = elementwise maximum of the incoming messages of each destination (0 where there is none).  No
+    backward on this path: ``update_all`` refuses inputs that require a gradient."""
+    return BuiltinReduce("max", msg, out)

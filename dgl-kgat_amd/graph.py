@@ -608,9 +608,10 @@ class DGLGraph:
             raise NotImplementedError("only builtin message/reduce pairs run on the HIP kernels; "
                                       "python UDF message passing is outside the KGAT path")
         pair = (message_func.name, reduce_func.name)
-        if pair not in (("u_mul_e", "sum"), ("copy_src", "sum"), ("copy_src", "mean")):
-            raise NotImplementedError("update_all runs (fn.u_mul_e, fn.sum) and (fn.copy_src, fn.sum | fn.mean) on the "
-                                      "HIP kernels; got %s/%s" % pair)
+        if pair not in (("u_mul_e", "sum"), ("copy_src", "sum"), ("copy_src", "mean"), ("u_mul_e", "max"),
+                        ("copy_src", "max")):
+            raise NotImplementedError("update_all runs (fn.u_mul_e, fn.sum | fn.max) and (fn.copy_src, fn.sum | fn.mean "
+                                      "| fn.max) on the HIP kernels; got %s/%s" % pair)
         if message_func.out_field != reduce_func.msg_field:
             raise DGLError("reduce reads message field %r but the message function writes %r"
                            % (reduce_func.msg_field, message_func.out_field))
@@ -619,7 +620,11 @@ class DGLGraph:
         if message_func.edge_field is not None and message_func.edge_field not in self._edge_frame:
             raise KeyError(message_func.edge_field)
         x = self._node_frame[message_func.src_field]
-        if message_func.name == "copy_src":
+        if reduce_func.name == "max":
+            from .autograd import max_reduce
+            w = None if message_func.edge_field is None else self._edge_frame[message_func.edge_field]
+            self._node_frame[reduce_func.out_field] = max_reduce(self, x, w)
+        elif message_func.name == "copy_src":
             from .autograd import copy_reduce
             self._node_frame[reduce_func.out_field] = copy_reduce(self, x, reduce_func.name)
         else:

@@ -273,6 +273,13 @@ class KGATPropagation(nn.Module):
         return g.kgat_attention(self._node_embeddings(g), self.W_R, self.relation_embed.weight, algo=algo,
                                 differentiable=differentiable)
 
+    def explain(self, g, users, items, max_len=None):
+        """The highest-attention walks from items[q] to users[q] under the edge weights in ``g.edata['w']``
+        (explain.attention_paths; the case study of the KGAT paper, section 4.5).  max_len defaults to the number of
+        propagation layers: the walks the stack can carry information along."""
+        from .explain import attention_paths
+        return attention_paths(g, g.edata["w"], users, items, max_len=len(self.layers) if max_len is None else max_len)
+
     # -- propagation (models.py:156-168)
     def gnn(self, g, x=None, fused=None):
         if self._sage_stack():

@@ -660,6 +660,44 @@ def spmm(indptr, col, row_of, X, w, eid=None, out=None, order=None, mul_self=Fal
     return out
 
 
+def spmm_max_workspace(n_edges, D, device):
+    return _workspace(_lib.load().kgat_spmm_max_workspace_bytes(n_edges, D), device)
+
+
+def spmm_max(indptr, col, row_of, X, w=None, eid=None, want_arg=True, out=None, rows=None, e_range=None, workspace=None):
+    """(out, arg): out[v - row0] = max_p w_p X[col[p]] over the CSR rows `rows` = (row0, n_rows) whose CSR positions
+    are `e_range` (defaults: the whole graph), arg (int32, None without want_arg) the edge that attains it - eid[p] when
+    `eid` is given, else the position p (kgat_spmm_umule_max_f32: dgl.function.max over u_mul_e, or over copy_src with
+    w=None).  w is in CSR order.  Equal products: the smallest edge id wins; a row without in-edges is (0, -1).  Exact
+    and bitwise reproducible; no backward."""
+    X = _need(X, torch.float32, "X")
+    if X.dim() != 2:
+        raise ValueError("X must be (N, D)")
+    D = X.shape[1]
+    indptr = _need(indptr, torch.int32, "indptr")
+    col = _need(col, torch.int32, "col")
+    row_of = _need(row_of, torch.int32, "row_of", col.shape)
+    if w is not None:
+        w = _need(w, torch.float32, "w", col.shape)
+    if eid is not None:
+        eid = _need(eid, torch.int32, "eid", col.shape)
+    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
+    e0, e1 = (0, col.numel()) if e_range is None else e_range
+    if out is None:
+        out = torch.empty((n_rows, D), dtype=torch.float32, device=X.device)
+    else:
+        out = _need(out, torch.float32, "out", (n_rows, D))
+    arg = torch.empty((n_rows, D), dtype=torch.int32, device=X.device) if want_arg else None
+    if workspace is None:
+        workspace = spmm_max_workspace(e1 - e0, D, X.device)
+    with _timed("spmm_max", (e1 - e0, n_rows, D)):
+        check(_lib.load().kgat_spmm_umule_max_f32(n_rows, row0, e0, e1, D, _ptr(indptr), _ptr(col), _ptr(row_of),
+                                                  _ptr(eid), _ptr(X), _ptr(w), _ptr(out), _ptr(arg), _ptr(workspace),
+                                                  workspace.numel(), _stream(X)),
+              "kgat_spmm_umule_max_f32")
+    return out, arg
+
+
 REDUCE = {"sum": 0, "mean": 1}
 ACT = {None: 0, "none": 0, "relu": 1}
 

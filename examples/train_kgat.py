@@ -16,6 +16,7 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
   python examples/train_kgat.py --planted --epochs 12 --lr 0.03 --batch_size 512 --batch_size_kg 512 --eval_before
                                                                           # planted structure: recall@20 must rise
   python examples/train_kgat.py --synthetic 0.01 --gpus 2                # CF phase on destination shards
+  python examples/train_kgat.py --planted --epochs 3 --explain 5         # + why the top-1 item: its best attention walk
 
 ``--gpus N``: one process per GPU (started here as a child ``torch.distributed.run``),
 parameters replicated, the training graph sharded by destination range.  Every rank draws the same
@@ -175,8 +176,17 @@ def parse_args(argv=None):
                          "hit ratio at every cut-off (metrics.calc_metrics)")
     ap.add_argument("--grad_digest", action="store_true",
                     help="print |grad| sums of the first CF step (to compare an N-GPU run with the one-GPU run)")
+    ap.add_argument("--explain", type=int, default=0, metavar="N",
+                    help="after the last evaluation: for the first N test users, the top-1 recommended item and the "
+                         "highest-attention walk from it to the user (KGATPropagation.explain; the KGAT paper's case study)")
     args = ap.parse_args(argv)
     # (before --gpus starts its ranks: a refused combination fails once, here)
+    if args.explain < 0:
+        ap.error("--explain takes a number of users >= 0")
+    if args.explain and args.gpus > 1:
+        ap.error("--explain runs on one GPU: a walk crosses shards")
+    if args.explain and args.gnn_model == "graphsage":
+        ap.error("--explain follows the edge weights; --gnn_model graphsage aggregates without weights")
     if args.res_type != "Bi" and args.gnn_model != "kgat":
         ap.error("--res_type %s selects the aggregator of --gnn_model kgat; graphsage takes none" % args.res_type)
     if args.res_type != "Bi" and args.gpus > 1:
@@ -373,6 +383,21 @@ def _run(args, argv):
         rec["epoch_s"] = clock() - t_epoch
         say("           | epoch %.4fs" % rec["epoch_s"])
         history.append(rec)
+    if args.explain:
+        # why the top-1 item?  the walk of highest attention product from it to the user, within as many hops as the
+        # model has layers (test graph, the weights of the last evaluation's parameters)
+        model.eval()
+        with torch.no_grad():
+            test_g.edata["w"] = model.compute_attention(test_g)
+            emb = model.gnn(test_g, test_g.ndata["id"])
+            users = sorted(test_dict)[:args.explain]
+            top1 = metrics.recommend(emb, users, ds.item_id_range, 1, seen=train_valid_dict)[0][:, 0].tolist()
+            paths = model.explain(test_g, users, [max(i, 0) for i in top1])
+        for q, (u, i) in enumerate(zip(users, top1)):
+            if i < 0:
+                say("explain | user %d: no unseen item" % u)
+                continue
+            say("explain | user %d item %d | score %.6g | %s" % (u, i, paths.best(q)[2], paths.describe(q)))
     if args.log_json and rank == 0:
         import json
         with open(args.log_json, "w") as f:

@@ -389,6 +389,27 @@ int kgat_sddmm_dot_f32(int64_t n_edges, int D, const int32_t* src, const int32_t
                        const float* X, const float* grad_out, float* grad_w,
                        kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- max reducer with argmax (additive within ABI 16)
+ * g.update_all(fn.u_mul_e('h','w','m') | fn.copy_src('h','m'), fn.max('m','o')) - DGL's fn.max reducer - and, with the
+ * winning edge recorded, the max-times product behind the attention-path explanations of the KGAT paper (section 4.5,
+ * figure 4: the walk of highest attention product from an item to a user):
+ *   out[v - row0, j] = max over CSR positions p of row v of  w[p] * X[col[p], j]    (w == NULL: X[col[p], j])
+ *   arg[v - row0, j] = the edge that attains it: eid[p] (eid != NULL: CSR position -> edge id), else p
+ * over rows v in [row0, row0 + n_rows) whose CSR positions are [e_begin, e_end), as kgat_spmm_umule_sum_f32; w is in
+ * CSR order.  arg [n_rows x D int32] may be NULL (not written).  Comparison is IEEE > on the fp32 products (-0.0 ties
+ * with 0.0); among equal products the smallest edge id (without eid: position) wins and `out` carries its bits.  The
+ * identity is -inf: a row of negative products returns a negative maximum.  A row without in-edges: out = 0 (as DGL),
+ * arg = -1.  Inputs finite or +-inf; NaN: unspecified.  The sum kernel's tile decomposition (tiles of
+ * kgat_spmm_tile_edges edges - any D outside {16, 32, 64, 128}: the D = 64 tile, sixteen columns per pass; a row cut
+ * by tile boundaries is completed from the tiles' (value, edge) partials); no atomics, bitwise reproducible.  row_of is
+ * required; D in {16, 32, 64, 128}: X, out, arg 16-byte aligned.  workspace: kgat_spmm_max_workspace_bytes of
+ * (e_end - e_begin, D).  No backward. */
+size_t kgat_spmm_max_workspace_bytes(int64_t n_edges, int D);
+int kgat_spmm_umule_max_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_t e_end, int D, const int32_t* indptr,
+                            const int32_t* col, const int32_t* row_of, const int32_t* eid, const float* X,
+                            const float* w, float* out, int32_t* arg, void* workspace, size_t workspace_bytes,
+                            kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- bi-interaction (B1 + B2)
  * Forward of the dense part of KGATConv (reference models.py:66) fused with the readout
  * normalisation (models.py:165-167):  Z = LeakyReLU_slope(P @ W2^T), P = h * h_N (n_rows x d_in,
