@@ -124,6 +124,14 @@ SIGNATURES = {
                                          _p, _sz, _p]),
     "kgat_adam_max_tensors": (_i32, []),
     "kgat_adam_step_f32": (_i32, [_i32, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _i32, _p]),
+    # global-norm gradient clipping: reference kgat.py:32,162 (ABI 16, additive)
+    "kgat_grad_norm_chain": (_i32, []),
+    "kgat_grad_sumsq_partials": (_i64, [_i32, _p]),
+    "kgat_grad_sumsq_f32": (_i32, [_i32, _p, _p, _p, _i64, _p]),
+    "kgat_grad_norm_finish_f32": (_i32, [_i64, _p, C.c_double, _p, _p, _p]),
+    "kgat_adam_step_clipped_f32": (_i32, [_i32, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          _i32, _p, _p]),
+    "kgat_scale_grads_f32": (_i32, [_i32, _p, _p, _p, _p]),
     "kgat_copy_reduce_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _sz, _p]),
     "kgat_sage_dense_supported": (_i32, [_i32, _i32]),
     "kgat_sage_dense_f32": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i64, _p, _i64, _p]),

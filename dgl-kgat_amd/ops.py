@@ -1515,3 +1515,91 @@ def bpr_grad(emb, u, p, n, coef, reg_lambda, grad_scale=None, workspace=None):
                                     _ptr(coef), float(reg_lambda), _ptr(grad_scale), _ptr(grad), _ptr(ws), ws.numel(),
                                     _stream(emb)), "kgat_bpr_grad_f32")
     return grad
+
+
+# ---------------------------------------------------------------- global-norm gradient clipping (kgat.py:32,162)
+def __getattr__(name):
+    # GRAD_NORM_CHAIN: the compile-time constant of the library (kgat_grad_norm_chain), read when first asked for
+    if name == "GRAD_NORM_CHAIN":
+        return int(_lib.load().kgat_grad_norm_chain())
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def check_max_norm(max_norm):
+    """`max_norm` as a float; ValueError unless it is finite and > 0."""
+    import math
+    max_norm = float(max_norm)
+    if not (math.isfinite(max_norm) and max_norm > 0):
+        raise ValueError("max_norm must be finite and > 0, got %r" % (max_norm,))
+    return max_norm
+
+
+def _grad_list(tensors, what):
+    import ctypes as C
+    tensors = [_need(t, torch.float32, "%s: tensor %d" % (what, i)) for i, t in enumerate(tensors)]
+    if len({t.device for t in tensors}) > 1:
+        raise KGATLibraryError("%s: tensors on more than one device (%s)" % (
+            what, ", ".join(sorted({str(t.device) for t in tensors}))))
+    cap = _lib.load().kgat_adam_max_tensors()
+    groups = []
+    for lo in range(0, len(tensors), cap):
+        chunk = tensors[lo:lo + cap]
+        groups.append((len(chunk), (C.c_int64 * len(chunk))(*[t.numel() for t in chunk]),
+                       (C.c_void_p * len(chunk))(*[t.data_ptr() for t in chunk])))
+    return tensors, groups
+
+
+def grad_norm(tensors, max_norm, norm_out=None):
+    """The global 2-norm of `tensors` (contiguous fp32 HIP tensors on one device: the gradients) and the coefficient
+    torch.nn.utils.clip_grad_norm_ would scale them by, min(max_norm / (norm + 1e-6), 1), as 0-dim DEVICE tensors
+    (norm, coef): one kgat_grad_sumsq_f32 launch per kgat_adam_max_tensors() tensors, then kgat_grad_norm_finish_f32.
+    Fixed summation order (bitwise reproducible); nothing is read back.  `norm_out`: a 1-element fp32 tensor or view on
+    the same device that receives the norm (and is returned, as a 0-dim view).  An empty list gives norm 0 and coef 1
+    on `norm_out`'s device, else on the current one."""
+    max_norm = check_max_norm(max_norm)
+    tensors, groups = _grad_list(tensors, "grad_norm")
+    if tensors:
+        dev = tensors[0].device
+    else:
+        dev = norm_out.device if norm_out is not None else torch.device("cuda", torch.cuda.current_device())
+    if norm_out is not None:
+        if (not isinstance(norm_out, torch.Tensor) or not norm_out.is_cuda or norm_out.dtype != torch.float32
+                or norm_out.numel() != 1 or norm_out.device != dev):
+            raise KGATLibraryError("grad_norm: norm_out must be a 1-element float32 tensor on %s" % dev)
+        norm = norm_out.view(())
+    else:
+        norm = torch.empty((), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    counts = [int(lib.kgat_grad_sumsq_partials(n, sizes)) for n, sizes, _ in groups]
+    if any(c < 0 for c in counts):
+        check(-1, "kgat_grad_sumsq_partials")
+    total = sum(counts)
+    partials = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    coef = torch.empty((), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev), _timed("grad_norm", (len(tensors), total)):
+        off = 0
+        for (n, sizes, ptrs), c in zip(groups, counts):
+            check(lib.kgat_grad_sumsq_f32(n, sizes, ptrs, partials.data_ptr() + 4 * off, total - off, stream),
+                  "kgat_grad_sumsq_f32")
+            off += c
+        check(lib.kgat_grad_norm_finish_f32(total, partials.data_ptr(), max_norm, norm.data_ptr(), coef.data_ptr(),
+                                            stream), "kgat_grad_norm_finish_f32")
+    return norm, coef
+
+
+def scale_grads(tensors, coef):
+    """tensors[i] *= coef in place (kgat_scale_grads_f32; `coef` a 1-element fp32 device tensor): one launch per
+    kgat_adam_max_tensors() tensors."""
+    tensors, groups = _grad_list(tensors, "scale_grads")
+    if not tensors:
+        return
+    dev = tensors[0].device
+    coef = _need(coef.reshape(1), torch.float32, "coef")
+    if coef.device != dev:
+        raise KGATLibraryError("scale_grads: coef is on %s, the tensors on %s" % (coef.device, dev))
+    lib = _lib.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev), _timed("scale_grads", len(tensors)):
+        for n, sizes, ptrs in groups:
+            check(lib.kgat_scale_grads_f32(n, sizes, ptrs, coef.data_ptr(), stream), "kgat_scale_grads_f32")

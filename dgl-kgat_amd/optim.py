@@ -4,13 +4,40 @@
 Same hyper-parameters, same state (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter: a ``state_dict`` moves
 between this class and ``torch.optim.Adam``), same dense semantics - the reference's embedding table moves in every
 step, also in rows whose gradient is zero.  fp32 HIP parameters only (anything else raises: there is no fallback);
-``amsgrad`` / ``weight_decay`` / ``maximize`` are not part of the reference's call and are refused."""
+``amsgrad`` / ``weight_decay`` / ``maximize`` are not part of the reference's call and are refused.
+
+Global-norm gradient clipping (reference kgat.py:32 ``--grad_norm``, kgat.py:162 ``clip_grad_norm_`` between backward
+and step) comes in two forms: ``FusedAdam.step(max_grad_norm=c)``, which applies the clip coefficient inside the Adam
+launch, and ``clip_grad_norm_``, torch's function on this package's kernels for any other optimiser."""
 import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import KGATLibraryError, check
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
+    """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` on the HIP kernels: the global 2-norm of the gradients
+    (``ops.grad_norm``), then every gradient scaled IN PLACE by min(max_norm / (norm + 1e-6), 1) in one launch per 16
+    tensors.  Returns the total norm (a 0-dim device tensor), as torch does; nothing is read back to the host, a
+    non-finite norm propagates into the gradients (torch's ``error_if_nonfinite=False``).  Only ``norm_type=2``."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("clip_grad_norm_: norm_type=%r (the reference clips by the 2-norm, kgat.py:162)" % (norm_type,))
+    max_norm = ops.check_max_norm(max_norm)
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    for g in grads:
+        if g.is_sparse or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+            raise KGATLibraryError("clip_grad_norm_: gradients must be contiguous dense float32 HIP tensors (got %s on %s)"
+                                   % (g.dtype, g.device))
+    with torch.no_grad():
+        norm, coef = ops.grad_norm(grads, max_norm)
+        ops.scale_grads(grads, coef)
+    return norm
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -21,15 +48,43 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("invalid Adam hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False))
         self._zero_grads = bool(zero_grads)   # also clear the gradients in the same pass (zero_grad(set_to_none=False))
+        self.last_grad_norm = None            # step(max_grad_norm=c) without norm_out: that step's norm (0-dim, device)
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, max_grad_norm=None, norm_out=None):
+        """One Adam step.  ``max_grad_norm=c`` (per call: the reference shares one Adam between its two phases and
+        clips only in the CF loop) first takes ONE global 2-norm over every parameter that has a gradient - all
+        parameter groups, all launches of 16 - and applies min(c / (norm + 1e-6), 1) to each gradient element inside the
+        Adam launch: the bits of ``torch.nn.utils.clip_grad_norm_(params, c)`` followed by the plain step, at two extra
+        launches and one extra read of the gradients, with norm and coefficient staying on the device.  The norm goes to
+        ``norm_out`` (a 1-element fp32 device tensor or view) if given, else to ``self.last_grad_norm``.  The one
+        difference from torch's in-place clip: the stored gradient is read, not rewritten - without ``zero_grads`` it
+        keeps its unclipped bits after the step.  A non-finite norm propagates into the parameters (torch's
+        ``error_if_nonfinite=False``).  ``max_grad_norm=None``: the plain step."""
+        if max_grad_norm is not None:
+            max_grad_norm = ops.check_max_norm(max_grad_norm)
+        elif norm_out is not None:
+            raise ValueError("norm_out needs max_grad_norm")
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
         cap = lib.kgat_adam_max_tensors()
+        coef, contiguous = None, {}
+        if max_grad_norm is not None:
+            with_grad = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+            for p in with_grad:
+                if not p.is_cuda or p.dtype != torch.float32 or p.grad.is_sparse or p.grad.dtype != torch.float32:
+                    raise KGATLibraryError("FusedAdam: parameters must be contiguous float32 HIP tensors with dense "
+                                           "gradients (got %s on %s)" % (p.dtype, p.device))
+            if len({p.device for p in with_grad}) > 1:
+                raise KGATLibraryError("FusedAdam: max_grad_norm takes one norm over all parameters; they are on %s"
+                                       % ", ".join(sorted({str(p.device) for p in with_grad})))
+            contiguous = {id(p): p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in with_grad}
+            norm, coef = ops.grad_norm([contiguous[id(p)] for p in with_grad], max_grad_norm, norm_out=norm_out)
+            if norm_out is None:
+                self.last_grad_norm = norm
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             for p in ps:
@@ -55,7 +110,8 @@ class FusedAdam(torch.optim.Optimizer):
                     st = self.state[p]
                     st["step"] += 1                      # (a CPU scalar tensor, as torch.optim.Adam keeps it)
                     steps.append(int(st["step"]))
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in chunk]
+                grads = [contiguous[id(p)] if coef is not None else
+                         p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in chunk]
                 arr_p = (C.c_void_p * n)(*[p.data_ptr() for p in chunk])
                 arr_g = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
                 arr_m = (C.c_void_p * n)(*[self.state[p]["exp_avg"].data_ptr() for p in chunk])
@@ -64,6 +120,12 @@ class FusedAdam(torch.optim.Optimizer):
                 arr_t = (C.c_int64 * n)(*steps)
                 zero = self._zero_grads and all(g is p.grad for g, p in zip(grads, chunk))
                 with torch.cuda.device(dv):
+                    if coef is not None:
+                        check(lib.kgat_adam_step_clipped_f32(
+                            n, arr_n, arr_p, arr_g, arr_m, arr_v, arr_t, float(group["lr"]), float(group["betas"][0]),
+                            float(group["betas"][1]), float(group["eps"]), int(zero), coef.data_ptr(),
+                            torch.cuda.current_stream(dv).cuda_stream), "kgat_adam_step_clipped_f32")
+                        continue
                     check(lib.kgat_adam_step_f32(n, arr_n, arr_p, arr_g, arr_m, arr_v, arr_t, float(group["lr"]),
                                                  float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                                                  int(zero), torch.cuda.current_stream(dv).cuda_stream),

@@ -17,6 +17,7 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
                                                                           # planted structure: recall@20 must rise
   python examples/train_kgat.py --synthetic 0.01 --gpus 2                # CF phase on destination shards
   python examples/train_kgat.py --planted --epochs 3 --explain 5         # + why the top-1 item: its best attention walk
+  python examples/train_kgat.py --synthetic 1.0 --grad_norm 1.0          # clip the CF gradient's global norm (kgat.py:32,162)
 
 ``--gpus N``: one process per GPU (started here as a child ``torch.distributed.run``),
 parameters replicated, the training graph sharded by destination range.  Every rank draws the same
@@ -163,6 +164,9 @@ def parse_args(argv=None):
                          "table also receive the BPR gradient through them (the reference computes them once per "
                          "epoch under no_grad, kgat.py:139-145)")
     ap.add_argument("--lr", type=float, default=0.0001)
+    ap.add_argument("--grad_norm", type=float, default=0.0,
+                    help="norm to clip the CF step's gradient to (reference kgat.py:32; its clip_grad_norm_ call, "
+                         "kgat.py:162, ships commented out): global 2-norm clipping inside the fused Adam step.  0 = off")
     ap.add_argument("--batch_size", type=int, default=10240)
     ap.add_argument("--batch_size_kg", type=int, default=2048)
     ap.add_argument("--max_iters", type=int, default=0, help="cap on iterations per phase (0 = full epoch)")
@@ -191,6 +195,8 @@ def parse_args(argv=None):
         ap.error("--res_type %s selects the aggregator of --gnn_model kgat; graphsage takes none" % args.res_type)
     if args.res_type != "Bi" and args.gpus > 1:
         ap.error("--res_type %s runs on one GPU: sharded models run the Bi aggregator only" % args.res_type)
+    if not (0.0 <= args.grad_norm < float("inf")):
+        ap.error("--grad_norm takes a finite norm > 0, or 0 for no clipping")
     if not 0.0 <= args.node_dropout < 1.0:
         ap.error("--node_dropout must be in [0, 1)")
     if args.node_dropout > 0 and args.gnn_model == "graphsage":
@@ -358,6 +364,8 @@ def _run(args, argv):
         n_all = torch.randint(off, off + ds.n_items, (n_it, bs), device=dev, dtype=torch.int32)
         total = torch.zeros((), dtype=torch.float32, device=dev)
         w_r_before = model.W_R.detach().clone()
+        # --grad_norm: every step leaves its gradient norm here; one readback at the end of the phase
+        norms = torch.zeros(n_it, dtype=torch.float32, device=dev) if args.grad_norm > 0 else None
         for i in range(n_it):
             if args.attention_grad:
                 train_g.edata["w"] = model.compute_attention(train_g, differentiable=True)
@@ -368,12 +376,26 @@ def _run(args, argv):
                 say("           | grad digest: loss %.9g  " % loss.item() + "  ".join(
                     "%s %.9g" % (k, p.grad.double().abs().sum().item()) for k, p in model.named_parameters()
                     if p.grad is not None))
-            opt.step()
+            if norms is not None:   # clip_grad_norm_(model.parameters(), args.grad_norm) of kgat.py:162, inside the step
+                opt.step(max_grad_norm=args.grad_norm, norm_out=norms[i])
+            else:
+                opt.step()
             opt.zero_grad()
             total += loss.detach()
         rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
         rec["cf_loss"] = float(total) / n_it
         rec["cf_W_R_change"] = float((model.W_R.detach() - w_r_before).abs().max())   # 0 unless --attention_grad 1
+        if norms is not None:
+            seen = norms.cpu().numpy()
+            if not np.isfinite(seen).all():
+                raise RuntimeError("epoch %d: the gradient norm of CF step %d is %r" % (
+                    epoch, int(np.flatnonzero(~np.isfinite(seen))[0]), float(seen[~np.isfinite(seen)][0])))
+            rec["cf_grad_norm_max"], rec["cf_grad_norm_mean"] = float(seen.max()), float(seen.mean())
+            # (the test the kernel applies: coef = min(c / (norm + 1e-6), 1) in fp32 is below 1)
+            c32 = np.float32(args.grad_norm)
+            rec["cf_clipped_steps"] = int((c32 / (seen + np.float32(1e-6)) < np.float32(1)).sum())
+            say("           | grad norm max %.4g mean %.4g, %d of %d steps clipped at %g" % (
+                rec["cf_grad_norm_max"], rec["cf_grad_norm_mean"], rec["cf_clipped_steps"], n_it, args.grad_norm))
         say("           | GNN %.4fs (%d it, %.4f ms/it) loss %.4f" % (rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it, rec["cf_loss"]))
         del idx, u_all, p_all, n_all
         replicas_agree("epoch %d" % epoch)

@@ -838,6 +838,50 @@ int kgat_adam_step_f32(int n_tensors, const int64_t* sizes_host, float* const* p
                        float* const* exp_avg_host, float* const* exp_avg_sq_host, const int64_t* steps_host, double lr,
                        double beta1, double beta2, double eps, int zero_grads, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- global-norm gradient clipping (additive within ABI 16)
+ * reference kgat.py:32,162: `--grad_norm` ("norm to clip gradient to") and the call it feeds,
+ * th.nn.utils.clip_grad_norm_(model.parameters(), args.grad_norm), between loss.backward() and optimizer.step() of the
+ * CF loop.  The semantics of torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) followed by Adam's step,
+ * with every bit determined:
+ *   sumsq = sum of g*g over every element of every gradient, in a FIXED order (no float atomics: bitwise reproducible);
+ *   norm  = (float)sqrt(sumsq);   coef = fminf((float)max_norm / (norm + 1e-6f), 1.0f)      (fp32 DEVICE scalars)
+ *   step:  gs = g * coef (its own rounding), then the element update of kgat_adam_step_f32 on gs.
+ * A non-finite norm propagates (torch's error_if_nonfinite=False: a NaN norm gives a NaN coef, as torch.clamp keeps
+ * it, where fminf alone would give 1); nothing is read back to the host.
+ *
+ * kgat_grad_norm_chain (kgat.py:32,162): the longest chain of fp32 additions any one square passes through - 16 serial
+ * adds in a lane, 6 + 2 tree levels in the workgroup = 24; the per-chunk sums are then added in double.  The norm's
+ * relative error against exact arithmetic is at most gamma(chain + 1) / 2 + 2u, u = 2^-24.
+ * kgat_grad_sumsq_partials (kgat.py:32,162): the number of partials kgat_grad_sumsq_f32 writes for these sizes (one per
+ * started chunk of 4,096 elements of each tensor); -1 on a bad argument.
+ * kgat_grad_sumsq_f32 (kgat.py:32,162): ONE launch over up to kgat_adam_max_tensors() gradient tensors (HOST arrays of
+ * sizes / device pointers, as kgat_adam_step_f32); partials[0 .. count) receive one fp32 sum of squares per chunk, in
+ * tensor then chunk order.  partials_cap: floats available at `partials` (checked).  16-byte loads where a tensor's
+ * pointer is 16-byte aligned, 4-byte loads otherwise - the same bits either way.  More tensors: one call per group,
+ * each writing at its own offset of one buffer.
+ * kgat_grad_norm_finish_f32 (kgat.py:32,162): ONE workgroup adds partials[0 .. n_partials) in double in a fixed order
+ * and writes *norm and *coef (n_partials == 0: norm 0, coef 1).  max_norm finite and > 0.
+ * kgat_adam_step_clipped_f32 (kgat.py:32,162): kgat_adam_step_f32 with every gradient element multiplied by the device
+ * scalar *grad_coef first.  The stored gradient is READ, not rewritten: with zero_grads == 0 it keeps its unclipped
+ * bits (torch's clip scales it in place), with zero_grads != 0 it is cleared.  *grad_coef == 1 gives the bits of
+ * kgat_adam_step_f32.
+ * kgat_scale_grads_f32 (kgat.py:32,162): ONE launch, g <- g * (*coef) in place over up to kgat_adam_max_tensors()
+ * tensors: torch's in-place clip, for optimisers other than the fused one.
+ * All: KGAT_E_BADARG on a null pointer, a negative size, more tensors than kgat_adam_max_tensors(), max_norm not finite
+ * and > 0, before any device work. */
+int kgat_grad_norm_chain(void);
+int64_t kgat_grad_sumsq_partials(int n_tensors, const int64_t* sizes_host);
+int kgat_grad_sumsq_f32(int n_tensors, const int64_t* sizes_host, float* const* grads_host, float* partials,
+                        int64_t partials_cap, kgat_stream_t stream);
+int kgat_grad_norm_finish_f32(int64_t n_partials, const float* partials, double max_norm, float* norm, float* coef,
+                              kgat_stream_t stream);
+int kgat_adam_step_clipped_f32(int n_tensors, const int64_t* sizes_host, float* const* params_host,
+                               float* const* grads_host, float* const* exp_avg_host, float* const* exp_avg_sq_host,
+                               const int64_t* steps_host, double lr, double beta1, double beta2, double eps,
+                               int zero_grads, const float* grad_coef, kgat_stream_t stream);
+int kgat_scale_grads_f32(int n_tensors, const int64_t* sizes_host, float* const* grads_host, const float* coef,
+                         kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- BPR loss of the CF phase (8f #1)
  * reference models.py:170-178 (get_loss; _L2_loss_mean :9-11) on the readout `emb` (n_nodes rows of emb_stride
  * floats, the first F used; F and emb_stride multiples of 4):
