@@ -327,7 +327,7 @@ class _GNNTrain(torch.autograd.Function):
             w_csr = ops.edge_dropout(w_csr, csr.eid, edge[0], edge[1])
         first = [0]  # layer li's weights: weights[first[li]:first[li + 1]]
         for f in forms:
-            first.append(first[-1] + (2 if f == ops.BI2_FORM else 1))
+            first.append(first[-1] + ops.form_weights(f))
         widths = [h.shape[1]] + [weights[first[li]].shape[0] for li in range(len(forms))]
         out = torch.empty((h.shape[0], sum(widths)), dtype=torch.float32, device=dev)
         # the ego block (out[:, :d] = h0, models.py:159,168) is written by layer 0's dense kernel from the rows it loads
@@ -339,14 +339,11 @@ class _GNNTrain(torch.autograd.Function):
         hs, hns, signs = [h], [], []
         for li, form in enumerate(forms):
             hn = ops.spmm(csr.indptr, csr.col, csr.row_of, hs[-1], w_csr)
-            lw = [w.detach().contiguous() for w in weights[first[li]:first[li + 1]]]
-            kw = dict(norm_out=out[:, off:off + widths[li + 1]],
-                      self_out=out[:, :widths[0]] if (li == 0 and ego_in_kernel) else None)
-            if form == ops.BI2_FORM:
-                y, sg = ops.bi2_train(hs[-1], hn, lw[0], lw[1], slope, drop_p, seed + li, **kw)
-                signs.append(sg)
-            else:
-                y = ops.aggregator_train(form, hs[-1], hn, lw[0], slope, drop_p, seed + li, **kw)
+            # (a two-term layer also returns its sign record)
+            y, *sg = _each(ops.aggregator_train(form, hs[-1], hn, _layer_weights(weights, first, li), slope, drop_p,
+                                                seed + li, norm_out=out[:, off:off + widths[li + 1]],
+                                                self_out=out[:, :widths[0]] if (li == 0 and ego_in_kernel) else None))
+            signs += sg
             hs.append(y)
             hns.append(hn)
             off += widths[li + 1]
@@ -376,49 +373,35 @@ class _GNNTrain(torch.autograd.Function):
         grad_w = [None] * first[-1]
         pending = []  # (index into weights, that weight gradient's per-workgroup partials)
         for li in range(n_l - 1, -1, -1):
-            if ctx.forms[li] == ops.BI2_FORM:
-                wi = first[li]
-                gz1, gz2 = ops.bi2_bwd_pre(hs[li + 1], signs.pop(), g_a, g_b, grad_out[:, offs[li + 1]:offs[li + 2]],
-                                           ctx.slope, ctx.drop_p, ctx.seed + li)
-                kernels = ops.bi2_bwd_supported(hs[li].shape[1], gz1.shape[1])
-                w1, w2 = weights[wi].detach().contiguous(), weights[wi + 1].detach().contiguous()
-                if ctx.needs_input_grad[7 + wi] or ctx.needs_input_grad[8 + wi]:
-                    if kernels:
-                        p1, p2 = ops.bi2_bwd_weight(gz1, gz2, hs[li], hns[li], want_partials=True)
-                        pending += [(wi, p1), (wi + 1, p2)]
-                    else:
-                        grad_w[wi] = tall_weight_grad(gz1, hs[li] + hns[li])
-                        grad_w[wi + 1] = tall_weight_grad(gz2, hs[li] * hns[li])
+            form, wi, h, hn = ctx.forms[li], first[li], hs[li], hns[li]
+            n_w = first[li + 1] - wi
+            # one gradient per weight: grad_z, or (gz1, gz2) from the two-term layer's sign record
+            gz = ops.aggregator_bwd_pre(form, hs[li + 1], signs.pop() if n_w == 2 else None, g_a, g_b,
+                                        grad_out[:, offs[li + 1]:offs[li + 2]], ctx.slope, ctx.drop_p, ctx.seed + li)
+            kernels = ops.aggregator_bwd_supported(form, h.shape[1], _each(gz)[0].shape[1])
+            if any(ctx.needs_input_grad[7 + wi:7 + wi + n_w]):
                 if kernels:
-                    # P1 + P2 * h (to be aggregated) and P1 + P2 * h_N (to h directly), P1 = gz1 W1, P2 = gz2 W2 per tile
-                    t, g_b = ops.bi2_bwd_input(gz1, gz2, w1, w2, hs[li], hns[li])
+                    # grad_z^T (h * h_N) (h + h_N, [h | h_N]; both of the two-term layer) as per-workgroup partials;
+                    # every layer's set is summed by ONE launch at the end
+                    parts = ops.aggregator_bwd_weight(form, gz, h, hn, want_partials=True)
+                    pending += [(wi + k, p) for k, p in enumerate(_each(parts))]
                 else:
-                    p1, p2 = gz1 @ w1, gz2 @ w2
-                    t, g_b = p1 + p2 * hs[li], p1 + p2 * hns[li]
-                g_a = ops.spmm(rev.indptr, rev.col, rev.row_of, t, w_rev)
-                continue
-            gz = ops.bi_interaction_bwd_pre(hs[li + 1], g_a, g_b, grad_out[:, offs[li + 1]:offs[li + 2]], ctx.slope,
-                                            ctx.drop_p, ctx.seed + li)
-            form, d_in = ctx.forms[li], hs[li].shape[1]
-            kernels = ops.aggregator_bwd_supported(form, d_in, gz.shape[1])
-            if ctx.needs_input_grad[7 + first[li]]:
-                if kernels:
-                    # grad_z^T (h * h_N) (h + h_N, [h | h_N]) as per-workgroup partials; every layer's set is summed by
-                    # ONE launch at the end
-                    pending.append((first[li], ops.aggregator_bwd_weight(form, gz, hs[li], hns[li], want_partials=True)))
-                else:
-                    grad_w[first[li]] = tall_weight_grad(gz, _combine(form, hs[li], hns[li]))
-            w_l = weights[first[li]].detach().contiguous()
+                    for k, (g, x) in enumerate(zip(_each(gz), _combine(form, h, hn))):
+                        grad_w[wi + k] = tall_weight_grad(g, x)
+            w_l = _layer_weights(weights, first, li)
             if kernels:
                 # grad_P = grad_z W formed per tile: the part to be aggregated (grad_P * h for Bi) and the part that goes to
-                # h directly (grad_P * h_N)
-                t, g_b = ops.aggregator_bwd_input(form, gz, w_l, hs[li], hns[li])
+                # h directly (grad_P * h_N); the two-term layer: P1 + P2 * h and P1 + P2 * h_N, P1 = gz1 W1, P2 = gz2 W2
+                t, g_b = ops.aggregator_bwd_input(form, gz, w_l, h, hn)
+            elif form == ops.BI2_FORM:
+                p1, p2 = gz[0] @ w_l[0], gz[1] @ w_l[1]
+                t, g_b = p1 + p2 * h, p1 + p2 * hn
             elif form == ops.FORMS["Bi"]:
-                t, g_b = ops.mul2(gz @ w_l, hs[li], hns[li])
+                t, g_b = ops.mul2(gz @ w_l, h, hn)
             elif form == ops.FORMS["GCN"]:
                 t = g_b = gz @ w_l
             else:
-                gp = gz @ w_l
+                gp, d_in = gz @ w_l, h.shape[1]
                 t, g_b = gp[:, d_in:].contiguous(), gp[:, :d_in].contiguous()
             g_a = ops.spmm(rev.indptr, rev.col, rev.row_of, t, w_rev)
         if pending:
@@ -435,13 +418,27 @@ class _GNNTrain(torch.autograd.Function):
         return (None, None, None, None, None, None, grad_h0, *grad_w)
 
 
+def _each(x):
+    """A per-weight value - one tensor, or the two-term layer's pair - as a tuple."""
+    return tuple(x) if isinstance(x, (tuple, list)) else (x,)
+
+
+def _layer_weights(weights, first, li):
+    """Layer li's weight out of the flat list, detached: a tensor, or the two-term layer's pair (ops' convention)."""
+    ws = tuple(w.detach().contiguous() for w in weights[first[li]:first[li + 1]])
+    return ws if len(ws) == 2 else ws[0]
+
+
 def _combine(form, h, hn):
-    """The A operand of a layer's dense part: h * h_N (Bi), h + h_N (GCN), [h | h_N] (GraphSage)."""
+    """The A operand of each of the layer's weights: h * h_N (Bi), h + h_N (GCN), [h | h_N] (GraphSage), both the sum
+    and the product (two-term)."""
+    if form == ops.BI2_FORM:
+        return h + hn, h * hn
     if form == ops.FORMS["GCN"]:
-        return h + hn
+        return (h + hn,)
     if form == ops.FORMS["GraphSage"]:
-        return torch.cat([h, hn], 1)
-    return h * hn
+        return (torch.cat([h, hn], 1),)
+    return (h * hn,)
 
 
 def tall_weight_grad(grad, x, slabs=128):

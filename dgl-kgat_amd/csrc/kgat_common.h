@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/kgat_hip.h"
 
 namespace kgat {
@@ -49,6 +51,36 @@ inline int device_cu_count() {
 __device__ __forceinline__ unsigned xcd_contiguous(unsigned b, unsigned n) {
   const unsigned q = n / 8, r = n % 8, x = b % 8;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
+}
+
+// Host-side width dispatch: the (d_in, d_out) a caller passes -> the kernel instantiation compiled for that pair.
+// dispatch_widths(table, a, b, f) calls the generic lambda f(A, B) with the two widths as
+// std::integral_constant<int, ...> (A() and B() are constant expressions: template arguments of the launch) and
+// returns what it returns, or KGAT_E_UNSUPPORTED for a pair the table does not hold.  f is instantiated once per
+// pair of the table and for no other, so the table IS the set of kernels built.
+template <int... D> struct WidthSquare {};              // every pair of D x D
+template <int A, int B> struct WidthPair {};
+template <typename... P> struct WidthPairs {};          // the listed pairs
+using MfmaWidths = WidthSquare<16, 32, 64, 128>;        // the MFMA dense kernels: whole 16-column tiles up to 128
+
+template <typename F, int A, int B>
+inline bool try_widths(WidthPair<A, B>, int a, int b, F& f, int& rc) {
+  if (a != A || b != B) return false;
+  rc = f(std::integral_constant<int, A>{}, std::integral_constant<int, B>{});
+  return true;
+}
+template <typename F, int... A, int... B>
+inline int dispatch_widths(WidthPairs<WidthPair<A, B>...>, int a, int b, F&& f) {
+  int rc = KGAT_E_UNSUPPORTED;
+  (void)(try_widths(WidthPair<A, B>{}, a, b, f, rc) || ...);
+  return rc;
+}
+template <typename F, int... D>
+inline int dispatch_widths(WidthSquare<D...>, int a, int b, F&& f) {
+  int rc = KGAT_E_UNSUPPORTED;
+  auto row = [&](auto wa) { return (try_widths(WidthPair<decltype(wa)::value, D>{}, a, b, f, rc) || ...); };
+  (void)((a == D && row(std::integral_constant<int, D>{})) || ...);
+  return rc;
 }
 
 // Device-side primitives implemented in kgat_graph.hip, reused by other translation units.

@@ -31,17 +31,6 @@ __device__ __forceinline__ float row16_sum_d(float v) {
   return v;
 }
 
-constexpr bool kBiMulAtLoad = false;   // (true: the first form of MODE >= 1, h * h_N multiplied in the load step - round 4's A/B)
-constexpr int kBiNtLoads = 0;   // A/B builds, bit mask: 1 = the rows of H (P), 2 = the rows of HN as non-temporal loads
-template <bool NT>
-__device__ __forceinline__ float4 ld_row4(const float4* p) {
-  if constexpr (NT) {
-    const floatx4_d v = __builtin_nontemporal_load(reinterpret_cast<const floatx4_d*>(p));
-    return make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    return *p;
-  }
-}
 __device__ __forceinline__ void st_final4(float4* p, const float4& v) {
   const floatx4_d x = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(x, reinterpret_cast<floatx4_d*>(p));
@@ -257,70 +246,6 @@ static DropArgs drop_args(float p, uint64_t seed, int64_t row0, int d_out) {
   return a;
 }
 
-template <int DI, int DO, int COMB = kCombMul>
-static int launch_bi(int64_t n_rows, const float* P, const float* HN, const float* W2, float slope,
-                     const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride, hipStream_t st,
-                     int mode, const EgoCopy ego, const DeferredRows* defer = nullptr) {
-  const int64_t tiles = (n_rows + 15) / 16;
-  int64_t blocks = (tiles + 3) / 4;  // at least one tile per wave ...
-constexpr int kBiMaxBlocks = 512;
-  if (blocks > kBiMaxBlocks) blocks = kBiMaxBlocks;    // ... two workgroups per CU (each stages W2 once; measured 256: 22.7, 512: 21.2, 1024: 22.1, 2048: 24.1 us avg)
-  // 16-byte stores into the normalised copy need its slice 16-byte aligned with a row stride that keeps it so
-  const bool vec = norm_out == nullptr ||
-                   ((reinterpret_cast<uintptr_t>(norm_out) & 15u) == 0 && norm_stride % 4 == 0);
-  const DeferredRows no_defer{nullptr, nullptr, 0, 0, 0};
-#define KGAT_BI_LAUNCH(MD, VEC)                                                                                     \
-  hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, MD, VEC, false, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,\
-                     (int32_t)n_rows, P, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,     \
-                     norm_out, norm_stride, ego, no_defer)
-  if (mode == 1 && defer != nullptr) {
-    if (vec)
-      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, 1, true, true, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,
-                         (int32_t)n_rows, P, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,
-                         norm_out, norm_stride, ego, *defer);
-    else
-      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, 1, false, true, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,
-                         (int32_t)n_rows, P, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,
-                         norm_out, norm_stride, ego, *defer);
-  } else if (mode == 2) {
-    if (vec) KGAT_BI_LAUNCH(2, true); else KGAT_BI_LAUNCH(2, false);
-  } else if (mode == 1) {
-    if (vec) KGAT_BI_LAUNCH(1, true); else KGAT_BI_LAUNCH(1, false);
-  } else if constexpr (COMB == kCombMul) {  // (MODE 0 - P formed elsewhere - exists for the product only)
-    if (vec) KGAT_BI_LAUNCH(0, true); else KGAT_BI_LAUNCH(0, false);
-  }
-#undef KGAT_BI_LAUNCH
-  KGAT_CHECK_LAUNCH("bi_interaction");
-  return KGAT_OK;
-}
-
-// The two-term form: mode 1 (no-grad, optionally with the deferred rows) or 2 (training, with the sign record)
-template <int DI, int DO>
-static int launch_bi2(int64_t n_rows, const float* H, const float* HN, const float* W1, const float* W2, float slope,
-                      const DropArgs& dr, float* h_out, uint8_t* signs, float* norm_out, int64_t norm_stride,
-                      hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer) {
-  const int64_t tiles = (n_rows + 15) / 16;
-  int64_t blocks = (tiles + 3) / 4;
-  if (blocks > 512) blocks = 512;  // (as launch_bi)
-  const bool vec = norm_out == nullptr ||
-                   ((reinterpret_cast<uintptr_t>(norm_out) & 15u) == 0 && norm_stride % 4 == 0);
-  const DeferredRows no_defer{nullptr, nullptr, 0, 0, 0};
-#define KGAT_BI2_LAUNCH(MD, VEC, DEF, DFV)                                                                            \
-  hipLaunchKernelGGL((bi2_kernel<DI, DO, MD, VEC, DEF>), dim3((unsigned)blocks), dim3(256), 0, st, (int32_t)n_rows, H, \
-                     HN, W1, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out, signs, norm_out,      \
-                     norm_stride, ego, DFV)
-  if (mode == 2) {
-    if (vec) KGAT_BI2_LAUNCH(2, true, false, no_defer); else KGAT_BI2_LAUNCH(2, false, false, no_defer);
-  } else if (defer != nullptr) {
-    if (vec) KGAT_BI2_LAUNCH(1, true, true, *defer); else KGAT_BI2_LAUNCH(1, false, true, *defer);
-  } else {
-    if (vec) KGAT_BI2_LAUNCH(1, true, false, no_defer); else KGAT_BI2_LAUNCH(1, false, false, no_defer);
-  }
-#undef KGAT_BI2_LAUNCH
-  KGAT_CHECK_LAUNCH("bi2");
-  return KGAT_OK;
-}
-
 template <int DI, int DO>
 static int launch_bi_small(int64_t n_rows, const float* P, const float* HN, const float* W2, float slope,
                            const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride, hipStream_t st,
@@ -335,6 +260,43 @@ static int launch_bi_small(int64_t n_rows, const float* P, const float* HN, cons
   else KGAT_BI_SMALL_LAUNCH(0);
 #undef KGAT_BI_SMALL_LAUNCH
   KGAT_CHECK_LAUNCH("bi_interaction_small");
+  return KGAT_OK;
+}
+
+// The MFMA forward of every form: mode 0 (P formed elsewhere - the product only), 1 (no-grad, optionally with the
+// deferred rows) or 2 (training; the two-term form writes its sign record).  W1 and signs are the two-term form's.
+template <int DI, int DO, int COMB>
+static int launch_dense(int64_t n_rows, const float* H, const float* HN, const float* W1, const float* W2, float slope,
+                        const DropArgs& dr, float* h_out, uint8_t* signs, float* norm_out, int64_t norm_stride,
+                        hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer) {
+  const int64_t tiles = (n_rows + 15) / 16;
+  int64_t blocks = (tiles + 3) / 4;  // at least one tile per wave ...
+  constexpr int kBiMaxBlocks = 512;
+  if (blocks > kBiMaxBlocks) blocks = kBiMaxBlocks;    // ... two workgroups per CU (each stages W2 once; measured 256: 22.7, 512: 21.2, 1024: 22.1, 2048: 24.1 us avg)
+  // 16-byte stores into the normalised copy need its slice 16-byte aligned with a row stride that keeps it so
+  const bool vec = norm_out == nullptr ||
+                   ((reinterpret_cast<uintptr_t>(norm_out) & 15u) == 0 && norm_stride % 4 == 0);
+  const DeferredRows df = defer != nullptr ? *defer : DeferredRows{nullptr, nullptr, 0, 0, 0};
+  auto launch = [&](auto md, auto vn, auto def) {
+    constexpr int MD = decltype(md)::value;
+    constexpr bool VEC = decltype(vn)::value, DEF = decltype(def)::value;
+    if constexpr (COMB == kCombBi2)
+      hipLaunchKernelGGL((bi2_kernel<DI, DO, MD, VEC, DEF>), dim3((unsigned)blocks), dim3(256), 0, st, (int32_t)n_rows, H,
+                         HN, W1, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out, signs, norm_out,
+                         norm_stride, ego, df);
+    else
+      hipLaunchKernelGGL((bi_interaction_kernel<DI, DO, MD, VEC, DEF, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,
+                         (int32_t)n_rows, H, HN, W2, slope, dr.threshold, dr.keep_scale, dr.seed, dr.index0, h_out,
+                         norm_out, norm_stride, ego, df);
+  };
+  auto launch_vec = [&](auto md, auto def) {
+    if (vec) launch(md, std::true_type{}, def); else launch(md, std::false_type{}, def);
+  };
+  if (mode == 2) launch_vec(std::integral_constant<int, 2>{}, std::false_type{});
+  else if (mode == 1 && defer != nullptr) launch_vec(std::integral_constant<int, 1>{}, std::true_type{});
+  else if (mode == 1) launch_vec(std::integral_constant<int, 1>{}, std::false_type{});
+  else if constexpr (COMB == kCombMul) launch_vec(std::integral_constant<int, 0>{}, std::false_type{});
+  KGAT_CHECK_LAUNCH(COMB == kCombBi2 ? "bi2" : "bi_interaction");
   return KGAT_OK;
 }
 
@@ -848,101 +810,83 @@ __global__ __launch_bounds__(256) void mul2_kernel(int64_t n4, const float4* __r
   }
 }
 
-// The sum and the concatenation: the MFMA kernel's widths only (others are the caller's, in torch)
-template <int COMB>
-static int comb_dispatch(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W,
-                         float negative_slope, const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride,
-                         hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer) {
-#define KGAT_COMB_CASE(DI, DO) \
-  if (d_in == DI && d_out == DO) \
-    return launch_bi<DI, DO, COMB>(n_rows, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st, mode, ego, defer);
-  KGAT_COMB_CASE(16, 16) KGAT_COMB_CASE(16, 32) KGAT_COMB_CASE(16, 64) KGAT_COMB_CASE(16, 128)
-  KGAT_COMB_CASE(32, 16) KGAT_COMB_CASE(32, 32) KGAT_COMB_CASE(32, 64) KGAT_COMB_CASE(32, 128)
-  KGAT_COMB_CASE(64, 16) KGAT_COMB_CASE(64, 32) KGAT_COMB_CASE(64, 64) KGAT_COMB_CASE(64, 128)
-  KGAT_COMB_CASE(128, 16) KGAT_COMB_CASE(128, 32) KGAT_COMB_CASE(128, 64) KGAT_COMB_CASE(128, 128)
-#undef KGAT_COMB_CASE
-  set_error("aggregator: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+// the widths of the narrow kernel (bi_interaction_small_kernel): d_in or d_out in {4, 8}, the other up to 32
+using SmallWidths = WidthPairs<WidthPair<4, 4>, WidthPair<4, 8>, WidthPair<4, 16>, WidthPair<4, 32>, WidthPair<8, 4>,
+                               WidthPair<8, 8>, WidthPair<8, 16>, WidthPair<8, 32>, WidthPair<16, 4>, WidthPair<16, 8>,
+                               WidthPair<32, 4>, WidthPair<32, 8>>;
+
+// form (KGAT_FORM_* or the two-term form) -> COMB as a compile-time value for the generic lambda f
+template <typename F>
+static int with_comb(int form, bool bi2, F&& f) {
+  if (bi2) return f(std::integral_constant<int, kCombBi2>{});
+  if (form == KGAT_FORM_GCN) return f(std::integral_constant<int, kCombSum>{});
+  if (form == KGAT_FORM_GRAPHSAGE) return f(std::integral_constant<int, kCombCat>{});
+  return f(std::integral_constant<int, kCombMul>{});
 }
 
-template <int COMB>
-static int launch_bwd_input(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W, const float* H,
-                            const float* HN, float* t, float* gb, hipStream_t st) {
+// The forward of every form and mode.  The product form alone has the narrow kernel behind the MFMA widths (not with
+// the deferred rows); `what` names the entry in the error.
+static int dense_dispatch(const char* what, int form, bool bi2, int64_t n_rows, int d_in, int d_out, const float* H,
+                          const float* HN, const float* W1, const float* W2, float negative_slope, const DropArgs& dr,
+                          float* h_out, uint8_t* signs, float* norm_out, int64_t norm_stride, hipStream_t st, int mode,
+                          const EgoCopy ego, const DeferredRows* defer) {
+  int rc = with_comb(form, bi2, [&](auto comb) {
+    return dispatch_widths(MfmaWidths{}, d_in, d_out, [&](auto di, auto dout) {
+      return launch_dense<decltype(di)::value, decltype(dout)::value, decltype(comb)::value>(
+          n_rows, H, HN, W1, W2, negative_slope, dr, h_out, signs, norm_out,
+          norm_stride, st, mode, ego, defer);
+    });
+  });
+  if (rc == KGAT_E_UNSUPPORTED && !bi2 && form == KGAT_FORM_BI && defer == nullptr)
+    rc = dispatch_widths(SmallWidths{}, d_in, d_out, [&](auto di, auto dout) {
+      return launch_bi_small<decltype(di)::value, decltype(dout)::value>(n_rows, H, HN, W2, negative_slope, dr, h_out,
+                                                                         norm_out, norm_stride, st, mode, ego);
+    });
+  if (rc == KGAT_E_UNSUPPORTED) set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
+  return rc;
+}
+
+static int bwd_input_dispatch(const char* what, int form, bool bi2, int64_t n_rows, int d_in, int d_out, const float* gz1,
+                              const float* gz2, const float* W1, const float* W2, const float* H, const float* HN,
+                              float* t, float* gb, hipStream_t st) {
   const int64_t tiles = (n_rows + 15) / 16;
   int64_t blocks = (tiles + 3) / 4;
-  if (blocks > 512) blocks = 512;
-#define KGAT_BWD_CASE(DK, DN)                                                                                         \
-  if (d_out == DK && d_in == DN) {                                                                                    \
-    hipLaunchKernelGGL((bi_bwd_input_kernel<DK, DN, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,                 \
-                       (int32_t)n_rows, grad_z, W, H, HN, t, gb);                                                     \
-    KGAT_CHECK_LAUNCH("bi_bwd_input");                                                                                \
-    return KGAT_OK;                                                                                                   \
-  }
-  KGAT_BWD_CASE(16, 16) KGAT_BWD_CASE(16, 32) KGAT_BWD_CASE(16, 64) KGAT_BWD_CASE(16, 128)
-  KGAT_BWD_CASE(32, 16) KGAT_BWD_CASE(32, 32) KGAT_BWD_CASE(32, 64) KGAT_BWD_CASE(32, 128)
-  KGAT_BWD_CASE(64, 16) KGAT_BWD_CASE(64, 32) KGAT_BWD_CASE(64, 64) KGAT_BWD_CASE(64, 128)
-  KGAT_BWD_CASE(128, 16) KGAT_BWD_CASE(128, 32) KGAT_BWD_CASE(128, 64) KGAT_BWD_CASE(128, 128)
-#undef KGAT_BWD_CASE
-  set_error("bi_interaction_bwd_input: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  if (blocks > 512) blocks = 512;  // (as launch_dense)
+  const int rc = with_comb(form, bi2, [&](auto comb) {
+    return dispatch_widths(MfmaWidths{}, d_out, d_in, [&](auto dk, auto dn) -> int {
+      constexpr int DK = decltype(dk)::value, DN = decltype(dn)::value, COMB = decltype(comb)::value;
+      if constexpr (COMB == kCombBi2)
+        hipLaunchKernelGGL((bi2_bwd_input_kernel<DK, DN>), dim3((unsigned)blocks), dim3(256), 0, st, (int32_t)n_rows,
+                           gz1, gz2, W1, W2, H, HN, t, gb);
+      else
+        hipLaunchKernelGGL((bi_bwd_input_kernel<DK, DN, COMB>), dim3((unsigned)blocks), dim3(256), 0, st,
+                           (int32_t)n_rows, gz1, W1, H, HN, t, gb);
+      KGAT_CHECK_LAUNCH(what);
+      return KGAT_OK;
+    });
+  });
+  if (rc == KGAT_E_UNSUPPORTED) set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
+  return rc;
 }
 
-static int launch_bi2_bwd_input(int64_t n_rows, int d_in, int d_out, const float* gz1, const float* gz2, const float* W1,
-                                const float* W2, const float* H, const float* HN, float* t, float* gb, hipStream_t st) {
-  const int64_t tiles = (n_rows + 15) / 16;
-  int64_t blocks = (tiles + 3) / 4;
-  if (blocks > 512) blocks = 512;
-#define KGAT_BI2_BWD_CASE(DK, DN)                                                                                      \
-  if (d_out == DK && d_in == DN) {                                                                                    \
-    hipLaunchKernelGGL((bi2_bwd_input_kernel<DK, DN>), dim3((unsigned)blocks), dim3(256), 0, st, (int32_t)n_rows, gz1, \
-                       gz2, W1, W2, H, HN, t, gb);                                                                    \
-    KGAT_CHECK_LAUNCH("bi2_bwd_input");                                                                               \
-    return KGAT_OK;                                                                                                   \
-  }
-  KGAT_BI2_BWD_CASE(16, 16) KGAT_BI2_BWD_CASE(16, 32) KGAT_BI2_BWD_CASE(16, 64) KGAT_BI2_BWD_CASE(16, 128)
-  KGAT_BI2_BWD_CASE(32, 16) KGAT_BI2_BWD_CASE(32, 32) KGAT_BI2_BWD_CASE(32, 64) KGAT_BI2_BWD_CASE(32, 128)
-  KGAT_BI2_BWD_CASE(64, 16) KGAT_BI2_BWD_CASE(64, 32) KGAT_BI2_BWD_CASE(64, 64) KGAT_BI2_BWD_CASE(64, 128)
-  KGAT_BI2_BWD_CASE(128, 16) KGAT_BI2_BWD_CASE(128, 32) KGAT_BI2_BWD_CASE(128, 64) KGAT_BI2_BWD_CASE(128, 128)
-#undef KGAT_BI2_BWD_CASE
-  set_error("bi2_bwd_input: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
-}
-
-static int launch_bi2_bwd_weight(int64_t n_rows, int d_in, int d_out, const float* gz1, const float* gz2, const float* H,
-                                 const float* HN, float* partials1, float* partials2, int64_t n_partials, hipStream_t st) {
-#define KGAT_BI2_BWW_CASE(DO_, DI_)                                                                                    \
-  if (d_out == DO_ && d_in == DI_) {                                                                                  \
-    hipLaunchKernelGGL((bi2_bwd_weight_kernel<DO_, DI_>), dim3((unsigned)n_partials), dim3(256), 0, st,               \
-                       (int32_t)n_rows, gz1, gz2, H, HN, partials1, partials2);                                       \
-    KGAT_CHECK_LAUNCH("bi2_bwd_weight");                                                                              \
-    return KGAT_OK;                                                                                                   \
-  }
-  KGAT_BI2_BWW_CASE(16, 16) KGAT_BI2_BWW_CASE(16, 32) KGAT_BI2_BWW_CASE(16, 64) KGAT_BI2_BWW_CASE(16, 128)
-  KGAT_BI2_BWW_CASE(32, 16) KGAT_BI2_BWW_CASE(32, 32) KGAT_BI2_BWW_CASE(32, 64) KGAT_BI2_BWW_CASE(32, 128)
-  KGAT_BI2_BWW_CASE(64, 16) KGAT_BI2_BWW_CASE(64, 32) KGAT_BI2_BWW_CASE(64, 64) KGAT_BI2_BWW_CASE(64, 128)
-  KGAT_BI2_BWW_CASE(128, 16) KGAT_BI2_BWW_CASE(128, 32) KGAT_BI2_BWW_CASE(128, 64) KGAT_BI2_BWW_CASE(128, 128)
-#undef KGAT_BI2_BWW_CASE
-  set_error("bi2_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
-}
-
-template <int COMB>
-static int launch_bwd_weight(int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H, const float* HN,
-                             float* partials, int64_t n_partials, hipStream_t st) {
-#define KGAT_BWW_CASE(DO_, DI_)                                                                                        \
-  if (d_out == DO_ && d_in == DI_) {                                                                                  \
-    hipLaunchKernelGGL((bi_bwd_weight_kernel<DO_, DI_, COMB>), dim3((unsigned)n_partials), dim3(256), 0, st,          \
-                       (int32_t)n_rows, grad_z, H, HN, partials);                                                     \
-    KGAT_CHECK_LAUNCH("bi_bwd_weight");                                                                               \
-    return KGAT_OK;                                                                                                   \
-  }
-  KGAT_BWW_CASE(16, 16) KGAT_BWW_CASE(16, 32) KGAT_BWW_CASE(16, 64) KGAT_BWW_CASE(16, 128)
-  KGAT_BWW_CASE(32, 16) KGAT_BWW_CASE(32, 32) KGAT_BWW_CASE(32, 64) KGAT_BWW_CASE(32, 128)
-  KGAT_BWW_CASE(64, 16) KGAT_BWW_CASE(64, 32) KGAT_BWW_CASE(64, 64) KGAT_BWW_CASE(64, 128)
-  KGAT_BWW_CASE(128, 16) KGAT_BWW_CASE(128, 32) KGAT_BWW_CASE(128, 64) KGAT_BWW_CASE(128, 128)
-#undef KGAT_BWW_CASE
-  set_error("bi_interaction_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+static int bwd_weight_dispatch(const char* what, int form, bool bi2, int64_t n_rows, int d_in, int d_out,
+                               const float* gz1, const float* gz2, const float* H, const float* HN, float* partials1,
+                               float* partials2, int64_t n_partials, hipStream_t st) {
+  const int rc = with_comb(form, bi2, [&](auto comb) {
+    return dispatch_widths(MfmaWidths{}, d_out, d_in, [&](auto dout, auto di) -> int {
+      constexpr int DO = decltype(dout)::value, DI = decltype(di)::value, COMB = decltype(comb)::value;
+      if constexpr (COMB == kCombBi2)
+        hipLaunchKernelGGL((bi2_bwd_weight_kernel<DO, DI>), dim3((unsigned)n_partials), dim3(256), 0, st,
+                           (int32_t)n_rows, gz1, gz2, H, HN, partials1, partials2);
+      else
+        hipLaunchKernelGGL((bi_bwd_weight_kernel<DO, DI, COMB>), dim3((unsigned)n_partials), dim3(256), 0, st,
+                           (int32_t)n_rows, gz1, H, HN, partials1);
+      KGAT_CHECK_LAUNCH(what);
+      return KGAT_OK;
+    });
+  });
+  if (rc == KGAT_E_UNSUPPORTED) set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
+  return rc;
 }
 
 }  // namespace kgat
@@ -989,90 +933,99 @@ int kgat_readout_concat_f32(int64_t n_rows, int n_blocks, const float* const* bl
   return KGAT_OK;
 }
 
-int kgat_bi_interaction_supported(int d_in, int d_out) {
+static bool mfma_widths(int d_in, int d_out) {
   auto ok = [](int d) { return d == 16 || d == 32 || d == 64 || d == 128; };
+  return ok(d_in) && ok(d_out);
+}
+
+int kgat_bi_interaction_supported(int d_in, int d_out) {
   auto narrow = [](int d) { return d == 4 || d == 8; };
   auto small = [](int d) { return d == 4 || d == 8 || d == 16 || d == 32; };
-  return (ok(d_in) && ok(d_out)) || (narrow(d_in) && small(d_out)) || (small(d_in) && narrow(d_out));
-}
-
-static int bi_dispatch(int64_t n_rows, int d_in, int d_out, const float* P, const float* HN, const float* W2,
-                       float negative_slope, const DropArgs& dr, float* h_out, float* norm_out,
-                       int64_t norm_stride, hipStream_t st, int mode, const EgoCopy ego = EgoCopy{nullptr, 0},
-                       const DeferredRows* defer = nullptr) {
-#define KGAT_BI_CASE(DI, DO) \
-  if (d_in == DI && d_out == DO) \
-    return launch_bi<DI, DO>(n_rows, P, HN, W2, negative_slope, dr, h_out, norm_out, norm_stride, st, mode, ego, defer);
-  KGAT_BI_CASE(16, 16) KGAT_BI_CASE(16, 32) KGAT_BI_CASE(16, 64) KGAT_BI_CASE(16, 128)
-  KGAT_BI_CASE(32, 16) KGAT_BI_CASE(32, 32) KGAT_BI_CASE(32, 64) KGAT_BI_CASE(32, 128)
-  KGAT_BI_CASE(64, 16) KGAT_BI_CASE(64, 32) KGAT_BI_CASE(64, 64) KGAT_BI_CASE(64, 128)
-  KGAT_BI_CASE(128, 16) KGAT_BI_CASE(128, 32) KGAT_BI_CASE(128, 64) KGAT_BI_CASE(128, 128)
-#undef KGAT_BI_CASE
-  if (defer != nullptr) {
-    set_error("bi_interaction_mul_deferred: widths %d -> %d are outside the MFMA kernel's {16, 32, 64, 128}", d_in, d_out);
-    return KGAT_E_UNSUPPORTED;
-  }
-#define KGAT_BI_SMALL(DI, DO) \
-  if (d_in == DI && d_out == DO) \
-    return launch_bi_small<DI, DO>(n_rows, P, HN, W2, negative_slope, dr, h_out, norm_out, norm_stride, st, mode, ego);
-  KGAT_BI_SMALL(4, 4) KGAT_BI_SMALL(4, 8) KGAT_BI_SMALL(4, 16) KGAT_BI_SMALL(4, 32)
-  KGAT_BI_SMALL(8, 4) KGAT_BI_SMALL(8, 8) KGAT_BI_SMALL(8, 16) KGAT_BI_SMALL(8, 32)
-  KGAT_BI_SMALL(16, 4) KGAT_BI_SMALL(16, 8) KGAT_BI_SMALL(32, 4) KGAT_BI_SMALL(32, 8)
-#undef KGAT_BI_SMALL
-  set_error("bi_interaction: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
-}
-
-// form (KGAT_FORM_*) -> the kernels: KGAT_FORM_BI is bi_dispatch itself
-static int form_dispatch(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W,
-                         float negative_slope, const DropArgs& dr, float* h_out, float* norm_out, int64_t norm_stride,
-                         hipStream_t st, int mode, const EgoCopy ego, const DeferredRows* defer = nullptr) {
-  if (form == KGAT_FORM_GCN)
-    return comb_dispatch<kCombSum>(n_rows, d_in, d_out, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st,
-                                   mode, ego, defer);
-  if (form == KGAT_FORM_GRAPHSAGE)
-    return comb_dispatch<kCombCat>(n_rows, d_in, d_out, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st,
-                                   mode, ego, defer);
-  return bi_dispatch(n_rows, d_in, d_out, H, HN, W, negative_slope, dr, h_out, norm_out, norm_stride, st, mode, ego, defer);
+  return mfma_widths(d_in, d_out) || (narrow(d_in) && small(d_out)) || (small(d_in) && narrow(d_out));
 }
 
 int kgat_aggregator_supported(int form, int d_in, int d_out) {
-  auto ok = [](int d) { return d == 16 || d == 32 || d == 64 || d == 128; };
   if (form == KGAT_FORM_BI) return kgat_bi_interaction_supported(d_in, d_out);
-  return (form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) && ok(d_in) && ok(d_out);
+  return (form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) && mfma_widths(d_in, d_out);
 }
+
+int kgat_bi2_supported(int d_in, int d_out) { return mfma_widths(d_in, d_out); }
+
+// ---- the argument checks the entries of both families share (`what` names the entry in the message)
+// the forward entries: 1 = nothing to do (no rows).  `inputs`: H, HN and the weight(s) are there
+static int check_forward(const char* what, bool supported, int64_t n_rows, int d_in, int d_out, bool inputs,
+                         const float* h_out, const float* norm_out, int64_t norm_stride, const float* self_out,
+                         int64_t self_stride, bool need_h_out) {
+  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "%s: bad row count", what);
+  if (n_rows == 0) return 1;
+  KGAT_CHECK_ARG(inputs && (h_out || (norm_out && !need_h_out)), "%s: null pointer", what);
+  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "%s: bad norm_stride", what);
+  KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
+                                         (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
+                 "%s: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in", what);
+  if (!supported) {
+    set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
+    return KGAT_E_UNSUPPORTED;
+  }
+  return KGAT_OK;
+}
+
+// the dropout arguments of the training entries and the backward heads: the hash takes a 32-bit element index
+static int check_dropout(const char* what, int64_t n_rows, int d_out, int64_t row0, float drop_p) {
+  KGAT_CHECK_ARG(n_rows >= 0 && row0 >= 0 && d_out > 0 && (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32),
+                 "%s: bad row count", what);
+  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "%s: dropout probability outside [0, 1)", what);
+  return KGAT_OK;
+}
+
+// the deferred-rows arguments -> DeferredRows
+static int check_deferred(const char* what, const int32_t* indptr_rows, int64_t e_begin, int64_t e_end,
+                          const void* spmm_workspace, int tile_edges, DeferredRows* df) {
+  KGAT_CHECK_ARG(indptr_rows != nullptr, "%s: null pointer", what);
+  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "%s: bad edge range", what);
+  KGAT_CHECK_ARG(e_end == e_begin || spmm_workspace != nullptr, "%s: null workspace", what);
+  KGAT_CHECK_ARG(tile_edges > 0 && (tile_edges & (tile_edges - 1)) == 0,
+                 "%s: tile_edges must be kgat_spmm_tile_edges() of the aggregation (a power of two)", what);
+  int shift = 0;
+  while ((1 << shift) < tile_edges) ++shift;
+  *df = DeferredRows{indptr_rows, static_cast<const float4*>(spmm_workspace), (int32_t)e_begin, (int32_t)e_end, shift};
+  return KGAT_OK;
+}
+
+// the two backward entries: the row count, the widths, then the entry's own pointers
+static int check_backward(const char* what, bool supported, int64_t n_rows, int d_in, int d_out) {
+  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "%s: bad row count", what);
+  if (!supported) {
+    set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
+    return KGAT_E_UNSUPPORTED;
+  }
+  return KGAT_OK;
+}
+
+#define KGAT_RETURN_IF(rc_expr)                    \
+  do {                                             \
+    const int rc__ = (rc_expr);                    \
+    if (rc__ != KGAT_OK) return rc__ > 0 ? KGAT_OK : rc__; \
+  } while (0)
 
 int kgat_bi_interaction_f32(int64_t n_rows, int d_in, int d_out, const float* P, const float* W2,
                             float negative_slope, float* h_out, float* norm_out,
                             int64_t norm_stride, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction: bad row count");
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(P && W2 && (h_out || norm_out), "bi_interaction: null pointer");
-  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "bi_interaction: bad norm_stride");
-  if (!kgat_bi_interaction_supported(d_in, d_out)) {
-    set_error("bi_interaction: unsupported widths %d -> %d", d_in, d_out);
-    return KGAT_E_UNSUPPORTED;
-  }
-  return bi_dispatch(n_rows, d_in, d_out, P, nullptr, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
-                     as_stream(stream), 0);
+  KGAT_RETURN_IF(check_forward("bi_interaction", kgat_bi_interaction_supported(d_in, d_out), n_rows, d_in, d_out, P && W2,
+                               h_out, norm_out, norm_stride, nullptr, 0, false));
+  return dense_dispatch("bi_interaction", KGAT_FORM_BI, false, n_rows, d_in, d_out, P, nullptr, nullptr, W2,
+                        negative_slope, DropArgs(), h_out, nullptr, norm_out, norm_stride, as_stream(stream), 0,
+                        EgoCopy{nullptr, 0}, nullptr);
 }
 
 int kgat_aggregator_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W2,
                         float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
                         int64_t self_stride, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_mul: bad row count");
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(H && HN && W2 && (h_out || norm_out), "bi_interaction_mul: null pointer");
-  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "bi_interaction_mul: bad norm_stride");
-  KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
-                                         (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
-                 "bi_interaction_mul: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
-  if (!kgat_aggregator_supported(form, d_in, d_out)) {
-    set_error("bi_interaction_mul: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
-    return KGAT_E_UNSUPPORTED;
-  }
-  return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
-                       as_stream(stream), 1, EgoCopy{self_out, self_stride});
+  KGAT_RETURN_IF(check_forward("aggregator", kgat_aggregator_supported(form, d_in, d_out), n_rows, d_in, d_out,
+                               H && HN && W2, h_out, norm_out, norm_stride, self_out, self_stride, false));
+  return dense_dispatch("aggregator", form, false, n_rows, d_in, d_out, H, HN, nullptr, W2, negative_slope, DropArgs(),
+                        h_out, nullptr, norm_out, norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride},
+                        nullptr);
 }
 
 int kgat_aggregator_deferred_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
@@ -1081,184 +1034,168 @@ int kgat_aggregator_deferred_f32(int form, int64_t n_rows, int d_in, int d_out, 
                                  int64_t e_begin, int64_t e_end, const void* spmm_workspace, int tile_edges,
                                  kgat_stream_t stream) {
   KGAT_CHECK_ARG(form == KGAT_FORM_BI || form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE,
-                 "bi_interaction_mul_deferred: unknown form %d", form);
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_mul_deferred: bad row count");
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(H && HN && W2 && (h_out || norm_out) && indptr_rows, "bi_interaction_mul_deferred: null pointer");
-  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "bi_interaction_mul_deferred: bad edge range");
-  KGAT_CHECK_ARG(e_end == e_begin || spmm_workspace != nullptr, "bi_interaction_mul_deferred: null workspace");
-  KGAT_CHECK_ARG(tile_edges > 0 && (tile_edges & (tile_edges - 1)) == 0,
-                 "bi_interaction_mul_deferred: tile_edges must be kgat_spmm_tile_edges() of the aggregation (a power of two)");
-  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "bi_interaction_mul_deferred: bad norm_stride");
-  KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
-                                         (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
-                 "bi_interaction_mul_deferred: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
-  int shift = 0;
-  while ((1 << shift) < tile_edges) ++shift;
-  const DeferredRows df{indptr_rows, static_cast<const float4*>(spmm_workspace), (int32_t)e_begin, (int32_t)e_end, shift};
-  return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, DropArgs(), h_out, norm_out, norm_stride,
-                       as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
+                 "aggregator_deferred: unknown form %d", form);
+  // (the narrow kernel has no deferred form: the MFMA widths only)
+  KGAT_RETURN_IF(check_forward("aggregator_deferred", mfma_widths(d_in, d_out), n_rows, d_in, d_out, H && HN && W2, h_out,
+                               norm_out, norm_stride, self_out, self_stride, false));
+  DeferredRows df;
+  KGAT_RETURN_IF(check_deferred("aggregator_deferred", indptr_rows, e_begin, e_end, spmm_workspace, tile_edges, &df));
+  return dense_dispatch("aggregator_deferred", form, false, n_rows, d_in, d_out, H, HN, nullptr, W2, negative_slope,
+                        DropArgs(), h_out, nullptr, norm_out, norm_stride, as_stream(stream), 1,
+                        EgoCopy{self_out, self_stride}, &df);
 }
 
 int kgat_aggregator_train_f32(int form, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
                               const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0,
                               float* h_out, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
                               kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX && row0 >= 0 &&
-                     (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32),
-                 "bi_interaction_train: bad row count");
-  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "bi_interaction_train: dropout probability outside [0, 1)");
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(H && HN && W2 && h_out, "bi_interaction_train: null pointer");
-  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "bi_interaction_train: bad norm_stride");
-  if (!kgat_aggregator_supported(form, d_in, d_out)) {
-    set_error("bi_interaction_train: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
-    return KGAT_E_UNSUPPORTED;
-  }
-  KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
-                                         (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
-                 "bi_interaction_train: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
-  return form_dispatch(form, n_rows, d_in, d_out, H, HN, W2, negative_slope, drop_args(drop_p, seed, row0, d_out), h_out,
-                       norm_out, norm_stride, as_stream(stream), 2, EgoCopy{self_out, self_stride});
+  KGAT_RETURN_IF(check_dropout("aggregator_train", n_rows, d_out, row0, drop_p));
+  KGAT_RETURN_IF(check_forward("aggregator_train", kgat_aggregator_supported(form, d_in, d_out), n_rows, d_in, d_out,
+                               H && HN && W2, h_out, norm_out, norm_stride, self_out, self_stride, true));
+  return dense_dispatch("aggregator_train", form, false, n_rows, d_in, d_out, H, HN, nullptr, W2, negative_slope,
+                        drop_args(drop_p, seed, row0, d_out), h_out, nullptr, norm_out, norm_stride, as_stream(stream), 2,
+                        EgoCopy{self_out, self_stride}, nullptr);
 }
 
 // ---- the two-term Bi-Interaction ("Bi2"): entries of their own (two weights, the sign record)
-int kgat_bi2_supported(int d_in, int d_out) {
-  auto ok = [](int d) { return d == 16 || d == 32 || d == 64 || d == 128; };
-  return ok(d_in) && ok(d_out);
-}
-
 int kgat_bi2_bwd_supported(int d_in, int d_out) { return kgat_bi2_supported(d_in, d_out); }
-
-static int bi2_dispatch(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
-                        const float* W2, float negative_slope, const DropArgs& dr, float* h_out, uint8_t* signs,
-                        float* norm_out, int64_t norm_stride, hipStream_t st, int mode, const EgoCopy ego,
-                        const DeferredRows* defer) {
-#define KGAT_BI2_CASE(DI, DO) \
-  if (d_in == DI && d_out == DO) \
-    return launch_bi2<DI, DO>(n_rows, H, HN, W1, W2, negative_slope, dr, h_out, signs, norm_out, norm_stride, st, mode, ego, defer);
-  KGAT_BI2_CASE(16, 16) KGAT_BI2_CASE(16, 32) KGAT_BI2_CASE(16, 64) KGAT_BI2_CASE(16, 128)
-  KGAT_BI2_CASE(32, 16) KGAT_BI2_CASE(32, 32) KGAT_BI2_CASE(32, 64) KGAT_BI2_CASE(32, 128)
-  KGAT_BI2_CASE(64, 16) KGAT_BI2_CASE(64, 32) KGAT_BI2_CASE(64, 64) KGAT_BI2_CASE(64, 128)
-  KGAT_BI2_CASE(128, 16) KGAT_BI2_CASE(128, 32) KGAT_BI2_CASE(128, 64) KGAT_BI2_CASE(128, 128)
-#undef KGAT_BI2_CASE
-  set_error("bi2: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
-}
-
-// the checks the three forward entries share; 1 = nothing to do (no rows)
-static int bi2_check_forward(const char* what, int64_t n_rows, int d_in, int d_out, const float* H, const float* HN,
-                             const float* W1, const float* W2, const float* h_out, const float* norm_out,
-                             int64_t norm_stride, const float* self_out, int64_t self_stride, bool need_h_out) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "%s: bad row count", what);
-  if (n_rows == 0) return 1;
-  KGAT_CHECK_ARG(H && HN && W1 && W2 && (h_out || (norm_out && !need_h_out)), "%s: null pointer", what);
-  KGAT_CHECK_ARG(norm_out == nullptr || norm_stride >= d_out, "%s: bad norm_stride", what);
-  KGAT_CHECK_ARG(self_out == nullptr || (self_stride >= d_in && self_stride % 4 == 0 &&
-                                         (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0),
-                 "%s: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in", what);
-  if (!kgat_bi2_supported(d_in, d_out)) {
-    set_error("%s: unsupported widths %d -> %d", what, d_in, d_out);
-    return KGAT_E_UNSUPPORTED;
-  }
-  return KGAT_OK;
-}
 
 int kgat_bi2_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1, const float* W2,
                  float negative_slope, float* h_out, float* norm_out, int64_t norm_stride, float* self_out,
                  int64_t self_stride, kgat_stream_t stream) {
-  const int rc = bi2_check_forward("bi2", n_rows, d_in, d_out, H, HN, W1, W2, h_out, norm_out, norm_stride, self_out,
-                                   self_stride, false);
-  if (rc != KGAT_OK) return rc > 0 ? KGAT_OK : rc;
-  return bi2_dispatch(n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, DropArgs(), h_out, nullptr, norm_out,
-                      norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride}, nullptr);
+  KGAT_RETURN_IF(check_forward("bi2", kgat_bi2_supported(d_in, d_out), n_rows, d_in, d_out, H && HN && W1 && W2, h_out,
+                               norm_out, norm_stride, self_out, self_stride, false));
+  return dense_dispatch("bi2", 0, true, n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, DropArgs(), h_out, nullptr,
+                        norm_out, norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride}, nullptr);
 }
 
 int kgat_bi2_deferred_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
                           const float* W2, float negative_slope, float* h_out, float* norm_out, int64_t norm_stride,
                           float* self_out, int64_t self_stride, const int32_t* indptr_rows, int64_t e_begin,
                           int64_t e_end, const void* spmm_workspace, int tile_edges, kgat_stream_t stream) {
-  const int rc = bi2_check_forward("bi2_deferred", n_rows, d_in, d_out, H, HN, W1, W2, h_out, norm_out, norm_stride,
-                                   self_out, self_stride, false);
-  if (rc != KGAT_OK) return rc > 0 ? KGAT_OK : rc;
-  KGAT_CHECK_ARG(indptr_rows != nullptr, "bi2_deferred: null pointer");
-  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "bi2_deferred: bad edge range");
-  KGAT_CHECK_ARG(e_end == e_begin || spmm_workspace != nullptr, "bi2_deferred: null workspace");
-  KGAT_CHECK_ARG(tile_edges > 0 && (tile_edges & (tile_edges - 1)) == 0,
-                 "bi2_deferred: tile_edges must be kgat_spmm_tile_edges() of the aggregation (a power of two)");
-  int shift = 0;
-  while ((1 << shift) < tile_edges) ++shift;
-  const DeferredRows df{indptr_rows, static_cast<const float4*>(spmm_workspace), (int32_t)e_begin, (int32_t)e_end, shift};
-  return bi2_dispatch(n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, DropArgs(), h_out, nullptr, norm_out,
-                      norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
+  KGAT_RETURN_IF(check_forward("bi2_deferred", kgat_bi2_supported(d_in, d_out), n_rows, d_in, d_out, H && HN && W1 && W2,
+                               h_out, norm_out, norm_stride, self_out, self_stride, false));
+  DeferredRows df;
+  KGAT_RETURN_IF(check_deferred("bi2_deferred", indptr_rows, e_begin, e_end, spmm_workspace, tile_edges, &df));
+  return dense_dispatch("bi2_deferred", 0, true, n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, DropArgs(), h_out,
+                        nullptr, norm_out, norm_stride, as_stream(stream), 1, EgoCopy{self_out, self_stride}, &df);
 }
 
 int kgat_bi2_train_f32(int64_t n_rows, int d_in, int d_out, const float* H, const float* HN, const float* W1,
                        const float* W2, float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* h_out,
                        uint8_t* signs, float* norm_out, int64_t norm_stride, float* self_out, int64_t self_stride,
                        kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && row0 >= 0 && d_out > 0 && (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32),
-                 "bi2_train: bad row count");
-  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "bi2_train: dropout probability outside [0, 1)");
-  const int rc = bi2_check_forward("bi2_train", n_rows, d_in, d_out, H, HN, W1, W2, h_out, norm_out, norm_stride,
-                                   self_out, self_stride, true);
-  if (rc != KGAT_OK) return rc > 0 ? KGAT_OK : rc;
+  KGAT_RETURN_IF(check_dropout("bi2_train", n_rows, d_out, row0, drop_p));
+  KGAT_RETURN_IF(check_forward("bi2_train", kgat_bi2_supported(d_in, d_out), n_rows, d_in, d_out, H && HN && W1 && W2,
+                               h_out, norm_out, norm_stride, self_out, self_stride, true));
   KGAT_CHECK_ARG(signs != nullptr && (reinterpret_cast<uintptr_t>(signs) & 3u) == 0,
                  "bi2_train: the sign record must be a 4-byte aligned buffer of n_rows * d_out bytes");
-  return bi2_dispatch(n_rows, d_in, d_out, H, HN, W1, W2, negative_slope, drop_args(drop_p, seed, row0, d_out), h_out,
-                      signs, norm_out, norm_stride, as_stream(stream), 2, EgoCopy{self_out, self_stride}, nullptr);
+  return dense_dispatch("bi2_train", 0, true, n_rows, d_in, d_out, H, HN, W1, W2, negative_slope,
+                        drop_args(drop_p, seed, row0, d_out), h_out, signs, norm_out, norm_stride, as_stream(stream), 2,
+                        EgoCopy{self_out, self_stride}, nullptr);
+}
+
+// Backward head of both families: `signs` and `grad_z2` are the two-term form's (two_terms)
+static int launch_bwd_pre(const char* what, bool two_terms, int64_t n_rows, int d_out, const float* h_out, const uint8_t* signs,
+                          const float* grad_a, const float* grad_b, const float* grad_norm, int64_t grad_norm_stride,
+                          float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* grad_z1,
+                          float* grad_z2, kgat_stream_t stream) {
+  KGAT_CHECK_ARG(d_out <= 128, "%s: bad size", what);
+  KGAT_RETURN_IF(check_dropout(what, n_rows, d_out, row0, drop_p));
+  if (n_rows == 0) return KGAT_OK;
+  KGAT_CHECK_ARG(h_out && grad_z1 && (!two_terms || (signs && grad_z2 && grad_z1 != grad_z2)), "%s: null pointer", what);
+  KGAT_CHECK_ARG(grad_norm == nullptr || grad_norm_stride >= d_out, "%s: bad stride", what);
+  const DropArgs dr = drop_args(drop_p, seed, row0, d_out);
+  int64_t blocks = (n_rows + 15) / 16;
+  if (blocks > 8192) blocks = 8192;
+  if (two_terms)
+    hipLaunchKernelGGL(bi2_bwd_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), n_rows, d_out, h_out,
+                       signs, grad_a, grad_b, grad_norm, grad_norm_stride, negative_slope, dr.threshold, dr.keep_scale,
+                       dr.seed, dr.index0, grad_z1, grad_z2);
+  else
+    hipLaunchKernelGGL(bi_bwd_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), n_rows, d_out, h_out,
+                       grad_a, grad_b, grad_norm, grad_norm_stride, negative_slope, dr.threshold, dr.keep_scale, dr.seed,
+                       dr.index0, grad_z1);
+  KGAT_CHECK_LAUNCH(what);
+  return KGAT_OK;
 }
 
 int kgat_bi2_bwd_pre_f32(int64_t n_rows, int d_out, const float* h_out, const uint8_t* signs, const float* grad_a,
                          const float* grad_b, const float* grad_norm, int64_t grad_norm_stride, float negative_slope,
                          float drop_p, uint64_t seed, int64_t row0, float* grad_z1, float* grad_z2,
                          kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && d_out > 0 && d_out <= 128 && row0 >= 0 &&
-                     (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32), "bi2_bwd_pre: bad size");
-  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "bi2_bwd_pre: dropout probability outside [0, 1)");
+  return launch_bwd_pre("bi2_bwd_pre", true, n_rows, d_out, h_out, signs, grad_a, grad_b, grad_norm, grad_norm_stride,
+                        negative_slope, drop_p, seed, row0, grad_z1, grad_z2, stream);
+}
+
+int kgat_bi_interaction_bwd_pre_f32(int64_t n_rows, int d_out, const float* h_out, const float* grad_a,
+                                    const float* grad_b, const float* grad_norm, int64_t grad_norm_stride,
+                                    float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* grad_z,
+                                    kgat_stream_t stream) {
+  return launch_bwd_pre("bi_interaction_bwd_pre", false, n_rows, d_out, h_out, nullptr, grad_a, grad_b, grad_norm,
+                        grad_norm_stride, negative_slope, drop_p, seed, row0, grad_z, nullptr, stream);
+}
+
+int kgat_bi_interaction_bwd_input_supported(int d_in, int d_out) { return mfma_widths(d_in, d_out); }
+
+int kgat_aggregator_bwd_supported(int form, int d_in, int d_out) {
+  return (form == KGAT_FORM_BI || form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) && mfma_widths(d_in, d_out);
+}
+
+int kgat_aggregator_bwd_input_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W,
+                                  const float* H, const float* HN, float* grad_agg, float* grad_self,
+                                  kgat_stream_t stream) {
+  KGAT_RETURN_IF(check_backward("aggregator_bwd_input", kgat_aggregator_bwd_supported(form, d_in, d_out), n_rows, d_in,
+                                d_out));
   if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(h_out && signs && grad_z1 && grad_z2 && grad_z1 != grad_z2, "bi2_bwd_pre: null pointer");
-  KGAT_CHECK_ARG(grad_norm == nullptr || grad_norm_stride >= d_out, "bi2_bwd_pre: bad stride");
-  const DropArgs dr = drop_args(drop_p, seed, row0, d_out);
-  int64_t blocks = (n_rows + 15) / 16;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(bi2_bwd_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), n_rows, d_out, h_out,
-                     signs, grad_a, grad_b, grad_norm, grad_norm_stride, negative_slope, dr.threshold, dr.keep_scale,
-                     dr.seed, dr.index0, grad_z1, grad_z2);
-  KGAT_CHECK_LAUNCH("bi2_bwd_pre");
-  return KGAT_OK;
+  KGAT_CHECK_ARG(grad_z && W && grad_agg && (form == KGAT_FORM_GCN || grad_self) && (form != KGAT_FORM_BI || (H && HN)),
+                 "aggregator_bwd_input: null pointer");
+  // (the sum and the concatenation read neither H nor HN; the sum writes grad_agg alone)
+  return bwd_input_dispatch("aggregator_bwd_input", form, false, n_rows, d_in, d_out, grad_z, nullptr, W, nullptr, H, HN,
+                            grad_agg, grad_self, as_stream(stream));
 }
 
 int kgat_bi2_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z1, const float* grad_z2,
                            const float* W1, const float* W2, const float* H, const float* HN, float* grad_agg,
                            float* grad_self, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi2_bwd_input: bad row count");
+  KGAT_RETURN_IF(check_backward("bi2_bwd_input", kgat_bi2_bwd_supported(d_in, d_out), n_rows, d_in, d_out));
   if (n_rows == 0) return KGAT_OK;
-  if (!kgat_bi2_bwd_supported(d_in, d_out)) {
-    set_error("bi2_bwd_input: unsupported widths %d -> %d", d_in, d_out);
-    return KGAT_E_UNSUPPORTED;
-  }
   KGAT_CHECK_ARG(grad_z1 && grad_z2 && W1 && W2 && H && HN && grad_agg && grad_self && grad_agg != grad_self,
                  "bi2_bwd_input: null pointer");
-  return launch_bi2_bwd_input(n_rows, d_in, d_out, grad_z1, grad_z2, W1, W2, H, HN, grad_agg, grad_self,
-                              as_stream(stream));
+  return bwd_input_dispatch("bi2_bwd_input", 0, true, n_rows, d_in, d_out, grad_z1, grad_z2, W1, W2, H, HN, grad_agg,
+                            grad_self, as_stream(stream));
+}
+
+int64_t kgat_bi_interaction_bwd_weight_partials(int64_t n_rows) {
+  int64_t nb = (n_rows + 63) / 64;
+  if (nb > 768) nb = 768;   // three workgroups per CU; each partial is d_out x d_in floats
+  return nb < 1 ? 1 : nb;
+}
+
+int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
+                                   const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream) {
+  KGAT_RETURN_IF(check_backward("aggregator_bwd_weight", kgat_aggregator_bwd_supported(form, d_in, d_out), n_rows, d_in,
+                                d_out));
+  KGAT_CHECK_ARG(n_partials == kgat_bi_interaction_bwd_weight_partials(n_rows),
+                 "aggregator_bwd_weight: n_partials must be kgat_bi_interaction_bwd_weight_partials(n_rows)");
+  KGAT_CHECK_ARG(partials != nullptr && (n_rows == 0 || (grad_z && H && HN)), "aggregator_bwd_weight: null pointer");
+  return bwd_weight_dispatch("aggregator_bwd_weight", form, false, n_rows, d_in, d_out, grad_z, nullptr, H, HN, partials,
+                             nullptr, n_partials, as_stream(stream));
 }
 
 int kgat_bi2_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_z1, const float* grad_z2,
                             const float* H, const float* HN, float* partials_w1, float* partials_w2, int64_t n_partials,
                             kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi2_bwd_weight: bad row count");
+  KGAT_RETURN_IF(check_backward("bi2_bwd_weight", kgat_bi2_bwd_supported(d_in, d_out), n_rows, d_in, d_out));
   KGAT_CHECK_ARG(n_partials == kgat_bi_interaction_bwd_weight_partials(n_rows),
                  "bi2_bwd_weight: n_partials must be kgat_bi_interaction_bwd_weight_partials(n_rows)");
   KGAT_CHECK_ARG(partials_w1 && partials_w2 && partials_w1 != partials_w2 &&
                      (n_rows == 0 || (grad_z1 && grad_z2 && H && HN)), "bi2_bwd_weight: null pointer");
-  if (!kgat_bi2_bwd_supported(d_in, d_out)) {
-    set_error("bi2_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
-    return KGAT_E_UNSUPPORTED;
-  }
-  return launch_bi2_bwd_weight(n_rows, d_in, d_out, grad_z1, grad_z2, H, HN, partials_w1, partials_w2, n_partials,
-                               as_stream(stream));
+  return bwd_weight_dispatch("bi2_bwd_weight", 0, true, n_rows, d_in, d_out, grad_z1, grad_z2, H, HN, partials_w1,
+                             partials_w2, n_partials, as_stream(stream));
 }
+
+#undef KGAT_RETURN_IF
 
 // out = a + b + c over n_rows x d (a: rows of a_stride floats - a column slice of a wider matrix; b, c, out contiguous)
 __global__ __launch_bounds__(256) void add3_rows_kernel(int64_t n4, int d4, int64_t a_stride4, const float4* __restrict__ a,
@@ -1287,79 +1224,6 @@ int kgat_add3_rows_f32(int64_t n_rows, int d, const float* a, int64_t a_stride, 
                      reinterpret_cast<const float4*>(c), reinterpret_cast<float4*>(out));
   KGAT_CHECK_LAUNCH("add3_rows");
   return KGAT_OK;
-}
-
-int kgat_bi_interaction_bwd_pre_f32(int64_t n_rows, int d_out, const float* h_out, const float* grad_a,
-                                    const float* grad_b, const float* grad_norm, int64_t grad_norm_stride,
-                                    float negative_slope, float drop_p, uint64_t seed, int64_t row0, float* grad_z,
-                                    kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && d_out > 0 && d_out <= 128 && row0 >= 0 &&
-                     (uint64_t)(row0 + n_rows) * (uint64_t)d_out < (1ull << 32),
-                 "bi_interaction_bwd_pre: bad size");
-  KGAT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "bi_interaction_bwd_pre: dropout probability outside [0, 1)");
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(h_out && grad_z, "bi_interaction_bwd_pre: null pointer");
-  KGAT_CHECK_ARG(grad_norm == nullptr || grad_norm_stride >= d_out, "bi_interaction_bwd_pre: bad stride");
-  const DropArgs dr = drop_args(drop_p, seed, row0, d_out);
-  int64_t blocks = (n_rows + 15) / 16;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(bi_bwd_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), n_rows, d_out, h_out,
-                     grad_a, grad_b, grad_norm, grad_norm_stride, negative_slope, dr.threshold, dr.keep_scale, dr.seed,
-                     dr.index0, grad_z);
-  KGAT_CHECK_LAUNCH("bi_bwd_pre");
-  return KGAT_OK;
-}
-
-int kgat_bi_interaction_bwd_input_supported(int d_in, int d_out) {
-  auto ok = [](int d) { return d == 16 || d == 32 || d == 64 || d == 128; };
-  return ok(d_in) && ok(d_out);
-}
-
-int kgat_aggregator_bwd_supported(int form, int d_in, int d_out) {
-  return (form == KGAT_FORM_BI || form == KGAT_FORM_GCN || form == KGAT_FORM_GRAPHSAGE) &&
-         kgat_bi_interaction_bwd_input_supported(d_in, d_out);
-}
-
-int kgat_aggregator_bwd_input_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* W,
-                                  const float* H, const float* HN, float* grad_agg, float* grad_self,
-                                  kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "aggregator_bwd_input: bad row count");
-  if (n_rows == 0) return KGAT_OK;
-  if (!kgat_aggregator_bwd_supported(form, d_in, d_out)) {
-    set_error("bi_interaction_bwd_input: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
-    return KGAT_E_UNSUPPORTED;
-  }
-  KGAT_CHECK_ARG(grad_z && W && grad_agg && (form == KGAT_FORM_GCN || grad_self) && (form != KGAT_FORM_BI || (H && HN)),
-                 "aggregator_bwd_input: null pointer");
-  if (form == KGAT_FORM_GCN)
-    return launch_bwd_input<kCombSum>(n_rows, d_in, d_out, grad_z, W, nullptr, nullptr, grad_agg, nullptr, as_stream(stream));
-  if (form == KGAT_FORM_GRAPHSAGE)
-    return launch_bwd_input<kCombCat>(n_rows, d_in, d_out, grad_z, W, nullptr, nullptr, grad_agg, grad_self,
-                                      as_stream(stream));
-  return launch_bwd_input<kCombMul>(n_rows, d_in, d_out, grad_z, W, H, HN, grad_agg, grad_self, as_stream(stream));
-}
-
-int64_t kgat_bi_interaction_bwd_weight_partials(int64_t n_rows) {
-  int64_t nb = (n_rows + 63) / 64;
-  if (nb > 768) nb = 768;   // three workgroups per CU; each partial is d_out x d_in floats
-  return nb < 1 ? 1 : nb;
-}
-
-int kgat_aggregator_bwd_weight_f32(int form, int64_t n_rows, int d_in, int d_out, const float* grad_z, const float* H,
-                                   const float* HN, float* partials, int64_t n_partials, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && n_rows < INT32_MAX, "bi_interaction_bwd_weight: bad row count");
-  KGAT_CHECK_ARG(n_partials == kgat_bi_interaction_bwd_weight_partials(n_rows),
-                 "bi_interaction_bwd_weight: n_partials must be kgat_bi_interaction_bwd_weight_partials(n_rows)");
-  KGAT_CHECK_ARG(partials != nullptr && (n_rows == 0 || (grad_z && H && HN)), "bi_interaction_bwd_weight: null pointer");
-  if (!kgat_aggregator_bwd_supported(form, d_in, d_out)) {
-    set_error("bi_interaction_bwd_weight: unsupported widths %d -> %d (form %d)", d_in, d_out, form);
-    return KGAT_E_UNSUPPORTED;
-  }
-  if (form == KGAT_FORM_GCN)
-    return launch_bwd_weight<kCombSum>(n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, as_stream(stream));
-  if (form == KGAT_FORM_GRAPHSAGE)
-    return launch_bwd_weight<kCombCat>(n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, as_stream(stream));
-  return launch_bwd_weight<kCombMul>(n_rows, d_in, d_out, grad_z, H, HN, partials, n_partials, as_stream(stream));
 }
 
 // out[s][e] = sum over the partials of set s, for up to four sets in ONE launch (the weight gradients of a stack's

@@ -6,8 +6,8 @@
 // norm_stride, ego, df (W1 and signs are read by the two-term form only).  No include guard: included twice.
   constexpr bool TRAIN = MODE == 2;
   constexpr bool BI2 = COMB == kCombBi2;
-  static_assert(!DEFER || (MODE == 1 && !kBiMulAtLoad), "the deferred rows go with the late product");
-  static_assert(COMB == kCombMul || (MODE >= 1 && !kBiMulAtLoad), "the sum and the concatenation need H and HN apart");
+  static_assert(!DEFER || MODE == 1, "the deferred rows go with the no-grad form");
+  static_assert(COMB == kCombMul || MODE >= 1, "the sum and the concatenation need H and HN apart");
   constexpr int KS = DI / 4, KT = DO / 16;
   constexpr int DIW = COMB == kCombCat ? 2 * DI : DI, KSW = (BI2 ? 2 * DI : DIW) / 4;  // W's columns, the staged k-steps
   // W2 is staged once per workgroup through LDS (coalesced 16-byte reads of the whole matrix),
@@ -72,9 +72,9 @@ constexpr int kBiWLdsAbove = 128;  // (A/B builds: 0 = fragments always from LDS
   // MODE >= 1: the rows of H and of HN are REQUESTED here and multiplied when the tile is computed (round 4, second
   // form).  The first form multiplied here, which put the waits for both row sets - one after the other, the ego
   // copy in between - into the load step: two exposed memory round trips per tile with nothing else of the
-  // wavefront in flight, and no overlap with the previous tile's matrix work whatever kBiPrefetch said
-  // (kBiMulAtLoad = true restores that form.)
-  constexpr bool LATE_MUL = MODE >= 1 && !kBiMulAtLoad;
+  // wavefront in flight, and no overlap with the previous tile's matrix work whatever kBiPrefetch said (round 4's
+  // A/B, NOTEBOOK.md; non-temporal loads of the rows lost theirs as well).
+  constexpr bool LATE_MUL = MODE >= 1;
 constexpr int kBiPrefetch = 2;
   constexpr int PF = KS * kBiPrefetch <= 64 ? kBiPrefetch : (64 / KS >= 2 ? 64 / KS : 2);  // <= 64 VGPRs of rows in flight (x 2 with HN)
   // DEFER: per stage, the offsets of the row this lane loads NEXT (requested one load step ahead), and what the load
@@ -94,7 +94,7 @@ constexpr int kBiPrefetch = 2;
     const float4* pa = reinterpret_cast<const float4*>(P + (size_t)ra * DI) + q;
 #pragma unroll
     for (int m = 0; m < DI / 16; ++m) {
-      const float4 v = ld_row4<(kBiNtLoads & 1) != 0>(pa + m * 4);
+      const float4 v = pa[m * 4];
       a[4 * m + 0] = v.x; a[4 * m + 1] = v.y; a[4 * m + 2] = v.z; a[4 * m + 3] = v.w;
     }
     if constexpr (LATE_MUL) {
@@ -115,22 +115,10 @@ constexpr int kBiPrefetch = 2;
       }
 #pragma unroll
       for (int m = 0; m < DI / 16; ++m) {
-        const float4 v = ld_row4<(kBiNtLoads & 2) != 0>(pb + m * 4);
+        const float4 v = pb[m * 4];
         b[4 * m + 0] = v.x; b[4 * m + 1] = v.y; b[4 * m + 2] = v.z; b[4 * m + 3] = v.w;
       }
       if constexpr (DEFER) row_offsets(t + PF, d);  // (clamped to the last row past the end)
-    } else if (MODE >= 1) {
-      if (MODE >= 1 && ego.out != nullptr && (t << 4) + i < n_rows) {
-        float4* pe = reinterpret_cast<float4*>(ego.out + (size_t)ra * ego.stride) + q;
-#pragma unroll
-        for (int m = 0; m < DI / 16; ++m) st_final4(pe + m * 4, make_float4(a[4 * m + 0], a[4 * m + 1], a[4 * m + 2], a[4 * m + 3]));
-      }
-      const float4* pb = reinterpret_cast<const float4*>(HN + (size_t)ra * DI) + q;
-#pragma unroll
-      for (int m = 0; m < DI / 16; ++m) {
-        const float4 v = ld_row4<(kBiNtLoads & 2) != 0>(pb + m * 4);
-        a[4 * m + 0] *= v.x; a[4 * m + 1] *= v.y; a[4 * m + 2] *= v.z; a[4 * m + 3] *= v.w;
-      }
     }
   };
   auto tile = [&](int32_t t, float (&a)[KS], float (&b)[LATE_MUL ? KS : 1], const int32_t nf, const int32_t bh, const int32_t slot) {

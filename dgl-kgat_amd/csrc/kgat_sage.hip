@@ -689,26 +689,21 @@ int kgat_sage_dense_f32(int64_t n_rows, int d_in, int d_out, const float* H, con
   const int64_t tiles = (n_rows + 15) / 16;
   int64_t blocks = (tiles + 3) / 4;
   if (blocks > 512) blocks = 512;
-#define KGAT_SAGE_CASE(DI_, DO_)                                                                                  \
-  if (d_in == DI_ && d_out == DO_) {                                                                             \
-    if (act == KGAT_ACT_RELU)                                                                                    \
-      hipLaunchKernelGGL((sage_dense_kernel<DI_, DO_, true>), dim3((unsigned)blocks), dim3(256), 0,              \
-                         as_stream(stream), (int32_t)n_rows, H, HN, W_self, W_neigh, b_self, b_neigh, h_out,     \
-                         norm_out, norm_stride, self_out, self_stride);                                          \
-    else                                                                                                         \
-      hipLaunchKernelGGL((sage_dense_kernel<DI_, DO_, false>), dim3((unsigned)blocks), dim3(256), 0,             \
-                         as_stream(stream), (int32_t)n_rows, H, HN, W_self, W_neigh, b_self, b_neigh, h_out,     \
-                         norm_out, norm_stride, self_out, self_stride);                                          \
-    KGAT_CHECK_LAUNCH("sage_dense");                                                                             \
-    return KGAT_OK;                                                                                              \
-  }
-  KGAT_SAGE_CASE(16, 16) KGAT_SAGE_CASE(16, 32) KGAT_SAGE_CASE(16, 64) KGAT_SAGE_CASE(16, 128)
-  KGAT_SAGE_CASE(32, 16) KGAT_SAGE_CASE(32, 32) KGAT_SAGE_CASE(32, 64) KGAT_SAGE_CASE(32, 128)
-  KGAT_SAGE_CASE(64, 16) KGAT_SAGE_CASE(64, 32) KGAT_SAGE_CASE(64, 64) KGAT_SAGE_CASE(64, 128)
-  KGAT_SAGE_CASE(128, 16) KGAT_SAGE_CASE(128, 32) KGAT_SAGE_CASE(128, 64) KGAT_SAGE_CASE(128, 128)
-#undef KGAT_SAGE_CASE
-  set_error("sage_dense: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  const int rc = dispatch_widths(MfmaWidths{}, d_in, d_out, [&](auto di, auto dout) -> int {
+    constexpr int DI = decltype(di)::value, DO = decltype(dout)::value;
+    if (act == KGAT_ACT_RELU)
+      hipLaunchKernelGGL((sage_dense_kernel<DI, DO, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
+                         (int32_t)n_rows, H, HN, W_self, W_neigh, b_self, b_neigh, h_out, norm_out, norm_stride,
+                         self_out, self_stride);
+    else
+      hipLaunchKernelGGL((sage_dense_kernel<DI, DO, false>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
+                         (int32_t)n_rows, H, HN, W_self, W_neigh, b_self, b_neigh, h_out, norm_out, norm_stride,
+                         self_out, self_stride);
+    KGAT_CHECK_LAUNCH("sage_dense");
+    return KGAT_OK;
+  });
+  if (rc == KGAT_E_UNSUPPORTED) set_error("sage_dense: unsupported widths %d -> %d", d_in, d_out);
+  return rc;
 }
 
 int kgat_dropout_rows_f32(int64_t n_rows, int d, const float* x, const float* x2, float drop_p, uint64_t seed,
@@ -746,20 +741,15 @@ int kgat_sage_bwd_input_f32(int64_t n_rows, int d_in, int d_out, const float* gr
   const int64_t tiles = (n_rows + 15) / 16;
   int64_t blocks = (tiles + 3) / 4;
   if (blocks > 512) blocks = 512;
-#define KGAT_SBI_CASE(DI_, DO_)                                                                                   \
-  if (d_in == DI_ && d_out == DO_) {                                                                             \
-    hipLaunchKernelGGL((sage_bwd_input_kernel<DI_, DO_>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), \
-                       (int32_t)n_rows, grad_pre, W_self, W_neigh, indptr, grad_self, grad_agg);                \
-    KGAT_CHECK_LAUNCH("sage_bwd_input");                                                                         \
-    return KGAT_OK;                                                                                              \
-  }
-  KGAT_SBI_CASE(16, 16) KGAT_SBI_CASE(16, 32) KGAT_SBI_CASE(16, 64) KGAT_SBI_CASE(16, 128)
-  KGAT_SBI_CASE(32, 16) KGAT_SBI_CASE(32, 32) KGAT_SBI_CASE(32, 64) KGAT_SBI_CASE(32, 128)
-  KGAT_SBI_CASE(64, 16) KGAT_SBI_CASE(64, 32) KGAT_SBI_CASE(64, 64) KGAT_SBI_CASE(64, 128)
-  KGAT_SBI_CASE(128, 16) KGAT_SBI_CASE(128, 32) KGAT_SBI_CASE(128, 64) KGAT_SBI_CASE(128, 128)
-#undef KGAT_SBI_CASE
-  set_error("sage_bwd_input: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  const int rc = dispatch_widths(MfmaWidths{}, d_in, d_out, [&](auto di, auto dout) -> int {
+    hipLaunchKernelGGL((sage_bwd_input_kernel<decltype(di)::value, decltype(dout)::value>), dim3((unsigned)blocks),
+                       dim3(256), 0, as_stream(stream), (int32_t)n_rows, grad_pre, W_self, W_neigh, indptr, grad_self,
+                       grad_agg);
+    KGAT_CHECK_LAUNCH("sage_bwd_input");
+    return KGAT_OK;
+  });
+  if (rc == KGAT_E_UNSUPPORTED) set_error("sage_bwd_input: unsupported widths %d -> %d", d_in, d_out);
+  return rc;
 }
 
 int kgat_sage_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* grad_pre, const float* H,
@@ -776,20 +766,15 @@ int kgat_sage_bwd_weight_f32(int64_t n_rows, int d_in, int d_out, const float* g
                  "sage_bwd_weight: null pointer");
   KGAT_CHECK_ARG(n_rows == 0 || (aligned16(grad_pre) && aligned16(H) && aligned16(HN)),
                  "sage_bwd_weight: buffers must be 16-byte aligned");
-#define KGAT_SBW_CASE(DO_, DI_)                                                                                   \
-  if (d_out == DO_ && d_in == DI_) {                                                                             \
-    hipLaunchKernelGGL((sage_bwd_weight_kernel<DO_, DI_>), dim3((unsigned)n_partials), dim3(256), 0,             \
-                       as_stream(stream), (int32_t)n_rows, grad_pre, H, HN, part_self, part_neigh, part_bias);   \
-    KGAT_CHECK_LAUNCH("sage_bwd_weight");                                                                        \
-    return KGAT_OK;                                                                                              \
-  }
-  KGAT_SBW_CASE(16, 16) KGAT_SBW_CASE(16, 32) KGAT_SBW_CASE(16, 64) KGAT_SBW_CASE(16, 128)
-  KGAT_SBW_CASE(32, 16) KGAT_SBW_CASE(32, 32) KGAT_SBW_CASE(32, 64) KGAT_SBW_CASE(32, 128)
-  KGAT_SBW_CASE(64, 16) KGAT_SBW_CASE(64, 32) KGAT_SBW_CASE(64, 64) KGAT_SBW_CASE(64, 128)
-  KGAT_SBW_CASE(128, 16) KGAT_SBW_CASE(128, 32) KGAT_SBW_CASE(128, 64) KGAT_SBW_CASE(128, 128)
-#undef KGAT_SBW_CASE
-  set_error("sage_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  const int rc = dispatch_widths(MfmaWidths{}, d_out, d_in, [&](auto dout, auto di) -> int {
+    hipLaunchKernelGGL((sage_bwd_weight_kernel<decltype(dout)::value, decltype(di)::value>), dim3((unsigned)n_partials),
+                       dim3(256), 0, as_stream(stream), (int32_t)n_rows, grad_pre, H, HN, part_self, part_neigh,
+                       part_bias);
+    KGAT_CHECK_LAUNCH("sage_bwd_weight");
+    return KGAT_OK;
+  });
+  if (rc == KGAT_E_UNSUPPORTED) set_error("sage_bwd_weight: unsupported widths %d -> %d", d_in, d_out);
+  return rc;
 }
 
 }  // extern "C"

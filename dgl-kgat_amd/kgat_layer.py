@@ -20,14 +20,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import function as fn
-from .autograd import edge_softmax, u_mul_e_sum
+from .autograd import _combine, edge_softmax, u_mul_e_sum
 from .ops import BI2_FORM, FORMS
 from .options import options
 from .sage_layer import SAGEConv, draw_seed
 
 
-# what KGATConv's res_type may be -> the layer code's tag: the ops.FORMS values and the two-term Bi-Interaction, which is
-# no form of the kgat_aggregator_* entries (two weights, kgat_bi2_*)
+# what KGATConv's res_type may be -> the form ops.aggregator* take: the ops.FORMS values and the two-term Bi-Interaction
 RES_TYPES = dict(FORMS, Bi2=BI2_FORM)
 
 
@@ -45,18 +44,9 @@ def _layer_dense(layer):
     return form, lin.weight, lin.in_features // (2 if form == FORMS["GraphSage"] else 1), lin.out_features
 
 
-def _dense_supported(form, d_in, d_out):
-    """The forward kernels cover the layer's widths (every kernel form's backward covers the same MFMA widths)."""
-    from . import ops
-    return ops.bi2_supported(d_in, d_out) if form == BI2_FORM else ops.aggregator_supported(form, d_in, d_out)
-
-
-def _dense_no_grad(form, h, hn, W, **kw):
-    """The no-grad dense kernel of a layer (ops.aggregator, or ops.bi2 with the layer's pair of weights)."""
-    from . import ops
-    if form == BI2_FORM:
-        return ops.bi2(h, hn, W[0].detach(), W[1].detach(), 0.01, **kw)
-    return ops.aggregator(form, h, hn, W.detach(), 0.01, **kw)
+def _raw(W):
+    """A layer's weight as the kernels take it, detached and contiguous: a tensor, or the two-term layer's pair."""
+    return tuple(_raw(w) for w in W) if isinstance(W, tuple) else W.detach().contiguous()
 
 
 def ops_transr_supported(model, h):
@@ -117,24 +107,16 @@ class KGATConv(nn.Module):
 
     def _dense(self, h, h_neighbor, fused):
         """The GCN / GraphSage / Bi2 dense part: LeakyReLU(res_fc(h + h_N | [h | h_N])), for Bi2 plus
-        LeakyReLU(res_fc_2(h * h_N)).  fused and nothing to differentiate: the aggregator kernel (kgat_aggregator_f32,
-        kgat_bi2_f32) where it covers the widths; otherwise library GEMMs."""
+        LeakyReLU(res_fc_2(h * h_N)).  fused and nothing to differentiate: the aggregator kernel (ops.aggregator) where
+        it covers the widths; otherwise library GEMMs."""
         from . import ops
-        if self._res_type == "Bi2":
-            w1, w2 = self.res_fc.weight, self.res_fc_2.weight
-            if (fused and h.is_cuda and h.dtype == torch.float32 and ops.bi2_supported(h.shape[1], w1.shape[0]) and
-                    not (torch.is_grad_enabled() and (h.requires_grad or h_neighbor.requires_grad or w1.requires_grad or
-                                                      w2.requires_grad))):
-                return ops.bi2(h.contiguous(), h_neighbor.contiguous(), w1.detach().contiguous(), w2.detach().contiguous(), 0.01)
-            return (F.leaky_relu(_TallLinear.apply(h + h_neighbor, w1)) +
-                    F.leaky_relu(_TallLinear.apply(h * h_neighbor, w2)))
-        form, w = FORMS[self._res_type], self.res_fc.weight
-        d_in = h.shape[1]
-        if (fused and h.is_cuda and h.dtype == torch.float32 and ops.aggregator_supported(form, d_in, w.shape[0]) and
-                not (torch.is_grad_enabled() and (h.requires_grad or h_neighbor.requires_grad or w.requires_grad))):
-            return ops.aggregator(form, h.contiguous(), h_neighbor.contiguous(), w.detach().contiguous(), 0.01)
-        x = h + h_neighbor if form == FORMS["GCN"] else torch.cat([h, h_neighbor], 1)
-        return F.leaky_relu(_TallLinear.apply(x, w))
+        form, W, d_in, d_out = _layer_dense(self)
+        ws = W if isinstance(W, tuple) else (W,)
+        if (fused and h.is_cuda and h.dtype == torch.float32 and ops.aggregator_supported(form, d_in, d_out) and
+                not (torch.is_grad_enabled() and any(x.requires_grad for x in (h, h_neighbor, *ws)))):
+            return ops.aggregator(form, h.contiguous(), h_neighbor.contiguous(), _raw(W), 0.01)
+        terms = [F.leaky_relu(_TallLinear.apply(x, w)) for x, w in zip(_combine(form, h, h_neighbor), ws)]
+        return terms[0] if len(terms) == 1 else terms[0] + terms[1]
 
     def forward(self, g, nfeat, fused=None, seed=None):
         part = g.partition
@@ -375,7 +357,7 @@ class KGATPropagation(nn.Module):
             return False
         return ((g.partition is None) != sharded and w.is_cuda and w.dtype == torch.float32 and "w" in g.edata and
                 not g.edata["w"].requires_grad and
-                all(_dense_supported(form, d_in, d_out) and layer.mess_drop.p < 1.0
+                all(ops.aggregator_supported(form, d_in, d_out) and layer.mess_drop.p < 1.0
                     for layer, (form, _, d_in, d_out) in zip(self.layers, dense)))
 
     def _node_embeddings(self, g):
@@ -396,7 +378,7 @@ class KGATPropagation(nn.Module):
         if not all(isinstance(layer, KGATConv) or hasattr(layer, "res_fc_2") for layer in self.layers):
             return False
         drop_off = all((not layer.training) or layer.mess_drop.p == 0 for layer in self.layers)
-        return drop_off and all(_dense_supported(form, d_in, d_out)
+        return drop_off and all(ops.aggregator_supported(form, d_in, d_out)
                                 for form, _, d_in, d_out in map(_layer_dense, self.layers))
 
     def _gnn_fused(self, g):
@@ -449,7 +431,7 @@ class KGATPropagation(nn.Module):
                 hn, rows_left = ops.spmm(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), defer_finish=True)
             else:
                 hn, rows_left = u_mul_e_sum(g, h, w), None
-            h = _dense_no_grad(form, hc, hn, W, norm_out=norm_out, want_h=not last, deferred=rows_left,
+            h = ops.aggregator(form, hc, hn, _raw(W), 0.01, norm_out=norm_out, want_h=not last, deferred=rows_left,
                                self_out=self_out)
         # the ego-embedding block last: the pass ends having just touched the embedding table, which
         # is what the next attention refresh gathers from (a step's working set is about the size

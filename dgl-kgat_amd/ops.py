@@ -929,20 +929,8 @@ def add3_rows(a, b, c):
 
 
 def bi_interaction_bwd_pre(h_out, grad_a, grad_b, grad_norm, negative_slope, drop_p, seed, row0=0):
-    """grad_z of the training layer (kgat_bi_interaction_bwd_pre_f32); grad_a / grad_b / grad_norm may be
-    None; `row0` as in aggregator_train."""
-    h_out = _need(h_out, torch.float32, "h_out")
-    n, d = h_out.shape
-    for name, t in (("grad_a", grad_a), ("grad_b", grad_b)):
-        if t is not None:
-            _need(t, torch.float32, name, (n, d))
-    stride = _strided_rows(grad_norm, n, d, "grad_norm") if grad_norm is not None else 0
-    gz = torch.empty_like(h_out)
-    check(_lib.load().kgat_bi_interaction_bwd_pre_f32(n, d, _ptr(h_out), _ptr(grad_a), _ptr(grad_b), _ptr(grad_norm),
-                                                      stride, float(negative_slope), float(drop_p),
-                                                      int(seed) & (2 ** 64 - 1), int(row0), _ptr(gz), _stream(h_out)),
-          "kgat_bi_interaction_bwd_pre_f32")
-    return gz
+    """grad_z of a one-weight training layer: `aggregator_bwd_pre` without a sign record."""
+    return aggregator_bwd_pre(FORMS["Bi"], h_out, None, grad_a, grad_b, grad_norm, negative_slope, drop_p, seed, row0)
 
 
 def bi_interaction_bwd_input_supported(d_in, d_out):
@@ -982,60 +970,91 @@ def bi_interaction_bwd_weight(grad_z, H, HN, want_partials=False):
 # The KGAT layer's aggregators (KGATConv res_type; include/kgat_hip.h KGAT_FORM_*): Bi-Interaction LeakyReLU(W (h * h_N)),
 # GCN LeakyReLU(W (h + h_N)), GraphSage LeakyReLU(W [h | h_N]) - W is d_out x 2 d_in for GraphSage.
 FORMS = {"Bi": 0, "GCN": 1, "GraphSage": 2}
+# The KGAT paper's two-term Bi-Interaction (KGATConv res_type "Bi2"): LeakyReLU(W1 (h + h_N)) + LeakyReLU(W2 (h * h_N)),
+# W1 = res_fc.weight, W2 = res_fc_2.weight.  The fourth form of the functions below; in the C interface it has entries
+# of its own (kgat_bi2_*: two weights and a sign record), so the value is this layer's, not a KGAT_FORM_*.
+# Convention: where a one-weight form takes or returns ONE tensor per weight - the weight W, the gradient grad_z, the
+# weight gradient - this form takes or returns the pair, (W1, W2), (grad_z1, grad_z2), (grad_W1, grad_W2).
+BI2_FORM = 3
+
+
+def form_weights(form):
+    """How many weights a layer of this form has."""
+    return 2 if form == BI2_FORM else 1
+
+
+def _entry(form, suffix):
+    """The form's C entry: (function, its leading arguments, its name) - kgat_aggregator_* take the form first,
+    kgat_bi2_* have none."""
+    name = ("kgat_bi2" if form == BI2_FORM else "kgat_aggregator") + suffix
+    return getattr(_lib.load(), name), ([] if form == BI2_FORM else [int(form)]), name
 
 
 def aggregator_supported(form, d_in, d_out):
-    """The widths the form's forward kernels cover (kgat_aggregator_supported)."""
-    return bool(_lib.load().kgat_aggregator_supported(int(form), int(d_in), int(d_out)))
+    """The widths the form's forward kernels cover (kgat_aggregator_supported / kgat_bi2_supported)."""
+    fn, lead, _ = _entry(form, "_supported")
+    return bool(fn(*lead, int(d_in), int(d_out)))
 
 
 def aggregator_bwd_supported(form, d_in, d_out):
-    """The widths the form's backward kernels cover (kgat_aggregator_bwd_supported)."""
-    return bool(_lib.load().kgat_aggregator_bwd_supported(int(form), int(d_in), int(d_out)))
+    """The widths the form's backward kernels cover (kgat_aggregator_bwd_supported / kgat_bi2_bwd_supported)."""
+    fn, lead, _ = _entry(form, "_bwd_supported")
+    return bool(fn(*lead, int(d_in), int(d_out)))
+
+
+def _per_weight(form, x, name):
+    """`x` as the list of the form's per-weight tensors: [x], or the pair's two for BI2_FORM (same shape)."""
+    if form != BI2_FORM:
+        return [_need(x, torch.float32, name)]
+    if not (isinstance(x, (tuple, list)) and len(x) == 2):
+        raise ValueError("%s: the two-term form takes a pair of tensors" % name)
+    first = _need(x[0], torch.float32, name + "1")
+    return [first, _need(x[1], torch.float32, name + "2", first.shape)]
 
 
 def _form_weight(form, W, d_in):
-    W = _need(W, torch.float32, "W")
+    Ws = _per_weight(form, W, "W")
     k = 2 * d_in if form == FORMS["GraphSage"] else d_in
-    if W.dim() != 2 or W.shape[1] != k:
-        raise ValueError("W has shape %s, expected (*, %d) for form %d" % (tuple(W.shape), k, form))
-    return W, W.shape[0]
+    if Ws[0].dim() != 2 or Ws[0].shape[1] != k:
+        raise ValueError("W has shape %s, expected (*, %d) for form %d" % (tuple(Ws[0].shape), k, form))
+    return Ws, Ws[0].shape[0]
 
 
 def _agg_timed(form, n, d_in, d_out):
     # (Bi under the name and key of ops.bi_interaction: the KernelTimer summaries of the benchmark read that name)
+    if form == BI2_FORM:
+        return _timed("bi2", (n, d_in, d_out))
     return _timed("bi_interaction", (n, d_in, d_out)) if form == FORMS["Bi"] else _timed("aggregator", (form, n, d_in, d_out))
 
 
 def aggregator(form, H, HN, W, negative_slope=0.01, h_out=None, norm_out=None, want_h=True, self_out=None,
                deferred=None):
-    """Z = leaky_relu(combine(H, HN) @ W^T) with combine = H * HN (form 0), H + HN (1) or [H | HN] (2)
-    (kgat_aggregator_f32): the layer input H and the plain aggregation HN, combined while the rows are loaded;
-    `self_out`: an (n, d_in) column slice that also receives H (the ego block of the readout).  Otherwise as
+    """Z = leaky_relu(combine(H, HN) @ W^T) with combine = H * HN (form 0), H + HN (1) or [H | HN] (2), or - BI2_FORM,
+    W = (W1, W2) - leaky_relu((H + HN) @ W1^T) + leaky_relu((H * HN) @ W2^T)
+    (kgat_aggregator_f32 / kgat_bi2_f32): the layer input H and the plain aggregation HN, combined while the rows are
+    loaded; `self_out`: an (n, d_in) column slice that also receives H (the ego block of the readout).  Otherwise as
     bi_interaction.  `deferred`: the DeferredRows of the spmm(defer_finish=True) call that produced HN
-    (kgat_aggregator_deferred_f32; same bits)."""
+    (kgat_aggregator_deferred_f32 / kgat_bi2_deferred_f32; same bits)."""
     H = _need(H, torch.float32, "H")
     HN = _need(HN, torch.float32, "HN", H.shape)
     n, d_in = H.shape
-    W, d_out = _form_weight(form, W, d_in)
+    Ws, d_out = _form_weight(form, W, d_in)
     if want_h and h_out is None:
         h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
     if h_out is not None:
         h_out = _need(h_out, torch.float32, "h_out", (n, d_out))
     stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
     self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    args = [n, d_in, d_out, _ptr(H), _ptr(HN), *map(_ptr, Ws), float(negative_slope), _ptr(h_out), _ptr(norm_out), stride,
+            _ptr(self_out), self_stride]
+    if deferred is not None:
+        if deferred.n_rows != n or deferred.D != d_in:
+            raise ValueError("deferred rows of a (%d, %d) aggregation with a (%d, %d) input" % (deferred.n_rows, deferred.D, n, d_in))
+        args += [_ptr(deferred.indptr_rows), deferred.e_range[0], deferred.e_range[1], _ptr(deferred.workspace),
+                 deferred.tile_edges]
+    fn, lead, name = _entry(form, "_deferred_f32" if deferred is not None else "_f32")
     with _agg_timed(form, n, d_in, d_out):
-        if deferred is not None:
-            if deferred.n_rows != n or deferred.D != d_in:
-                raise ValueError("deferred rows of a (%d, %d) aggregation with a (%d, %d) input" % (deferred.n_rows, deferred.D, n, d_in))
-            check(_lib.load().kgat_aggregator_deferred_f32(
-                int(form), n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W), float(negative_slope), _ptr(h_out), _ptr(norm_out),
-                stride, _ptr(self_out), self_stride, _ptr(deferred.indptr_rows), deferred.e_range[0], deferred.e_range[1],
-                _ptr(deferred.workspace), deferred.tile_edges, _stream(H)), "kgat_aggregator_deferred_f32")
-        else:
-            check(_lib.load().kgat_aggregator_f32(int(form), n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W),
-                                                  float(negative_slope), _ptr(h_out), _ptr(norm_out), stride,
-                                                  _ptr(self_out), self_stride, _stream(H)), "kgat_aggregator_f32")
+        check(fn(*lead, *args, _stream(H)), name)
     return h_out
 
 
@@ -1043,186 +1062,85 @@ def aggregator_train(form, H, HN, W, negative_slope, drop_p, seed, norm_out=None
     """Training form of `aggregator`: h_out = dropout_p(leaky_relu(combine(H, HN) @ W^T)) and its normalised copy into
     `norm_out` (kgat_aggregator_train_f32; the mask is a hash of (seed, element); `row0`: the global index of row 0
     when H holds a row range of a larger matrix, so that a destination shard draws the mask the unsharded layer
-    draws)."""
+    draws).  BI2_FORM (kgat_bi2_train_f32) returns (h_out, signs): the dropped sum of the two terms and the (n, d_out)
+    uint8 sign record, bit 0 = (z1 > 0), bit 1 = (z2 > 0), that aggregator_bwd_pre reads."""
     H = _need(H, torch.float32, "H")
     HN = _need(HN, torch.float32, "HN", H.shape)
     n, d_in = H.shape
-    W, d_out = _form_weight(form, W, d_in)
+    Ws, d_out = _form_weight(form, W, d_in)
     h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
+    signs = [torch.empty((n, d_out), dtype=torch.uint8, device=H.device)] if form == BI2_FORM else []
     stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
     self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
+    fn, lead, name = _entry(form, "_train_f32")
     with _agg_timed(form, n, d_in, d_out):
-        check(_lib.load().kgat_aggregator_train_f32(int(form), n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W),
-                                                    float(negative_slope), float(drop_p), int(seed) & (2 ** 64 - 1),
-                                                    int(row0), _ptr(h_out), _ptr(norm_out), stride, _ptr(self_out),
-                                                    self_stride, _stream(H)), "kgat_aggregator_train_f32")
-    return h_out
+        check(fn(*lead, n, d_in, d_out, _ptr(H), _ptr(HN), *map(_ptr, Ws), float(negative_slope), float(drop_p),
+                 int(seed) & (2 ** 64 - 1), int(row0), _ptr(h_out), *map(_ptr, signs), _ptr(norm_out), stride,
+                 _ptr(self_out), self_stride, _stream(H)), name)
+    return (h_out, signs[0]) if signs else h_out
+
+
+def aggregator_bwd_pre(form, h_out, signs, grad_a, grad_b, grad_norm, negative_slope, drop_p, seed, row0=0):
+    """grad_z of the training layer (kgat_bi_interaction_bwd_pre_f32; `signs` is None); grad_a / grad_b / grad_norm
+    may be None; `row0` as in aggregator_train.  BI2_FORM (kgat_bi2_bwd_pre_f32): (grad_z1, grad_z2) - that gradient
+    times LeakyReLU'(z1) and times LeakyReLU'(z2), the slopes from aggregator_train's sign record."""
+    h_out = _need(h_out, torch.float32, "h_out")
+    n, d = h_out.shape
+    two = form == BI2_FORM
+    if two:
+        signs = _need(signs, torch.uint8, "signs", (n, d))
+    for name, t in (("grad_a", grad_a), ("grad_b", grad_b)):
+        if t is not None:
+            _need(t, torch.float32, name, (n, d))
+    stride = _strided_rows(grad_norm, n, d, "grad_norm") if grad_norm is not None else 0
+    gz = [torch.empty_like(h_out) for _ in range(form_weights(form))]
+    name = "kgat_bi2_bwd_pre_f32" if two else "kgat_bi_interaction_bwd_pre_f32"
+    check(getattr(_lib.load(), name)(n, d, _ptr(h_out), *([_ptr(signs)] if two else []), _ptr(grad_a), _ptr(grad_b),
+                                     _ptr(grad_norm), stride, float(negative_slope), float(drop_p),
+                                     int(seed) & (2 ** 64 - 1), int(row0), *map(_ptr, gz), _stream(h_out)), name)
+    return tuple(gz) if two else gz[0]
+
+
+def _bwd_operands(form, grad_z, H, HN):
+    gzs = _per_weight(form, grad_z, "grad_z")
+    n, d_out = gzs[0].shape
+    H = _need(H, torch.float32, "H")
+    if H.shape[0] != n:
+        raise ValueError("H has %d rows, grad_z %d" % (H.shape[0], n))
+    HN = _need(HN, torch.float32, "HN", H.shape)
+    return gzs, H, HN, n, H.shape[1], d_out
 
 
 def aggregator_bwd_input(form, grad_z, W, H, HN):
     """(grad_agg, grad_self) of the form's dense part (kgat_aggregator_bwd_input_f32): what the reversed-CSR aggregation
     sums and what goes to h directly - (grad_P * H, grad_P * HN) for Bi, (grad_P, grad_P) - one tensor - for GCN,
-    (grad_P[:, d_in:], grad_P[:, :d_in]) for GraphSage, grad_P = grad_z @ W."""
-    grad_z = _need(grad_z, torch.float32, "grad_z")
-    n, d_out = grad_z.shape
-    H = _need(H, torch.float32, "H")
-    d_in = H.shape[1]
-    W, _ = _form_weight(form, W, d_in)
-    if W.shape[0] != d_out:
-        raise ValueError("W has shape %s, expected (%d, *)" % (tuple(W.shape), d_out))
-    H = _need(H, torch.float32, "H", (n, d_in))
-    HN = _need(HN, torch.float32, "HN", (n, d_in))
+    (grad_P[:, d_in:], grad_P[:, :d_in]) for GraphSage, grad_P = grad_z @ W.  BI2_FORM (kgat_bi2_bwd_input_f32):
+    (P1 + P2 * H, P1 + P2 * HN) with P1 = grad_z1 @ W1, P2 = grad_z2 @ W2 in one pass."""
+    gzs, H, HN, n, d_in, d_out = _bwd_operands(form, grad_z, H, HN)
+    Ws, wd = _form_weight(form, W, d_in)
+    if wd != d_out:
+        raise ValueError("W has shape %s, expected (%d, *)" % (tuple(Ws[0].shape), d_out))
     t = torch.empty_like(H)
     gb = t if form == FORMS["GCN"] else torch.empty_like(H)
-    check(_lib.load().kgat_aggregator_bwd_input_f32(int(form), n, d_in, d_out, _ptr(grad_z), _ptr(W), _ptr(H), _ptr(HN),
-                                                    _ptr(t), _ptr(None if gb is t else gb), _stream(H)),
-          "kgat_aggregator_bwd_input_f32")
+    fn, lead, name = _entry(form, "_bwd_input_f32")
+    check(fn(*lead, n, d_in, d_out, *map(_ptr, gzs), *map(_ptr, Ws), _ptr(H), _ptr(HN), _ptr(t),
+             _ptr(None if gb is t else gb), _stream(H)), name)
     return t, gb
 
 
 def aggregator_bwd_weight(form, grad_z, H, HN, want_partials=False):
     """grad_W of the form's dense part (kgat_aggregator_bwd_weight_f32: per-workgroup partials over 64-row slabs,
     d_out x 2 d_in for GraphSage, the combination formed on the way; the partials are added here in index order - or,
-    want_partials=True, handed back for sum_partials, which sums several layers' sets in one launch)."""
-    grad_z = _need(grad_z, torch.float32, "grad_z")
-    n, d_out = grad_z.shape
-    H = _need(H, torch.float32, "H")
-    d_in = H.shape[1]
-    if H.shape[0] != n:
-        raise ValueError("H has %d rows, grad_z %d" % (H.shape[0], n))
-    HN = _need(HN, torch.float32, "HN", (n, d_in))
-    lib = _lib.load()
-    nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
+    want_partials=True, handed back for sum_partials, which sums several layers' sets in one launch).  BI2_FORM
+    (kgat_bi2_bwd_weight_f32): the pair (grad_z1^T (H + HN), grad_z2^T (H * HN)), H and HN read once for both."""
+    gzs, H, HN, n, d_in, d_out = _bwd_operands(form, grad_z, H, HN)
+    nb = int(_lib.load().kgat_bi_interaction_bwd_weight_partials(n))
     k = 2 * d_in if form == FORMS["GraphSage"] else d_in
-    partials = torch.empty((nb, d_out, k), dtype=torch.float32, device=H.device)
-    check(lib.kgat_aggregator_bwd_weight_f32(int(form), n, d_in, d_out, _ptr(grad_z), _ptr(H), _ptr(HN), _ptr(partials),
-                                             nb, _stream(H)), "kgat_aggregator_bwd_weight_f32")
-    return partials if want_partials else partials.sum(0)
-
-
-# The KGAT paper's two-term Bi-Interaction (KGATConv res_type "Bi2"; include/kgat_hip.h kgat_bi2_*):
-# LeakyReLU(W1 (h + h_N)) + LeakyReLU(W2 (h * h_N)), W1 = res_fc.weight, W2 = res_fc_2.weight.  Two weights and a sign
-# record: entries of their own, not a FORMS value.
-BI2_FORM = 3  # the layer code's tag for such a layer beside the FORMS values (autograd.gnn_train, kgat_layer)
-
-
-def bi2_supported(d_in, d_out):
-    """The widths the two-term forward kernels cover (kgat_bi2_supported)."""
-    return bool(_lib.load().kgat_bi2_supported(int(d_in), int(d_out)))
-
-
-def bi2_bwd_supported(d_in, d_out):
-    """The widths the two-term backward kernels cover (kgat_bi2_bwd_supported)."""
-    return bool(_lib.load().kgat_bi2_bwd_supported(int(d_in), int(d_out)))
-
-
-def _bi2_weights(W1, W2, d_in):
-    W1 = _need(W1, torch.float32, "W1")
-    if W1.dim() != 2 or W1.shape[1] != d_in:
-        raise ValueError("W1 has shape %s, expected (*, %d)" % (tuple(W1.shape), d_in))
-    W2 = _need(W2, torch.float32, "W2", W1.shape)
-    return W1, W2, W1.shape[0]
-
-
-def bi2(H, HN, W1, W2, negative_slope=0.01, h_out=None, norm_out=None, want_h=True, self_out=None, deferred=None):
-    """Z = leaky_relu((H + HN) @ W1^T) + leaky_relu((H * HN) @ W2^T) (kgat_bi2_f32 / kgat_bi2_deferred_f32); the other
-    arguments as bi_interaction_mul."""
-    H = _need(H, torch.float32, "H")
-    HN = _need(HN, torch.float32, "HN", H.shape)
-    n, d_in = H.shape
-    W1, W2, d_out = _bi2_weights(W1, W2, d_in)
-    if want_h and h_out is None:
-        h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
-    if h_out is not None:
-        h_out = _need(h_out, torch.float32, "h_out", (n, d_out))
-    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
-    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
-    with _timed("bi2", (n, d_in, d_out)):
-        if deferred is not None:
-            if deferred.n_rows != n or deferred.D != d_in:
-                raise ValueError("deferred rows of a (%d, %d) aggregation with a (%d, %d) input" % (deferred.n_rows, deferred.D, n, d_in))
-            check(_lib.load().kgat_bi2_deferred_f32(
-                n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W1), _ptr(W2), float(negative_slope), _ptr(h_out), _ptr(norm_out),
-                stride, _ptr(self_out), self_stride, _ptr(deferred.indptr_rows), deferred.e_range[0], deferred.e_range[1],
-                _ptr(deferred.workspace), deferred.tile_edges, _stream(H)), "kgat_bi2_deferred_f32")
-        else:
-            check(_lib.load().kgat_bi2_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W1), _ptr(W2), float(negative_slope),
-                                           _ptr(h_out), _ptr(norm_out), stride, _ptr(self_out), self_stride, _stream(H)),
-                  "kgat_bi2_f32")
-    return h_out
-
-
-def bi2_train(H, HN, W1, W2, negative_slope, drop_p, seed, norm_out=None, row0=0, self_out=None):
-    """Training form of `bi2` (kgat_bi2_train_f32): returns (h_out, signs) - the dropped sum of the two terms and the
-    (n, d_out) uint8 sign record, bit 0 = (z1 > 0), bit 1 = (z2 > 0), that bi2_bwd_pre reads."""
-    H = _need(H, torch.float32, "H")
-    HN = _need(HN, torch.float32, "HN", H.shape)
-    n, d_in = H.shape
-    W1, W2, d_out = _bi2_weights(W1, W2, d_in)
-    h_out = torch.empty((n, d_out), dtype=torch.float32, device=H.device)
-    signs = torch.empty((n, d_out), dtype=torch.uint8, device=H.device)
-    stride = _strided_rows(norm_out, n, d_out, "norm_out") if norm_out is not None else 0
-    self_stride = _strided_rows(self_out, n, d_in, "self_out") if self_out is not None else 0
-    with _timed("bi2", (n, d_in, d_out)):
-        check(_lib.load().kgat_bi2_train_f32(n, d_in, d_out, _ptr(H), _ptr(HN), _ptr(W1), _ptr(W2), float(negative_slope),
-                                             float(drop_p), int(seed) & (2 ** 64 - 1), int(row0), _ptr(h_out), _ptr(signs),
-                                             _ptr(norm_out), stride, _ptr(self_out), self_stride, _stream(H)),
-              "kgat_bi2_train_f32")
-    return h_out, signs
-
-
-def bi2_bwd_pre(h_out, signs, grad_a, grad_b, grad_norm, negative_slope, drop_p, seed, row0=0):
-    """(grad_z1, grad_z2) of the two-term training layer (kgat_bi2_bwd_pre_f32): bi_interaction_bwd_pre's gradient
-    times LeakyReLU'(z1) and times LeakyReLU'(z2), the slopes from bi2_train's sign record."""
-    h_out = _need(h_out, torch.float32, "h_out")
-    n, d = h_out.shape
-    signs = _need(signs, torch.uint8, "signs", (n, d))
-    for name, t in (("grad_a", grad_a), ("grad_b", grad_b)):
-        if t is not None:
-            _need(t, torch.float32, name, (n, d))
-    stride = _strided_rows(grad_norm, n, d, "grad_norm") if grad_norm is not None else 0
-    gz1, gz2 = torch.empty_like(h_out), torch.empty_like(h_out)
-    check(_lib.load().kgat_bi2_bwd_pre_f32(n, d, _ptr(h_out), _ptr(signs), _ptr(grad_a), _ptr(grad_b), _ptr(grad_norm),
-                                           stride, float(negative_slope), float(drop_p), int(seed) & (2 ** 64 - 1),
-                                           int(row0), _ptr(gz1), _ptr(gz2), _stream(h_out)), "kgat_bi2_bwd_pre_f32")
-    return gz1, gz2
-
-
-def _bi2_bwd_operands(grad_z1, grad_z2, H, HN):
-    grad_z1 = _need(grad_z1, torch.float32, "grad_z1")
-    grad_z2 = _need(grad_z2, torch.float32, "grad_z2", grad_z1.shape)
-    n, d_out = grad_z1.shape
-    H = _need(H, torch.float32, "H")
-    if H.shape[0] != n:
-        raise ValueError("H has %d rows, grad_z1 %d" % (H.shape[0], n))
-    HN = _need(HN, torch.float32, "HN", H.shape)
-    return grad_z1, grad_z2, H, HN, n, H.shape[1], d_out
-
-
-def bi2_bwd_input(grad_z1, grad_z2, W1, W2, H, HN):
-    """(grad_agg, grad_self) = (P1 + P2 * H, P1 + P2 * HN) with P1 = grad_z1 @ W1, P2 = grad_z2 @ W2 in one pass
-    (kgat_bi2_bwd_input_f32): what the reversed-CSR aggregation sums and what goes to h directly."""
-    grad_z1, grad_z2, H, HN, n, d_in, d_out = _bi2_bwd_operands(grad_z1, grad_z2, H, HN)
-    W1, W2, wd = _bi2_weights(W1, W2, d_in)
-    if wd != d_out:
-        raise ValueError("W1 has shape %s, expected (%d, *)" % (tuple(W1.shape), d_out))
-    t, gb = torch.empty_like(H), torch.empty_like(H)
-    check(_lib.load().kgat_bi2_bwd_input_f32(n, d_in, d_out, _ptr(grad_z1), _ptr(grad_z2), _ptr(W1), _ptr(W2), _ptr(H),
-                                             _ptr(HN), _ptr(t), _ptr(gb), _stream(H)), "kgat_bi2_bwd_input_f32")
-    return t, gb
-
-
-def bi2_bwd_weight(grad_z1, grad_z2, H, HN, want_partials=False):
-    """(grad_W1, grad_W2) = (grad_z1^T (H + HN), grad_z2^T (H * HN)) (kgat_bi2_bwd_weight_f32's partials, summed here
-    in index order - or, want_partials=True, handed back for sum_partials)."""
-    grad_z1, grad_z2, H, HN, n, d_in, d_out = _bi2_bwd_operands(grad_z1, grad_z2, H, HN)
-    lib = _lib.load()
-    nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
-    p1 = torch.empty((nb, d_out, d_in), dtype=torch.float32, device=H.device)
-    p2 = torch.empty_like(p1)
-    check(lib.kgat_bi2_bwd_weight_f32(n, d_in, d_out, _ptr(grad_z1), _ptr(grad_z2), _ptr(H), _ptr(HN), _ptr(p1), _ptr(p2),
-                                      nb, _stream(H)), "kgat_bi2_bwd_weight_f32")
-    return (p1, p2) if want_partials else (p1.sum(0), p2.sum(0))
+    partials = [torch.empty((nb, d_out, k), dtype=torch.float32, device=H.device) for _ in gzs]
+    fn, lead, name = _entry(form, "_bwd_weight_f32")
+    check(fn(*lead, n, d_in, d_out, *map(_ptr, gzs), _ptr(H), _ptr(HN), *map(_ptr, partials), nb, _stream(H)), name)
+    res = partials if want_partials else [p.sum(0) for p in partials]
+    return tuple(res) if form == BI2_FORM else res[0]
 
 
 def mul2(a, b, c):

@@ -265,11 +265,12 @@ def main():
                 fns[name + ".bwd_weight"] = lambda f=f: ops.aggregator_bwd_weight(f, GZ, X, HN, want_partials=True)
             W1, W2 = torch.randn(do, di, device=dev) * 0.1, torch.randn(do, di, device=dev) * 0.1
             GZ2 = torch.randn(n, do, device=dev)
-            fns["Bi2.layer"] = lambda W1=W1, W2=W2: ops.bi2(
-                X, ops.spmm(indptr, col, row_of, X, w, workspace=ws), W1, W2, 0.01, norm_out=norm)
-            fns["Bi2.dense"] = lambda W1=W1, W2=W2: ops.bi2(X, HN, W1, W2, 0.01, norm_out=norm)
-            fns["Bi2.bwd_input"] = lambda W1=W1, W2=W2: ops.bi2_bwd_input(GZ, GZ2, W1, W2, X, HN)
-            fns["Bi2.bwd_weight"] = lambda: ops.bi2_bwd_weight(GZ, GZ2, X, HN, want_partials=True)
+            W12, GZ12 = (W1, W2), (GZ, GZ2)
+            fns["Bi2.layer"] = lambda W12=W12: ops.aggregator(
+                ops.BI2_FORM, X, ops.spmm(indptr, col, row_of, X, w, workspace=ws), W12, 0.01, norm_out=norm)
+            fns["Bi2.dense"] = lambda W12=W12: ops.aggregator(ops.BI2_FORM, X, HN, W12, 0.01, norm_out=norm)
+            fns["Bi2.bwd_input"] = lambda W12=W12, GZ12=GZ12: ops.aggregator_bwd_input(ops.BI2_FORM, GZ12, W12, X, HN)
+            fns["Bi2.bwd_weight"] = lambda GZ12=GZ12: ops.aggregator_bwd_weight(ops.BI2_FORM, GZ12, X, HN, want_partials=True)
             t = timeit(fns, args.rounds)
             med = {k: float(np.median(v)) for k, v in t.items()}
             print("%d -> %d" % (di, do))

@@ -362,10 +362,11 @@ def test_node_dropout_training_unit_sees_one_edge_set(dev, train_case, res_type,
 def test_node_dropout_per_layer_fallback(dev, train_case, res_type):
     """Widths 24 -> 24 are outside the dense kernels: the per-layer path puts the dropped edge-id-ordered weights on its
     local_var graph.  Readout bitwise; gradients within the 1e-5 of tensor scale the aggregator tests ask of that path."""
-    from dgl_kgat_amd.kgat_layer import _dense_supported, _layer_dense
+    from dgl_kgat_amd import ops
+    from dgl_kgat_amd.kgat_layer import _layer_dense
     A, (out_a, grads_a), (out_b, grads_b) = _ab(dev, train_case, res_type, (24, 24), layers=1)
     form, _, d_in, d_out = _layer_dense(A.layers[0])
-    assert (d_in, d_out) == (24, 24) and not _dense_supported(form, d_in, d_out)
+    assert (d_in, d_out) == (24, 24) and not ops.aggregator_supported(form, d_in, d_out)
     assert not type(out_a.grad_fn).__name__.startswith("_GNNTrain")
     assert torch.equal(out_a, out_b), res_type
     for k, ga, gb in zip([k for k, _ in A.named_parameters()], grads_a, grads_b):

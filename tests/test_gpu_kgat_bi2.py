@@ -125,7 +125,7 @@ def test_bi2_kernels_every_width(dev, kind, capsys):
         HN = ops.spmm(csr.indptr, csr.col, csr.row_of, H, w_csr)
         h64, hn64 = _np(H), _np(HN)
         for d_out in WIDTHS:
-            assert ops.bi2_supported(d_in, d_out) and ops.bi2_bwd_supported(d_in, d_out)
+            assert ops.aggregator_supported(ops.BI2_FORM, d_in, d_out) and ops.aggregator_bwd_supported(ops.BI2_FORM, d_in, d_out)
             W1 = torch.randn(d_out, d_in, device=dev) / d_in ** 0.5
             W2 = torch.randn(d_out, d_in, device=dev) / d_in ** 0.5
             z1, z2 = _pre64(h64, hn64, _np(W1), _np(W2))
@@ -133,34 +133,34 @@ def test_bi2_kernels_every_width(dev, kind, capsys):
             tag = (kind, d_in, d_out)
             # no-grad form: rows, normalised slice of a wider readout, ego block, padding untouched
             ro = torch.full((n, d_in + d_out + 4), 7.0, device=dev)
-            z = ops.bi2(H, HN, W1, W2, SLOPE, norm_out=ro[:, d_in:d_in + d_out], self_out=ro[:, :d_in])
+            z = ops.aggregator(ops.BI2_FORM, H, HN, (W1, W2), SLOPE, norm_out=ro[:, d_in:d_in + d_out], self_out=ro[:, :d_in])
             note("h_out", _scale_err(_np(z), z64), tag)
             note("norm", _scale_err(_np(ro[:, d_in:d_in + d_out]), _normalize(z64)), tag)
             assert torch.equal(ro[:, :d_in], H) and bool((ro[:, d_in + d_out:] == 7.0).all()), tag
-            assert torch.equal(z, ops.bi2(H, HN, W1, W2, SLOPE)), tag
+            assert torch.equal(z, ops.aggregator(ops.BI2_FORM, H, HN, (W1, W2), SLOPE)), tag
             # deferred: the aggregation's second launch left to the dense kernel - the same bits
             hn_d, rows = ops.spmm(csr.indptr, csr.col, csr.row_of, H, w_csr, defer_finish=True)
             ro_d = torch.full_like(ro, 7.0)
-            z_d = ops.bi2(H, hn_d, W1, W2, SLOPE, norm_out=ro_d[:, d_in:d_in + d_out], self_out=ro_d[:, :d_in],
+            z_d = ops.aggregator(ops.BI2_FORM, H, hn_d, (W1, W2), SLOPE, norm_out=ro_d[:, d_in:d_in + d_out], self_out=ro_d[:, :d_in],
                           deferred=rows)
             assert torch.equal(z_d, z) and torch.equal(ro_d, ro), tag
             # training form: LeakyReLU per term, sum, hash dropout on the sum, normalised slice, sign record
             p, seed = 0.3, 1234 + d_out
             nrm = torch.empty(n, d_out, device=dev)
-            y, signs = ops.bi2_train(H, HN, W1, W2, SLOPE, p, seed, norm_out=nrm)
+            y, signs = ops.aggregator_train(ops.BI2_FORM, H, HN, (W1, W2), SLOPE, p, seed, norm_out=nrm)
             keep = ops.dropout_keep_mask(seed, n, d_out, p)
             y64 = np.where(keep, z64 / (1 - p), 0.0)
             assert bool((_np(y)[~keep] == 0).all()), tag
             note("train", _scale_err(_np(y), y64), tag)
             note("train_norm", _scale_err(_np(nrm), _normalize(y64)), tag)
-            y_b, signs_b = ops.bi2_train(H, HN, W1, W2, SLOPE, p, seed)
+            y_b, signs_b = ops.aggregator_train(ops.BI2_FORM, H, HN, (W1, W2), SLOPE, p, seed)
             assert torch.equal(y, y_b) and torch.equal(signs, signs_b), tag
             band = max(band, _check_signs(signs, z1, z2, tag))
             # backward head from a given gradient: the slopes come from the record
             gA = torch.randn(n, d_out, device=dev)
             gB = torch.randn(n, d_out, device=dev)
             gN = torch.randn(n, d_out + 8, device=dev)[:, 4:4 + d_out]
-            gz1, gz2 = ops.bi2_bwd_pre(y, signs, gA, gB, gN, SLOPE, p, seed)
+            gz1, gz2 = ops.aggregator_bwd_pre(ops.BI2_FORM, y, signs, gA, gB, gN, SLOPE, p, seed)
             yv, gn = _np(y), _np(gN)
             nr = np.maximum(np.sqrt((yv * yv).sum(1, keepdims=True)), 1e-12)
             g64 = (gn - yv * ((yv * gn).sum(1, keepdims=True) / nr ** 2)) / nr + _np(gA) + _np(gB)
@@ -168,20 +168,20 @@ def test_bi2_kernels_every_width(dev, kind, capsys):
             s1, s2 = _slopes(signs)
             note("gz1", _scale_err(_np(gz1), g64 * s1), tag)
             note("gz2", _scale_err(_np(gz2), g64 * s2), tag)
-            a1, a2 = ops.bi2_bwd_pre(y, signs, gA, gB, gN, SLOPE, p, seed)
+            a1, a2 = ops.aggregator_bwd_pre(ops.BI2_FORM, y, signs, gA, gB, gN, SLOPE, p, seed)
             assert torch.equal(gz1, a1) and torch.equal(gz2, a2), tag
             # backward towards the inputs and the weights, from the kernel's own gz1 / gz2
             p1, p2 = _np(gz1) @ _np(W1), _np(gz2) @ _np(W2)
-            t, gb = ops.bi2_bwd_input(gz1, gz2, W1, W2, H, HN)
+            t, gb = ops.aggregator_bwd_input(ops.BI2_FORM, (gz1, gz2), (W1, W2), H, HN)
             note("grad_agg", _scale_err(_np(t), p1 + p2 * h64), tag)
             note("grad_self", _scale_err(_np(gb), p1 + p2 * hn64), tag)
-            t2, gb2 = ops.bi2_bwd_input(gz1, gz2, W1, W2, H, HN)
+            t2, gb2 = ops.aggregator_bwd_input(ops.BI2_FORM, (gz1, gz2), (W1, W2), H, HN)
             assert torch.equal(t, t2) and torch.equal(gb, gb2), tag
-            gw1, gw2 = ops.bi2_bwd_weight(gz1, gz2, H, HN)
+            gw1, gw2 = ops.aggregator_bwd_weight(ops.BI2_FORM, (gz1, gz2), H, HN)
             assert tuple(gw1.shape) == tuple(gw2.shape) == (d_out, d_in)
             note("grad_W1", _scale_err(_np(gw1), _np(gz1).T @ (h64 + hn64)), tag)
             note("grad_W2", _scale_err(_np(gw2), _np(gz2).T @ (h64 * hn64)), tag)
-            b1, b2 = ops.bi2_bwd_weight(gz1, gz2, H, HN)
+            b1, b2 = ops.aggregator_bwd_weight(ops.BI2_FORM, (gz1, gz2), H, HN)
             assert torch.equal(gw1, b1) and torch.equal(gw2, b2), tag
     with capsys.disabled():
         print("\nBi2 kernels (%s): worst error / scale %s; largest share of pre-activations inside the sign band %.2e"
@@ -270,14 +270,15 @@ def test_stack_training_unit_gradients(dev):
     torch.manual_seed(0)
     assert type(model.gnn(g).grad_fn).__name__.startswith("_GNNTrain")
     masks = [ops.dropout_keep_mask(seed + li, n, w1.shape[0], p) for li, (w1, _) in enumerate(pairs)]
-    # replay the layers through ops.bi2_train (bit-reproducible kernels) for the sign records
+    # replay the layers through ops.aggregator_train (bit-reproducible kernels) for the sign records
     st = g._st
     csr = st.csr(dev)
     w_csr = st.csr_weights(g.edata["w"])
     records, x = [], emb.detach().contiguous()
     for li, (w1, w2) in enumerate(pairs):
         hn = ops.spmm(csr.indptr, csr.col, csr.row_of, x, w_csr)
-        x, sg = ops.bi2_train(x, hn, w1.detach().contiguous(), w2.detach().contiguous(), SLOPE, p, seed + li)
+        x, sg = ops.aggregator_train(ops.BI2_FORM, x, hn, (w1.detach().contiguous(), w2.detach().contiguous()), SLOPE, p,
+                                     seed + li)
         records.append(sg)
     # fp64 autograd of the restatement with the recorded slopes; every record is within the forward bar of the fp64 sign
     src = torch.as_tensor(trip[:, 2], device=dev)
@@ -309,7 +310,7 @@ def test_width_off_the_kernels_takes_the_fallback(dev):
     """Item 6."""
     from dgl_kgat_amd import ops
     model, g, n, trip = _setup(dev, dim=8, layers=1)
-    assert not ops.bi2_supported(8, 8)
+    assert not ops.aggregator_supported(ops.BI2_FORM, 8, 8)
     model.eval()
     assert not model._can_fuse_readout()
     with torch.no_grad():

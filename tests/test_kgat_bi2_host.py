@@ -131,8 +131,9 @@ def test_bi2_entries_answer_without_gpu():
     assert lib.kgat_bi2_f32(0, 64, 64, None, None, None, None, 0.01, None, None, 0, None, 0, None) == 0
     # the Python wrappers refuse CPU tensors like their siblings
     with pytest.raises(_lib.KGATLibraryError):
-        ops.bi2(torch.zeros(4, 16), torch.zeros(4, 16), torch.zeros(16, 16), torch.zeros(16, 16))
-    assert ops.bi2_supported(64, 32) and ops.bi2_bwd_supported(32, 16) and not ops.bi2_supported(8, 8)
+        ops.aggregator(ops.BI2_FORM, torch.zeros(4, 16), torch.zeros(4, 16), (torch.zeros(16, 16), torch.zeros(16, 16)))
+    assert (ops.aggregator_supported(ops.BI2_FORM, 64, 32) and ops.aggregator_bwd_supported(ops.BI2_FORM, 32, 16) and
+            not ops.aggregator_supported(ops.BI2_FORM, 8, 8))
 
 
 def _train_kgat():
