@@ -172,24 +172,16 @@ __global__ __launch_bounds__(kAttThreads) void att_score_generic_kernel(
   }
 }
 
-template <int D_, int K_, int TILES, int ACC_TANH>
+// The workgroup-chunk form of the one-kernel attention, W_r in LDS: what runs at d = 128, beyond kAttMaxRelLds relations,
+// for tables of 4 GiB and more and when asked for (KGAT_ATT_ALGO_MFMA_CHUNK), where the persistent kernel (W_r in
+// registers, d <= 64; kgat_att_persistent.hip) does not.  Two 16-edge tiles per wave step; one at d = 128.
+template <int D_>
 static int launch_att_mfma(const AttArgs& a) {
-  hipLaunchKernelGGL((att_score_mfma_kernel<D_, K_, TILES, ACC_TANH>), dim3(a.grid), dim3(kAttThreads),
-                     0, a.st, a.n_rel, a.rel_ptr, a.perm, a.src_g, a.dst_g, a.ent, a.W_R, a.rel,
-                     a.logits, a.logits_csr, a.pos_g);
+  constexpr int TILES = D_ >= 128 ? 1 : 2;
+  hipLaunchKernelGGL((att_score_mfma_kernel<D_, D_, TILES, 0>), dim3(a.n_blocks), dim3(kAttThreads), 0, a.st, a.n_rel,
+                     a.rel_ptr, a.perm, a.src_g, a.dst_g, a.ent, a.W_R, a.rel, a.logits, a.logits_csr, a.pos_g);
   KGAT_CHECK_LAUNCH("att_score_mfma");
   return KGAT_OK;
-}
-
-// The MFMA forms of the one-kernel attention: persistent wavefronts with W_r in registers (d <= 64), or - at d = 128,
-// beyond kAttMaxRelLds relations, for tables of 4 GiB and more, and when asked for (KGAT_ATT_ALGO_MFMA_CHUNK) - the
-// workgroup-chunk kernel with W_r in LDS (two 16-edge tiles per wave step; one at d = 128).
-template <int D_>
-static int dispatch_att_mfma(const AttArgs& a, bool force_chunk) {
-  const bool chunk = force_chunk || D_ >= 128 || a.n_rel > kAttMaxRelLds || a.table_bytes >= (1ull << 32);
-  if (D_ <= 64 && !chunk) return launch_att_persistent_any(D_, a);
-  if constexpr (D_ >= 128) return launch_att_mfma<D_, D_, 1, 0>(a);
-  else return launch_att_mfma<D_, D_, 2, 0>(a);
 }
 
 // Per-edge half of the folded form (head half: att_fold_head_kernel): logit = e_t . V[group].
@@ -432,6 +424,39 @@ static int launch_att_fold_tail(const AttArgs& a) {
 
 using namespace kgat;
 
+using AttTailWidths = WidthList<8, 16, 32, 64, 128>;  // att_fold_tail_kernel: the MFMA widths and the small kernels' d = 8
+
+// The arrays every entry passes on; the entry adds its form's own.
+static AttArgs att_args(const char* entry, int64_t n_edges, int n_rel, const int32_t* rel_ptr, const int32_t* perm,
+                        const int32_t* src_g, const int32_t* pos_g, const float* ent, const float* W_R, const float* rel,
+                        float* logits, float* logits_csr, kgat_stream_t stream) {
+  return AttArgs{entry, as_stream(stream), n_rel, n_edges, rel_ptr, perm, src_g, pos_g, ent, W_R, rel, logits, logits_csr};
+}
+
+// ---- the argument checks the three group forms share, in the order their entries make them
+// the sizes, the flags and the support rule (`needs`: the widths it covers, for the message); 1 = no edges, nothing to do
+static int check_att_shape(const AttArgs& a, int64_t n_nodes, int64_t n_groups, int d, int k, int flags, bool supported,
+                           const char* needs) {
+  KGAT_CHECK_ARG(n_nodes >= 0 && a.n_edges >= 0 && n_groups >= 0 && a.n_edges < INT32_MAX, "%s: bad size", a.entry);
+  KGAT_CHECK_ARG((flags & ~KGAT_ATT_F32_PRODUCTS) == 0, "%s: unknown flag", a.entry);
+  if (a.n_edges == 0) return 1;
+  if (!supported) {
+    set_error("%s: needs %s, 0 < R <= %d, N*d*4 < 4 GiB (d=%d k=%d R=%d)", a.entry, needs, kAttMaxRelLds, d, k, a.n_rel);
+    return KGAT_E_UNSUPPORTED;
+  }
+  return KGAT_OK;
+}
+
+// the pointers.  `inputs`: the entry's index arrays and parameters are there; `with_outputs`: so is what the outputs
+// asked for need beside pos_g (`missing` says what)
+static int check_att_pointers(const AttArgs& a, bool inputs, bool with_outputs, const char* missing) {
+  KGAT_CHECK_ARG(inputs, "%s: null pointer", a.entry);
+  KGAT_CHECK_ARG(a.logits || a.logits_csr || a.logits_g, "%s: no output requested", a.entry);
+  KGAT_CHECK_ARG(with_outputs, "%s: %s", a.entry, missing);
+  KGAT_CHECK_ARG(a.logits_csr == nullptr || a.pos_g != nullptr, "%s: logits_csr needs pos_g", a.entry);
+  return KGAT_OK;
+}
+
 extern "C" {
 
 int kgat_att_score_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel,
@@ -446,15 +471,16 @@ int kgat_att_score_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel
   KGAT_CHECK_ARG(logits != nullptr, "att_score: logits is null");
   KGAT_CHECK_ARG(logits_csr == nullptr || pos_g != nullptr, "att_score: logits_csr needs pos_g");
   KGAT_CHECK_ARG(algo >= KGAT_ATT_ALGO_AUTO && algo <= KGAT_ATT_ALGO_MFMA_CHUNK, "att_score: bad algo");
-  hipStream_t st = as_stream(stream);
+  AttArgs a = att_args("att_score", n_edges, n_rel, rel_ptr, perm, src_g, pos_g, ent, W_R, rel, logits, logits_csr, stream);
+  a.dst_g = dst_g;
+  a.n_blocks = (unsigned)((n_edges + kAttChunk - 1) / kAttChunk + n_rel);
   // edges whose type is outside [0, R) keep logit 0 (DGL zero-initialised column): the
   // persistent kernel clears that tail itself, the other kernels rely on a memset
-  const bool persistent = (d == k) && (d == 16 || d == 32 || d == 64) && n_rel > 0 &&
-                          n_rel <= kAttMaxRelLds && (unsigned long long)n_nodes * d * 4ull < (1ull << 32) &&
+  const bool persistent = att_shape_ok(n_nodes, d, k, n_rel, AttWidths{}) &&
                           (algo == KGAT_ATT_ALGO_AUTO || algo == KGAT_ATT_ALGO_MFMA);
   if (!persistent) {
-    hipError_t e = hipMemsetAsync(logits, 0, sizeof(float) * (size_t)n_edges, st);
-    if (e == hipSuccess && logits_csr) e = hipMemsetAsync(logits_csr, 0, sizeof(float) * (size_t)n_edges, st);
+    hipError_t e = hipMemsetAsync(logits, 0, sizeof(float) * (size_t)n_edges, a.st);
+    if (e == hipSuccess && logits_csr) e = hipMemsetAsync(logits_csr, 0, sizeof(float) * (size_t)n_edges, a.st);
     if (e != hipSuccess) {
       set_error("att_score: memset failed: %s", hipGetErrorString(e));
       return KGAT_E_HIP;
@@ -462,43 +488,27 @@ int kgat_att_score_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel
   }
   if (n_rel == 0) return KGAT_OK;
   KGAT_CHECK_ARG(rel_ptr && perm && src_g && dst_g && ent && W_R && rel, "att_score: null pointer");
-  AttArgs a;
-  a.grid = (unsigned)((n_edges + kAttChunk - 1) / kAttChunk + n_rel);
-  a.st = st; a.n_rel = n_rel; a.rel_ptr = rel_ptr; a.perm = perm; a.src_g = src_g; a.dst_g = dst_g;
-  a.ent = ent; a.W_R = W_R; a.rel = rel; a.logits = logits; a.logits_csr = logits_csr;
-  a.pos_g = pos_g;
-  a.table_bytes = (unsigned long long)n_nodes * (unsigned long long)d * 4ull;
-  a.n_edges = n_edges;
-  const unsigned grid = a.grid;
-  const bool mfma_ok = (d == k) && (d == 16 || d == 32 || d == 64 || d == 128);
-  const bool force_chunk = algo == KGAT_ATT_ALGO_MFMA_CHUNK;
-  if (force_chunk) algo = KGAT_ATT_ALGO_MFMA;
-  if (algo == KGAT_ATT_ALGO_MFMA && !mfma_ok) {
+  if (persistent) return launch_att_persistent_any(d, a);
+  const bool mfma_ok = d == k && has_width(AttWidths128{}, d);
+  if ((algo == KGAT_ATT_ALGO_MFMA || algo == KGAT_ATT_ALGO_MFMA_CHUNK) && !mfma_ok) {
     set_error("att_score: the MFMA kernel covers d == k in {16,32,64,128}, got d=%d k=%d", d, k);
     return KGAT_E_UNSUPPORTED;
   }
-  if (mfma_ok && algo != KGAT_ATT_ALGO_GENERIC) {
-    switch (d) {
-      case 16: return dispatch_att_mfma<16>(a, force_chunk);
-      case 32: return dispatch_att_mfma<32>(a, force_chunk);
-      case 64: return dispatch_att_mfma<64>(a, force_chunk);
-      default: return dispatch_att_mfma<128>(a, force_chunk);
-    }
-  }
+  if (mfma_ok && algo != KGAT_ATT_ALGO_GENERIC)
+    return dispatch_width(AttWidths128{}, d, [&](auto w) { return launch_att_mfma<decltype(w)::value>(a); });
   const size_t lds = sizeof(float) * (size_t)d * k;
   if (lds > 64 * 1024) {
     set_error("att_score: d*k = %d exceeds the generic kernel's LDS tile", d * k);
     return KGAT_E_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(att_score_generic_kernel, dim3(grid), dim3(kAttThreads), lds, st, d, k, n_rel,
+  hipLaunchKernelGGL(att_score_generic_kernel, dim3(a.n_blocks), dim3(kAttThreads), lds, a.st, d, k, n_rel,
                      rel_ptr, perm, src_g, dst_g, ent, W_R, rel, logits, logits_csr, pos_g);
   KGAT_CHECK_LAUNCH("att_score_generic");
   return KGAT_OK;
 }
 
 int kgat_att_score_split_supported(int64_t n_nodes, int d, int k, int n_rel) {
-  return d == k && (d == 16 || d == 32 || d == 64) && n_rel > 0 && n_rel <= kAttMaxRelLds &&
-         (unsigned long long)n_nodes * (unsigned long long)d * 4ull < (1ull << 32);
+  return att_shape_ok(n_nodes, d, k, n_rel, AttWidths{});
 }
 
 int kgat_att_score_split_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel,
@@ -507,38 +517,26 @@ int kgat_att_score_split_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int
                              const int32_t* g_node, int64_t n_groups, const float* ent,
                              const float* W_R, const float* rel, float* G_tab, float* logits,
                              float* logits_csr, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_groups >= 0 && n_edges < INT32_MAX,
-                 "att_score_split: bad size");
-  if (n_edges == 0) return KGAT_OK;
-  if (!kgat_att_score_split_supported(n_nodes, d, k, n_rel)) {
-    set_error("att_score_split: needs d == k in {16,32,64}, 0 < R <= %d, N*d*4 < 4 GiB (d=%d k=%d R=%d)",
-              kAttMaxRelLds, d, k, n_rel);
-    return KGAT_E_UNSUPPORTED;
-  }
-  KGAT_CHECK_ARG(rel_ptr && perm && src_g && gid && gptr && ent && W_R && rel, "att_score_split: null pointer");
-  KGAT_CHECK_ARG(logits || logits_csr, "att_score_split: no output requested");
-  KGAT_CHECK_ARG(n_groups == 0 || (g_node && G_tab), "att_score_split: null group table");
-  KGAT_CHECK_ARG(logits_csr == nullptr || pos_g != nullptr, "att_score_split: logits_csr needs pos_g");
-  AttArgs a;
-  a.grid = 0;
-  a.st = as_stream(stream);
-  a.n_rel = n_rel; a.rel_ptr = rel_ptr; a.perm = perm; a.src_g = src_g; a.dst_g = nullptr;
-  a.ent = ent; a.W_R = W_R; a.rel = rel; a.logits = logits; a.logits_csr = logits_csr;
-  a.pos_g = pos_g;
-  a.table_bytes = (unsigned long long)n_nodes * (unsigned long long)d * 4ull;
-  a.n_edges = n_edges;
+  AttArgs a = att_args("att_score_split", n_edges, n_rel, rel_ptr, perm, src_g, pos_g, ent, W_R, rel, logits, logits_csr,
+                       stream);
   a.gid = gid; a.gptr = gptr; a.g_node = g_node; a.G_tab = G_tab;
+  KGAT_RETURN_IF(check_att_shape(a, n_nodes, n_groups, d, k, 0, kgat_att_score_split_supported(n_nodes, d, k, n_rel),
+                                 "d == k in {16,32,64}"));
+  KGAT_RETURN_IF(check_att_pointers(a, rel_ptr && perm && src_g && gid && gptr && ent && W_R && rel,
+                                    n_groups == 0 || (g_node && G_tab), "null group table"));
   return launch_att_split_any(d, a);
 }
 
+// the small head kernel's widths: d and k independent
 static bool fold_small(int d, int k) {
   return (d == 8 || d == 16 || d == 32) && k >= 1 && k <= kSmallMaxDim && !(d == k && d >= 16);
 }
 
 int kgat_att_score_folded_supported(int64_t n_nodes, int d, int k, int n_rel) {
-  const bool mfma = d == k && (d == 16 || d == 32 || d == 64 || d == 128);
-  return (mfma || fold_small(d, k)) && n_rel > 0 && n_rel <= kAttMaxRelLds &&
-         (unsigned long long)n_nodes * (unsigned long long)d * 4ull < (1ull << 32);
+  // the small head kernel has its own rule for (d, k); passing d for k leaves the predicate's R and table-size terms,
+  // its width term being true of every d that fold_small lets through
+  return att_shape_ok(n_nodes, d, k, n_rel, AttWidths128{}) ||
+         (fold_small(d, k) && att_shape_ok(n_nodes, d, d, n_rel, AttTailWidths{}));
 }
 
 int kgat_att_score_folded_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel,
@@ -547,48 +545,27 @@ int kgat_att_score_folded_f32(int64_t n_nodes, int64_t n_edges, int d, int k, in
                               const int32_t* g_node, int64_t n_groups, const float* ent,
                               const float* W_R, const float* rel, float* V_tab, float* logits,
                               float* logits_csr, int flags, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_groups >= 0 && n_edges < INT32_MAX,
-                 "att_score_folded: bad size");
-  KGAT_CHECK_ARG((flags & ~KGAT_ATT_F32_PRODUCTS) == 0, "att_score_folded: unknown flag");
-  if (n_edges == 0) return KGAT_OK;
-  if (!kgat_att_score_folded_supported(n_nodes, d, k, n_rel)) {
-    set_error("att_score_folded: needs d == k in {16,32,64,128} or d in {8,16,32} with k <= 32, 0 < R <= %d, N*d*4 < 4 GiB (d=%d k=%d R=%d)",
-              kAttMaxRelLds, d, k, n_rel);
-    return KGAT_E_UNSUPPORTED;
-  }
-  KGAT_CHECK_ARG(rel_ptr && perm && src_g && gid && gptr && ent && W_R && rel, "att_score_folded: null pointer");
-  KGAT_CHECK_ARG(logits || logits_csr, "att_score_folded: no output requested");
-  KGAT_CHECK_ARG(n_groups == 0 || (g_node && V_tab), "att_score_folded: null group table");
-  KGAT_CHECK_ARG(logits_csr == nullptr || pos_g != nullptr, "att_score_folded: logits_csr needs pos_g");
+  AttArgs a = att_args("att_score_folded", n_edges, n_rel, rel_ptr, perm, src_g, pos_g, ent, W_R, rel, logits, logits_csr,
+                       stream);
+  a.gid = gid; a.gptr = gptr; a.g_node = g_node; a.G_tab = V_tab;
+  KGAT_RETURN_IF(check_att_shape(a, n_nodes, n_groups, d, k, flags, kgat_att_score_folded_supported(n_nodes, d, k, n_rel),
+                                 "d == k in {16,32,64,128} or d in {8,16,32} with k <= 32"));
+  KGAT_RETURN_IF(check_att_pointers(a, rel_ptr && perm && src_g && gid && gptr && ent && W_R && rel,
+                                    n_groups == 0 || (g_node && V_tab), "null group table"));
   KGAT_CHECK_ARG((unsigned long long)n_groups * (unsigned long long)d * 4ull < (1ull << 40),
                  "att_score_folded: group table too large");
-  AttArgs a;
-  a.grid = 0;
-  a.st = as_stream(stream);
-  a.n_rel = n_rel; a.rel_ptr = rel_ptr; a.perm = perm; a.src_g = src_g; a.dst_g = nullptr;
-  a.ent = ent; a.W_R = W_R; a.rel = rel; a.logits = logits; a.logits_csr = logits_csr;
-  a.pos_g = pos_g;
-  a.n_edges = n_edges;
-  a.gid = gid; a.gptr = gptr; a.g_node = g_node; a.G_tab = V_tab;
-  a.f32_products = (flags & KGAT_ATT_F32_PRODUCTS) != 0;
+  a.f32_products = (flags & KGAT_ATT_F32_PRODUCTS) != 0;  // (flags checked above)
   if (n_groups > 0) {
     const int rc = fold_small(d, k) ? launch_att_fold_head_small(d, k, a, n_groups) : launch_att_fold_head_any(d, a);
     if (rc != KGAT_OK) return rc;
   }
-  switch (d) {
-    case 8: return launch_att_fold_tail<8>(a);
-    case 16: return launch_att_fold_tail<16>(a);
-    case 32: return launch_att_fold_tail<32>(a);
-    case 64: return launch_att_fold_tail<64>(a);
-    default: return launch_att_fold_tail<128>(a);
-  }
+  return dispatch_width(AttTailWidths{}, d, [&](auto w) { return launch_att_fold_tail<decltype(w)::value>(a); });
 }
 
 int kgat_att_score_fused_supported(int64_t n_nodes, int d, int k, int n_rel) {
-  // d = k = 128 (round 3): bf16-piece products only (KGAT_ATT_F32_PRODUCTS at that width is
-  // KGAT_E_UNSUPPORTED here; the two-launch folded form has it)
-  return d == k && (d == 16 || d == 32 || d == 64 || d == 128) && n_rel > 0 && n_rel <= kAttMaxRelLds &&
-         n_nodes <= (1ll << 28) && (unsigned long long)n_nodes * (unsigned long long)d * 4ull < (1ull << 32);
+  // the packed records hold node ids below 2^28.  d = k = 128 (round 3): bf16-piece products only
+  // (KGAT_ATT_F32_PRODUCTS at that width is KGAT_E_UNSUPPORTED in the entry; the two-launch folded form has it)
+  return n_nodes <= (1ll << 28) && att_shape_ok(n_nodes, d, k, n_rel, AttWidths128{});
 }
 
 static int att_score_fused_run(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel,
@@ -599,39 +576,23 @@ static int att_score_fused_run(int64_t n_nodes, int64_t n_edges, int d, int k, i
                                const float* ent, const float* W_R, const float* rel, float* logits,
                                float* logits_csr, float* logits_g, int flags, long long* part_clocks,
                                kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges < INT32_MAX, "att_score_fused: bad size");
-  KGAT_CHECK_ARG((flags & ~KGAT_ATT_F32_PRODUCTS) == 0, "att_score_fused: unknown flag");
-  if (n_edges == 0) return KGAT_OK;
-  if (!kgat_att_score_fused_supported(n_nodes, d, k, n_rel)) {
-    set_error("att_score_fused: needs d == k in {16,32,64,128}, 0 < R <= %d, N*d*4 < 4 GiB (d=%d k=%d R=%d)",
-              kAttMaxRelLds, d, k, n_rel);
-    return KGAT_E_UNSUPPORTED;
-  }
+  AttArgs a = att_args("att_score_fused", n_edges, n_rel, rel_ptr, perm, nullptr, pos_g, ent, W_R, rel, logits, logits_csr,
+                       stream);
+  a.gptr = gptr; a.g_node = g_node; a.rec_g = rec_g; a.tiles = tiles; a.rel_tptr = rel_tptr;
+  a.part_tptr = part_tptr; a.logits_g = logits_g; a.part_clocks = part_clocks;
+  KGAT_RETURN_IF(check_att_shape(a, n_nodes, 0, d, k, flags, kgat_att_score_fused_supported(n_nodes, d, k, n_rel),
+                                 "d == k in {16,32,64,128}"));
   if (d == 128 && (flags & KGAT_ATT_F32_PRODUCTS)) {
     set_error("att_score_fused: d = 128 runs the bf16-piece products only (the folded form has KGAT_ATT_F32_PRODUCTS)");
     return KGAT_E_UNSUPPORTED;
   }
-  KGAT_CHECK_ARG(n_nodes <= (1ll << 28), "att_score_fused: packed records hold node ids below 2^28");
-  KGAT_CHECK_ARG(rel_ptr && rec_g && gptr && g_node && tiles && rel_tptr && ent && W_R && rel,
-                 "att_score_fused: null pointer");
-  KGAT_CHECK_ARG(logits || logits_csr || logits_g, "att_score_fused: no output requested");
-  KGAT_CHECK_ARG(logits == nullptr || perm != nullptr, "att_score_fused: edge-id ordered logits need perm");
-  KGAT_CHECK_ARG(logits_csr == nullptr || pos_g != nullptr, "att_score_fused: logits_csr needs pos_g");
+  KGAT_RETURN_IF(check_att_pointers(a, rel_ptr && rec_g && gptr && g_node && tiles && rel_tptr && ent && W_R && rel,
+                                    logits == nullptr || perm != nullptr, "edge-id ordered logits need perm"));
   KGAT_CHECK_ARG((part_tptr == nullptr) == (n_parts == 0) && n_parts >= 0 && n_parts <= 65536,
                  "att_score_fused: part_tptr and n_parts go together");
-  AttArgs a;
-  a.grid = (unsigned)n_parts;
-  a.part_tptr = part_tptr;
+  a.n_parts = (unsigned)n_parts;  // only once they are known to be good
   a.f32_products = (flags & KGAT_ATT_F32_PRODUCTS) != 0;
-  a.st = as_stream(stream);
-  a.n_rel = n_rel; a.rel_ptr = rel_ptr; a.perm = perm; a.src_g = nullptr; a.dst_g = nullptr;
-  a.ent = ent; a.W_R = W_R; a.rel = rel; a.logits = logits; a.logits_csr = logits_csr;
-  a.pos_g = pos_g;
-  a.n_edges = n_edges;
-  a.gid = nullptr; a.gptr = gptr; a.g_node = g_node;
-  a.rec_g = rec_g; a.logits_g = logits_g;
-  a.part_clocks = part_clocks;
-  return launch_att_fold_fused_any(d, a, rel_tptr, tiles);
+  return launch_att_fold_fused_any(d, a);
 }
 
 int kgat_att_score_fused_f32(int64_t n_nodes, int64_t n_edges, int d, int k, int n_rel,

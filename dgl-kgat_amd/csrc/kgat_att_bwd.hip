@@ -227,8 +227,6 @@ __global__ __launch_bounds__(256) void att_bwd_reduce_kernel(int n_rel, int dd, 
   else grad_rel[(size_t)r * k + (e - dd)] = s;
 }
 
-static bool bwd_width(int d) { return d == 16 || d == 32 || d == 64 || d == 128; }
-
 // workgroups of the dense kernel: a function of the sizes and of the device's compute-unit count (the partial slots and
 // the summation order follow it, so results are bitwise reproducible on one device model, not across models).  Per
 // compute unit: what the kernel's registers and LDS let be resident at once (d = 64: 138 VGPRs -> 3 waves per SIMD;
@@ -272,8 +270,7 @@ using namespace kgat;
 extern "C" {
 
 int kgat_att_score_bwd_supported(int64_t n_nodes, int d, int k, int n_rel) {
-  return d == k && bwd_width(d) && n_nodes >= 0 && n_rel > 0 && n_rel <= kAttMaxRelLds &&
-         (unsigned long long)n_nodes * (unsigned long long)d * 4ull < (1ull << 32);
+  return n_nodes >= 0 && att_shape_ok(n_nodes, d, k, n_rel, AttWidths128{});
 }
 
 size_t kgat_att_score_bwd_workspace_bytes(int64_t n_nodes, int64_t n_scored, int64_t n_groups, int d, int k, int n_rel) {

@@ -81,36 +81,52 @@ __device__ __forceinline__ void att_load_a(AFrag<D_, TILES>& f, const float* __r
 }
 
 
+// What a launcher gets from an entry of kgat_att.hip: the arrays every form reads, then each form's own.
 struct AttArgs {
-  unsigned grid;
+  const char* entry;  // names the entry in its messages
   hipStream_t st;
   int n_rel;
-  const int32_t *rel_ptr, *perm, *src_g, *dst_g;
+  int64_t n_edges;
+  const int32_t *rel_ptr, *perm, *src_g, *pos_g;
   const float *ent, *W_R, *rel;
   float *logits, *logits_csr;
-  const int32_t* pos_g;
-  // split form (head groups): gid per grouped position, gptr per relation, g_node per group,
-  // G table (n_groups x k)
+  // one-kernel form: the grouped head nodes; workgroups of the chunk and generic kernels
+  const int32_t* dst_g = nullptr;
+  unsigned n_blocks = 0;
+  // group forms: gid per grouped position, gptr per relation, g_node per group, the per-group scratch table
+  // (split: G, n_groups x k; folded: V, n_groups x d)
   const int32_t *gid = nullptr, *gptr = nullptr, *g_node = nullptr;
   float* G_tab = nullptr;
-  unsigned long long table_bytes = 0;
-  int64_t n_edges = 0;
-  bool needs_memset = true;
-  const int32_t* part_tptr = nullptr;  // fused form: tile range per workgroup (grid = number of parts)
-  const int32_t* rec_g = nullptr;      // fused form: packed (source node | group slot << 28) per grouped position
-  float* logits_g = nullptr;           // fused form: logits in grouped order
   bool f32_products = false;           // fused / folded forms: fp32 MFMA products instead of the bf16-piece products
-  long long* part_clocks = nullptr;    // fused form, measurement aid: s_memrealtime at every workgroup's start and end
+  // fused form
+  const int32_t* rec_g = nullptr;      // packed (source node | group slot << 28) per grouped position
+  const int32_t *tiles = nullptr, *rel_tptr = nullptr;  // work tiles (kgat_fold_tiles) and their range per relation
+  const int32_t* part_tptr = nullptr;  // tile range per workgroup, n_parts of them (null: one workgroup per CU)
+  unsigned n_parts = 0;
+  float* logits_g = nullptr;           // logits in grouped order
+  long long* part_clocks = nullptr;    // measurement aid: s_memrealtime at every workgroup's start and end
 };
 
+// The widths with W_r in a wavefront's registers (persistent, split, fold-head, fused kernels) and with the d = 128
+// kernels that keep it in LDS beside them.
+using AttWidths = WidthList<16, 32, 64>;
+using AttWidths128 = WidthList<16, 32, 64, 128>;
+constexpr int kAttMaxRelLds = 4096;
+
+// The support rule of every MFMA form: one square width of the form's list, a per-relation tile prefix that fits the kernels'
+// LDS table, node rows addressed with 32-bit byte offsets.
+template <typename Widths>
+inline bool att_shape_ok(int64_t n_nodes, int d, int k, int n_rel, Widths widths) {
+  return d == k && has_width(widths, d) && n_rel > 0 && n_rel <= kAttMaxRelLds &&
+         (unsigned long long)n_nodes * (unsigned long long)d * 4ull < (1ull << 32);
+}
 
 // kgat_att_persistent.hip (compiled with -amdgpu-mfma-vgpr-form: its epilogue reads the MFMA
-// results from VGPRs directly); returns KGAT_E_UNSUPPORTED for widths it does not cover.
+// results from VGPRs directly); each returns KGAT_E_UNSUPPORTED for widths it does not cover.
 int launch_att_persistent_any(int d, const AttArgs& a);
 int launch_att_split_any(int d, const AttArgs& a);
 int launch_att_fold_head_any(int d, const AttArgs& a);  // writes V (n_groups x d) into a.G_tab
-int launch_att_fold_fused_any(int d, const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles);
-constexpr int kAttMaxRelLds = 4096;
+int launch_att_fold_fused_any(int d, const AttArgs& a);
 
 // Lanes that share one edge in the per-edge dot product of the folded forms (a lane holds
 // d / (4 * lanes) float4 pieces of the tail row and of the group's V row).  Fewer lanes per edge

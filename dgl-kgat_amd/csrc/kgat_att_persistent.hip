@@ -1462,27 +1462,33 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
   }
 }
 
-template <int D_, int OUT, bool X3>
-static void launch_att_fold_fused_form(const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles) {
-  const unsigned grid = a.part_tptr ? a.grid : (unsigned)device_cu_count();
-  hipLaunchKernelGGL((att_fold_fused_kernel<D_, OUT, X3>), dim3(grid), dim3(kFusedThreads), 0, a.st, a.n_rel,
-                     a.n_edges, a.rel_ptr, rel_tptr, reinterpret_cast<const int4*>(tiles), a.gptr, a.g_node, a.rec_g,
-                     a.perm, a.pos_g, a.ent, a.W_R, a.rel, a.logits, a.logits_csr, a.logits_g, a.part_tptr, a.part_clocks);
+// Where the logits go -> the fused kernels' OUT, as an integral_constant: edge-id order asked for 2, else CSR order 1,
+// else grouped order only 0.
+template <typename F>
+static void dispatch_att_out(const AttArgs& a, F&& f) {
+  if (a.logits) f(std::integral_constant<int, 2>{});
+  else if (a.logits_csr) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
-template <int D_, bool X3>
-static void launch_att_fold_fused_out(const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles) {
-  if (a.logits) launch_att_fold_fused_form<D_, 2, X3>(a, rel_tptr, tiles);
-  else if (a.logits_csr) launch_att_fold_fused_form<D_, 1, X3>(a, rel_tptr, tiles);
-  else launch_att_fold_fused_form<D_, 0, X3>(a, rel_tptr, tiles);
+// One launch of a fused kernel (this one or att_fold_fused128_kernel: the same parameters): a workgroup per part of the
+// tile split, or per compute unit without one.
+template <typename Kernel>
+static void launch_att_fused_kernel(Kernel kernel, int threads, const AttArgs& a) {
+  const unsigned grid = a.part_tptr ? a.n_parts : (unsigned)device_cu_count();
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, a.st, a.n_rel, a.n_edges, a.rel_ptr, a.rel_tptr,
+                     reinterpret_cast<const int4*>(a.tiles), a.gptr, a.g_node, a.rec_g, a.perm, a.pos_g, a.ent, a.W_R,
+                     a.rel, a.logits, a.logits_csr, a.logits_g, a.part_tptr, a.part_clocks);
 }
-
 
 template <int D_>
-static int launch_att_fold_fused(const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles) {
+static int launch_att_fold_fused(const AttArgs& a) {
   constexpr bool kCanSplit = D_ % 32 == 0;
-  if (kCanSplit && !a.f32_products) launch_att_fold_fused_out<D_, kCanSplit>(a, rel_tptr, tiles);
-  else launch_att_fold_fused_out<D_, false>(a, rel_tptr, tiles);
+  dispatch_att_out(a, [&](auto out) {
+    constexpr int OUT = decltype(out)::value;
+    if (kCanSplit && !a.f32_products) launch_att_fused_kernel(att_fold_fused_kernel<D_, OUT, kCanSplit>, kFusedThreads, a);
+    else launch_att_fused_kernel(att_fold_fused_kernel<D_, OUT, false>, kFusedThreads, a);
+  });
   KGAT_CHECK_LAUNCH("att_fold_fused");
   return KGAT_OK;
 }
@@ -1835,61 +1841,31 @@ constexpr int kF128Passes = 2;
   }
 }
 
-// Round 3's wave-role experiments (producer / consumer waves; measured, not adopted - notes in the file)
-
-template <int OUT>
-static void launch_att_fold_fused128_form(const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles) {
-  const unsigned grid = a.part_tptr ? a.grid : (unsigned)device_cu_count();
-  hipLaunchKernelGGL((att_fold_fused128_kernel<OUT>), dim3(grid), dim3(kFused128Threads), 0, a.st, a.n_rel, a.n_edges,
-                     a.rel_ptr, rel_tptr, reinterpret_cast<const int4*>(tiles), a.gptr, a.g_node, a.rec_g, a.perm,
-                     a.pos_g, a.ent, a.W_R, a.rel, a.logits, a.logits_csr, a.logits_g, a.part_tptr, a.part_clocks);
-}
-
-static int launch_att_fold_fused128(const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles) {
-  if (a.logits) launch_att_fold_fused128_form<2>(a, rel_tptr, tiles);
-  else if (a.logits_csr) launch_att_fold_fused128_form<1>(a, rel_tptr, tiles);
-  else launch_att_fold_fused128_form<0>(a, rel_tptr, tiles);
+static int launch_att_fold_fused128(const AttArgs& a) {
+  dispatch_att_out(a, [&](auto out) {
+    launch_att_fused_kernel(att_fold_fused128_kernel<decltype(out)::value>, kFused128Threads, a);
+  });
   KGAT_CHECK_LAUNCH("att_fold_fused128");
   return KGAT_OK;
 }
 
-
-int launch_att_fold_fused_any(int d, const AttArgs& a, const int32_t* rel_tptr, const int32_t* tiles) {
-  switch (d) {
-    case 16: return launch_att_fold_fused<16>(a, rel_tptr, tiles);
-    case 32: return launch_att_fold_fused<32>(a, rel_tptr, tiles);
-    case 64: return launch_att_fold_fused<64>(a, rel_tptr, tiles);
-    case 128: return a.f32_products ? KGAT_E_UNSUPPORTED : launch_att_fold_fused128(a, rel_tptr, tiles);
-    default: return KGAT_E_UNSUPPORTED;
-  }
+// ---- width -> launcher: the lists are the kernels built (dispatch_width, kgat_common.h); d = 128 has kernels of its own
+int launch_att_fold_fused_any(int d, const AttArgs& a) {
+  if (d == 128) return a.f32_products ? KGAT_E_UNSUPPORTED : launch_att_fold_fused128(a);
+  return dispatch_width(AttWidths{}, d, [&](auto w) { return launch_att_fold_fused<decltype(w)::value>(a); });
 }
 
 int launch_att_fold_head_any(int d, const AttArgs& a) {
-  switch (d) {
-    case 16: return launch_att_fold_head<16>(a);
-    case 32: return launch_att_fold_head<32>(a);
-    case 64: return launch_att_fold_head<64>(a);
-    case 128: return launch_att_fold_head_lds<128>(a);
-    default: return KGAT_E_UNSUPPORTED;
-  }
+  if (d == 128) return launch_att_fold_head_lds<128>(a);
+  return dispatch_width(AttWidths{}, d, [&](auto w) { return launch_att_fold_head<decltype(w)::value>(a); });
 }
 
 int launch_att_split_any(int d, const AttArgs& a) {
-  switch (d) {
-    case 16: return launch_att_split_d<16>(a);
-    case 32: return launch_att_split_d<32>(a);
-    case 64: return launch_att_split_d<64>(a);
-    default: return KGAT_E_UNSUPPORTED;
-  }
+  return dispatch_width(AttWidths{}, d, [&](auto w) { return launch_att_split_d<decltype(w)::value>(a); });
 }
 
 int launch_att_persistent_any(int d, const AttArgs& a) {
-  switch (d) {
-    case 16: return launch_att_persistent<16, 0>(a);
-    case 32: return launch_att_persistent<32, 0>(a);
-    case 64: return launch_att_persistent<64, 0>(a);
-    default: return KGAT_E_UNSUPPORTED;
-  }
+  return dispatch_width(AttWidths{}, d, [&](auto w) { return launch_att_persistent<decltype(w)::value, 0>(a); });
 }
 
 }  // namespace kgat

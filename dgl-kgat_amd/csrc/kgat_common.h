@@ -82,6 +82,15 @@ inline int dispatch_widths(WidthSquare<D...>, int a, int b, F&& f) {
   (void)((a == D && row(std::integral_constant<int, D>{})) || ...);
   return rc;
 }
+// One width: a list is the diagonal of a pair table, so the same machinery serves it.  dispatch_width(list, d, f) calls
+// f(D) under the contract above; has_width(list, d) is the membership test a `_supported` predicate states.
+template <int... D> using WidthList = WidthPairs<WidthPair<D, D>...>;
+template <typename F, typename... P>
+inline int dispatch_width(WidthPairs<P...> list, int d, F&& f) {
+  return dispatch_widths(list, d, d, [&](auto w, auto) { return f(w); });
+}
+template <int... D>
+constexpr bool has_width(WidthPairs<WidthPair<D, D>...>, int d) { return ((d == D) || ...); }
 
 // Device-side primitives implemented in kgat_graph.hip, reused by other translation units.
 size_t scan_workspace_elems(int64_t n);
@@ -103,6 +112,13 @@ int radix_sort_index(const int32_t* keys_in, int64_t n, int key_bits, int32_t* v
       kgat::set_error(__VA_ARGS__); \
       return KGAT_E_BADARG;         \
     }                               \
+  } while (0)
+
+// A check function's result: an error is returned, a positive value ("nothing to do") ends the entry with KGAT_OK.
+#define KGAT_RETURN_IF(rc_expr)                            \
+  do {                                                     \
+    const int rc__ = (rc_expr);                            \
+    if (rc__ != KGAT_OK) return rc__ > 0 ? KGAT_OK : rc__; \
   } while (0)
 
 #define KGAT_CHECK_LAUNCH(what)                                                    \

@@ -1002,12 +1002,6 @@ static int check_backward(const char* what, bool supported, int64_t n_rows, int 
   return KGAT_OK;
 }
 
-#define KGAT_RETURN_IF(rc_expr)                    \
-  do {                                             \
-    const int rc__ = (rc_expr);                    \
-    if (rc__ != KGAT_OK) return rc__ > 0 ? KGAT_OK : rc__; \
-  } while (0)
-
 int kgat_bi_interaction_f32(int64_t n_rows, int d_in, int d_out, const float* P, const float* W2,
                             float negative_slope, float* h_out, float* norm_out,
                             int64_t norm_stride, kgat_stream_t stream) {

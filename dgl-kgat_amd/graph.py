@@ -760,50 +760,49 @@ class DGLGraph:
         # with the per-group vectors in LDS / two launches with a table); "split" keeps the
         # reference's contraction order (bit-identical to "one")
 
-        def run(form):
-            if form == "fused":
-                tiles = _fused_tiles(groups, d)  # graph-static work tiles of the fused kernel
-                rec, _ = _fused_statics(groups)
-                # the logits leave in grouped order (coalesced stores); the softmax reads them through
-                # the inverse position map (a 4-byte scatter into CSR order wrote 73 MB for 14.6 MB of
-                # logits on the benchmark graph)
-                return ops.att_score_fused(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.pos_g,
-                                           groups.gid, groups.gptr, groups.g_node, tiles[0], tiles[1],
-                                           ent_c, W_c, rel_c, want_eid=False, want_csr=False, want_grouped=True,
-                                           part_tptr=tiles[2], f32_products=_f32_products(), rec_g=rec)[2]
-            if form in ("folded", "split"):
-                folded = form == "folded"
-                width = d if folded else k
-                g_tab = groups.g_tab.get(width)  # per-group scratch table, kept with the graph
-                if g_tab is None:
-                    g_tab = groups.g_tab[width] = torch.empty((max(groups.n_groups, 1), width), dtype=torch.float32,
-                                                              device=dev)
-                return ops.att_score_split(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.pos_g,
-                                           groups.gid, groups.gptr, groups.g_node, groups.n_groups,
-                                           ent_c, W_c, rel_c, g_tab=g_tab, want_eid=False, folded=folded,
-                                           f32_products=folded and _f32_products())[1]
-            return ops.att_score(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.dst_g,
-                                 ent_c, W_c, rel_c, pos_g=groups.pos_g, algo="auto" if form == "one" else form)[1]
+        def fused():
+            tiles = _fused_tiles(groups, d)  # graph-static work tiles of the fused kernel
+            rec, _ = _fused_statics(groups)
+            # the logits leave in grouped order (coalesced stores); the softmax reads them through
+            # the inverse position map (a 4-byte scatter into CSR order wrote 73 MB for 14.6 MB of
+            # logits on the benchmark graph)
+            return ops.att_score_fused(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.pos_g,
+                                       groups.gid, groups.gptr, groups.g_node, tiles[0], tiles[1],
+                                       ent_c, W_c, rel_c, want_eid=False, want_csr=False, want_grouped=True,
+                                       part_tptr=tiles[2], f32_products=_f32_products(), rec_g=rec)[2]
 
-        form = options.att_form if algo == "auto" else algo
-        race = form == "race"
+        def two_launch(folded):
+            width = d if folded else k
+            g_tab = groups.g_tab.get(width)  # per-group scratch table, kept with the graph
+            if g_tab is None:
+                g_tab = groups.g_tab[width] = torch.empty((max(groups.n_groups, 1), width), dtype=torch.float32,
+                                                          device=dev)
+            return ops.att_score_split(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.pos_g,
+                                       groups.gid, groups.gptr, groups.g_node, groups.n_groups,
+                                       ent_c, W_c, rel_c, g_tab=g_tab, want_eid=False, folded=folded,
+                                       f32_products=folded and _f32_products())[1]
+
+        def one():
+            return ops.att_score(st.n_nodes, groups.rel_ptr, groups.perm, groups.src_g, groups.dst_g,
+                                 ent_c, W_c, rel_c, pos_g=groups.pos_g, algo=one_algo)[1]
+
+        # form -> (runner, order of the logits it returns: "grouped", read through the inverse position map - it takes
+        # the place of `eid` on the softmax's input side - or "csr")
+        forms = {"fused": (fused, "grouped"), "folded": (lambda: two_launch(True), "csr"),
+                 "split": (lambda: two_launch(False), "csr"), "one": (one, "csr")}
+        form, one_algo = options.att_form if algo == "auto" else algo, "auto"
         if form in ("auto", "race"):
+            race_run = (lambda f: forms[f][0]()) if form == "race" else None
             form = groups.g_tab.get(("form", d, k))
-        if form is None:
-            form = self._pick_attention_form(groups, n_rel, d, k, run if race else None)
-            groups.g_tab[("form", d, k)] = form
-        logits = run(form)
-        if form not in ("fused", "folded", "split"):
-            form = "one"
+            if form is None:
+                form = groups.g_tab[("form", d, k)] = self._pick_attention_form(groups, n_rel, d, k, race_run)
+        elif form not in forms:   # a kernel choice of the one-kernel entry (ops.ATT_ALGO)
+            form, one_algo = "one", form
+        run, order = forms[form]
+        logits = run()
         st.last_att_form = (form, groups.n_groups)
-        if form == "fused":
-            # grouped-order logits: the sweep gathers logits[gpos_csr[q]] for CSR position q (the map
-            # takes the place of `eid` on the input side; no edge-id-ordered output is asked for)
-            _, a_csr = ops.edge_softmax(csr.indptr, csr.row_of, _gpos_csr(groups), logits,
-                                        in_csr_order=False, want_out=False, want_csr=True)
-        else:
-            _, a_csr = ops.edge_softmax(csr.indptr, csr.row_of, csr.eid, logits, in_csr_order=True,
-                                        want_out=False, want_csr=True)
+        _, a_csr = ops.edge_softmax(csr.indptr, csr.row_of, _gpos_csr(groups) if order == "grouped" else csr.eid, logits,
+                                    in_csr_order=order == "csr", want_out=False, want_csr=True)
         from . import lazy as lazy_mod
         if lazy is None:
             lazy = lazy_mod.enabled()

@@ -151,18 +151,30 @@ def gather(index, values, out=None):
     return out
 
 
-def att_score(n_nodes, rel_ptr, perm, src_g, dst_g, ent, W_R, rel, pos_g=None, algo="auto"):
-    """Attention logits (E,) in edge-id order; with pos_g (CSR position of edge perm[i]) also
-    in CSR order."""
+def _att_params(n_nodes, ent, W_R, rel):
+    """The parameters every attention entry takes, checked: (ent, W_R, rel, n_rel, d, k)."""
     ent = _need(ent, torch.float32, "ent")
     n_rel, d, k = W_R.shape
     W_R = _need(W_R, torch.float32, "W_R")
     rel = _need(rel, torch.float32, "rel", (n_rel, k))
     if ent.shape != (n_nodes, d):
         raise ValueError("ent has shape %s, expected %s" % (tuple(ent.shape), (n_nodes, d)))
+    return ent, W_R, rel, n_rel, d, k
+
+
+def _att_rel_arrays(n_rel, **arrays):
+    """The per-relation index arrays of an attention entry (rel_ptr, gptr, rel_tptr): int32, (R+1,)."""
+    for name, t in arrays.items():
+        _need(t, torch.int32, name, (n_rel + 1,))
+
+
+def att_score(n_nodes, rel_ptr, perm, src_g, dst_g, ent, W_R, rel, pos_g=None, algo="auto"):
+    """Attention logits (E,) in edge-id order; with pos_g (CSR position of edge perm[i]) also
+    in CSR order."""
+    ent, W_R, rel, n_rel, d, k = _att_params(n_nodes, ent, W_R, rel)
     perm = _need(perm, torch.int32, "perm")
     e = perm.numel()
-    rel_ptr = _need(rel_ptr, torch.int32, "rel_ptr", (n_rel + 1,))
+    _att_rel_arrays(n_rel, rel_ptr=rel_ptr)
     src_g = _need(src_g, torch.int32, "src_g", (e,))
     dst_g = _need(dst_g, torch.int32, "dst_g", (e,))
     logits = torch.empty(e, dtype=torch.float32, device=ent.device)
@@ -212,16 +224,12 @@ def att_score_split(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, n_g
     """Attention logits via head groups (see kgat_att_score_split_f32; folded=True:
     kgat_att_score_folded_f32, whose scratch table is n_groups x d; f32_products: its
     KGAT_ATT_F32_PRODUCTS flag).  Returns (logits edge-id order, logits CSR order or None)."""
-    ent = _need(ent, torch.float32, "ent")
-    n_rel, d, k = W_R.shape
-    W_R = _need(W_R, torch.float32, "W_R")
-    rel = _need(rel, torch.float32, "rel", (n_rel, k))
+    ent, W_R, rel, n_rel, d, k = _att_params(n_nodes, ent, W_R, rel)
     perm = _need(perm, torch.int32, "perm")
     e = perm.numel()
     for name, t in (("src_g", src_g), ("pos_g", pos_g), ("gid", gid)):
         _need(t, torch.int32, name, (e,))
-    _need(rel_ptr, torch.int32, "rel_ptr", (n_rel + 1,))
-    _need(gptr, torch.int32, "gptr", (n_rel + 1,))
+    _att_rel_arrays(n_rel, rel_ptr=rel_ptr, gptr=gptr)
     _need(g_node, torch.int32, "g_node")
     width = d if folded else k
     if g_tab is None:
@@ -338,12 +346,8 @@ def att_score_fused(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, til
     default when d % 32 == 0.  `part_clocks` (int64, 2 x n_parts): measurement aid
     (kgat_att_score_fused_timed_f32) - every workgroup's start / end time in 100 MHz ticks.  Returns (logits edge-id
     order, logits CSR order) - unrequested ones None - and, with want_grouped, a third item: the logits in grouped order."""
-    ent = _need(ent, torch.float32, "ent")
-    n_rel, d, k = W_R.shape
-    W_R = _need(W_R, torch.float32, "W_R")
-    rel = _need(rel, torch.float32, "rel", (n_rel, k))
-    _need(rel_ptr, torch.int32, "rel_ptr", (n_rel + 1,))
-    _need(gptr, torch.int32, "gptr", (n_rel + 1,))
+    ent, W_R, rel, n_rel, d, k = _att_params(n_nodes, ent, W_R, rel)
+    _att_rel_arrays(n_rel, rel_ptr=rel_ptr, gptr=gptr, rel_tptr=rel_tptr)
     if rec_g is None:
         rec_g = att_pack_records(rel_ptr, gptr, gid, src_g)
     rec_g = _need(rec_g, torch.int32, "rec_g")
@@ -352,7 +356,6 @@ def att_score_fused(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, til
         perm = _need(perm, torch.int32, "perm", (e,))
     if want_csr:
         pos_g = _need(pos_g, torch.int32, "pos_g", (e,))
-    _need(rel_tptr, torch.int32, "rel_tptr", (n_rel + 1,))
     _need(g_node, torch.int32, "g_node")
     _need(tiles, torch.int32, "tiles")
     n_parts = 0

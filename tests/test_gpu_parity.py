@@ -489,6 +489,40 @@ def test_att_score_mfma_vs_oracle(K, dev, d):
         assert rel_err_inf(logits, ref) < 1e-5, algo
 
 
+@pytest.mark.parametrize("algo", ["mfma", "mfma_chunk"])
+def test_att_score_named_mfma_refuses_other_widths(K, dev, algo):
+    """A caller who names an MFMA kernel at a (d, k) it does not cover is refused, not handed the generic kernel."""
+    from dgl_kgat_amd import ops
+    n, e, R, d, k = 50, 400, 3, 12, 20
+    src, dst = random_graph(14, n, e)
+    et = np.random.default_rng(15).integers(0, R, e).astype(np.int32)
+    rel_ptr, perm = ops.group_by_relation(t32(et, dev), R)
+    sg, dg = ops.gather(perm, t32(src, dev)), ops.gather(perm, t32(dst, dev))
+    ent, W, rel = (torch.zeros(s, device=dev) for s in ((n, d), (R, d, k), (R, k)))
+    with pytest.raises(ops.KGATLibraryError) as info:
+        ops.att_score(n, rel_ptr, perm, sg, dg, ent, W, rel, algo=algo)
+    assert "att_score: the MFMA kernel covers d == k in {16,32,64,128}, got d=12 k=20" in str(info.value)
+    logits, _ = ops.att_score(n, rel_ptr, perm, sg, dg, ent, W, rel, algo="generic")   # the kernel that does cover it
+    assert logits.shape == (e,) and not logits.any()
+
+
+def test_att_wrappers_refuse_a_wrong_ent_shape_alike(K, dev):
+    """The three wrappers check their parameters through one helper: an `ent` of the wrong height is a ValueError
+    from each, in the same words (tests/test_att_host.py has the one-kernel wrapper's, without a device)."""
+    from dgl_kgat_amd import ops
+    n, e, R, d = 100, 10, 2, 16
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)   # noqa: E731
+    ent, W, rel = (torch.zeros(s, device=dev) for s in ((n + 1, d), (R, d, d), (R, d)))
+    calls = [lambda: ops.att_score(n, i32(R + 1), i32(e), i32(e), i32(e), ent, W, rel),
+             lambda: ops.att_score_split(n, i32(R + 1), i32(e), i32(e), i32(e), i32(e), i32(R + 1), i32(4), 4, ent, W, rel),
+             lambda: ops.att_score_fused(n, i32(R + 1), i32(e), i32(e), i32(e), i32(e), i32(R + 1), i32(4), i32(3, 4),
+                                         i32(R + 1), ent, W, rel, rec_g=i32(e))]
+    for call in calls:
+        with pytest.raises(ValueError) as info:
+            call()
+        assert "ent has shape (101, 16), expected (100, 16)" in str(info.value)
+
+
 def _grouped_by_relation_and_destination(ops, n, src, dst, et, R, dev):
     """The structure DGLGraph.rel_groups builds: CSR-ordered edges grouped stably by relation."""
     indptr, col, eid, row_of = ops.csr_from_coo(n, t32(src, dev), t32(dst, dev))
