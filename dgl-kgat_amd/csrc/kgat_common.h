@@ -18,6 +18,8 @@ inline hipStream_t as_stream(kgat_stream_t s) { return reinterpret_cast<hipStrea
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }  // float4 / int4 accesses
+
 // Carves 256-byte aligned regions out of a caller-provided workspace.
 struct Carver {
   char* base;
@@ -83,7 +85,8 @@ inline int dispatch_widths(WidthSquare<D...>, int a, int b, F&& f) {
   return rc;
 }
 // One width: a list is the diagonal of a pair table, so the same machinery serves it.  dispatch_width(list, d, f) calls
-// f(D) under the contract above; has_width(list, d) is the membership test a `_supported` predicate states.
+// f(D) under the contract above; has_width(list, d) / has_widths(table, a, b) are the membership tests a `_supported`
+// predicate states.
 template <int... D> using WidthList = WidthPairs<WidthPair<D, D>...>;
 template <typename F, typename... P>
 inline int dispatch_width(WidthPairs<P...> list, int d, F&& f) {
@@ -91,6 +94,8 @@ inline int dispatch_width(WidthPairs<P...> list, int d, F&& f) {
 }
 template <int... D>
 constexpr bool has_width(WidthPairs<WidthPair<D, D>...>, int d) { return ((d == D) || ...); }
+template <int... A, int... B>
+constexpr bool has_widths(WidthPairs<WidthPair<A, B>...>, int a, int b) { return ((a == A && b == B) || ...); }
 
 // Device-side primitives implemented in kgat_graph.hip, reused by other translation units.
 size_t scan_workspace_elems(int64_t n);

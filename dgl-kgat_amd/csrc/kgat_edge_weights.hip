@@ -18,8 +18,6 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 constexpr int kBlock = 256;
 constexpr int64_t kMaxBlocks = 2048;  // 256 CUs x 8 blocks; the rest of a larger E is grid-strided
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 inline unsigned grid_for(int64_t n_vec, int64_t n_tail) {
   const int64_t items = n_vec > n_tail ? n_vec : n_tail;
   int64_t blocks = (items + kBlock - 1) / kBlock;

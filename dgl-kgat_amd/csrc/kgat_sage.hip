@@ -1,340 +1,22 @@
 // GraphSAGE (mean aggregator) layer for gfx950: the kernels behind dgl.nn.pytorch.conv.SAGEConv(aggregator_type="mean")
 // of reference models.py:98-100,107-109 (gnn_model = "graphsage").  DGL 0.4.x SAGEConv.forward, homogeneous graph:
 //   hd = feat_drop(h);  h_neigh[v] = mean_{u->v} hd[u] (0 without in-edges);  rst = fc_self(hd) + fc_neigh(h_neigh)
-//   followed by the activation.  Four operators:
-//  * copy_reduce: update_all(fn.copy_src, fn.sum | fn.mean).  The aggregation's merge-path decomposition
-//    (kgat_spmm_impl.h) without a weight stream: an edge tile's (col, row) pairs are staged in LDS as 8-byte records
-//    (the weighted form needs 16), a lane group walks a run of consecutive CSR positions and adds the gathered rows,
-//    the run's first / last row go through LDS (the workgroup combines them in run order) and the tile's first / last
-//    row through a global partial buffer that the finish launch sums in tile order.  The mean divides the fp32 sum by
-//    the in-degree where a row is completed.  No float atomics: bitwise reproducible.  Other widths: one wavefront per
-//    row.  The backward of copy_src -> mean w.r.t. the source feature is the same operator (sum) on the reversed CSR
-//    over rows pre-scaled by 1 / max(deg, 1) of their destination (sage_bwd_input_kernel writes them so).
+//   followed by the activation.  The dense operators:
+//  * the aggregation itself is kgat_copy_reduce_f32 (update_all(fn.copy_src, fn.sum | fn.mean)), which lives with the
+//    other merge-path reducers in kgat_spmm.hip.  The backward of copy_src -> mean w.r.t. the source feature is the same
+//    operator (sum) on the reversed CSR over rows pre-scaled by 1 / max(deg, 1) of their destination
+//    (sage_bwd_input_kernel writes them so).
 //  * sage_dense: Z = act(H W_self^T + HN W_neigh^T + b_self + b_neigh) on v_mfma_f32_16x16x4_f32 (exact fp32): one
 //    wavefront per 16-row tile, both weights staged once per workgroup in MFMA fragment order in LDS; optional
 //    L2-normalised copy into a slice of the readout and the ego block (a copy of H) as kgat_aggregator_f32.
 //  * dropout_rows: out = (x [+ x2]) * keep / (1 - p) with the counter hash of the bi-interaction's dropout.
 //  * sage_bwd_input / sage_bwd_weight: grad_pre W_self, (grad_pre W_neigh) / max(deg, 1) and per-workgroup partials
 //    of grad_pre^T H, grad_pre^T HN and the column sums of grad_pre.
-#include "kgat_spmm_impl.h"
+#include "kgat_common.h"
 
 namespace kgat {
 
 typedef float floatx4_g __attribute__((ext_vector_type(4)));
-
-// --------------------------------------------------------------------------------------------- copy_src -> sum | mean
-template <bool MEAN>
-__device__ __forceinline__ float4 reduce_fin(const float4& v, int32_t cnt) {
-  if (!MEAN) return v;
-  const float c = (float)(cnt > 1 ? cnt : 1);
-  return make_float4(v.x / c, v.y / c, v.z / c, v.w / c);
-}
-
-template <int LPR, int C, bool MEAN>
-__global__ __launch_bounds__(SpmmGeom<LPR>::THREADS) void copy_merge_kernel(
-    int64_t e0, int64_t e1, int32_t row0, const int32_t* __restrict__ col, const int32_t* __restrict__ row_of,
-    const float4* __restrict__ X, float4* __restrict__ out, float4* __restrict__ bpart) {
-  constexpr int NSUB = SpmmGeom<LPR>::NSUB;
-  constexpr int TE = NSUB * C;
-  constexpr int G = 4;  // edges per group
-  static_assert(C % G == 0, "run length must be a multiple of the group size");
-  __shared__ int2 s_rec[TE];  // (source row, destination row)
-  __shared__ float4 s_part[NSUB][2][LPR];
-  __shared__ int32_t s_row[NSUB][2];
-  __shared__ int32_t s_cnt[NSUB][2];
-
-  const int tid = threadIdx.x;
-  const int sub = tid / LPR, sl = tid % LPR;
-  const unsigned tile = blockIdx.x;
-  const int64_t tile0 = e0 + (int64_t)tile * TE;
-  const int64_t tile1 = (tile0 + TE < e1) ? tile0 + TE : e1;
-  const int n_tile = (int)(tile1 - tile0);
-  for (int k = tid; k < TE; k += SpmmGeom<LPR>::THREADS) {
-    int2 rec = make_int2(0, -1);
-    if (k < n_tile) {
-      const int64_t p = tile0 + k;
-      rec = make_int2(__builtin_nontemporal_load(col + p), __builtin_nontemporal_load(row_of + p));
-    }
-    s_rec[k] = rec;
-  }
-  __syncthreads();
-  const int32_t first_row = __builtin_amdgcn_readfirstlane(s_rec[0].y);
-  const int32_t last_row = __builtin_amdgcn_readfirstlane(s_rec[n_tile - 1].y);
-
-  const int2* run = s_rec + sub * C;
-  const float4* const Xl = X + sl;
-  int n_run = n_tile - sub * C;
-  n_run = n_run < 0 ? 0 : (n_run > C ? C : n_run);
-  const int ng = n_run / G;
-
-  int32_t cur_row = n_run > 0 ? run[0].y : -1;
-  int32_t cnt = 0;
-  bool head_done = false;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  auto flush = [&]() {  // the open row ends here
-    if (!head_done) {
-      s_part[sub][0][sl] = acc;
-      if (sl == 0) { s_row[sub][0] = cur_row; s_cnt[sub][0] = cnt; }
-      head_done = true;
-    } else {
-      // opened and closed inside this run: all its edges are here
-      out[(size_t)(cur_row - row0) * LPR + sl] = reduce_fin<MEAN>(acc, cnt);
-    }
-    acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    cnt = 0;
-  };
-  auto load_group = [&](int g, int2 (&rec)[G], float4 (&x)[G]) {
-#pragma unroll
-    for (int i = 0; i < G; ++i) rec[i] = run[g * G + i];
-#pragma unroll
-    for (int i = 0; i < G; ++i) x[i] = Xl[(size_t)rec[i].x * LPR];
-  };
-  auto consume = [&](const int2 (&rec)[G], const float4 (&x)[G]) {
-    if (__ballot(rec[G - 1].y != cur_row) == 0ull) {  // rows are sorted: the group stays in the open row
-#pragma unroll
-      for (int i = 0; i < G; ++i) acc = add4(acc, x[i]);
-      cnt += G;
-    } else {
-#pragma unroll
-      for (int i = 0; i < G; ++i) {
-        if (rec[i].y != cur_row) {
-          flush();
-          cur_row = rec[i].y;
-        }
-        acc = add4(acc, x[i]);
-        ++cnt;
-      }
-    }
-  };
-  int2 ra[G], rb[G];
-  float4 xa[G], xb[G];
-  // (the next group is requested unconditionally - past the run's end its last group again - as in spmm_merge2_kernel)
-  if (ng > 0) load_group(0, ra, xa);
-  for (int g = 0; g < ng; g += 2) {
-    load_group(g + 1 < ng ? g + 1 : ng - 1, rb, xb);
-    consume(ra, xa);
-    load_group(g + 2 < ng ? g + 2 : ng - 1, ra, xa);
-    if (g + 1 < ng) consume(rb, xb);
-  }
-  for (int j = ng * G; j < n_run; ++j) {  // only the last run of the edge range is ragged
-    const int2 rec = run[j];
-    const float4 x = Xl[(size_t)rec.x * LPR];
-    if (rec.y != cur_row) {
-      flush();
-      cur_row = rec.y;
-    }
-    acc = add4(acc, x);
-    ++cnt;
-  }
-  if (!head_done) {
-    s_part[sub][0][sl] = acc;
-    if (sl == 0) {
-      s_row[sub][0] = cur_row;  // -1 for an empty run
-      s_cnt[sub][0] = cnt;
-      s_row[sub][1] = -1;
-    }
-  } else {
-    s_part[sub][1][sl] = acc;
-    if (sl == 0) { s_row[sub][1] = cur_row; s_cnt[sub][1] = cnt; }
-  }
-  __syncthreads();
-
-  // In-order combine of the run-boundary partials by lane group 0: rows inside the tile are complete, the tile's
-  // first and last row go to the partial buffer (raw sums; the finish launch divides).
-  if (sub == 0) {
-    float4* bp = bpart + (size_t)tile * 2 * LPR;
-    int32_t crow = -1, ccnt = 0;
-    float4 cacc = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto emit = [&](int32_t rr, const float4& v, int32_t n) {
-      if (rr < 0) return;
-      if (rr == first_row) bp[sl] = v;
-      else if (rr == last_row) bp[LPR + sl] = v;
-      else out[(size_t)(rr - row0) * LPR + sl] = reduce_fin<MEAN>(v, n);
-    };
-    for (int s = 0; s < NSUB; ++s) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int32_t rr = s_row[s][t];
-        if (rr < 0) continue;
-        const float4 v = s_part[s][t][sl];
-        const int32_t n = s_cnt[s][t];
-        if (rr == crow) {
-          cacc = add4(cacc, v);
-          ccnt += n;
-        } else {
-          emit(crow, cacc, ccnt);
-          crow = rr;
-          cacc = v;
-          ccnt = n;
-        }
-      }
-    }
-    emit(crow, cacc, ccnt);
-  }
-}
-
-// Finish: blocks [0, fix_blocks): one lane group per (tile, first / last row) item; the tile that holds a row's first
-// edge owns it and sums the row's partials in tile order, eight at a time (a hub row's chain has hundreds),
-// then divides for the mean.  Blocks from fix_blocks on: rows without in-edges are written as zeros (one lane tests
-// one row's offsets).
-template <int LPR, int C, bool MEAN>
-__global__ __launch_bounds__(SpmmGeom<LPR>::THREADS) void copy_finish_kernel(
-    int64_t e0, int64_t e1, int32_t row0, int32_t n_rows, int32_t n_tiles, const int32_t* __restrict__ indptr,
-    const int32_t* __restrict__ row_of, float4* __restrict__ out, const float4* __restrict__ bpart, int32_t fix_blocks) {
-  constexpr int NSUB = SpmmGeom<LPR>::NSUB;
-  constexpr int TE = NSUB * C;
-  constexpr int WPB = SpmmGeom<LPR>::THREADS / kWave;
-  const int tid = threadIdx.x;
-  if ((int32_t)blockIdx.x < fix_blocks) {
-    const int sub = tid / LPR, sl = tid % LPR;
-    const int64_t item = (int64_t)blockIdx.x * NSUB + sub;
-    const int32_t b = (int32_t)(item >> 1);
-    const int s = (int)(item & 1);
-    if (b >= n_tiles) return;
-    const int64_t t0 = e0 + (int64_t)b * TE;
-    const int64_t t1 = (t0 + TE < e1) ? t0 + TE : e1;
-    const int32_t fr = row_of[t0], lr = row_of[t1 - 1];
-    if (s == 1 && lr == fr) return;
-    const int32_t r = s == 0 ? fr : lr;
-    const int64_t rb = indptr[r], re = indptr[r + 1];
-    if ((int32_t)((rb - e0) / TE) != b) return;  // another tile owns the row
-    const int32_t bl = (int32_t)((re - 1 - e0) / TE);
-    float4 acc = bpart[((size_t)b * 2 + s) * LPR + sl];
-    int32_t bb = b + 1;
-    constexpr int U = 8;
-    for (; bb + U - 1 <= bl; bb += U) {
-      float4 v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = bpart[((size_t)(bb + u) * 2) * LPR + sl];
-      // eight partials summed first, then added to the chain: a hub row's hundreds of tile partials are no single
-      // sequential fp32 sum
-      float4 part = v[0];
-#pragma unroll
-      for (int u = 1; u < U; ++u) part = add4(part, v[u]);
-      acc = add4(acc, part);
-    }
-    for (; bb <= bl; ++bb) acc = add4(acc, bpart[((size_t)bb * 2) * LPR + sl]);
-    out[(size_t)(r - row0) * LPR + sl] = reduce_fin<MEAN>(acc, (int32_t)(re - rb));
-  } else {
-    const int lane = tid % kWave;
-    constexpr int SPW = kWave / LPR >= 1 ? kWave / LPR : 1;
-    const int q = (LPR < kWave) ? lane / LPR : 0, sl = tid % LPR;
-    const int64_t n_waves = (int64_t)(gridDim.x - fix_blocks) * WPB;
-    const int64_t wave = (int64_t)(blockIdx.x - fix_blocks) * WPB + tid / kWave;
-    for (int64_t v0 = wave * kWave; v0 < n_rows; v0 += n_waves * kWave) {
-      const int64_t v = v0 + lane;
-      bool empty = false;
-      if (v < n_rows) {
-        const int32_t row = row0 + (int32_t)v;
-        empty = indptr[row] == indptr[row + 1];
-      }
-      unsigned long long m = __ballot(empty);
-      int turn = 0;
-      while (m) {
-        const int bt = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (turn == q) out[(size_t)(v0 + bt) * LPR + sl] = make_float4(0.f, 0.f, 0.f, 0.f);
-        turn = turn + 1 == SPW ? 0 : turn + 1;
-      }
-    }
-  }
-}
-
-// Any width: one wavefront per row, lane j covers columns j, j + 64, ...; the row's positions in CSR order, summed in
-// chunks of kCopyChunk positions whose sums are then added in order (a hub row of 10^5 edges summed in one sequential
-// chain lands 1e-5 of the tensor's scale away from the exact sum; in chunks, as the merge path's tiles do, 1e-7).
-constexpr int kCopyChunk = 128;
-template <bool MEAN>
-__global__ __launch_bounds__(256) void copy_rows_generic_kernel(int32_t n_rows, int32_t row0, int D,
-                                                                const int32_t* __restrict__ indptr,
-                                                                const int32_t* __restrict__ col,
-                                                                const float* __restrict__ X, float* __restrict__ out) {
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int64_t v = (int64_t)blockIdx.x * (256 / kWave) + wave;
-  if (v >= n_rows) return;
-  const int32_t row = row0 + (int32_t)v;
-  const int32_t beg = indptr[row], end = indptr[row + 1];
-  const float cntf = (float)(end - beg > 1 ? end - beg : 1);
-  for (int d0 = 0; d0 < D; d0 += kWave) {
-    const int d = d0 + lane;
-    if (d < D) {
-      float acc = 0.f;
-      for (int32_t p0 = beg; p0 < end; p0 += kCopyChunk) {
-        const int32_t p1 = end - p0 < kCopyChunk ? end : p0 + kCopyChunk;
-        float part = 0.f;
-        for (int32_t p = p0; p < p1; ++p) part += X[(size_t)col[p] * D + d];
-        acc += part;
-      }
-      out[(size_t)v * D + d] = MEAN ? acc / cntf : acc;
-    }
-  }
-}
-
-struct CopyArgs {
-  int64_t n_rows, row0;
-  int D;
-  const int32_t *indptr, *col, *row_of;
-  const float* X;
-  float* out;
-  void* ws;
-  size_t ws_bytes;
-  int32_t e0, e1;
-  hipStream_t st;
-};
-
-template <int LPR, int C, bool MEAN>
-static int launch_copy_c(const CopyArgs& a) {
-  const int64_t e0 = a.e0, e1 = a.e1;
-  const int64_t tiles = merge_tiles_c<LPR, C>(e1 - e0);
-  const size_t need = (size_t)tiles * 2 * LPR * sizeof(float4);
-  if (tiles > 0 && (a.ws == nullptr || a.ws_bytes < need)) {
-    set_error("copy_reduce: workspace too small (%zu < %zu)", a.ws_bytes, need);
-    return KGAT_E_WORKSPACE;
-  }
-  float4* bpart = static_cast<float4*>(a.ws);
-  constexpr int kThreads = SpmmGeom<LPR>::THREADS;
-  if (tiles > 0) {
-    hipLaunchKernelGGL((copy_merge_kernel<LPR, C, MEAN>), dim3((unsigned)tiles), dim3(kThreads), 0, a.st, e0, e1,
-                       (int32_t)a.row0, a.col, a.row_of, (const float4*)a.X, (float4*)a.out, bpart);
-    KGAT_CHECK_LAUNCH("copy_merge");
-  }
-  constexpr int kItemsPerBlock = SpmmGeom<LPR>::NSUB;  // one per lane group
-  const int32_t fix_blocks = (int32_t)((tiles * 2 + kItemsPerBlock - 1) / kItemsPerBlock);
-  int64_t nz_blocks = (a.n_rows + kThreads - 1) / kThreads;
-  if (nz_blocks > 2048) nz_blocks = 2048;
-  if (nz_blocks < 1) nz_blocks = 1;
-  hipLaunchKernelGGL((copy_finish_kernel<LPR, C, MEAN>), dim3((unsigned)(fix_blocks + nz_blocks)), dim3(kThreads), 0,
-                     a.st, e0, e1, (int32_t)a.row0, (int32_t)a.n_rows, (int32_t)tiles, a.indptr, a.row_of,
-                     (float4*)a.out, (const float4*)bpart, fix_blocks);
-  KGAT_CHECK_LAUNCH("copy_finish");
-  return KGAT_OK;
-}
-
-// the aggregation's run-length choice (launch_merge): the tiles fit the workspace kgat_spmm_workspace_bytes sizes
-template <int LPR, bool MEAN>
-static int launch_copy(const CopyArgs& a) {
-  const int64_t n = (int64_t)a.e1 - a.e0;
-  if (use_short_runs<LPR>(n)) return launch_copy_c<LPR, short_run_len(LPR), MEAN>(a);
-  if (use_mid_runs<LPR>(n)) return launch_copy_c<LPR, mid_run_len(LPR), MEAN>(a);
-  return launch_copy_c<LPR, run_len(LPR), MEAN>(a);
-}
-
-template <bool MEAN>
-static int dispatch_copy(const CopyArgs& a) {
-  switch (a.D) {
-    case 16: return launch_copy<4, MEAN>(a);
-    case 32: return launch_copy<8, MEAN>(a);
-    case 64: return launch_copy<16, MEAN>(a);
-    case 128: return launch_copy<32, MEAN>(a);
-    default: {
-      const int64_t blocks = (a.n_rows + 3) / 4;
-      hipLaunchKernelGGL((copy_rows_generic_kernel<MEAN>), dim3((unsigned)blocks), dim3(256), 0, a.st,
-                         (int32_t)a.n_rows, (int32_t)a.row0, a.D, a.indptr, a.col, a.X, a.out);
-      KGAT_CHECK_LAUNCH("copy_rows_generic");
-      return KGAT_OK;
-    }
-  }
-}
 
 // --------------------------------------------------------------------------------------------- dense forward
 // Waves per SIMD the dense kernels ask the compiler for: two up to 2,048 weight elements; beyond, the weight fragments
@@ -635,35 +317,11 @@ __global__ __launch_bounds__(256) void sage_bwd_weight_kernel(int32_t n_rows, co
 
 static bool sage_width(int d) { return d == 16 || d == 32 || d == 64 || d == 128; }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace kgat
 
 using namespace kgat;
 
 extern "C" {
-
-int kgat_copy_reduce_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_t e_end, int D, const int32_t* indptr,
-                         const int32_t* col, const int32_t* row_of, const float* X, float* out, int reduce,
-                         void* workspace, size_t workspace_bytes, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && row0 >= 0 && D > 0, "copy_reduce: bad size (n_rows=%lld row0=%lld D=%d)",
-                 (long long)n_rows, (long long)row0, D);
-  KGAT_CHECK_ARG(row0 + n_rows < INT32_MAX, "copy_reduce: row range exceeds int32");
-  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "copy_reduce: bad edge range");
-  KGAT_CHECK_ARG(reduce == KGAT_REDUCE_SUM || reduce == KGAT_REDUCE_MEAN, "copy_reduce: unknown reduce %d", reduce);
-  if (n_rows == 0) return KGAT_OK;
-  KGAT_CHECK_ARG(indptr && X && out, "copy_reduce: null pointer");
-  const bool merge = sage_width(D);
-  KGAT_CHECK_ARG(e_end == e_begin || (col && (row_of || !merge)), "copy_reduce: null col / row_of");
-  KGAT_CHECK_ARG(!merge || (aligned16(X) && aligned16(out)), "copy_reduce: X and out must be 16-byte aligned");
-  CopyArgs a;
-  a.n_rows = n_rows; a.row0 = row0; a.D = D;
-  a.indptr = indptr; a.col = col; a.row_of = row_of; a.X = X; a.out = out;
-  a.ws = workspace; a.ws_bytes = workspace_bytes;
-  a.e0 = (int32_t)e_begin; a.e1 = (int32_t)e_end;
-  a.st = as_stream(stream);
-  return reduce == KGAT_REDUCE_MEAN ? dispatch_copy<true>(a) : dispatch_copy<false>(a);
-}
 
 int kgat_sage_dense_supported(int d_in, int d_out) { return sage_width(d_in) && sage_width(d_out) ? 1 : 0; }
 

@@ -18,22 +18,13 @@
 
 using namespace kgat;
 
-namespace {
-
-template <int DI, int DO>
-int launch_fused(const SpmmArgs& a) {
-  return launch_merge<DI / 4, true, false, DO>(a);
-}
-
-}  // namespace
+// The (d_in, d_out) pairs built: kgat_spmm_bi_fused_supported and the entry's dispatch both read this table.
+using FusedPairs = WidthPairs<WidthPair<64, 64>, WidthPair<64, 32>, WidthPair<64, 16>, WidthPair<32, 32>, WidthPair<32, 16>,
+                              WidthPair<16, 16>>;
 
 extern "C" {
 
-
-int kgat_spmm_bi_fused_supported(int d_in, int d_out) {
-  auto ok = [](int d) { return d == 16 || d == 32 || d == 64; };
-  return ok(d_in) && ok(d_out) && d_out <= d_in;
-}
+int kgat_spmm_bi_fused_supported(int d_in, int d_out) { return has_widths(FusedPairs{}, d_in, d_out); }
 
 int kgat_spmm_bi_fused_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_t e_end, int d_in, int d_out,
                            const int32_t* indptr, const int32_t* col, const int32_t* row_of,
@@ -41,10 +32,7 @@ int kgat_spmm_bi_fused_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_
                            float* h_out, float* norm_out, int64_t norm_stride, float* scratch,
                            void* workspace, size_t workspace_bytes, float* self_out, int64_t self_stride,
                            kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && row0 >= 0, "spmm_bi_fused: bad size (n_rows=%lld row0=%lld)", (long long)n_rows,
-                 (long long)row0);
-  KGAT_CHECK_ARG(row0 + n_rows < INT32_MAX, "spmm_bi_fused: row range exceeds int32");
-  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "spmm_bi_fused: bad edge range");
+  KGAT_RETURN_IF(check_rows("spmm_bi_fused", n_rows, row0, e_begin, e_end));
   if (!kgat_spmm_bi_fused_supported(d_in, d_out)) {
     set_error("spmm_bi_fused: unsupported widths %d -> %d", d_in, d_out);
     return KGAT_E_UNSUPPORTED;
@@ -52,28 +40,24 @@ int kgat_spmm_bi_fused_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_
   if (n_rows == 0) return KGAT_OK;
   KGAT_CHECK_ARG(indptr && X && W2 && scratch && (h_out || norm_out), "spmm_bi_fused: null pointer");
   KGAT_CHECK_ARG(e_end == e_begin || (col && w && row_of), "spmm_bi_fused: null col / w / row_of");
-  KGAT_CHECK_ARG(norm_out == nullptr || (norm_stride >= d_out && norm_stride % 4 == 0 &&
-                                         (reinterpret_cast<uintptr_t>(norm_out) & 15u) == 0),
+  KGAT_CHECK_ARG(norm_out == nullptr || (norm_stride >= d_out && norm_stride % 4 == 0 && aligned16(norm_out)),
                  "spmm_bi_fused: norm_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_out");
   if (self_out != nullptr)
-    KGAT_CHECK_ARG(self_stride >= d_in && self_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(self_out) & 15u) == 0,
+    KGAT_CHECK_ARG(self_stride >= d_in && self_stride % 4 == 0 && aligned16(self_out),
                    "spmm_bi_fused: self_out must be 16-byte aligned with a row stride that is a multiple of 4 floats >= d_in");
   SpmmArgs a;
   a.self_out = self_out; a.self_stride = self_stride;
   a.n_rows = n_rows; a.row0 = row0; a.D = d_in;
-  a.indptr = indptr; a.col = col; a.row_of = row_of; a.eid = nullptr; a.order = nullptr;
+  a.indptr = indptr; a.col = col; a.row_of = row_of;
   a.X = X; a.w = w; a.out = scratch; a.ws = workspace; a.ws_bytes = workspace_bytes;
   a.flags = KGAT_SPMM_MUL_SELF; a.algo = KGAT_SPMM_ALGO_MERGE;
-  a.e0_host = (int32_t)e_begin; a.e1_host = (int32_t)e_end;
+  a.e0 = (int32_t)e_begin; a.e1 = (int32_t)e_end;
   a.st = as_stream(stream);
   a.bi.W2 = W2; a.bi.slope = negative_slope; a.bi.h_out = h_out; a.bi.norm_out = norm_out;
   a.bi.norm_stride = norm_stride; a.bi.indptr = indptr;
-#define KGAT_FUSED_CASE(DI, DO) if (d_in == DI && d_out == DO) return launch_fused<DI, DO>(a);
-  KGAT_FUSED_CASE(64, 64) KGAT_FUSED_CASE(64, 32) KGAT_FUSED_CASE(64, 16)
-  KGAT_FUSED_CASE(32, 32) KGAT_FUSED_CASE(32, 16) KGAT_FUSED_CASE(16, 16)
-#undef KGAT_FUSED_CASE
-  set_error("spmm_bi_fused: unsupported widths %d -> %d", d_in, d_out);
-  return KGAT_E_UNSUPPORTED;
+  return dispatch_widths(FusedPairs{}, d_in, d_out, [&](auto di, auto dout) {
+    return launch_merge<decltype(di)::value / 4, true, false, decltype(dout)::value>(a);
+  });
 }
 
 }  // extern "C"

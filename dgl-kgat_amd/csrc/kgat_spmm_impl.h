@@ -1,8 +1,9 @@
 // Kernel templates and launchers of the u_mul_e -> sum aggregation (included by kgat_spmm.hip, which
-// instantiates the plain operator, and by kgat_spmm_bi.hip, which instantiates the forms with the
-// bi-interaction fused behind the aggregation).  Not part of the ABI.
+// instantiates the plain operator and builds the copy reducer on the same geometry, and by kgat_spmm_bi.hip, which
+// instantiates the forms with the bi-interaction fused behind the aggregation).  The tile rule, the width lists and
+// the shared argument checks are host code of their own: kgat_spmm_plan.h.  Not part of the ABI.
 #pragma once
-#include "kgat_common.h"
+#include "kgat_spmm_plan.h"
 
 namespace kgat {
 
@@ -15,18 +16,6 @@ __device__ __forceinline__ float4 add4(const float4& a, const float4& b) {
 __device__ __forceinline__ float4 mul4(const float4& a, const float4& b) {
   return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
-
-// (128-thread workgroups with half-size tiles, round 3: D = 64 0.0993 vs 0.0987 ms, D = 128 0.187 vs 0.179, D = 8 0.058 vs 0.066)
-constexpr int kSpmmThreads = 256;
-
-// Threads per workgroup of the kernels that are laid out in lane groups of LPR lanes.  D <= 8 (two lanes per
-// row and fewer): 128 - a 256-thread workgroup holds 128 runs there, i.e. 256 run partials to combine per
-// tile; halving the workgroup (not the run length, which was tried and lost) took the D = 8 launch on the
-// last-fm graph from 0.066 to 0.058 ms (round 3, AB_FLAG=-DKGAT_SPMM_THREADS=128).  Round 6 re-scanned workgroup size
-// x run length for the narrow rows (scripts/micro/spmm_narrow_scan.sh, profiles/r06_spmm_narrow_scan.txt): 128 threads
-// also at D = 16 / 32 - 16 runs and 32 run partials per tile, as a D = 64 tile has - with the half-length runs:
-// D = 32 49.4 -> 47.6 us, D = 16 47.8 -> 44.7 (full-length runs 50.9 / 46.1, quarter-length 54.2 / 51.8); D >= 64 flat.
-constexpr int spmm_threads(int lpr) { return (lpr <= 8 && kSpmmThreads == 256) ? 128 : kSpmmThreads; }
 
 template <int LPR>
 struct SpmmGeom {
@@ -909,127 +898,65 @@ __global__ __launch_bounds__(kSpmmThreads) void spmm_rows_generic_kernel(
   }
 }
 
+// One call of the family: the sum operator, its fused form and the copy reducer (which reads neither w, eid, order,
+// flags, algo nor the two records at the end).
 struct SpmmArgs {
   int64_t n_rows, row0;
   int D;
-  const int32_t *indptr, *col, *row_of, *eid, *order;
-  const float *X, *w;
+  const int32_t *indptr, *col, *row_of, *eid = nullptr, *order = nullptr;
+  const float *X, *w = nullptr;
   float* out;
   void* ws;
   size_t ws_bytes;
-  unsigned flags;
-  int algo;
-  int32_t e0_host, e1_host;  // CSR position range of the row range
+  unsigned flags = 0;
+  int algo = KGAT_SPMM_ALGO_MERGE;
+  int32_t e0, e1;  // CSR position range of the row range
   hipStream_t st;
   float* self_out = nullptr;  // MUL_SELF launches of the merge algorithm: also copy X[v] here (SelfCopy)
   int64_t self_stride = 0;    // row stride of self_out in floats (a multiple of 4)
   BiArgs bi;                  // fused dense part (kernels with DO > 0)
 };
 
-// C: edges per lane-group run in the merge kernels; tiles are NSUB * C <= 2048 edges (the
-// LDS record stage of the second form holds one tile).  A launch over few edges - a destination
-// shard of a multi-GPU run holds E/P of them - takes the short run length: a tile is walked
-// serially by its lane groups, so a launch cannot be shorter than one tile's time (~25 us at
-// C = 64, which is what a 458 k-edge shard's launch took: a third of the whole graph's time for an
-// eighth of its edges); a quarter of the run length gives four times the tiles, each a quarter as long.
-constexpr int run_len(int lpr) { return lpr >= 8 ? 64 : (lpr == 4 ? 32 : (lpr == 2 ? 16 : 8)); }
-constexpr int short_run_len(int lpr) { return run_len(lpr) / 4 >= 4 ? run_len(lpr) / 4 : 4; }
-constexpr int64_t kShortRunTileLimit = 4096;  // use the short runs while they give at most this many tiles
-// Between the two, for rows of 64 and 128 bytes (LPR = 4, 8: a tile is 2,048 edges there): half
-// the run length while that gives at most kMidRunTileLimit tiles.  A launch of a few thousand
-// full-length tiles ends with its last, longest tiles running on a nearly empty chip (tile times
-// spread 14 k - 52 k cycles; 1,789 tiles on 1,280 workgroup slots at D = 32 on the amazon-book
-// graph), and half-length tiles halve that tail: D = 32 0.079 -> 0.066 ms, D = 16 0.066 -> 0.060
-// (quarter length: 0.076; at D = 64 / 128, 16-KB tiles of 1,024 edges, half length changes nothing,
-// at D = 8 it costs 6-10 %: scripts/micro/spmm_runlen_ab.py).  The two macros exist for that A/B build only.
-constexpr int kSpmmMidDiv = 2;
-constexpr int mid_run_len(int lpr) {
-  return (lpr == 8 || lpr == 4) ? run_len(lpr) / kSpmmMidDiv : run_len(lpr);
-}
-constexpr int kSpmmMidLimit = 16384;
-constexpr int64_t kMidRunTileLimit = kSpmmMidLimit;
-
-template <int LPR, int C>
-static int64_t merge_tiles_c(int64_t n_edges) {
-  constexpr int TE = SpmmGeom<LPR>::NSUB * C;
-  return (n_edges + TE - 1) / TE;
-}
-
-template <int LPR>
-static bool use_short_runs(int64_t n_edges) {
-  return merge_tiles_c<LPR, short_run_len(LPR)>(n_edges) <= kShortRunTileLimit;
-}
-template <int LPR>
-static bool use_mid_runs(int64_t n_edges) {
-  return merge_tiles_c<LPR, mid_run_len(LPR)>(n_edges) <= kMidRunTileLimit;
-}
+inline MergePlan merge_plan(int lpr, const SpmmArgs& a) { return merge_plan(lpr, (int64_t)a.e1 - a.e0, a.n_rows); }
 
 template <int LPR, int C, bool MUL_SELF, bool HAS_EID, bool COPY_SELF = false, int DO = 0>
-static int launch_merge_c(const SpmmArgs& a) {
-  if (MUL_SELF && !HAS_EID && !COPY_SELF && a.self_out != nullptr) return launch_merge_c<LPR, C, MUL_SELF, HAS_EID, MUL_SELF && !HAS_EID, DO>(a);
+static int launch_merge_c(const SpmmArgs& a, const MergePlan& p) {
+  if (MUL_SELF && !HAS_EID && !COPY_SELF && a.self_out != nullptr) return launch_merge_c<LPR, C, MUL_SELF, HAS_EID, MUL_SELF && !HAS_EID, DO>(a, p);
   const SelfCopy sc{reinterpret_cast<float4*>(a.self_out), a.self_stride / 4};
-  const int64_t e0 = a.e0_host, e1 = a.e1_host;
-  const int64_t tiles = merge_tiles_c<LPR, C>(e1 - e0);
-  const size_t need = (size_t)tiles * 2 * LPR * sizeof(float4);
-  if (tiles > 0 && (a.ws == nullptr || a.ws_bytes < need)) {
-    set_error("spmm: workspace too small (%zu < %zu)", a.ws_bytes, need);
-    return KGAT_E_WORKSPACE;
-  }
+  const int64_t e0 = a.e0, e1 = a.e1;
+  KGAT_RETURN_IF(check_workspace("spmm", p, p.part_elems * sizeof(float4), a.ws, a.ws_bytes));
   float4* bpart = static_cast<float4*>(a.ws);
-  if (tiles > 0) {
+  constexpr int kThreads = SpmmGeom<LPR>::THREADS;
+  if (p.tiles > 0) {
     if (!HAS_EID && a.algo != KGAT_SPMM_ALGO_MERGE1) {
-      hipLaunchKernelGGL((spmm_merge2_kernel<LPR, C, MUL_SELF, COPY_SELF, DO>), dim3((unsigned)tiles),
-                         dim3(SpmmGeom<LPR>::THREADS), 0, a.st, e0, e1, (int32_t)a.row0, a.col, a.row_of,
+      hipLaunchKernelGGL((spmm_merge2_kernel<LPR, C, MUL_SELF, COPY_SELF, DO>), dim3((unsigned)p.tiles),
+                         dim3(kThreads), 0, a.st, e0, e1, (int32_t)a.row0, a.col, a.row_of,
                          (const float4*)a.X, a.w, (float4*)a.out, bpart, sc, a.bi);
     } else if constexpr (DO > 0) {
       set_error("spmm: the fused form takes CSR-ordered weights and the merge algorithm");
       return KGAT_E_UNSUPPORTED;
     } else {
-      hipLaunchKernelGGL((spmm_merge_kernel<LPR, C, MUL_SELF, HAS_EID>), dim3((unsigned)tiles),
-                         dim3(SpmmGeom<LPR>::THREADS), 0, a.st, e0, e1, (int32_t)a.row0, a.col, a.row_of,
+      hipLaunchKernelGGL((spmm_merge_kernel<LPR, C, MUL_SELF, HAS_EID>), dim3((unsigned)p.tiles),
+                         dim3(kThreads), 0, a.st, e0, e1, (int32_t)a.row0, a.col, a.row_of,
                          a.eid, (const float4*)a.X, a.w, (float4*)a.out, bpart);
     }
     KGAT_CHECK_LAUNCH("spmm_merge");
   }
-  constexpr int kThreads = SpmmGeom<LPR>::THREADS;
-  constexpr int kItemsPerBlock = (kThreads / kWave) * (kWave / LPR >= 1 ? kWave / LPR : 1);  // one per lane group
-  const int32_t fix_blocks = (int32_t)((tiles * 2 + kItemsPerBlock - 1) / kItemsPerBlock);
-  int64_t nz_blocks = (a.n_rows + kThreads - 1) / kThreads;  // one lane per row
-  if (nz_blocks > 2048) nz_blocks = 2048;
-  if (nz_blocks < 1) nz_blocks = 1;
   // KGAT_SPMM_DEFER_FINISH: the consumer (kgat_aggregator_deferred_f32) forms the tiles' first / last rows
   // from the partials in the workspace, and the rows without in-edges, itself
   if (DO == 0 && (a.flags & KGAT_SPMM_DEFER_FINISH)) return KGAT_OK;
   hipLaunchKernelGGL((spmm_finish_kernel<LPR, C, MUL_SELF, COPY_SELF, DO>),
-                     dim3((unsigned)(fix_blocks + nz_blocks)), dim3(kThreads), 0, a.st, e0, e1,
-                     (int32_t)a.row0, (int32_t)a.n_rows, (int32_t)tiles, a.indptr, a.row_of,
-                     (const float4*)a.X, (float4*)a.out, (const float4*)bpart, fix_blocks, sc, a.bi);
+                     dim3((unsigned)(p.fix_blocks + p.nz_blocks)), dim3(kThreads), 0, a.st, e0, e1,
+                     (int32_t)a.row0, (int32_t)a.n_rows, (int32_t)p.tiles, a.indptr, a.row_of,
+                     (const float4*)a.X, (float4*)a.out, (const float4*)bpart, p.fix_blocks, sc, a.bi);
   KGAT_CHECK_LAUNCH("spmm_finish");
   return KGAT_OK;
 }
 
-// Run length of the fused form (DO > 0): the plain operator's, so that the aggregation's summation order - and
-// with it every bit of the result - is that of the two-launch sequence.  (A/B builds, KGAT_FUSED_HALF_RUNS=1: half
-// the run length at D = 64 - 512-edge tiles hold half the rows and leave LDS for a 56-row buffer at five
-// workgroups per CU; measured slower, profiles/r04_fused_bi_ab.txt: the per-tile phases around the edge loop
-// (stage, partials, combine, the dense tail) do not shrink with the tile.)
-constexpr int kFusedHalfRuns = 0;
-constexpr int fused_run_len(int lpr) { return (kFusedHalfRuns && lpr >= 16) ? run_len(lpr) / 2 : run_len(lpr); }
-
 template <int LPR, bool MUL_SELF, bool HAS_EID, int DO = 0>
 static int launch_merge(const SpmmArgs& a) {
-  if (use_short_runs<LPR>((int64_t)a.e1_host - a.e0_host))
-    return launch_merge_c<LPR, short_run_len(LPR), MUL_SELF, HAS_EID, false, DO>(a);
-  if (use_mid_runs<LPR>((int64_t)a.e1_host - a.e0_host))
-    return launch_merge_c<LPR, mid_run_len(LPR), MUL_SELF, HAS_EID, false, DO>(a);
-  return launch_merge_c<LPR, (DO > 0 ? fused_run_len(LPR) : run_len(LPR)), MUL_SELF, HAS_EID, false, DO>(a);
-}
-
-// edges per tile launch_merge picks for a launch over n_edges positions (kgat_spmm_tile_edges)
-template <int LPR>
-static int merge_tile_edges(int64_t n_edges) {
-  const int c = use_short_runs<LPR>(n_edges) ? short_run_len(LPR) : (use_mid_runs<LPR>(n_edges) ? mid_run_len(LPR) : run_len(LPR));
-  return SpmmGeom<LPR>::NSUB * c;
+  const MergePlan p = merge_plan(LPR, a);
+  return dispatch_run_len<LPR>(p, [&](auto c) { return launch_merge_c<LPR, decltype(c)::value, MUL_SELF, HAS_EID, false, DO>(a, p); });
 }
 
 template <int LPR, bool MUL_SELF, bool HAS_EID>
@@ -1052,32 +979,15 @@ static int launch_generic(const SpmmArgs& a) {
   return KGAT_OK;
 }
 
-template <int LPR, bool MUL_SELF, bool HAS_EID>
-static int dispatch_algo(const SpmmArgs& a) {
-  if (a.algo == KGAT_SPMM_ALGO_ROWS) return launch_rows<LPR, MUL_SELF, HAS_EID>(a);
-  return launch_merge<LPR, MUL_SELF, HAS_EID>(a);
-}
-
+// The entry has settled the algorithm: KGAT_SPMM_ALGO_GENERIC for every width outside SumWidths.
 template <bool MUL_SELF, bool HAS_EID>
-static int dispatch_width(const SpmmArgs& a) {
+static int launch_spmm(const SpmmArgs& a) {
   if (a.algo == KGAT_SPMM_ALGO_GENERIC) return launch_generic<MUL_SELF, HAS_EID>(a);
-  switch (a.D) {
-    case 4: return dispatch_algo<1, MUL_SELF, HAS_EID>(a);
-    case 8: return dispatch_algo<2, MUL_SELF, HAS_EID>(a);
-    case 16: return dispatch_algo<4, MUL_SELF, HAS_EID>(a);
-    case 32: return dispatch_algo<8, MUL_SELF, HAS_EID>(a);
-    case 64: return dispatch_algo<16, MUL_SELF, HAS_EID>(a);
-    case 128: return dispatch_algo<32, MUL_SELF, HAS_EID>(a);
-    case 256: return dispatch_algo<64, MUL_SELF, HAS_EID>(a);
-    default: return launch_generic<MUL_SELF, HAS_EID>(a);
-  }
-}
-
-static int lpr_for(int D) {
-  switch (D) {
-    case 4: case 8: case 16: case 32: case 64: case 128: case 256: return D / 4;
-    default: return 0;
-  }
+  return dispatch_width(SumWidths{}, a.D, [&](auto d) {
+    constexpr int LPR = decltype(d)::value / 4;
+    if (a.algo == KGAT_SPMM_ALGO_ROWS) return launch_rows<LPR, MUL_SELF, HAS_EID>(a);
+    return launch_merge<LPR, MUL_SELF, HAS_EID>(a);
+  });
 }
 
 }  // namespace kgat

@@ -9,7 +9,7 @@
 // is a strict total order and the maximum does not depend on the order in which pairs are combined: runs, tiles and
 // lane groups may combine in any grouping and every launch gives the same bits.  No atomics.
 //
-// Decomposition: the sum kernel's.  The CSR positions of the call are cut into tiles of kgat_spmm_tile_edges edges,
+// Decomposition: the sum kernel's.  The CSR positions of the call are cut into merge_plan's tiles (kgat_spmm_plan.h),
 // one workgroup per tile; LPR lanes (a lane group) cover a row of X and walk a run of consecutive edges, U gathers in
 // flight, flushing when the destination row changes.  A run's first and last row may continue in a neighbour run:
 // those (value, id) partials are combined through LDS, each lane group looking at its own two entries.  The tile's
@@ -20,12 +20,11 @@
 // (blockIdx.y) - the same kernels, no row is walked by one wavefront beyond a tile at any width.
 #include <limits.h>
 
-#include "kgat_common.h"
+#include "kgat_spmm_plan.h"
 
 namespace kgat {
 namespace {
 
-constexpr int max_threads(int lpr) { return lpr <= 8 ? 128 : 256; }  // the sum kernel's workgroups (SpmmGeom)
 constexpr int kGenericLpr = 16;                                      // lanes per row of the any-width path
 constexpr int kNoEdge = INT32_MAX;                                   // id of the identity (-inf, kNoEdge)
 
@@ -76,12 +75,12 @@ __device__ __forceinline__ size_t part_index(int64_t tile, int slot, int sl) {
 }
 
 template <int LPR, int V>
-__global__ __launch_bounds__(max_threads(LPR)) void spmm_max_tile_kernel(
+__global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max_tile_kernel(
     int64_t e0, int64_t e1, int32_t te, int32_t row0, int D, const int32_t* __restrict__ col,
     const int32_t* __restrict__ row_of, const int32_t* __restrict__ eid, const float* __restrict__ X,
     const float* __restrict__ w, float* __restrict__ out, int32_t* __restrict__ arg, float* __restrict__ bval,
     int32_t* __restrict__ barg) {
-  constexpr int NSUB = max_threads(LPR) / LPR;
+  constexpr int NSUB = spmm_threads(LPR) / LPR;
   constexpr int U = 4;  // X rows in flight per lane group
   constexpr int W = LPR * V;
   __shared__ float s_val[NSUB][2][W];
@@ -196,12 +195,12 @@ __global__ __launch_bounds__(max_threads(LPR)) void spmm_max_tile_kernel(
 // striding over the tiles of a chain of kLongChain and more; (b) rows without in-edges: out = 0, arg = -1 (one lane
 // tests one row, the rows found are written by the wavefront's lane groups in turn).
 template <int LPR, int V>
-__global__ __launch_bounds__(max_threads(LPR)) void spmm_max_finish_kernel(
+__global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max_finish_kernel(
     int64_t e0, int64_t e1, int32_t te, int32_t row0, int32_t n_rows, int32_t n_tiles, int D,
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ row_of, float* __restrict__ out,
     int32_t* __restrict__ arg, const float* __restrict__ bval, const int32_t* __restrict__ barg, int32_t fix_blocks) {
   constexpr int SPW = kWave / LPR;  // lane groups per wavefront
-  constexpr int WPB = max_threads(LPR) / kWave;
+  constexpr int WPB = spmm_threads(LPR) / kWave;
   constexpr int kLongChain = 8;
   static_assert(LPR <= kWave / 2, "a wavefront holds at least two lane groups");
   const int tid = threadIdx.x;
@@ -297,47 +296,39 @@ struct MaxArgs {
 };
 
 struct MaxPlan {
-  int lpr, v, te, passes;
-  int64_t tiles;
+  int lpr, v, passes;
+  MergePlan m;
   size_t part_elems;  // values (and as many ids) in the workspace
 };
 
-// Tile size: the sum kernel's for the same edge count (the any-width path: its sixteen-lane geometry, D = 64).
-MaxPlan max_plan(int64_t n_edges, int D) {
+// The sum kernel's tiles for the same edge count (the any-width path: its sixteen-lane geometry, D = 64, with one
+// value per lane and a column pass per sixteen columns).
+MaxPlan max_plan(int64_t n_edges, int64_t n_rows, int D) {
   MaxPlan p;
-  const bool fast = D == 16 || D == 32 || D == 64 || D == 128;
+  const bool fast = has_width(TileWidths{}, D);
   p.lpr = fast ? D / 4 : kGenericLpr;
   p.v = fast ? 4 : 1;
   p.passes = fast ? 1 : (D + kGenericLpr - 1) / kGenericLpr;
-  p.te = kgat_spmm_tile_edges(n_edges > 0 ? n_edges : 0, fast ? D : 4 * kGenericLpr);
-  p.tiles = (p.te > 0 && n_edges > 0) ? (n_edges + p.te - 1) / p.te : 0;
-  p.part_elems = (size_t)p.tiles * p.passes * 2 * p.lpr * p.v;
+  p.m = merge_plan(p.lpr, n_edges, n_rows);
+  p.part_elems = p.m.part_elems * p.passes * p.v;
   return p;
 }
 
 template <int LPR, int V>
 int launch_max(const MaxArgs& a, const MaxPlan& p) {
-  constexpr int kThreads = max_threads(LPR);
-  if (p.tiles > 0 && p.te % (kThreads / LPR) != 0) {  // a tile is cut into one run per lane group
-    set_error("spmm_max: tile of %d edges does not divide into %d runs", p.te, kThreads / LPR);
-    return KGAT_E_UNSUPPORTED;
-  }
+  constexpr int kThreads = spmm_threads(LPR);
   float* bval = static_cast<float*>(a.ws);
   int32_t* barg = reinterpret_cast<int32_t*>(bval + p.part_elems);
-  if (p.tiles > 0) {
-    hipLaunchKernelGGL((spmm_max_tile_kernel<LPR, V>), dim3((unsigned)p.tiles, (unsigned)p.passes), dim3(kThreads), 0, a.st,
-                       a.e0, a.e1, (int32_t)p.te, (int32_t)a.row0, a.D, a.col, a.row_of, a.eid, a.X, a.w, a.out, a.arg,
-                       bval, barg);
+  if (p.m.tiles > 0) {
+    hipLaunchKernelGGL((spmm_max_tile_kernel<LPR, V>), dim3((unsigned)p.m.tiles, (unsigned)p.passes), dim3(kThreads), 0, a.st,
+                       a.e0, a.e1, (int32_t)p.m.tile_edges, (int32_t)a.row0, a.D, a.col, a.row_of, a.eid, a.X, a.w, a.out,
+                       a.arg, bval, barg);
     KGAT_CHECK_LAUNCH("spmm_max_tile");
   }
-  constexpr int kItemsPerBlock = (kThreads / kWave) * (kWave / LPR);  // one per lane group
-  const int32_t fix_blocks = (int32_t)((p.tiles * 2 + kItemsPerBlock - 1) / kItemsPerBlock);
-  int64_t nz_blocks = (a.n_rows + kThreads - 1) / kThreads;  // one lane per row
-  if (nz_blocks > 2048) nz_blocks = 2048;
-  hipLaunchKernelGGL((spmm_max_finish_kernel<LPR, V>), dim3((unsigned)(fix_blocks + nz_blocks), (unsigned)p.passes),
-                     dim3(kThreads), 0, a.st, a.e0, a.e1, (int32_t)p.te, (int32_t)a.row0, (int32_t)a.n_rows,
-                     (int32_t)p.tiles, a.D, a.indptr, a.row_of, a.out, a.arg, (const float*)bval, (const int32_t*)barg,
-                     fix_blocks);
+  hipLaunchKernelGGL((spmm_max_finish_kernel<LPR, V>), dim3((unsigned)(p.m.fix_blocks + p.m.nz_blocks), (unsigned)p.passes),
+                     dim3(kThreads), 0, a.st, a.e0, a.e1, (int32_t)p.m.tile_edges, (int32_t)a.row0, (int32_t)a.n_rows,
+                     (int32_t)p.m.tiles, a.D, a.indptr, a.row_of, a.out, a.arg, (const float*)bval, (const int32_t*)barg,
+                     p.m.fix_blocks);
   KGAT_CHECK_LAUNCH("spmm_max_finish");
   return KGAT_OK;
 }
@@ -351,45 +342,30 @@ extern "C" {
 
 size_t kgat_spmm_max_workspace_bytes(int64_t n_edges, int D) {
   if (n_edges <= 0 || D <= 0) return 256;
-  return align_up(max_plan(n_edges, D).part_elems * (sizeof(float) + sizeof(int32_t)), 256) + 256;
+  return plan_workspace_bytes(max_plan(n_edges, 0, D).part_elems, sizeof(float) + sizeof(int32_t));
 }
 
 int kgat_spmm_umule_max_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_t e_end, int D, const int32_t* indptr,
                             const int32_t* col, const int32_t* row_of, const int32_t* eid, const float* X,
                             const float* w, float* out, int32_t* arg, void* workspace, size_t workspace_bytes,
                             kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_rows >= 0 && row0 >= 0 && D > 0, "spmm_max: bad size (n_rows=%lld row0=%lld D=%d)",
-                 (long long)n_rows, (long long)row0, D);
-  KGAT_CHECK_ARG(row0 + n_rows < INT32_MAX, "spmm_max: row range exceeds int32");
-  KGAT_CHECK_ARG(e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX, "spmm_max: bad edge range");
+  KGAT_RETURN_IF(check_rows("spmm_max", n_rows, row0, e_begin, e_end, D));
   KGAT_CHECK_ARG(D <= kGenericLpr * 65535, "spmm_max: D = %d is beyond the grid's column passes", D);
   if (n_rows == 0) return KGAT_OK;
   KGAT_CHECK_ARG(indptr && X && out, "spmm_max: null pointer");
   KGAT_CHECK_ARG(e_end == e_begin || (col && row_of), "spmm_max: null col/row_of");
-  const MaxPlan p = max_plan(e_end - e_begin, D);
+  const MaxPlan p = max_plan(e_end - e_begin, n_rows, D);
   if (p.v == 4) {
-    KGAT_CHECK_ARG(((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(arg)) & 15u) == 0,
+    KGAT_CHECK_ARG(aligned16(X) && aligned16(out) && aligned16(arg),
                    "spmm_max: X, out and arg must be 16-byte aligned at D = %d", D);
   }
-  if (e_end > e_begin && p.te <= 0) {
-    set_error("spmm_max: no tile geometry for D = %d", D);
-    return KGAT_E_UNSUPPORTED;
-  }
-  const size_t need = p.part_elems * (sizeof(float) + sizeof(int32_t));
-  if (p.tiles > 0 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("spmm_max: workspace too small (%zu < %zu)", workspace_bytes, need);
-    return KGAT_E_WORKSPACE;
-  }
+  KGAT_RETURN_IF(check_workspace("spmm_max", p.m, p.part_elems * (sizeof(float) + sizeof(int32_t)), workspace, workspace_bytes));
   MaxArgs a;
   a.n_rows = n_rows; a.row0 = row0; a.e0 = e_begin; a.e1 = e_end; a.D = D;
   a.indptr = indptr; a.col = col; a.row_of = row_of; a.eid = eid; a.X = X; a.w = w;
   a.out = out; a.arg = arg; a.ws = workspace; a.st = as_stream(stream);
-  switch (p.lpr * p.v) {
-    case 16: return p.v == 4 ? launch_max<4, 4>(a, p) : launch_max<kGenericLpr, 1>(a, p);
-    case 32: return launch_max<8, 4>(a, p);
-    case 64: return launch_max<16, 4>(a, p);
-    default: return launch_max<32, 4>(a, p);
-  }
+  if (p.v == 1) return launch_max<kGenericLpr, 1>(a, p);  // any other width
+  return dispatch_width(TileWidths{}, D, [&](auto d) { return launch_max<decltype(d)::value / 4, 4>(a, p); });
 }
 
 }  // extern "C"

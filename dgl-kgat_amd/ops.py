@@ -618,6 +618,34 @@ def bi_interaction_deferral_supported(d_in, d_out):
     return int(d_in) in (16, 32, 64, 128) and int(d_out) in (16, 32, 64, 128)
 
 
+def _csr_operands(X, indptr, col, row_of, eid, rows, e_range, workspace, workspace_for, out=None, want_out=True,
+                  need_row_of=False):
+    """What spmm, spmm_max, copy_reduce and spmm_bi_fused do alike with their operands: X is (N, D) float32, indptr and
+    col are int32, row_of / eid int32 of col's shape or None (row_of not with need_row_of), `rows` = (row0, n_rows) and
+    `e_range` = (e0, e1) default to the whole graph, `out` is allocated or checked as (n_rows, D) (not with
+    want_out=False), and a missing workspace is sized by `workspace_for(n_edges, D, device)`.
+    Returns X, indptr, col, row_of, eid, (row0, n_rows, e0, e1), out, workspace."""
+    X = _need(X, torch.float32, "X")
+    if X.dim() != 2:
+        raise ValueError("X must be (N, D)")
+    indptr = _need(indptr, torch.int32, "indptr")
+    col = _need(col, torch.int32, "col")
+    if row_of is not None or need_row_of:
+        row_of = _need(row_of, torch.int32, "row_of", col.shape)
+    if eid is not None:
+        eid = _need(eid, torch.int32, "eid", col.shape)
+    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
+    e0, e1 = (0, col.numel()) if e_range is None else e_range
+    if want_out:
+        if out is None:
+            out = torch.empty((n_rows, X.shape[1]), dtype=torch.float32, device=X.device)
+        else:
+            out = _need(out, torch.float32, "out", (n_rows, X.shape[1]))
+    if workspace is None:
+        workspace = workspace_for(e1 - e0, X.shape[1], X.device)
+    return X, indptr, col, row_of, eid, (row0, n_rows, e0, e1), out, workspace
+
+
 def spmm(indptr, col, row_of, X, w, eid=None, out=None, order=None, mul_self=False, algo="auto",
          rows=None, e_range=None, workspace=None, self_out=None, defer_finish=False):
     """out[v - row0] = sum_p w_p X[col[p]] over the CSR rows `rows` = (row0, n_rows) whose CSR
@@ -626,27 +654,12 @@ def spmm(indptr, col, row_of, X, w, eid=None, out=None, order=None, mul_self=Fal
     row-major buffer that also receives X[v] (the ego block of the readout).
     defer_finish=True (KGAT_SPMM_DEFER_FINISH): returns (out, DeferredRows) - the rows the edge tiles cut and the
     rows without in-edges are NOT in `out`; bi_interaction_mul(deferred=...) forms them on the way."""
-    X = _need(X, torch.float32, "X")
-    if X.dim() != 2:
-        raise ValueError("X must be (N, D)")
+    X, indptr, col, row_of, eid, (row0, n_rows, e0, e1), out, workspace = _csr_operands(
+        X, indptr, col, row_of, eid, rows, e_range, workspace, spmm_workspace, out)
     D = X.shape[1]
-    indptr = _need(indptr, torch.int32, "indptr")
-    col = _need(col, torch.int32, "col")
     w = _need(w, torch.float32, "w", col.shape)
-    if row_of is not None:
-        row_of = _need(row_of, torch.int32, "row_of", col.shape)
-    if eid is not None:
-        eid = _need(eid, torch.int32, "eid", col.shape)
     if order is not None:
         order = _need(order, torch.int32, "order")
-    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
-    e0, e1 = (0, col.numel()) if e_range is None else e_range
-    if out is None:
-        out = torch.empty((n_rows, D), dtype=torch.float32, device=X.device)
-    else:
-        out = _need(out, torch.float32, "out", (n_rows, D))
-    if workspace is None:
-        workspace = spmm_workspace(e1 - e0, D, X.device)
     self_stride = 0
     if self_out is not None:
         self_stride = _strided_rows(self_out, n_rows, D, "self_out")
@@ -673,26 +686,12 @@ def spmm_max(indptr, col, row_of, X, w=None, eid=None, want_arg=True, out=None, 
     `eid` is given, else the position p (kgat_spmm_umule_max_f32: dgl.function.max over u_mul_e, or over copy_src with
     w=None).  w is in CSR order.  Equal products: the smallest edge id wins; a row without in-edges is (0, -1).  Exact
     and bitwise reproducible; no backward."""
-    X = _need(X, torch.float32, "X")
-    if X.dim() != 2:
-        raise ValueError("X must be (N, D)")
+    X, indptr, col, row_of, eid, (row0, n_rows, e0, e1), out, workspace = _csr_operands(
+        X, indptr, col, row_of, eid, rows, e_range, workspace, spmm_max_workspace, out, need_row_of=True)
     D = X.shape[1]
-    indptr = _need(indptr, torch.int32, "indptr")
-    col = _need(col, torch.int32, "col")
-    row_of = _need(row_of, torch.int32, "row_of", col.shape)
     if w is not None:
         w = _need(w, torch.float32, "w", col.shape)
-    if eid is not None:
-        eid = _need(eid, torch.int32, "eid", col.shape)
-    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
-    e0, e1 = (0, col.numel()) if e_range is None else e_range
-    if out is None:
-        out = torch.empty((n_rows, D), dtype=torch.float32, device=X.device)
-    else:
-        out = _need(out, torch.float32, "out", (n_rows, D))
     arg = torch.empty((n_rows, D), dtype=torch.int32, device=X.device) if want_arg else None
-    if workspace is None:
-        workspace = spmm_max_workspace(e1 - e0, D, X.device)
     with _timed("spmm_max", (e1 - e0, n_rows, D)):
         check(_lib.load().kgat_spmm_umule_max_f32(n_rows, row0, e0, e1, D, _ptr(indptr), _ptr(col), _ptr(row_of),
                                                   _ptr(eid), _ptr(X), _ptr(w), _ptr(out), _ptr(arg), _ptr(workspace),
@@ -709,24 +708,11 @@ def copy_reduce(indptr, col, row_of, X, reduce="sum", out=None, rows=None, e_ran
     """out[v - row0] = sum | mean_p X[col[p]] over the CSR rows `rows` = (row0, n_rows) whose CSR positions are
     `e_range` (kgat_copy_reduce_f32: update_all(copy_src, sum | mean); no edge weight is read; the mean divides by the
     row's number of positions, rows without in-edges are 0)."""
-    X = _need(X, torch.float32, "X")
-    if X.dim() != 2:
-        raise ValueError("X must be (N, D)")
     if reduce not in REDUCE:
         raise ValueError("reduce must be 'sum' or 'mean', got %r" % (reduce,))
+    X, indptr, col, row_of, _, (row0, n_rows, e0, e1), out, workspace = _csr_operands(
+        X, indptr, col, row_of, None, rows, e_range, workspace, spmm_workspace, out)
     D = X.shape[1]
-    indptr = _need(indptr, torch.int32, "indptr")
-    col = _need(col, torch.int32, "col")
-    if row_of is not None:
-        row_of = _need(row_of, torch.int32, "row_of", col.shape)
-    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
-    e0, e1 = (0, col.numel()) if e_range is None else e_range
-    if out is None:
-        out = torch.empty((n_rows, D), dtype=torch.float32, device=X.device)
-    else:
-        out = _need(out, torch.float32, "out", (n_rows, D))
-    if workspace is None:
-        workspace = spmm_workspace(e1 - e0, D, X.device)
     with _timed("copy_reduce", (e1 - e0, n_rows, D, reduce)):
         check(_lib.load().kgat_copy_reduce_f32(n_rows, row0, e0, e1, D, _ptr(indptr), _ptr(col), _ptr(row_of), _ptr(X),
                                                _ptr(out), REDUCE[reduce], _ptr(workspace), workspace.numel(),
@@ -841,12 +827,9 @@ def spmm_bi_fused(indptr, col, row_of, X, w, W2, negative_slope=0.01, h_out=None
     if X.dim() != 2 or W2.dim() != 2 or W2.shape[1] != X.shape[1]:
         raise ValueError("X must be (N, d_in) and W2 (d_out, d_in)")
     d_in, d_out = X.shape[1], W2.shape[0]
-    indptr = _need(indptr, torch.int32, "indptr")
-    col = _need(col, torch.int32, "col")
+    X, indptr, col, row_of, _, (row0, n_rows, e0, e1), _, workspace = _csr_operands(
+        X, indptr, col, row_of, None, rows, e_range, workspace, spmm_workspace, want_out=False, need_row_of=True)
     w = _need(w, torch.float32, "w", col.shape)
-    row_of = _need(row_of, torch.int32, "row_of", col.shape)
-    row0, n_rows = (0, indptr.numel() - 1) if rows is None else rows
-    e0, e1 = (0, col.numel()) if e_range is None else e_range
     if want_h and h_out is None:
         h_out = torch.empty((n_rows, d_out), dtype=torch.float32, device=X.device)
     if h_out is not None:
@@ -861,8 +844,6 @@ def spmm_bi_fused(indptr, col, row_of, X, w, W2, negative_slope=0.01, h_out=None
         scratch = torch.empty((n_rows, d_in), dtype=torch.float32, device=X.device)
     else:
         scratch = _need(scratch, torch.float32, "scratch", (n_rows, d_in))
-    if workspace is None:
-        workspace = spmm_workspace(e1 - e0, d_in, X.device)
     with _timed("spmm_bi_fused", (e1 - e0, n_rows, d_in, d_out)):
         check(_lib.load().kgat_spmm_bi_fused_f32(n_rows, row0, e0, e1, d_in, d_out, _ptr(indptr), _ptr(col),
                                                  _ptr(row_of), _ptr(X), _ptr(w), _ptr(W2), float(negative_slope),
