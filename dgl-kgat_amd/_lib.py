@@ -17,6 +17,7 @@ SOURCES = {
     "kgat_graph.hip": [],
     "kgat_spmm.hip": [],
     "kgat_spmm_max.hip": [],
+    "kgat_spmm_kmax.hip": [],
     "kgat_spmm_bi.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_softmax.hip": [],
     "kgat_att.hip": [],
@@ -84,6 +85,9 @@ SIGNATURES = {
     # DGL's fn.max reducer with argmax; the max-times product of explain.attention_paths (ABI 16, additive)
     "kgat_spmm_max_workspace_bytes": (_sz, [_i64, _i32]),
     "kgat_spmm_umule_max_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # the top-4 reducer with (edge, slot) back-pointers: explain.attention_paths(top=2..4) (ABI 16, additive)
+    "kgat_spmm_max4_workspace_bytes": (_sz, [_i64, _i32]),
+    "kgat_spmm_umule_max4_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_bi_interaction_supported": (_i32, [_i32, _i32]),
     "kgat_spmm_bi_fused_supported": (_i32, [_i32, _i32]),
     "kgat_spmm_bi_fused_f32": (_i32, [_i64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p,

@@ -1,10 +1,10 @@
-// Host side of the merge-path reducers (u_mul_e -> sum, the fused Bi form, copy_src -> sum | mean, u_mul_e -> max):
-// the geometry constants, the ONE rule that cuts a call's CSR positions into tiles (MergePlan), the argument checks
-// the four entries share and their width lists.  No kernel code: kgat_spmm_impl.h (the sum / copy kernel templates)
-// and kgat_spmm_max.hip both include it.  Not part of the ABI.
+// Host side of the merge-path reducers (u_mul_e -> sum, the fused Bi form, copy_src -> sum | mean, u_mul_e -> max and
+// -> top-4): the geometry constants, the ONE rule that cuts a call's CSR positions into tiles (MergePlan), the argument
+// checks the five entries share and their width lists.  No kernel code: kgat_spmm_impl.h (the sum / copy kernel
+// templates), kgat_spmm_max.hip and kgat_spmm_kmax.hip include it.  Not part of the ABI.
 //
 // A run-length retune is made HERE and nowhere else: the launchers, the workspace functions, kgat_spmm_tile_edges
-// and the max reducer all read merge_plan().
+// and the max and top-4 reducers all read merge_plan().
 #pragma once
 #include "kgat_common.h"
 
@@ -57,7 +57,7 @@ static_assert(fused_run_len(16) == run_len(16),
 
 // The widths with a lane-group geometry (LPR = D / 4 lanes per row, one 16-byte access each).
 using SumWidths = WidthList<4, 8, 16, 32, 64, 128, 256>;  // the sum operator's merge and rows kernels
-using TileWidths = WidthList<16, 32, 64, 128>;            // kgat_spmm_tile_edges, the copy, max and probe kernels
+using TileWidths = WidthList<16, 32, 64, 128>;            // kgat_spmm_tile_edges, the copy, max, top-4 (D = 4 Q) and probe kernels
 
 // How the CSR positions of one call are cut: every reducer's launcher, the workspace functions and
 // kgat_spmm_tile_edges read this and decide nothing themselves.

@@ -255,12 +255,14 @@ class KGATPropagation(nn.Module):
         return g.kgat_attention(self._node_embeddings(g), self.W_R, self.relation_embed.weight, algo=algo,
                                 differentiable=differentiable)
 
-    def explain(self, g, users, items, max_len=None):
+    def explain(self, g, users, items, max_len=None, top=1):
         """The highest-attention walks from items[q] to users[q] under the edge weights in ``g.edata['w']``
         (explain.attention_paths; the case study of the KGAT paper, section 4.5).  max_len defaults to the number of
-        propagation layers: the walks the stack can carry information along."""
+        propagation layers: the walks the stack can carry information along.  top in 2..4: that many ranked walks per
+        length (a ``TopAttentionPaths``)."""
         from .explain import attention_paths
-        return attention_paths(g, g.edata["w"], users, items, max_len=len(self.layers) if max_len is None else max_len)
+        return attention_paths(g, g.edata["w"], users, items, max_len=len(self.layers) if max_len is None else max_len,
+                               top=top)
 
     # -- propagation (models.py:156-168)
     def gnn(self, g, x=None, fused=None):

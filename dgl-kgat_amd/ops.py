@@ -700,7 +700,38 @@ def spmm_max(indptr, col, row_of, X, w=None, eid=None, want_arg=True, out=None, 
     return out, arg
 
 
-REDUCE = {"sum": 0, "mean": 1}
+def spmm_max4_workspace(n_edges, D, device):
+    """Workspace of spmm_max4 for rows of D = 4 Q floats."""
+    return _workspace(_lib.load().kgat_spmm_max4_workspace_bytes(n_edges, D // 4), device)
+
+
+def spmm_max4(indptr, col, row_of, X, w=None, eid=None, want_arg=True, rows=None, e_range=None, workspace=None):
+    """(out, arg_edge, arg_slot): the four largest of {w_p X[col[p], q, s]} over the CSR positions p of a row and the
+    slots s, per query q, in order (kgat_spmm_umule_max4_f32).  X is (N, Q, 4) or (N, 4 Q) float32 with Q in
+    {4, 8, 16, 32}; out is (n_rows, Q, 4), arg_edge (int32) the winners' edges - eid[p] when `eid` is given, else p -
+    and arg_slot (uint8) their source slots, both None without want_arg.  Equal products: the smallest edge, then the
+    smallest slot wins; a row without in-edges is (0, -1, 255).  w is in CSR order.  Exact and bitwise reproducible; no
+    backward."""
+    X = _need(X, torch.float32, "X")
+    if (X.dim() == 3 and X.shape[2] != 4) or (X.dim() == 2 and X.shape[1] % 4):
+        raise ValueError("X must be (N, Q, 4) or (N, 4 Q), got %s" % (tuple(X.shape),))
+    X2 = X.reshape(X.shape[0], -1) if X.dim() == 3 else X
+    X2, indptr, col, row_of, eid, (row0, n_rows, e0, e1), out, workspace = _csr_operands(
+        X2, indptr, col, row_of, eid, rows, e_range, workspace, spmm_max4_workspace, need_row_of=True)
+    Q = X2.shape[1] // 4
+    if w is not None:
+        w = _need(w, torch.float32, "w", col.shape)
+    arg_edge = torch.empty((n_rows, Q, 4), dtype=torch.int32, device=X.device) if want_arg else None
+    arg_slot = torch.empty((n_rows, Q, 4), dtype=torch.uint8, device=X.device) if want_arg else None
+    with _timed("spmm_max4", (e1 - e0, n_rows, Q)):
+        check(_lib.load().kgat_spmm_umule_max4_f32(n_rows, row0, e0, e1, Q, _ptr(indptr), _ptr(col), _ptr(row_of),
+                                                   _ptr(eid), _ptr(X2), _ptr(w), _ptr(out), _ptr(arg_edge),
+                                                   _ptr(arg_slot), _ptr(workspace), workspace.numel(), _stream(X2)),
+              "kgat_spmm_umule_max4_f32")
+    return out.view(n_rows, Q, 4), arg_edge, arg_slot
+
+
+REDUCE ={"sum": 0, "mean": 1}
 ACT = {None: 0, "none": 0, "relu": 1}
 
 

@@ -17,6 +17,7 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
                                                                           # planted structure: recall@20 must rise
   python examples/train_kgat.py --synthetic 0.01 --gpus 2                # CF phase on destination shards
   python examples/train_kgat.py --planted --epochs 3 --explain 5         # + why the top-1 item: its best attention walk
+  python examples/train_kgat.py --planted --epochs 3 --explain 5 --explain_top 3   # + its three best walks, ranked
   python examples/train_kgat.py --synthetic 1.0 --grad_norm 1.0          # clip the CF gradient's global norm (kgat.py:32,162)
 
 ``--gpus N``: one process per GPU (started here as a child ``torch.distributed.run``),
@@ -183,10 +184,17 @@ def parse_args(argv=None):
     ap.add_argument("--explain", type=int, default=0, metavar="N",
                     help="after the last evaluation: for the first N test users, the top-1 recommended item and the "
                          "highest-attention walk from it to the user (KGATPropagation.explain; the KGAT paper's case study)")
+    ap.add_argument("--explain_top", type=int, default=1, metavar="K",
+                    help="with --explain: also the K (1..4) highest-attention walks of each pair over all lengths, "
+                         "ranked (explain.attention_paths(top=K)); 1 prints the best walk only")
     args = ap.parse_args(argv)
     # (before --gpus starts its ranks: a refused combination fails once, here)
     if args.explain < 0:
         ap.error("--explain takes a number of users >= 0")
+    if not 1 <= args.explain_top <= 4:
+        ap.error("--explain_top takes 1, 2, 3 or 4")
+    if args.explain_top > 1 and not args.explain:
+        ap.error("--explain_top ranks the walks of --explain N: give a number of users")
     if args.explain and args.gpus > 1:
         ap.error("--explain runs on one GPU: a walk crosses shards")
     if args.explain and args.gnn_model == "graphsage":
@@ -414,12 +422,21 @@ def _run(args, argv):
             emb = model.gnn(test_g, test_g.ndata["id"])
             users = sorted(test_dict)[:args.explain]
             top1 = metrics.recommend(emb, users, ds.item_id_range, 1, seen=train_valid_dict)[0][:, 0].tolist()
-            paths = model.explain(test_g, users, [max(i, 0) for i in top1])
+            if args.explain_top == 1:
+                paths, ranked = model.explain(test_g, users, [max(i, 0) for i in top1]), None
+            else:
+                ranked = model.explain(test_g, users, [max(i, 0) for i in top1], top=args.explain_top)
+                paths = ranked.first()
         for q, (u, i) in enumerate(zip(users, top1)):
             if i < 0:
                 say("explain | user %d: no unseen item" % u)
                 continue
             say("explain | user %d item %d | score %.6g | %s" % (u, i, paths.best(q)[2], paths.describe(q)))
+            for r in range(args.explain_top if ranked is not None else 0):
+                if int(ranked.ranked_len[q, r]) == 0:
+                    break
+                say("explain+ | user %d item %d | rank %d | len %d | score %.6g | %s"
+                    % (u, i, r + 1, int(ranked.ranked_len[q, r]), float(ranked.ranked_score[q, r]), ranked.describe(q, r)))
     if args.log_json and rank == 0:
         import json
         with open(args.log_json, "w") as f:

@@ -410,6 +410,30 @@ int kgat_spmm_umule_max_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64
                             const float* w, float* out, int32_t* arg, void* workspace, size_t workspace_bytes,
                             kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- top-4 reducer with back-pointers (additive within ABI 16)
+ * The k-best max-times product behind explain.attention_paths(top = 2..4): the four walks of highest attention product
+ * per (node, query) instead of one.  X is [N x Q x 4] fp32 - Q queries with four slots each, rows of 4 Q floats.  For
+ * every row v in [row0, row0 + n_rows), whose CSR positions are [e_begin, e_end), and every query q the candidates are
+ *   { (w[p] * X[col[p], q, s], id(p), s) : p a CSR position of row v, s in 0..3 },   id(p) = eid[p] (eid != NULL) or p
+ * (w == NULL: times 1.0f; w in CSR order) and the four largest are returned in order:
+ *   out      [n_rows x Q x 4 fp32]   the winners' product bits
+ *   arg_edge [n_rows x Q x 4 int32]  their ids
+ *   arg_slot [n_rows x Q x 4 uint8]  their source slots (a query's four bytes are one 32-bit word)
+ * (a, i, r) beats (b, k, s) iff a > b, or a == b and (i < k, or i == k and r < s): IEEE comparison on the fp32 products,
+ * -0.0 ties with 0.0; the (id, slot) pairs are distinct, so the order is total and the result does not depend on how
+ * the tiles split a row - no atomics, bitwise reproducible.  Nothing is assumed about the order of a source's slots or
+ * about signs: the identity is (-inf, INT32_MAX, 4), and every row with an in-edge has four candidates and more.  A row
+ * without in-edges: out = 0, arg_edge = -1, arg_slot = 255.  Inputs finite or +-inf; NaN: unspecified.  arg_edge and
+ * arg_slot may each be NULL (not written).  Q in {4, 8, 16, 32}, any other Q: KGAT_E_BADARG, as are a null pointer, a
+ * negative size and workspace_bytes < kgat_spmm_max4_workspace_bytes(e_end - e_begin, Q).  row_of is required; X, out,
+ * arg_edge and the workspace 16-byte aligned, arg_slot 4-byte aligned.  The tiles are kgat_spmm_tile_edges(n, 4 Q)
+ * edges.  No backward. */
+size_t kgat_spmm_max4_workspace_bytes(int64_t n_edges, int Q);
+int kgat_spmm_umule_max4_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int64_t e_end, int Q, const int32_t* indptr,
+                             const int32_t* col, const int32_t* row_of, const int32_t* eid, const float* X,
+                             const float* w, float* out, int32_t* arg_edge, uint8_t* arg_slot, void* workspace,
+                             size_t workspace_bytes, kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- bi-interaction (B1 + B2)
  * Forward of the dense part of KGATConv (reference models.py:66) fused with the readout
  * normalisation (models.py:165-167):  Z = LeakyReLU_slope(P @ W2^T), P = h * h_N (n_rows x d_in,
