@@ -209,10 +209,13 @@ __device__ __forceinline__ void small_sort_body(const SortJob& job) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int32_t v = 4 * tid + q;
-      if (v <= n_keys) chunk_ptr[v] = base;
-      if (v < n_keys)
+      if (v < n_keys) {
+        chunk_ptr[v] = base;
         for (int32_t j = 0; j < c[q]; ++j) chunks[base + j] = make_int2(v, s_off[v] + j * kTrChunk);
+      }
       base += c[q];
+      // the total, from the owner of the last key: at n_keys = kTrMaxRel = 4 x 1024 no thread has v = n_keys
+      if (v + 1 == n_keys) chunk_ptr[n_keys] = base;
     }
   }
 }
