@@ -89,6 +89,65 @@ def test_csr_large_ids_three_radix_passes(K, dev):
     assert np.array_equal(col.cpu().numpy(), oc)
 
 
+def _csr_bit_exact(ops, dev, n, src, dst):
+    """All four outputs of csr_from_coo against numpy (stable argsort, bincount)."""
+    indptr, col, eid, row_of = ops.csr_from_coo(n, t32(src, dev), t32(dst, dev))
+    oe = np.argsort(dst, kind="stable")
+    oi = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))])
+    assert np.array_equal(indptr.cpu().numpy(), oi)
+    assert np.array_equal(eid.cpu().numpy(), oe)
+    assert np.array_equal(col.cpu().numpy(), src[oe])
+    assert np.array_equal(row_of.cpu().numpy(), dst[oe])
+
+
+SORT_CLASS_SIZES = [(1 << 20) - 1, 1 << 20, (1 << 20) + 1]  # 256 keys per block below 2^20 keys, 4,096 from there on
+
+
+@pytest.mark.parametrize("e", SORT_CLASS_SIZES)
+def test_csr_sort_size_classes(K, dev, e):
+    """Both sides of the sort's switch of tile (a ragged last block of 255 keys, of 1 key, whole blocks), two passes."""
+    from dgl_kgat_amd import ops
+    src, dst = random_graph(3, 3000, e, hub=300_000, isolated_tail=100)
+    _csr_bit_exact(ops, dev, 3000, src, dst)
+
+
+@pytest.mark.parametrize("e", SORT_CLASS_SIZES)
+def test_group_by_relation_sort_size_classes(K, dev, e):
+    from dgl_kgat_amd import ops
+    n_rel = 41
+    et = np.random.default_rng(e).integers(-2, n_rel + 3, e).astype(np.int32)  # [-2, 43]: types outside [0, R) included
+    rel_ptr, perm = ops.group_by_relation(t32(et, dev), n_rel)
+    key = np.where((et >= 0) & (et < n_rel), et, n_rel)
+    assert np.array_equal(rel_ptr.cpu().numpy(), np.concatenate([[0], np.cumsum(np.bincount(key, minlength=n_rel + 1)[:n_rel])]))
+    assert np.array_equal(perm.cpu().numpy(), np.argsort(key, kind="stable"))
+
+
+@pytest.mark.parametrize("n", SORT_CLASS_SIZES)
+def test_row_order_by_degree_sort_size_classes(K, dev, n):
+    """2^20 rows: degrees 0 .. 40, some rows of 65,534 .. 65,537 and one of 300,000 in-edges (the key holds a degree
+    up to 65,535; larger ones tie there and keep their row order)."""
+    from dgl_kgat_amd import ops
+    rng = np.random.default_rng(n)
+    deg = rng.integers(0, 41, n).astype(np.int64)
+    deg[rng.choice(n, 9, replace=False)] = [65534, 65535, 65536, 65537, 300_000, 65535, 65536, 70_000, 65534]
+    indptr = np.concatenate([[0], np.cumsum(deg)])
+    assert indptr[-1] < 2 ** 31
+    order = ops.row_order_by_degree(t32(indptr, dev)).cpu().numpy()
+    assert np.array_equal(order, np.argsort(-np.minimum(deg, 65535), kind="stable"))
+
+
+def test_csr_large_ids_four_radix_passes(K, dev):
+    """Node ids of 25 bits: four 8-bit passes, so the ping-pong buffers start on the other side than with three."""
+    from dgl_kgat_amd import ops
+    n, e = (1 << 24) + 1000, 5000
+    rng = np.random.default_rng(4)
+    low, high = rng.integers(0, 51, e), rng.integers((1 << 24) - 50, (1 << 24) + 1000, e)
+    dst = np.where(rng.random(e) < 0.5, low, high).astype(np.int32)
+    assert dst.min() <= 50 and dst.max() >= 1 << 24 and np.any((dst < 1 << 24) & (dst >= (1 << 24) - 50))
+    src = rng.integers(0, n, e).astype(np.int32)
+    _csr_bit_exact(ops, dev, n, src, dst)
+
+
 @pytest.mark.parametrize("n_rel,e", [(1, 10), (5, 5000), (41, 70000), (300, 9000)])
 def test_group_by_relation_bit_exact(K, dev, n_rel, e):
     from dgl_kgat_amd import ops
@@ -364,9 +423,10 @@ def test_edge_softmax_vs_oracle(K, dev, name, n, e, hub, iso):
 
 @pytest.mark.parametrize("e", [1, 15, 16, 17, 1023, 1024, 1025, 2048, 70001])
 def test_edge_softmax_range_boundaries_and_hubs(K, dev, e):
-    """Rows cut by the 1,024-position wavefront ranges (incl. rows spanning many ranges and a row
-    that is the whole graph), sizes around the lane / range granularity, destination-range
-    sub-ranges (shards), and agreement with the independent three-pass implementation."""
+    """Rows cut by the 512-position wavefront ranges of the 8-positions-per-lane form every call here takes (incl.
+    rows spanning many ranges and a row that is the whole graph; the 1,024-position form: test_gpu_softmax_wide.py),
+    sizes around the lane / range granularity, destination-range sub-ranges (shards), and agreement with the
+    independent three-pass implementation."""
     from dgl_kgat_amd import ops
     rng = np.random.default_rng(100 + e)
     n = 300
