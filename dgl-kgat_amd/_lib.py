@@ -15,6 +15,7 @@ SO_PATH = os.path.join(_HERE, "libkgat_hip.so")
 # LDS-staged chunk kernels lose occupancy with it and are built without.
 SOURCES = {
     "kgat_graph.hip": [],
+    "kgat_permute.hip": [],
     "kgat_spmm.hip": [],
     "kgat_spmm_max.hip": [],
     "kgat_spmm_kmax.hip": [],
@@ -113,6 +114,10 @@ SIGNATURES = {
     "kgat_gather_probe_f32": (_i32, [_i64, _i32, _p, _p, _p, _p]),
     "kgat_gather_f32": (_i32, [_i64, _p, _p, _p, _p]),
     "kgat_gather_i32": (_i32, [_i64, _p, _p, _p, _p]),
+    # a graph-static permutation as two streaming passes over a plan (ABI 16, additive)
+    "kgat_permute_tile": (_i32, []),
+    "kgat_permute_supported": (_i32, [_i64]),
+    "kgat_permute_f32": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p]),
     "kgat_eval_supported": (_i32, [_i32, _i32]),
     "kgat_eval_items_elems": (_i64, [_i64, _i32]),
     "kgat_eval_items_kmajor_f32": (_i32, [_i64, _i32, _p, _i64, _p, _p, _p]),

@@ -258,6 +258,25 @@ class _Structure:
             c["rel_groups"] = hit
         return hit[1]
 
+    def permuted(self, name, src_of, values, out=None):
+        """out[i] = values[src_of[i]] for one of the graph's static E-sized permutations (`name`: the key its plan is
+        kept under; `src_of`: the cached int32 index itself).  fp32 values go through the planned two-pass form
+        (ops.permute: no random global access) where kgat_permute_supported says it streams - the plan is built on
+        first use and kept with the structure, as is the one scratch buffer per device, which the launches of one
+        stream share; larger graphs and values or outputs off a 16-byte boundary keep the gather."""
+        planned = (values.dtype == torch.float32 and ops.permute_supported(src_of.numel())
+                   and values.data_ptr() % 16 == 0 and (out is None or out.data_ptr() % 16 == 0))
+        if not planned:
+            return ops.gather(src_of, values, out=out)
+        c = self._cache(values.device)
+        plan = c.get(("permute_plan", name))
+        if plan is None or plan[0] is not src_of:
+            plan = c[("permute_plan", name)] = (src_of, ops.permute_plan(src_of))
+        tmp = c.get("permute_tmp")
+        if tmp is None or tmp.numel() != src_of.numel():
+            tmp = c["permute_tmp"] = torch.empty(src_of.numel(), dtype=torch.float32, device=values.device)
+        return ops.permute(plan[1], values, out=out, tmp=tmp)
+
     def weight_in_csr_order(self, w_flat):
         """Per-edge weights permuted to CSR order once per distinct weight tensor; the SpMM
         then streams them coalesced (kgat.py:144 sets 'w' once per epoch, models.py:63 uses
@@ -266,7 +285,7 @@ class _Structure:
         key = (w_flat.data_ptr(), w_flat._version, w_flat.numel())
         hit = c.get("w_csr")
         if hit is None or hit[0] != key:
-            hit = (key, ops.gather(self.csr(w_flat.device).eid, w_flat), w_flat)
+            hit = (key, self.permuted("csr_eid", self.csr(w_flat.device).eid, w_flat), w_flat)
             c["w_csr"] = hit
         return hit[1]
 
@@ -320,7 +339,7 @@ class _Structure:
         if hit is None or hit[0] is not w_csr:
             if "rev_from_csr" not in c:  # CSR position of the edge at every reversed-CSR position
                 c["rev_from_csr"] = ops.gather(self.csr_rev(w_csr.device).eid, self.csr_pos(w_csr.device))
-            hit = c["w_rev_of_csr"] = (w_csr, ops.gather(c["rev_from_csr"], w_csr))
+            hit = c["w_rev_of_csr"] = (w_csr, self.permuted("rev_from_csr", c["rev_from_csr"], w_csr))
         return hit[1]
 
     def remember_weight(self, w_flat, w_csr):
@@ -715,7 +734,7 @@ class DGLGraph:
             flat = store.view(-1)
 
             def fill():
-                ops.gather(st.csr_pos(dev), w_csr, out=flat)
+                st.permuted("csr_pos", st.csr_pos(dev), w_csr, out=flat)
                 st.remember_weight(flat, w_csr)
             a = LazyEdgeWeights(store, fill, st, w_csr)
         c[("laplacian", adj_type)] = (a, w_csr, a._version)
@@ -811,8 +830,8 @@ class DGLGraph:
         a = torch.empty((st.n_edges, 1), dtype=torch.float32, device=dev)
         a_flat = a.view(-1)
 
-        def fill():  # edge-id order: coalesced writes, cached reads
-            ops.gather(st.csr_pos(dev), a_csr, out=a_flat)
+        def fill():  # edge-id order: two streaming passes over the graph's plan (the gather beyond its size rule)
+            st.permuted("csr_pos", st.csr_pos(dev), a_csr, out=a_flat)
             st.remember_weight(a_flat, a_csr)
         if not lazy:
             fill()

@@ -4,8 +4,9 @@
 and the training loop stores it as ``g.edata['w']`` (kgat.py:142-144); the only reader on the
 path is ``update_all(u_mul_e('h','w','m'), sum)`` (models.py:63), whose kernel streams the
 weights in destination-major CSR order - the order the softmax kernel produces them in.  The
-edge-id-ordered copy is a permutation of 4-byte items (a full pass through the cache fabric at
-sector granularity, ~30 us on the amazon-book CKG, 5 % of a step) that nothing on the path reads.
+edge-id-ordered copy is a permutation of 4-byte items (two streaming passes over a static plan,
+~18 us on the amazon-book CKG, 4 % of a step; a random gather beyond the plan's size rule) that nothing
+on the path reads.
 
 ``LazyEdgeWeights`` is that tensor with the permutation deferred: it owns real, correctly shaped
 device storage from the start; the graph structure keeps the CSR-ordered values next to it and
@@ -26,7 +27,7 @@ operator or ``data_ptr()`` on the Python side.
 environment, or ``lazy=True`` on one ``kgat_attention`` call.  Importing this package changes nothing in torch;
 only ``enable()`` wraps ``torch.utils.dlpack.to_dlpack`` (one process-wide wrapper, undone by ``enable(False)``),
 because a library that rewrites a torch global at import is a liability inside someone else's training process.
-By default ``compute_attention`` therefore returns an ordinary, fully written tensor (6 % of a step on the
+By default ``compute_attention`` therefore returns an ordinary, fully written tensor (4 % of a step on the
 benchmark graph); ``KGAT_EAGER_EDGE_WEIGHTS=1`` forces that even after ``enable()``.
 """
 import copy

@@ -5,6 +5,8 @@ and nothing else: every arithmetic step of the path happens inside libkgat_hip.s
 functions validate device / dtype / contiguity before the call and turn a non-zero return
 code into KGATLibraryError.  CPU tensors are rejected: this path has no CPU implementation.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _lib
@@ -148,6 +150,72 @@ def gather(index, values, out=None):
     fn = _lib.load().kgat_gather_f32 if dtype == torch.float32 else _lib.load().kgat_gather_i32
     with _timed("gather", (index.numel(),)):
         check(fn(index.numel(), _ptr(index), _ptr(values), _ptr(out), _stream(index)), "kgat_gather")
+    return out
+
+
+def permute_tile():
+    """Chunk / block length of the planned permutation (kgat_permute_tile)."""
+    return int(_lib.load().kgat_permute_tile())
+
+
+def permute_supported(n):
+    """Whether the planned permutation streams at n items (kgat_permute_supported); beyond, call `gather`."""
+    return bool(_lib.load().kgat_permute_supported(int(n)))
+
+
+PermutePlan = namedtuple("PermutePlan", "n slot_a dst_a slot_b")
+
+
+def permute_plan_arrays(src_of, tile):
+    """(slot_a, dst_a, slot_b) of include/kgat_hip.h for the permutation `src_of` (an integer tensor holding every
+    value of range(n) once; not checked here) at chunk / block length `tile` <= 32,768: index arithmetic and two
+    stable sorts on whatever device `src_of` is on.  The 16-bit ranks are held as int16 (same bits below 2^15)."""
+    n, dev = src_of.numel(), src_of.device
+    pos = torch.arange(n, dtype=torch.int64, device=dev)
+    dst_of = torch.zeros_like(pos)
+    dst_of[src_of.long()] = pos                                  # destination of every source position
+    blk = dst_of // tile
+    order = torch.argsort(blk, stable=True)                      # tmp[j] holds source position order[j]
+    tmp_of = torch.empty_like(pos)
+    tmp_of[order] = pos
+    slot_b = (dst_of[order] % tile).to(torch.int16)
+    n_blk = (n + tile - 1) // tile
+    order2 = torch.argsort((pos // tile) * n_blk + blk, stable=True)  # order2[c * tile + i]: source at rank i of chunk c
+    slot_a = torch.empty(n, dtype=torch.int16, device=dev)
+    slot_a[order2] = (pos % tile).to(torch.int16)
+    return slot_a, tmp_of[order2].to(torch.int32), slot_b
+
+
+def permute_plan(src_of):
+    """The static plan of kgat_permute_f32 for out[i] = in[src_of[i]] (`src_of` an int32 permutation of range(n)):
+    one-off setup.  The sorts run on the HOST (about a second at 4 M items): on the device their temporaries - a dozen
+    arrays of odd sizes - stay behind in torch's caching allocator as free blocks that the step's buffers are then carved
+    from, and that placement cost bench.py's step 6 us (profiles/r07_permute_ab.txt); this way the device allocator
+    sees the three plan arrays, which stay, and blocks of n floats.  The plan is proved before it is returned: it must
+    move arange(n) onto src_of, bit for bit."""
+    src_of = _need(src_of, torch.int32, "src_of")
+    n, dev = src_of.numel(), src_of.device
+    if not permute_supported(n):
+        raise KGATLibraryError("permute_plan: %d items are beyond kgat_permute_supported" % n)
+    host = src_of.cpu()
+    if n and (int(host.min()) < 0 or int(host.max()) >= n):
+        raise ValueError("permute_plan: src_of is not a permutation of range(%d)" % n)
+    plan = PermutePlan(n, *(t.to(dev) for t in permute_plan_arrays(host, permute_tile())))
+    probe = torch.arange(n, dtype=torch.int32, device=dev).view(torch.float32)
+    if not torch.equal(permute(plan, probe).view(torch.int32), src_of):
+        raise KGATLibraryError("permute_plan: the plan does not reproduce the permutation it was built from")
+    return plan
+
+
+def permute(plan, values, out=None, tmp=None):
+    """out[i] = values[src_of[i]] through the plan of `permute_plan(src_of)`: two streaming launches
+    (kgat_permute_f32).  `tmp`: n floats of scratch a caller may keep between calls on one stream."""
+    values = _need(values, torch.float32, "values", (plan.n,))
+    out = torch.empty_like(values) if out is None else _need(out, torch.float32, "out", (plan.n,))
+    tmp = torch.empty_like(values) if tmp is None else _need(tmp, torch.float32, "tmp", (plan.n,))
+    with _timed("permute", (plan.n,)):
+        check(_lib.load().kgat_permute_f32(plan.n, _ptr(plan.slot_a), _ptr(plan.dst_a), _ptr(plan.slot_b), _ptr(values),
+                                           _ptr(out), _ptr(tmp), _stream(values)), "kgat_permute_f32")
     return out
 
 
@@ -1297,6 +1365,7 @@ def sddmm_dot(src, dst, X, G):
 
 
 __all__ = ["csr_from_coo", "group_by_relation", "invert_permutation", "row_order_by_degree", "gather",
+           "permute_tile", "permute_supported", "permute_plan_arrays", "permute_plan", "permute", "PermutePlan",
            "att_score", "att_score_split", "att_score_split_supported", "att_score_folded_supported", "att_score_fused", "att_pack_records", "att_score_fused_supported", "fold_tiles", "fold_tile_cost", "bi_interaction_train", "add3_rows", "bi_interaction_bwd_pre", "bi_interaction_bwd_input", "bi_interaction_bwd_input_supported", "bi_interaction_bwd_weight", "sum_partials", "mul2", "dropout_keep_mask", "transr_loss_grad", "transr_supported", "transr_presort", "transr_adam_step", "TransRAdamState", "head_groups", "edge_softmax", "edge_softmax_bwd", "spmm", "spmm_workspace", "sddmm_dot",
            "bi_interaction", "bi_interaction_supported", "l2_normalize_rows", "readout_concat",
            "FORMS", "aggregator", "aggregator_supported", "aggregator_bwd_supported", "aggregator_train",

@@ -489,6 +489,25 @@ int kgat_gather_f32(int64_t n, const int32_t* index, const float* in, float* out
 int kgat_gather_i32(int64_t n, const int32_t* index, const int32_t* in, int32_t* out,
                     kgat_stream_t stream);
 
+/* The same permutation of fp32 values, out[i] = in[src_of[i]], for a permutation src_of that stays the same from call
+ * to call (graph-static: CSR position of every edge id and the like), without a random global access: two streaming
+ * passes through LDS over a plan the caller builds once per permutation.  With T = kgat_permute_tile, sources cut into
+ * chunks and destinations into blocks of T consecutive items, and an intermediate array tmp[n] ordered by
+ * (destination block, source position):
+ *   slot_a[p]       rank of source position p inside its chunk under the order (destination block, p)
+ *   dst_a[c*T + i]  index in tmp of the item at rank i of chunk c
+ *   slot_b[j]       offset inside its destination block of the item at tmp[j]
+ * (ranks and offsets < T, 16 bit).  Launch 1 writes tmp, launch 2 reads it and writes out; in, out and tmp are three
+ * distinct buffers of n floats; slot_a, slot_b, in, out and tmp 16-byte aligned.  Values move as 32-bit words.  A
+ * damaged plan gives wrong values, never an access outside the buffers.
+ * kgat_permute_supported: 1 while the mean (chunk, block) run T * T / n is at least a 64-byte sector (16 items) -
+ * beyond that (n > 16,777,216 at T = 16,384) the passes stop streaming and kgat_gather_f32 stays the form to call;
+ * the entry returns KGAT_E_UNSUPPORTED there. */
+int kgat_permute_tile(void);
+int kgat_permute_supported(int64_t n);
+int kgat_permute_f32(int64_t n, const uint16_t* slot_a, const int32_t* dst_a, const uint16_t* slot_b, const float* in,
+                     float* out, float* tmp, kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- training form of the layer (8f #1)
  * The forward of one KGATConv under autograd is kgat_aggregator_train_f32 (below); these are the pieces around it.
  * kgat_add3_rows_f32: out = (a + b) + c over n_rows x d, a being a column slice (rows of a_stride floats) of a wider
