@@ -16,7 +16,9 @@ from ._lib import KGATLibraryError  # noqa: F401
 from .lazy import enable as enable_lazy_edge_weights  # noqa: F401
 from .partition import GraphedForward  # noqa: F401
 from .optim import FusedAdam, clip_grad_norm_  # noqa: F401
+from . import kg_eval  # noqa: F401
+from .kg_eval import KGRanks, KnownTriples, kg_complete, kg_metrics, kg_rank  # noqa: F401
 
 __all__ = ["DGLGraph", "DGLError", "ALL", "function", "explain", "edge_softmax", "KGATConv", "KGATPropagation", "SAGEConv",
            "install_as_dgl", "accelerate", "KGATLibraryError", "CKGDataset", "enable_lazy_edge_weights", "GraphedForward",
-           "FusedAdam", "clip_grad_norm_"]
+           "FusedAdam", "clip_grad_norm_", "kg_eval", "KnownTriples", "KGRanks", "kg_rank", "kg_metrics", "kg_complete"]

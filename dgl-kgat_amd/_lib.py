@@ -25,6 +25,7 @@ SOURCES = {
     "kgat_att_persistent.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_transr.hip": [],
+    "kgat_transr_rank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_eval.hip": [],
     "kgat_eval_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_optim.hip": [],
@@ -175,6 +176,11 @@ SIGNATURES = {
     "kgat_eval_metrics_at_ks": (_i32, [_i64, _i32, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "kgat_edge_norm_f32": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p]),
     "kgat_edge_dropout_f32": (_i32, [_i64, _p, _p, C.c_float, C.c_uint64, _p, _p]),
+    # TransR link prediction: projection + filtered rank counts (ABI 16, additive)
+    "kgat_transr_project_supported": (_i32, [_i32, _i32]),
+    "kgat_transr_project_f32": (_i32, [_i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p, C.c_float, _p, _p, _p]),
+    "kgat_transr_rank_supported": (_i32, [_i32]),
+    "kgat_transr_rank_f32": (_i32, [_i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
 }
 
 _lib = None

@@ -607,6 +607,22 @@ class KGATPropagation(nn.Module):
                 s_["step"].fill_(float(t))
         return losses
 
+    # -- link prediction with the TransR embedding (kg_eval.py)
+    def kg_rank(self, h, r, t, known=None, side="tail", candidates=None):
+        """Filtered ranks of the triples under the TransR score (kg_eval.kg_rank): KGRanks(lt, eq, rank)."""
+        from .kg_eval import kg_rank
+        return kg_rank(self, h, r, t, known=known, side=side, candidates=candidates)
+
+    def kg_metrics(self, h, r, t, known=None, side="both", hits=(1, 3, 10), batch=2048):
+        """MR / MRR / Hits@k of the filtered ranks (kg_eval.kg_metrics)."""
+        from .kg_eval import kg_metrics
+        return kg_metrics(self, h, r, t, known=known, side=side, hits=hits, batch=batch)
+
+    def kg_complete(self, h, r, K, known=None, candidates=None):
+        """The K entities closest to (h, r, ?) with their distances (kg_eval.kg_complete)."""
+        from .kg_eval import kg_complete
+        return kg_complete(self, h, r, K, known=known, candidates=candidates)
+
     def _gnn_fused_sharded(self, g):
         """No-grad path on a destination-range shard: per layer the local aggregation, the
         bi-interaction kernel on the owned rows, one all-reduce, and the row normalisation of the

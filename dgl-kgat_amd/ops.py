@@ -1484,6 +1484,125 @@ def eval_metrics_at_ks(topk, test_ptr, test_items, ks):
     return out
 
 
+# ---------------------------------------------------------------- TransR link prediction (models.py:120-126)
+def transr_project_supported(d, k):
+    return bool(_lib.load().kgat_transr_project_supported(int(d), int(k)))
+
+
+def transr_rank_supported(k):
+    return bool(_lib.load().kgat_transr_rank_supported(int(k)))
+
+
+def transr_project(ent, W_r, rel_row=None, sign=1.0, ids=None, rows=None, want_n2=True, out=None, n2_out=None):
+    """normalise(ent[rows] W_r) + sign * normalise(rel_row) per row (kgat_transr_project_f32; the normalisation is
+    x / max(|x|, 1e-12), the training kernel's).  `ent` (N, d), `W_r` (d, k); the rows are `ids` (int32 entity ids) or
+    the contiguous range `rows = (lo, hi)` (default: all of ent); rel_row None: the pure projection.  Returns
+    (out (n, k), n2 (n,)) - n2 the squared norm of the normalised projection (None with want_n2=False); `out` / `n2_out`: buffers to write them into.  Widths outside
+    transr_project_supported raise KGATLibraryError (kg_eval restates them in torch)."""
+    if not isinstance(ent, torch.Tensor) or not isinstance(W_r, torch.Tensor):
+        raise TypeError("ent and W_r must be torch.Tensors")
+    if ent.dtype != torch.float32 or W_r.dtype != torch.float32:
+        raise TypeError("ent and W_r must be torch.float32, got %s and %s" % (ent.dtype, W_r.dtype))
+    if ent.dim() != 2 or W_r.dim() != 2 or W_r.shape[0] != ent.shape[1]:
+        raise ValueError("transr_project: ent (N, d) and W_r (d, k), got %s and %s" % (tuple(ent.shape), tuple(W_r.shape)))
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("transr_project: sign must be +1 or -1, got %r" % (sign,))
+    if ids is not None and rows is not None:
+        raise ValueError("transr_project: give `ids` or `rows`, not both")
+    n_ent, d = ent.shape
+    k = W_r.shape[1]
+    if ids is not None:
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1:
+            raise TypeError("ids must be a 1-d torch.int32 tensor")
+        n, row0 = ids.numel(), 0
+        if n and (int(ids.min()) < 0 or int(ids.max()) >= n_ent):
+            raise IndexError("transr_project: ids outside [0, %d)" % n_ent)
+    else:
+        lo, hi = (0, n_ent) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= lo <= hi <= n_ent:
+            raise IndexError("transr_project: rows (%d, %d) outside [0, %d]" % (lo, hi, n_ent))
+        n, row0 = hi - lo, lo
+    ent = _need(ent, torch.float32, "ent")
+    W_r = _need(W_r, torch.float32, "W_r")
+    if rel_row is not None:
+        rel_row = _need(rel_row, torch.float32, "rel_row", (k,))
+    if ids is not None:
+        ids = _need(ids, torch.int32, "ids")
+    lib = _lib.load()
+    if not lib.kgat_transr_project_supported(d, k):
+        raise KGATLibraryError("transr_project: widths %d -> %d outside the kernel's {16, 32, 64, 128}" % (d, k))
+    out = torch.empty((n, k), dtype=torch.float32, device=ent.device) if out is None else \
+        _need(out, torch.float32, "out", (n, k))
+    if want_n2:
+        n2 = torch.empty(n, dtype=torch.float32, device=ent.device) if n2_out is None else \
+            _need(n2_out, torch.float32, "n2_out", (n,))
+    else:
+        n2 = None
+    with _timed("transr_project", (n, d, k)):
+        check(lib.kgat_transr_project_f32(n, n_ent, d, k, _ptr(ent), _ptr(ids), row0, _ptr(W_r), _ptr(rel_row),
+                                          float(sign), _ptr(out), _ptr(n2), _stream(ent)), "kgat_transr_project_f32")
+    return out, n2
+
+
+def check_rank_lists(t, c0, n_c, filter_ptr, filter_ids):
+    """What kgat_transr_rank_f32 leaves to its caller, on any device: every t inside [c0, c0 + n_c), filter_ptr from 0
+    to len(filter_ids) without a decrease, every query's filter ids strictly ascending.  One host read."""
+    n_q = t.numel()
+    if filter_ptr.numel() != n_q + 1:
+        raise ValueError("filter_ptr has %d entries, expected n_q + 1 = %d" % (filter_ptr.numel(), n_q + 1))
+    bad_t = ((t < c0) | (t >= c0 + n_c)).any()
+    ptr = filter_ptr.long()
+    bad_ptr = (ptr[0] != 0) | (ptr[-1] != filter_ids.numel()) | (ptr[1:] < ptr[:-1]).any()
+    flags = [bool(x) for x in torch.stack([bad_t, bad_ptr]).tolist()]
+    if flags[0]:
+        raise IndexError("transr_rank: a true answer `t` lies outside the candidate range [%d, %d)" % (c0, c0 + n_c))
+    if flags[1]:
+        raise ValueError("transr_rank: filter_ptr must run from 0 to len(filter_ids) without a decrease")
+    if filter_ids.numel() > 1:
+        # a descent (or a repeat) is allowed only where a new query's list begins
+        starts = torch.zeros(filter_ids.numel() + 1, dtype=torch.bool, device=filter_ids.device)
+        starts[ptr] = True
+        if bool(((filter_ids[1:] <= filter_ids[:-1]) & ~starts[1:-1]).any()):
+            raise ValueError("transr_rank: the filter ids of a query must be sorted (strictly ascending)")
+
+
+def transr_rank(Q, t, P, n2, c0, filter_ptr, filter_ids):
+    """Filtered rank counts (kgat_transr_rank_f32): queries `Q` (n_q, k) with the entity ids `t` of their true answers,
+    candidates `P` (n_c, k) / `n2` (n_c,) = the entities [c0, c0 + n_c), per query the sorted ids
+    filter_ids[filter_ptr[j]:filter_ptr[j + 1]] to leave out (the true answer always is).  Returns int32 (lt, eq): the
+    candidates with n2_i - 2 Q_j . P_i below / equal to the true answer's.  Exact integer sums: bitwise reproducible."""
+    for x, name, dt, nd in ((Q, "Q", torch.float32, 2), (t, "t", torch.int32, 1), (P, "P", torch.float32, 2),
+                            (n2, "n2", torch.float32, 1), (filter_ptr, "filter_ptr", torch.int32, 1),
+                            (filter_ids, "filter_ids", torch.int32, 1)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if x.dtype != dt:
+            raise TypeError("%s must be %s, got %s" % (name, dt, x.dtype))
+        if x.dim() != nd:
+            raise ValueError("%s must have %d dimension(s), got shape %s" % (name, nd, tuple(x.shape)))
+    n_q, k = Q.shape
+    n_c, c0 = P.shape[0], int(c0)
+    if P.shape[1] != k or n2.numel() != n_c or t.numel() != n_q:
+        raise ValueError("transr_rank: Q (n_q, k), t (n_q,), P (n_c, k), n2 (n_c,): got %s, %s, %s, %s"
+                         % (tuple(Q.shape), tuple(t.shape), tuple(P.shape), tuple(n2.shape)))
+    if n_q < 1 or n_c < 1 or c0 < 0:
+        raise ValueError("transr_rank: needs n_q, n_c >= 1 and c0 >= 0")
+    check_rank_lists(t, c0, n_c, filter_ptr, filter_ids)
+    Q, P, n2 = _need(Q, torch.float32, "Q"), _need(P, torch.float32, "P"), _need(n2, torch.float32, "n2")
+    t = _need(t, torch.int32, "t")
+    filter_ptr, filter_ids = _need(filter_ptr, torch.int32, "filter_ptr"), _need(filter_ids, torch.int32, "filter_ids")
+    lib = _lib.load()
+    if not lib.kgat_transr_rank_supported(k):
+        raise KGATLibraryError("transr_rank: width %d outside the kernel's {16, 32, 64, 128}" % k)
+    lt = torch.empty(n_q, dtype=torch.int32, device=Q.device)
+    eq = torch.empty(n_q, dtype=torch.int32, device=Q.device)
+    with _timed("transr_rank", (n_q, n_c, k)):
+        check(lib.kgat_transr_rank_f32(n_q, n_c, c0, k, _ptr(Q), _ptr(t), _ptr(P), _ptr(n2), _ptr(filter_ptr),
+                                       _ptr(filter_ids) if filter_ids.numel() else None, filter_ids.numel(), _ptr(lt),
+                                       _ptr(eq), _stream(Q)), "kgat_transr_rank_f32")
+    return lt, eq
+
+
 def bpr_loss(emb, u, p, n, reg_lambda):
     """BPR loss of reference models.py:170-178 on the readout (kgat_bpr_loss_f32).  Returns (loss (0-dim), coef (B,),
     workspace) - the last two feed bpr_grad."""

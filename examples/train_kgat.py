@@ -19,6 +19,8 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
   python examples/train_kgat.py --planted --epochs 3 --explain 5         # + why the top-1 item: its best attention walk
   python examples/train_kgat.py --planted --epochs 3 --explain 5 --explain_top 3   # + its three best walks, ranked
   python examples/train_kgat.py --synthetic 1.0 --grad_norm 1.0          # clip the CF gradient's global norm (kgat.py:32,162)
+  python examples/train_kgat.py --planted --epochs 6 --kg_eval 2000 --kg_holdout 0.1   # + filtered MRR / MR / Hits@10 of
+                                                                          # held-out KG triples under the TransR score
 
 ``--gpus N``: one process per GPU (started here as a child ``torch.distributed.run``),
 parameters replicated, the training graph sharded by destination range.  Every rank draws the same
@@ -124,6 +126,27 @@ def user_dict(pairs, item_offset):
     return {int(u): p[s:e, 1] - item_offset for u, s, e in zip(users, start, list(start[1:]) + [len(p)])}
 
 
+def kg_holdout_mask(triplets, is_interaction, fraction, seed):
+    """Which rows of ``triplets`` (h, r, t) stay when a ``fraction`` of the item-KG triples is held out for
+    --kg_eval: a boolean keep mask.  Interaction rows (``is_interaction``) always stay.  The draw is over unordered
+    entity pairs {h, t}: a triple leaves together with every triple between the same two entities - its reverse twin
+    (t, ., h) in particular - so an inverse relation cannot leak it.  Only the item-KG rows enter the draw, so two
+    arrays that share them (the training and the test CKG) lose the same triples."""
+    triplets = np.asarray(triplets)
+    keep = np.ones(len(triplets), bool)
+    kg = np.flatnonzero(~np.asarray(is_interaction, bool))
+    if fraction <= 0 or len(kg) == 0:
+        return keep
+    h, t = triplets[kg, 0].astype(np.int64), triplets[kg, 2].astype(np.int64)
+    pair = np.minimum(h, t) * (int(max(h.max(), t.max())) + 1) + np.maximum(h, t)
+    pairs, inverse = np.unique(pair, return_inverse=True)
+    rng = np.random.default_rng(seed)
+    out = np.zeros(len(pairs), bool)
+    out[rng.permutation(len(pairs))[:int(round(fraction * len(pairs)))]] = True
+    keep[kg[out[inverse]]] = False
+    return keep
+
+
 def _cutoffs(text):
     try:
         ks = [int(x) for x in text.split(",")]
@@ -187,7 +210,22 @@ def parse_args(argv=None):
     ap.add_argument("--explain_top", type=int, default=1, metavar="K",
                     help="with --explain: also the K (1..4) highest-attention walks of each pair over all lengths, "
                          "ranked (explain.attention_paths(top=K)); 1 prints the best walk only")
+    ap.add_argument("--kg_eval", type=int, default=0, metavar="N",
+                    help="after each evaluation: filtered link-prediction metrics (kg_mrr, kg_mr, kg_hits@10; both "
+                         "sides, KGATPropagation.kg_metrics) of N triples fixed by --seed - the triples --kg_holdout "
+                         "removed, or without it training triples (a fit measure, not a generalisation one).  0 = off")
+    ap.add_argument("--kg_holdout", type=float, default=0.0, metavar="F",
+                    help="hold a fraction F of the item-KG triples (never an interaction; a triple leaves with its "
+                         "reverse twin) out of the KG phase and of the propagation graphs, for --kg_eval to rank")
     args = ap.parse_args(argv)
+    if args.kg_eval < 0:
+        ap.error("--kg_eval takes a number of triples >= 0")
+    if not 0.0 <= args.kg_holdout < 1.0:
+        ap.error("--kg_holdout must be in [0, 1)")
+    if args.kg_holdout > 0 and not args.kg_eval:
+        ap.error("--kg_holdout holds triples out for --kg_eval N: give a number of triples")
+    if args.kg_eval and args.gpus > 1:
+        ap.error("--kg_eval runs on one GPU")
     # (before --gpus starts its ranks: a refused combination fails once, here)
     if args.explain < 0:
         ap.error("--explain takes a number of users >= 0")
@@ -264,6 +302,26 @@ def _run(args, argv):
     ds = ckg_io.CKGDataset(args.data_dir)
     say("users %d items %d | CKG: %d entities, %d relations, %d train triplets" % (
         ds.n_users, ds.n_items, ds.n_KG_entity, ds.n_KG_relation, len(ds.train_KG_triplet)))
+    kg_pool = kg_known = None
+    if args.kg_eval:
+        # every triple that counts as true, before anything is held out; n_KG_entity / n_KG_relation stay the full data's
+        full = np.unique(np.vstack([ds.train_KG_triplet, ds.test_KG_triplet]), axis=0)
+        if args.kg_holdout > 0:
+            held = []
+            for name in ("train_KG_triplet", "test_KG_triplet"):
+                trip = getattr(ds, name)
+                keep = kg_holdout_mask(trip, (trip[:, 0] < ds.n_users) | (trip[:, 2] < ds.n_users), args.kg_holdout,
+                                       args.seed)
+                held.append(trip[~keep])
+                setattr(ds, name, trip[keep])
+            kg_pool = held[0]
+            say("kg_holdout %.3f: %d item-KG triples held out of the KG phase and the graphs" % (args.kg_holdout, len(kg_pool)))
+        else:
+            kg_pool = ds.train_KG_triplet
+        if len(kg_pool) == 0:
+            raise SystemExit("--kg_eval: no triple to rank")
+        pick = np.random.default_rng(args.seed).permutation(len(kg_pool))[:args.kg_eval]
+        kg_pool = kg_pool[pick].astype(np.int64)
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
                               gnn_model=args.gnn_model, res_type=args.res_type, use_attention=bool(args.use_attention),
@@ -312,6 +370,19 @@ def _run(args, argv):
         torch.cuda.synchronize()
         return time.perf_counter()
 
+    if args.kg_eval:
+        kg_known = K.KnownTriples(full[:, 0], full[:, 1], full[:, 2], ds.n_KG_entity, ds.n_KG_relation, device=dev)
+        kg_pool = [torch.as_tensor(np.ascontiguousarray(kg_pool[:, c]), device=dev) for c in range(3)]
+
+    def kg_evaluate(rec):
+        t0 = clock()
+        m = model.kg_metrics(*kg_pool, known=kg_known, side="both", hits=(1, 3, 10))
+        rec["kg_eval_s"] = clock() - t0
+        rec["kg_mrr"], rec["kg_mr"], rec["kg_hits@10"] = m["mrr"], m["mr"], m["hits@10"]
+        say("           | KG link prediction, %d %s triples, both sides, filtered: kg_mrr %.5f kg_mr %.1f kg_hits@10 %.5f "
+            "| %.4fs" % (kg_pool[0].numel(), "held-out" if args.kg_holdout > 0 else "TRAINING (a fit measure)",
+                         m["mrr"], m["mr"], m["hits@10"], rec["kg_eval_s"]))
+
     def evaluate(rec):
         t0 = clock()
         with torch.no_grad():
@@ -331,6 +402,8 @@ def _run(args, argv):
                         name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
         rec["eval_s"] = clock() - t0
         say("           | eval %.4fs" % rec["eval_s"])
+        if args.kg_eval:
+            kg_evaluate(rec)
 
     history = []
     if args.eval_before:

@@ -945,6 +945,42 @@ int kgat_bpr_grad_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
                       const int32_t* p, const int32_t* n, const float* coef, float reg_lambda, const float* grad_scale,
                       float* grad, void* workspace, size_t workspace_bytes, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- TransR link prediction (ABI 16, additive)
+ * The filtered rank of a triple's true tail (head) among the entities under the score of reference models.py:120-126,
+ * |u_h + u_r - u_t|^2 with the normalisation of the training kernel (u = a / max(|a|, 1e-12), a = e W_r).
+ *
+ * kgat_transr_project_f32: for i in [0, n_rows), with e_i = ent row (ids ? ids[i] : row0 + i) of n_ent x d floats,
+ *     a_i = e_i W_r (W_r: d x k row-major),  u_i = a_i / max(|a_i|, 1e-12),
+ *     out[i, :] = u_i + sign * rel_row / max(|rel_row|, 1e-12)      (rel_row NULL: out[i, :] = u_i)
+ *     n2[i]     = |u_i|^2  (fp32; 1 up to rounding, exactly 0 for a zero a_i; n2 NULL: not written)
+ * out is ROW-MAJOR n_rows x k: the layout kgat_transr_rank_f32 and kgat_eval_topk_f32 read.  sign is +1 or -1
+ * (else KGAT_E_BADARG).  fp32 MFMA (v_mfma_f32_16x16x4_f32), W_r staged once per workgroup in LDS.  Widths
+ * (kgat_transr_project_supported): d, k in {16, 32, 64, 128} independently, others KGAT_E_UNSUPPORTED.  ent, W_r and
+ * out 16-byte aligned.  Without ids the range [row0, row0 + n_rows) must lie inside [0, n_ent) (KGAT_E_BADARG); with
+ * ids the caller guarantees ids[i] in [0, n_ent) (the kernel clamps: a bad id reads a wrong row, never outside ent).
+ *
+ * kgat_transr_rank_f32: n_q query rows q (row-major, k columns) with the entity id t[j] of their true answer;
+ * candidates p (n_c x k row-major) with n2[n_c]: the entities [c0, c0 + n_c); a filter in CSR form - query j leaves out
+ * the entity ids filter_ids[filter_ptr[j] .. filter_ptr[j + 1]) (ascending; any int32 id is allowed, those
+ * outside the candidate range are ignored; n_filter = length of filter_ids) and always its true answer.  With s_i = n2_i - 2 q_j . p_i:
+ *     lt[j] = #{ i not left out : s_i <  s_t }        eq[j] = #{ i not left out : s_i == s_t }
+ * (int32; the entry zeroes them).  s_t is formed by the same tile routine as every s_i, so a candidate whose row and
+ * n2 are bit-identical to the true answer's counts in eq wherever it lies.  Candidate segments run in different
+ * workgroups and add integer counts with integer atomics: exact, bitwise reproducible; no workspace.  k in
+ * {16, 32, 64, 128} (kgat_transr_rank_supported), others KGAT_E_UNSUPPORTED; n_q, n_c >= 1, c0 >= 0, c0 + n_c below
+ * 2^31, q, p, n2 16-byte aligned, no null pointer (filter_ids may be NULL with n_filter = 0): else KGAT_E_BADARG.
+ * What only the device can see - t[j] inside [c0, c0 + n_c), filter lists ascending, filter_ptr non-decreasing within
+ * [0, n_filter] - is the caller's to guarantee (the Python layer checks it); the kernel clamps every index it derives
+ * from them, so a violation gives wrong counts and never an access outside the buffers. */
+int kgat_transr_project_supported(int d, int k);
+int kgat_transr_project_f32(int64_t n_rows, int64_t n_ent, int d, int k, const float* ent, const int32_t* ids,
+                            int64_t row0, const float* W_r, const float* rel_row, float sign, float* out, float* n2,
+                            kgat_stream_t stream);
+int kgat_transr_rank_supported(int k);
+int kgat_transr_rank_f32(int64_t n_q, int64_t n_c, int64_t c0, int k, const float* q, const int32_t* t, const float* p,
+                         const float* n2, const int32_t* filter_ptr, const int32_t* filter_ids, int64_t n_filter,
+                         int32_t* lt, int32_t* eq, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
