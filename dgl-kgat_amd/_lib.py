@@ -119,6 +119,9 @@ SIGNATURES = {
     "kgat_permute_tile": (_i32, []),
     "kgat_permute_supported": (_i32, [_i64]),
     "kgat_permute_f32": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p]),
+    # edge softmax + edge-id-ordered copy, the cut-row rescale folded into the bin pass (ABI 16, additive)
+    "kgat_edge_softmax_permuted_supported": (_i32, [_i64, _i64]),
+    "kgat_edge_softmax_permuted_f32": (_i32, [_i64, _i64, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_eval_supported": (_i32, [_i32, _i32]),
     "kgat_eval_items_elems": (_i64, [_i64, _i32]),
     "kgat_eval_items_kmajor_f32": (_i32, [_i64, _i32, _p, _i64, _p, _p, _p]),

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "kgat_common.h"
+#include "kgat_softmax_carry.h"
 
 // Cache policy of the sweep's streams: the position map (read once per step) as non-temporal loads - step 0.4178 ->
 // 0.4132 ms, it no longer displaces reused rows from the Infinity Cache.  Measured and not taken
@@ -195,45 +196,8 @@ __global__ __launch_bounds__(256) void softmax_norm_kernel(
 // address arithmetic per load, thirteen ds_bpermute scan steps carrying (m, s) pairs with an exp in every
 // combine, a compare pair per stored position) at 7 wavefronts per SIMD - bound by instruction issue.  This
 // form is ~350.
-// positions per lane: 16 (1,024 per wavefront), or 8 for launches over fewer than kSmSmallEdges
-// positions, where the sweep is a latency chain rather than a stream and twice the wavefronts with half
-// the chain each finish sooner.
-constexpr int kSmMaxEPL = 16;
-constexpr int64_t kSmSmallEdges = 8 << 20;
-template <int EPL> struct SmGeom {
-  static constexpr int EPW = kWave * EPL;   // positions per wavefront
-};
-constexpr float kSmNegBig = -3.0e38f;     // stands in for -inf (keeps the combine NaN-free)
-
-struct __attribute__((aligned(16))) SmCarry {
-  int32_t row;    // -1: no entry
-  int32_t count;  // positions of this wavefront that belong to the row
-  float m, s;     // partial max, partial sum of exp(x - m)
-  int32_t head;   // wavefront in which the row starts (its `b` entry heads the chain)
-  int32_t last;   // wavefront in which the row ends
-  int32_t pad0, pad1;
-};
-
-// exp(x) for x <= 0 on the hardware exp2: the product x*log2(e) is split into its rounded value
-// and the rounding remainder (fma), the remainder enters as a first-order factor - about 1.5 ulp,
-// against ~|x| ulp for exp2(x * log2e) alone.  Results below the normal range flush to zero.
-__device__ __forceinline__ float sm_exp(float x) {
-  x = fmaxf(x, -128.0f);  // exp2(-184) is already 0; keeps the split finite for the -3e38 stand-in
-  const float t = x * 1.44269504088896341f;
-  const float lo = fmaf(x, 1.44269504088896341f, -t) + x * 1.92596299112661746e-8f;
-  return __builtin_amdgcn_exp2f(t) * fmaf(lo, 0.693147180559945309f, 1.0f);
-}
-
-// (m, s) <- (m, s) (+) (m2, s2): the smaller maximum's sum is rescaled by exp(-|m - m2|).  Branch-free
-// (one exp, selects).  Used where partial results of different wavefronts meet (the chains of cut rows).
-__device__ __forceinline__ void sm_combine(float& m, float& s, float m2, float s2) {
-  const bool keep = m >= m2;
-  const float e = sm_exp(keep ? m2 - m : m - m2);
-  const float big = keep ? s : s2, small = keep ? s2 : s;
-  s = fmaf(small, e, big);
-  m = keep ? m : m2;
-}
-
+// (range geometry SmGeom, the carry record SmCarry and sm_exp / sm_combine / sm_chain_total: kgat_softmax_carry.h, shared
+// with the fused bin pass of kgat_permute.hip)
 // index of the wavefront in the launch, as a scalar (the compiler cannot see that threadIdx.x / 64 is
 // uniform; with it in an SGPR the range base is one, and loads take the base + 32-bit lane offset form)
 __device__ __forceinline__ int64_t sm_wave_index() {
@@ -523,31 +487,6 @@ __global__ __launch_bounds__(256) void softmax_local_kernel(
     sm_sweep<IN_CSR, kSmEPL, false>(e0, e1, w, base, end, indptr, row_of, eid, logits, out, out_csr, carry);
 }
 
-// (M, S) of a cut row from the carries of its chain: the head wavefront's `b` entry, then the `a`
-// entries of the followers head+1 .. last in blocks of 64 (ordered tree inside a block).  Every
-// wavefront of the chain runs exactly this sequence, so all of them normalise with the same bits.
-__device__ __forceinline__ void sm_chain_total(const SmCarry* __restrict__ carry, int32_t head, int32_t last,
-                                               int lane, float& M, float& S) {
-  const SmCarry h = carry[2 * (int64_t)head + 1];
-  float m = h.m, s = h.s;
-  for (int64_t j0 = (int64_t)head + 1; j0 <= last; j0 += kWave) {
-    const int64_t j = j0 + lane;
-    float pm = kSmNegBig, ps = 0.f;
-    if (j <= last) {
-      const SmCarry f = carry[2 * j];
-      pm = f.m; ps = f.s;
-    }
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const float m2 = __shfl_down(pm, d, kWave), s2 = __shfl_down(ps, d, kWave);
-      if ((lane & (2 * d - 1)) == 0) sm_combine(pm, ps, m2, s2);
-    }
-    pm = __shfl(pm, 0, kWave); ps = __shfl(ps, 0, kWave);
-    sm_combine(m, s, pm, ps);
-  }
-  M = m; S = s;
-}
-
 // provisional values of positions [lo, hi) of one row times f, 8 x 64 per step so that the loads of a
 // step are in flight together
 __device__ __forceinline__ void sm_rescale_span(int64_t lo, int64_t hi, int lane, float f,
@@ -670,10 +609,11 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(int32_t n_rows, int32_
 
 using namespace kgat;
 
+// cut_rows = false: the sweep alone - the caller finishes the cut rows from the carries (the fused bin pass)
 template <bool IN_CSR, int EPL>
 static void launch_softmax_sweep(int64_t e_begin, int64_t e_end, const int32_t* indptr, const int32_t* row_of,
                                  const int32_t* eid, const float* logits, float* out, float* out_csr, SmCarry* carry,
-                                 hipStream_t st) {
+                                 hipStream_t st, bool cut_rows = true) {
   const int64_t n_waves = (e_end - e_begin + SmGeom<EPL>::EPW - 1) / SmGeom<EPL>::EPW;
   const unsigned blocks = (unsigned)((n_waves + 3) / 4);
   // the 16-byte loads / stores of the sweep's full ranges need every array it touches that way aligned
@@ -681,6 +621,7 @@ static void launch_softmax_sweep(int64_t e_begin, int64_t e_end, const int32_t* 
   const int aligned = (bits % 16 == 0 && e_begin % 4 == 0) ? 1 : 0;
   hipLaunchKernelGGL((softmax_local_kernel<IN_CSR, EPL>), dim3(blocks), dim3(256), 0, st, e_begin, e_end, aligned, indptr,
                      row_of, eid, logits, out, out_csr, carry);
+  if (!cut_rows) return;
   hipLaunchKernelGGL((softmax_cut_rows_kernel<EPL>), dim3(blocks), dim3(256), 0, st, e_begin, e_end, eid, out, out_csr,
                      (const SmCarry*)carry);
 }
@@ -722,6 +663,57 @@ int kgat_edge_softmax_f32(int64_t n_nodes, int64_t e_begin, int64_t e_end, const
   }
   KGAT_CHECK_LAUNCH("edge_softmax");
   return KGAT_OK;
+}
+
+// Softmax + edge-id-ordered copy in three launches: the sweep (the same instantiations as above, CSR-ordered output
+// only), the permutation's bin pass with the cut-row rescale folded in - it reads every CSR-ordered value anyway and
+// writes the corrected ones back in place - and the place pass.  Same bits as kgat_edge_softmax_f32 + kgat_permute_f32.
+int kgat_edge_softmax_permuted_supported(int64_t e_begin, int64_t e_end) {
+  if (e_begin != 0 || e_end < 0 || e_end >= INT32_MAX || !kgat_permute_supported(e_end)) return 0;
+  return permute_softmax_fits(e_end < kSmSmallEdges ? SmGeom<8>::EPW : SmGeom<16>::EPW) ? 1 : 0;
+}
+
+int kgat_edge_softmax_permuted_f32(int64_t n_nodes, int64_t e_begin, int64_t e_end, const int32_t* indptr,
+                                   const int32_t* row_of, const int32_t* eid, const float* logits,
+                                   int logits_in_csr_order, const uint16_t* slot_a, const int32_t* dst_a,
+                                   const uint16_t* slot_b, float* out, float* out_csr, float* tmp, void* workspace,
+                                   size_t workspace_bytes, kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_nodes >= 0 && e_begin >= 0 && e_end >= e_begin && e_end < INT32_MAX,
+                 "edge_softmax_permuted: bad size");
+  if (!kgat_edge_softmax_permuted_supported(e_begin, e_end)) {
+    set_error("edge_softmax_permuted: needs e_begin = 0 (got %lld) and a size kgat_permute_supported takes (got %lld): "
+              "use kgat_edge_softmax_f32 and kgat_permute_f32 / kgat_gather_f32", (long long)e_begin, (long long)e_end);
+    return KGAT_E_UNSUPPORTED;
+  }
+  if (e_end == 0) return KGAT_OK;
+  KGAT_CHECK_ARG(indptr && row_of && logits && workspace, "edge_softmax_permuted: null pointer");
+  KGAT_CHECK_ARG(slot_a && dst_a && slot_b && out && out_csr && tmp, "edge_softmax_permuted: null pointer");
+  KGAT_CHECK_ARG(eid != nullptr || logits_in_csr_order, "edge_softmax_permuted: edge-id ordered input needs eid");
+  KGAT_CHECK_ARG(out != out_csr && out != tmp && out_csr != tmp && (const float*)out_csr != logits &&
+                     (const float*)out != logits && (const float*)tmp != logits,
+                 "edge_softmax_permuted: logits, out, out_csr and tmp must be four buffers");
+  if (!(aligned16(slot_a) && aligned16(slot_b) && aligned16(out) && aligned16(out_csr) && aligned16(tmp) &&
+        aligned16(workspace))) {
+    set_error("edge_softmax_permuted: slot_a, slot_b, out, out_csr, tmp and workspace must be 16-byte aligned");
+    return KGAT_E_UNSUPPORTED;
+  }
+  if (workspace_bytes < kgat_edge_softmax_workspace_bytes(n_nodes, e_end)) {
+    set_error("edge_softmax_permuted: workspace too small");
+    return KGAT_E_WORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  SmCarry* carry = static_cast<SmCarry*>(workspace);
+  const bool small = e_end < kSmSmallEdges;
+  if (logits_in_csr_order) {
+    if (small) launch_softmax_sweep<true, 8>(0, e_end, indptr, row_of, eid, logits, nullptr, out_csr, carry, st, false);
+    else launch_softmax_sweep<true, 16>(0, e_end, indptr, row_of, eid, logits, nullptr, out_csr, carry, st, false);
+  } else {
+    if (small) launch_softmax_sweep<false, 8>(0, e_end, indptr, row_of, eid, logits, nullptr, out_csr, carry, st, false);
+    else launch_softmax_sweep<false, 16>(0, e_end, indptr, row_of, eid, logits, nullptr, out_csr, carry, st, false);
+  }
+  KGAT_CHECK_LAUNCH("edge_softmax_permuted: sweep");
+  return permute_softmax_launch(small ? SmGeom<8>::EPW : SmGeom<16>::EPW, e_end, slot_a, dst_a, slot_b, carry, out_csr, out,
+                                tmp, st);
 }
 
 // The three-pass form (atomic row max / fixed-point atomic row sum / normalise) this file started

@@ -268,14 +268,19 @@ class _Structure:
                    and values.data_ptr() % 16 == 0 and (out is None or out.data_ptr() % 16 == 0))
         if not planned:
             return ops.gather(src_of, values, out=out)
-        c = self._cache(values.device)
+        plan, tmp = self.permute_plan(name, src_of, values.device)
+        return ops.permute(plan, values, out=out, tmp=tmp)
+
+    def permute_plan(self, name, src_of, device):
+        """(plan, scratch) `permuted` keeps for the static permutation `src_of` under `name`: built on first use."""
+        c = self._cache(device)
         plan = c.get(("permute_plan", name))
         if plan is None or plan[0] is not src_of:
             plan = c[("permute_plan", name)] = (src_of, ops.permute_plan(src_of))
         tmp = c.get("permute_tmp")
         if tmp is None or tmp.numel() != src_of.numel():
-            tmp = c["permute_tmp"] = torch.empty(src_of.numel(), dtype=torch.float32, device=values.device)
-        return ops.permute(plan[1], values, out=out, tmp=tmp)
+            tmp = c["permute_tmp"] = torch.empty(src_of.numel(), dtype=torch.float32, device=device)
+        return plan[1], tmp
 
     def weight_in_csr_order(self, w_flat):
         """Per-edge weights permuted to CSR order once per distinct weight tensor; the SpMM
@@ -820,8 +825,6 @@ class DGLGraph:
         run, order = forms[form]
         logits = run()
         st.last_att_form = (form, groups.n_groups)
-        _, a_csr = ops.edge_softmax(csr.indptr, csr.row_of, _gpos_csr(groups) if order == "grouped" else csr.eid, logits,
-                                    in_csr_order=order == "csr", want_out=False, want_csr=True)
         from . import lazy as lazy_mod
         if lazy is None:
             lazy = lazy_mod.enabled()
@@ -829,6 +832,18 @@ class DGLGraph:
             lazy_mod._guard_legacy_to_dlpack()   # an explicit lazy=True: the export guard must be in place
         a = torch.empty((st.n_edges, 1), dtype=torch.float32, device=dev)
         a_flat = a.view(-1)
+        index = _gpos_csr(groups) if order == "grouped" else csr.eid
+        # eager: softmax + edge-id-ordered copy in three launches, the permutation's bin pass finishing the rows the
+        # sweep's ranges cut (same bits).  The lazy form hands a_csr out before `fill` runs and keeps the two calls.
+        if (not lazy and options.softmax_permuted and logits.numel() and ops.edge_softmax_permuted_supported(logits.numel())
+                and a_flat.data_ptr() % 16 == 0):
+            plan, tmp = st.permute_plan("csr_pos", st.csr_pos(dev), dev)
+            _, a_csr = ops.edge_softmax_permuted(csr.indptr, csr.row_of, index, logits, plan, in_csr_order=order == "csr",
+                                                 out=a_flat, tmp=tmp)
+            st.remember_weight(a_flat, a_csr)
+            return a
+        _, a_csr = ops.edge_softmax(csr.indptr, csr.row_of, index, logits, in_csr_order=order == "csr", want_out=False,
+                                    want_csr=True)
 
         def fill():  # edge-id order: two streaming passes over the graph's plan (the gather beyond its size rule)
             st.permuted("csr_pos", st.csr_pos(dev), a_csr, out=a_flat)

@@ -651,6 +651,33 @@ def edge_softmax(indptr, row_of, eid, logits, in_csr_order=False, e_range=None, 
     return out, out_csr
 
 
+def edge_softmax_permuted_supported(n_edges, e_begin=0):
+    """Whether kgat_edge_softmax_permuted_f32 takes a softmax over CSR positions [e_begin, e_begin + n_edges)."""
+    return bool(_lib.load().kgat_edge_softmax_permuted_supported(int(e_begin), int(e_begin) + int(n_edges)))
+
+
+def edge_softmax_permuted(indptr, row_of, eid, logits, plan, in_csr_order=False, out=None, tmp=None):
+    """`edge_softmax(..., want_out=False, want_csr=True)` followed by `permute(plan, out_csr)` in three launches instead
+    of four, same bits (kgat_edge_softmax_permuted_f32): the permutation's bin pass finishes the rows the sweep's ranges
+    cut.  `plan`: `permute_plan` of the permutation CSR position -> edge id.  Returns (out in edge-id order, out_csr)."""
+    logits = _need(logits, torch.float32, "logits", (plan.n,))
+    indptr = _need(indptr, torch.int32, "indptr")
+    row_of = _need(row_of, torch.int32, "row_of", logits.shape)
+    eid = _need(eid, torch.int32, "eid", logits.shape)
+    out = torch.empty_like(logits) if out is None else _need(out, torch.float32, "out", (plan.n,))
+    tmp = torch.empty_like(logits) if tmp is None else _need(tmp, torch.float32, "tmp", (plan.n,))
+    out_csr = torch.empty_like(logits)
+    n_nodes = indptr.numel() - 1
+    lib = _lib.load()
+    with _timed("edge_softmax_permuted", (plan.n,)):
+        ws = _workspace(lib.kgat_edge_softmax_workspace_bytes(n_nodes, plan.n), logits.device)
+        check(lib.kgat_edge_softmax_permuted_f32(n_nodes, 0, plan.n, _ptr(indptr), _ptr(row_of), _ptr(eid), _ptr(logits),
+                                                 1 if in_csr_order else 0, _ptr(plan.slot_a), _ptr(plan.dst_a),
+                                                 _ptr(plan.slot_b), _ptr(out), _ptr(out_csr), _ptr(tmp), _ptr(ws),
+                                                 ws.numel(), _stream(logits)), "kgat_edge_softmax_permuted_f32")
+    return out, out_csr
+
+
 def edge_softmax_bwd(indptr, eid, a, grad_a, row_range=None):
     a = _need(a, torch.float32, "a")
     grad_a = _need(grad_a, torch.float32, "grad_a", a.shape)
@@ -1366,7 +1393,7 @@ def sddmm_dot(src, dst, X, G):
 
 __all__ = ["csr_from_coo", "group_by_relation", "invert_permutation", "row_order_by_degree", "gather",
            "permute_tile", "permute_supported", "permute_plan_arrays", "permute_plan", "permute", "PermutePlan",
-           "att_score", "att_score_split", "att_score_split_supported", "att_score_folded_supported", "att_score_fused", "att_pack_records", "att_score_fused_supported", "fold_tiles", "fold_tile_cost", "bi_interaction_train", "add3_rows", "bi_interaction_bwd_pre", "bi_interaction_bwd_input", "bi_interaction_bwd_input_supported", "bi_interaction_bwd_weight", "sum_partials", "mul2", "dropout_keep_mask", "transr_loss_grad", "transr_supported", "transr_presort", "transr_adam_step", "TransRAdamState", "head_groups", "edge_softmax", "edge_softmax_bwd", "spmm", "spmm_workspace", "sddmm_dot",
+           "att_score", "att_score_split", "att_score_split_supported", "att_score_folded_supported", "att_score_fused", "att_pack_records", "att_score_fused_supported", "fold_tiles", "fold_tile_cost", "bi_interaction_train", "add3_rows", "bi_interaction_bwd_pre", "bi_interaction_bwd_input", "bi_interaction_bwd_input_supported", "bi_interaction_bwd_weight", "sum_partials", "mul2", "dropout_keep_mask", "transr_loss_grad", "transr_supported", "transr_presort", "transr_adam_step", "TransRAdamState", "head_groups", "edge_softmax", "edge_softmax_permuted", "edge_softmax_permuted_supported", "edge_softmax_bwd", "spmm", "spmm_workspace", "sddmm_dot",
            "bi_interaction", "bi_interaction_supported", "l2_normalize_rows", "readout_concat",
            "FORMS", "aggregator", "aggregator_supported", "aggregator_bwd_supported", "aggregator_train",
            "aggregator_bwd_input", "aggregator_bwd_weight",

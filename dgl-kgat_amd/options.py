@@ -16,6 +16,7 @@ KGAT_FUSE_BI                   0        aggregation + dense part of a layer in o
 KGAT_GNN_DEFER_FINISH          1        the aggregation's second launch folded into the dense kernel
 KGAT_LAZY_EDGE_WEIGHTS         0        compute_attention defers its edge-id-ordered copy (lazy.py)
 KGAT_EAGER_EDGE_WEIGHTS        0        ... never, even after enable_lazy_edge_weights()
+KGAT_SOFTMAX_PERMUTED          1        compute_attention's softmax and edge-id-ordered copy in three launches (same bits)
 KGAT_PARTITION_ROW_WEIGHT      8        per-row weight of the destination-range split
 KGAT_FORCE_COLLECTIVES         0        a one-rank group still runs its collectives (RCCL on a one-GPU box)
 KGAT_EXCHANGE                  allreduce  layer-output exchange: allreduce / allgather / broadcast / p2p
@@ -33,7 +34,7 @@ def _flag(name, default):
 
 class Options:
     __slots__ = ("att_f32_products", "att_form", "fold_tile_cost", "fuse_bi", "gnn_defer_finish", "lazy_edge_weights",
-                 "eager_edge_weights", "partition_row_weight", "force_collectives", "exchange", "exchange_chunks")
+                 "eager_edge_weights", "softmax_permuted", "partition_row_weight", "force_collectives", "exchange", "exchange_chunks")
 
     def __init__(self):
         self.load()
@@ -48,6 +49,7 @@ class Options:
         self.gnn_defer_finish = _flag("KGAT_GNN_DEFER_FINISH", True)
         self.lazy_edge_weights = _flag("KGAT_LAZY_EDGE_WEIGHTS", False)
         self.eager_edge_weights = bool(e.get("KGAT_EAGER_EDGE_WEIGHTS"))
+        self.softmax_permuted = _flag("KGAT_SOFTMAX_PERMUTED", True)
         rw = e.get("KGAT_PARTITION_ROW_WEIGHT")
         self.partition_row_weight = int(rw) if rw else None
         self.force_collectives = _flag("KGAT_FORCE_COLLECTIVES", False)

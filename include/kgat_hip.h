@@ -508,6 +508,24 @@ int kgat_permute_supported(int64_t n);
 int kgat_permute_f32(int64_t n, const uint16_t* slot_a, const int32_t* dst_a, const uint16_t* slot_b, const float* in,
                      float* out, float* tmp, kgat_stream_t stream);
 
+/* kgat_edge_softmax_f32 (out = NULL, out_csr) followed by kgat_permute_f32 (out_csr -> out) in three launches instead
+ * of four, same bits (ABI 16, additive): the sweep; the permutation's bin pass, which also finishes the rows the
+ * sweep's ranges cut - it multiplies their provisional values by the row's factor while it holds them and writes the
+ * corrected 16-byte pieces back to out_csr in place - and the place pass.  Arguments as those two entries take them:
+ * eid is the index map the logits are read through (may be NULL with logits_in_csr_order = 1), slot_a / dst_a / slot_b
+ * the plan of the permutation CSR position -> edge id, out (edge-id order), out_csr, tmp and logits four distinct
+ * buffers of E floats, workspace of kgat_edge_softmax_workspace_bytes.
+ * The _supported companion: 1 when e_begin = 0 (the whole graph: chunk boundaries of the bin pass are then range
+ * boundaries of the sweep), kgat_permute_supported holds for E = e_end, and the permutation's tile is a whole number
+ * of sweep ranges.  Otherwise, and when slot_a, slot_b, out, out_csr, tmp or workspace is not 16-byte aligned, the
+ * entry launches nothing and returns KGAT_E_UNSUPPORTED: the two separate entries remain the form to call. */
+int kgat_edge_softmax_permuted_supported(int64_t e_begin, int64_t e_end);
+int kgat_edge_softmax_permuted_f32(int64_t n_nodes, int64_t e_begin, int64_t e_end, const int32_t* indptr,
+                                   const int32_t* row_of, const int32_t* eid, const float* logits,
+                                   int logits_in_csr_order, const uint16_t* slot_a, const int32_t* dst_a,
+                                   const uint16_t* slot_b, float* out, float* out_csr, float* tmp, void* workspace,
+                                   size_t workspace_bytes, kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- training form of the layer (8f #1)
  * The forward of one KGATConv under autograd is kgat_aggregator_train_f32 (below); these are the pieces around it.
  * kgat_add3_rows_f32: out = (a + b) + c over n_rows x d, a being a column slice (rows of a_stride floats) of a wider
