@@ -13,15 +13,9 @@
 //             reproducible; scaled by the incoming gradient read from device memory (no host synchronisation, no
 //             separate multiply pass)
 //   loss = -mean_b logsigmoid(<s,p> - <s,n>) + lambda (mean_b |s|^2/2 + mean_b |p|^2/2 + mean_b |n|^2/2)
-#include "kgat_common.h"
+#include "kgat_lds_sort.h"
 
 namespace kgat {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // per sample b: out[b] = logsigmoid(x), out[B + b] = (|s|^2 + 0)/2 ..., coef[b] = sigmoid(-x)
 __global__ __launch_bounds__(256) void bpr_sample_kernel(int64_t batch, int64_t n_nodes, int F,
@@ -260,8 +254,7 @@ __global__ __launch_bounds__(256) void bpr_carry_kernel(int64_t batch, int64_t n
 // ---- stable sort of the 3B row ids, role-major (i = role * B + b), beside the zero fill of the dense gradient.
 // The general device sort (kgat_graph.hip) takes four launches per digit - twelve dependent launches for 30,720
 // eighteen-bit keys, 0.10 of the CF step's 0.99 ms, all of it launch latency.  Here, up to 65,536 ids: launch one -
-// workgroup L sorts slice L (4,096 consecutive ids) in LDS: LSD radix, 8-bit digits, per-wavefront counter columns,
-// ballots for the rank inside 64 keys (equal keys keep their order: kgat_transr.hip's small sort), packed values
+// workgroup L sorts slice L (4,096 consecutive ids) in LDS (LdsSort, kgat_lds_sort.h), packed values
 // key << 17 | index; the workgroups behind the slices clear `zero` (the N x F gradient) meanwhile.  Launch two - one
 // thread per id finds its place among ALL ids: its rank in its own slice + what the earlier slices hold up to its
 // key + what the later slices hold below it (binary searches over <= 15 sorted slices): a stable merge without a
@@ -269,97 +262,31 @@ __global__ __launch_bounds__(256) void bpr_carry_kernel(int64_t batch, int64_t n
 // registers was measured first: 180 us - 1,440 wavefront-iterations of ~100 instructions on one CU.)
 constexpr int kSliceSort = 4096;
 constexpr int kSliceSortMaxLists = 16;
-constexpr int kSliceWaves = 16;
+constexpr int kSlicePosBits = 17;    // index among the 3B <= 65,536 ids
 constexpr int kSliceDigitBits = 9;   // 18-bit ids (the CKGs of the reference's datasets) in TWO passes; eight bits took three
-constexpr int kSliceDigits = 1 << kSliceDigitBits;
 
-__global__ __launch_bounds__(1024) void bpr_sort_zero_kernel(int32_t batch, int32_t n_lists, int64_t n_nodes, int key_bits,
-                                                             const int32_t* __restrict__ u, const int32_t* __restrict__ p,
-                                                             const int32_t* __restrict__ n, uint64_t* __restrict__ lists,
-                                                             float* __restrict__ zero, int64_t n_zero) {
+__global__ __launch_bounds__(kLdsSortThreads) void bpr_sort_zero_kernel(
+    int32_t batch, int32_t n_lists, int64_t n_nodes, int key_bits, const int32_t* __restrict__ u,
+    const int32_t* __restrict__ p, const int32_t* __restrict__ n, uint64_t* __restrict__ lists, float* __restrict__ zero,
+    int64_t n_zero) {
   if ((int32_t)blockIdx.x >= n_lists) {
-    const int64_t n4 = n_zero / 4, stride = (int64_t)(gridDim.x - n_lists) * 1024;
-    float4* z = reinterpret_cast<float4*>(zero);
-    for (int64_t i = (int64_t)(blockIdx.x - n_lists) * 1024 + threadIdx.x; i < n4; i += stride)
-      z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    zero_fill_behind(zero, n_zero, (unsigned)n_lists, kLdsSortThreads);
     return;
   }
-  __shared__ uint64_t s_buf[2][kSliceSort];
-  __shared__ int32_t s_cnt[kSliceDigits * kSliceWaves];
-  __shared__ int32_t s_wsum[kSliceWaves];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  __shared__ LdsSort<uint64_t, kSliceSort, kSliceDigitBits, kSlicePosBits> s_sort;
+  const int tid = threadIdx.x;
   const int32_t total = 3 * batch;
   const int32_t g0 = (int32_t)blockIdx.x * kSliceSort;
   const int32_t cnt = total - g0 < kSliceSort ? total - g0 : kSliceSort;
-  for (int32_t i = tid; i < cnt; i += 1024) {
+  for (int32_t i = tid; i < cnt; i += kLdsSortThreads) {
     const int32_t gi = g0 + i;
     const int32_t role = gi / batch, b = gi - role * batch;
     const int32_t id = role == 0 ? u[b] : (role == 1 ? p[b] : n[b]);
     const uint64_t key = (uint64_t)(uint32_t)id >= (uint64_t)n_nodes ? (uint64_t)n_nodes : (uint64_t)id;
-    s_buf[0][i] = (key << 17) | (uint64_t)gi;
+    s_sort.buf[0][i] = (key << kSlicePosBits) | (uint64_t)gi;
   }
-  const int32_t slice = ((cnt + kSliceWaves * 64 - 1) / (kSliceWaves * 64)) * 64;  // per wavefront, a multiple of 64
-  const int32_t lo = w * slice, hi = lo + slice < cnt ? lo + slice : cnt;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  const int passes = (key_bits + kSliceDigitBits - 1) / kSliceDigitBits;
-  int cur = 0;
-  for (int pass = 0; pass < passes; ++pass) {
-    const int shift = 17 + kSliceDigitBits * pass;
-    constexpr int CPT = kSliceDigits * kSliceWaves / 1024;   // counters per thread
-    for (int i = tid; i < kSliceDigits * kSliceWaves; i += 1024) s_cnt[i] = 0;
-    __syncthreads();
-    for (int32_t i = lo + lane; i < hi; i += 64)
-      atomicAdd(&s_cnt[(uint32_t)((s_buf[cur][i] >> shift) & (uint32_t)(kSliceDigits - 1)) * kSliceWaves + w], 1);
-    __syncthreads();
-    {  // exclusive scan of the counters in (digit, wavefront) order, CPT per thread
-      int32_t c[CPT];
-      int32_t mine = 0;
-#pragma unroll
-      for (int q = 0; q < CPT; ++q) { c[q] = s_cnt[CPT * tid + q]; mine += c[q]; }
-      int32_t inc = mine;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int32_t up = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += up;
-      }
-      if (lane == 63) s_wsum[w] = inc;
-      __syncthreads();
-      int32_t base = inc - mine;
-      for (int q = 0; q < w; ++q) base += s_wsum[q];
-#pragma unroll
-      for (int q = 0; q < CPT; ++q) {
-        s_cnt[CPT * tid + q] = base;
-        base += c[q];
-      }
-    }
-    __syncthreads();
-    for (int32_t i0 = lo; i0 < hi; i0 += 64) {
-      const int32_t i = i0 + lane;
-      const bool valid = i < hi;
-      const uint64_t v = valid ? s_buf[cur][i] : 0ull;
-      const uint32_t dgt = (uint32_t)((v >> shift) & (uint32_t)(kSliceDigits - 1));
-      uint64_t peers = __ballot(valid);
-#pragma unroll
-      for (int bit = 0; bit < kSliceDigitBits; ++bit) {
-        const bool on = (dgt >> bit) & 1u;
-        const uint64_t bal = __ballot(on);
-        peers &= on ? bal : ~bal;
-      }
-      const int rank = __popcll(peers & lt_mask);
-      const int32_t basep = valid ? s_cnt[dgt * kSliceWaves + w] : 0;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();  // every lane has its base before a leader moves it
-      if (valid) {
-        s_buf[cur ^ 1][basep + rank] = v;
-        if (rank == 0) s_cnt[dgt * kSliceWaves + w] = basep + __popcll(peers);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  for (int32_t i = tid; i < cnt; i += 1024) lists[g0 + i] = s_buf[cur][i];
+  const uint64_t* s = s_sort.sort(cnt, key_bits);
+  for (int32_t i = tid; i < cnt; i += kLdsSortThreads) lists[g0 + i] = s[i];
 }
 
 // the place of every id among all ids (see above); thread t = position t of the concatenated sorted slices
@@ -371,16 +298,13 @@ __global__ __launch_bounds__(256) void bpr_merge_kernel(int32_t total, int32_t n
   // the blocks behind the merge's own: the second part of the gradient's zero fill (see kgat_bpr_grad_f32)
   const int32_t merge_blocks = (total + 255) / 256;
   if ((int32_t)blockIdx.x >= merge_blocks) {
-    const int64_t n4 = n_zero / 4, stride = (int64_t)(gridDim.x - merge_blocks) * 256;
-    float4* z = reinterpret_cast<float4*>(zero);
-    for (int64_t i = (int64_t)(blockIdx.x - merge_blocks) * 256 + threadIdx.x; i < n4; i += stride)
-      z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    zero_fill_behind(zero, n_zero, (unsigned)merge_blocks, 256);
     return;
   }
   const int32_t t = (int32_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= total) return;
   const uint64_t v = lists[t];
-  const uint64_t key = v >> 17;
+  const uint64_t key = v >> kSlicePosBits;
   const int32_t mine = t / kSliceSort;
   int32_t pos = t - mine * kSliceSort;
   // One binary search per other slice - earlier slices: ids <= key come first (upper bound); later slices: ids < key
@@ -401,7 +325,7 @@ __global__ __launch_bounds__(256) void bpr_merge_kernel(int32_t total, int32_t n
       // (unconditional: a load under a lane mask is waited for on the spot - sixteen round trips per round again; an
       //  empty range probes entry 0 of its slice, or of slice 0 if the slice does not exist, and ignores it)
       const int32_t mid = lo[L] < hi[L] ? (lo[L] + hi[L]) >> 1 : 0;
-      probe[L] = lists[(L < n_lists ? L * kSliceSort : 0) + mid] >> 17;
+      probe[L] = lists[(L < n_lists ? L * kSliceSort : 0) + mid] >> kSlicePosBits;
     }
 #pragma unroll
     for (int L = 0; L < NL; ++L) {
@@ -414,14 +338,41 @@ __global__ __launch_bounds__(256) void bpr_merge_kernel(int32_t total, int32_t n
   }
 #pragma unroll
   for (int L = 0; L < NL; ++L) pos += lo[L];
-  order[pos] = (int32_t)(v & 0x1FFFFull);
+  order[pos] = (int32_t)(v & ((1ull << kSlicePosBits) - 1ull));
   sorted[pos] = (int32_t)key;
 }
 
-static int bits_for_id(int64_t max_id) {
-  int b = 1;
-  while (b < 31 && ((int64_t)1 << b) <= max_id) ++b;
-  return b;
+// The workspace of both entries: per-sample partials (4 B floats) | keys, order (3 B int32 each) | the window partials
+// of the gradient (two rows of F floats per 32 sorted positions) | sort scratch: the slice sort's packed lists + its
+// sorted keys (up to kSliceSort * kSliceSortMaxLists ids), or the device radix sort's, whichever is larger.  Carved
+// from `base`; over a null base `bytes` is all that is used.
+struct BprWorkspace {
+  float* part;
+  int32_t *keys, *order;
+  float* win_part;
+  size_t sort_off;   // the sort scratch begins here
+  uint64_t* lists = nullptr;
+  int32_t* sorted = nullptr;
+  size_t bytes;
+};
+static BprWorkspace bpr_workspace(void* base, int64_t batch, int F) {
+  if (batch < 1) batch = 1;
+  if (F < 4) F = 4;
+  BprWorkspace w;
+  Carver cv(base);
+  w.part = cv.take<float>((size_t)batch * 4);
+  w.keys = cv.take<int32_t>((size_t)batch * 3);
+  w.order = cv.take<int32_t>((size_t)batch * 3);
+  w.win_part = cv.take<float>((size_t)((3 * batch + kBprWin - 1) / kBprWin) * 2 * (size_t)F);
+  w.sort_off = cv.off;
+  Carver cs(cv.base + cv.off);
+  if (3 * batch <= kSliceSort * kSliceSortMaxLists) {
+    w.lists = cs.take<uint64_t>((size_t)batch * 3);
+    w.sorted = cs.take<int32_t>((size_t)batch * 3);
+  }
+  const size_t radix = radix_sort_workspace_bytes(3 * batch);
+  w.bytes = cv.off + (cs.off > radix ? cs.off : radix) + 256;
+  return w;
 }
 
 }  // namespace kgat
@@ -430,17 +381,7 @@ using namespace kgat;
 
 extern "C" {
 
-size_t kgat_bpr_workspace_bytes(int64_t batch, int F) {
-  if (batch < 1) batch = 1;
-  if (F < 4) F = 4;
-  // per-sample partials (4 B floats) | keys, order (3 B int32 each) | sort scratch: the device radix sort's, or the
-  // one-workgroup sort's two packed buffers + its sorted keys
-  const size_t one_wg = 3 * batch <= kSliceSort * kSliceSortMaxLists ? align_up((size_t)batch * 3 * 8, 256) + align_up((size_t)batch * 3 * 4, 256) : 0;
-  const size_t radix = radix_sort_workspace_bytes(3 * batch);
-  // + the window partials of the gradient (two rows of F floats per 32 sorted positions)
-  const size_t win = align_up((size_t)((3 * batch + kBprWin - 1) / kBprWin) * 2 * (size_t)F * 4, 256);
-  return align_up((size_t)batch * 4 * 4, 256) + 2 * align_up((size_t)batch * 3 * 4, 256) + win + (one_wg > radix ? one_wg : radix) + 256;
-}
+size_t kgat_bpr_workspace_bytes(int64_t batch, int F) { return bpr_workspace(nullptr, batch, F).bytes; }
 
 int kgat_bpr_loss_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stride, int64_t batch, const int32_t* u,
                       const int32_t* p, const int32_t* n, float reg_lambda, float* loss, float* coef, void* workspace,
@@ -450,17 +391,16 @@ int kgat_bpr_loss_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
   KGAT_CHECK_ARG(batch < ((int64_t)1 << 29), "bpr_loss: batch too large");
   KGAT_CHECK_ARG(emb && u && p && n && loss && coef && workspace, "bpr_loss: null pointer");
   KGAT_CHECK_ARG((reinterpret_cast<uintptr_t>(emb) & 15) == 0, "bpr_loss: emb must be 16-byte aligned");
-  if (workspace_bytes < kgat_bpr_workspace_bytes(batch, F)) {
+  const BprWorkspace w = bpr_workspace(workspace, batch, F);
+  if (workspace_bytes < w.bytes) {
     set_error("bpr_loss: workspace too small");
     return KGAT_E_WORKSPACE;
   }
-  Carver cv(workspace);
-  float* part = cv.take<float>((size_t)batch * 4);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(bpr_sample_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, batch, n_nodes, F, emb,
-                     emb_stride, u, p, n, part, coef);
+                     emb_stride, u, p, n, w.part, coef);
   KGAT_CHECK_LAUNCH("bpr_sample");
-  hipLaunchKernelGGL(bpr_reduce_kernel, dim3(1), dim3(1024), 0, st, batch, (const float*)part, reg_lambda, loss);
+  hipLaunchKernelGGL(bpr_reduce_kernel, dim3(1), dim3(1024), 0, st, batch, (const float*)w.part, reg_lambda, loss);
   KGAT_CHECK_LAUNCH("bpr_reduce");
   return KGAT_OK;
 }
@@ -474,22 +414,14 @@ int kgat_bpr_grad_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
   KGAT_CHECK_ARG(emb && u && p && n && coef && grad && workspace, "bpr_grad: null pointer");
   KGAT_CHECK_ARG(((reinterpret_cast<uintptr_t>(emb) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0,
                  "bpr_grad: emb and grad must be 16-byte aligned");
-  if (workspace_bytes < kgat_bpr_workspace_bytes(batch, F)) {
+  const BprWorkspace w = bpr_workspace(workspace, batch, F);
+  if (workspace_bytes < w.bytes) {
     set_error("bpr_grad: workspace too small");
     return KGAT_E_WORKSPACE;
   }
-  Carver cv(workspace);
-  cv.take<float>((size_t)batch * 4);
-  int32_t* keys = cv.take<int32_t>((size_t)batch * 3);
-  int32_t* order = cv.take<int32_t>((size_t)batch * 3);
-  float* win_part = cv.take<float>((size_t)((3 * batch + kBprWin - 1) / kBprWin) * 2 * (size_t)F);
-  void* sort_ws = cv.base + cv.off;
   hipStream_t st = as_stream(stream);
   const int32_t* sorted = nullptr;
-  if (3 * batch <= kSliceSort * kSliceSortMaxLists && n_nodes < ((int64_t)1 << 30)) {
-    Carver cs(sort_ws);
-    uint64_t* lists = cs.take<uint64_t>((size_t)batch * 3);
-    int32_t* sorted_w = cs.take<int32_t>((size_t)batch * 3);
+  if (w.lists != nullptr && n_nodes < ((int64_t)1 << 30)) {
     const int32_t total = (int32_t)(3 * batch), n_lists = (total + kSliceSort - 1) / kSliceSort;
     // The zero fill of the N x F gradient (112 MB at the amazon-book size: 25 us of stores) rides beside the two
     // launches in front of the scatter, both of them chains of round trips on a few workgroups: the sort's launch
@@ -498,23 +430,23 @@ int kgat_bpr_grad_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
     const unsigned zero_blocks = 2u * (unsigned)device_cu_count();
     const int64_t n_all = (int64_t)n_nodes * F;
     const int64_t n_first = (n_all * 75 / 100) / 4 * 4;
-    hipLaunchKernelGGL(bpr_sort_zero_kernel, dim3((unsigned)n_lists + zero_blocks), dim3(1024), 0, st, (int32_t)batch, n_lists,
-                       n_nodes, bits_for_id(n_nodes), u, p, n, lists, grad, n_first);
+    hipLaunchKernelGGL(bpr_sort_zero_kernel, dim3((unsigned)n_lists + zero_blocks), dim3(kLdsSortThreads), 0, st,
+                       (int32_t)batch, n_lists, n_nodes, bits_for(n_nodes), u, p, n, w.lists, grad, n_first);
     KGAT_CHECK_LAUNCH("bpr_sort_zero");
     const unsigned merge_blocks = (unsigned)((total + 255) / 256), zero_blocks2 = 8u * (unsigned)device_cu_count();
     if (n_lists <= 8)
       hipLaunchKernelGGL(bpr_merge_kernel<8>, dim3(merge_blocks + zero_blocks2), dim3(256), 0, st, total, n_lists,
-                         (const uint64_t*)lists, order, sorted_w, grad + n_first, n_all - n_first);
+                         (const uint64_t*)w.lists, w.order, w.sorted, grad + n_first, n_all - n_first);
     else
       hipLaunchKernelGGL(bpr_merge_kernel<kSliceSortMaxLists>, dim3(merge_blocks + zero_blocks2), dim3(256), 0, st, total,
-                         n_lists, (const uint64_t*)lists, order, sorted_w, grad + n_first, n_all - n_first);
+                         n_lists, (const uint64_t*)w.lists, w.order, w.sorted, grad + n_first, n_all - n_first);
     KGAT_CHECK_LAUNCH("bpr_merge");
-    sorted = sorted_w;
+    sorted = w.sorted;
   } else {
-    hipLaunchKernelGGL(bpr_keys_kernel, dim3((unsigned)((3 * batch + 255) / 256)), dim3(256), 0, st, batch, u, p, n, keys);
+    hipLaunchKernelGGL(bpr_keys_kernel, dim3((unsigned)((3 * batch + 255) / 256)), dim3(256), 0, st, batch, u, p, n, w.keys);
     KGAT_CHECK_LAUNCH("bpr_keys");
-    const int rc = radix_sort_index(keys, 3 * batch, bits_for_id(n_nodes - 1), order, &sorted, sort_ws,
-                                    workspace_bytes - cv.off, st);
+    const int rc = radix_sort_index(w.keys, 3 * batch, bits_for(n_nodes - 1), w.order, &sorted,
+                                    static_cast<char*>(workspace) + w.sort_off, workspace_bytes - w.sort_off, st);
     if (rc != KGAT_OK) return rc;
     if (hipMemsetAsync(grad, 0, (size_t)n_nodes * F * sizeof(float), st) != hipSuccess) {
       set_error("bpr_grad: memset failed");
@@ -524,10 +456,10 @@ int kgat_bpr_grad_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
   {
     const int64_t n_win = (3 * batch + kBprWin - 1) / kBprWin;
     hipLaunchKernelGGL(bpr_window_kernel, dim3((unsigned)((n_win + 3) / 4)), dim3(256), 0, st, batch, n_nodes, F, emb,
-                       emb_stride, u, p, n, coef, reg_lambda, grad_scale, sorted, (const int32_t*)order, grad, win_part);
+                       emb_stride, u, p, n, coef, reg_lambda, grad_scale, sorted, (const int32_t*)w.order, grad, w.win_part);
     KGAT_CHECK_LAUNCH("bpr_window");
     hipLaunchKernelGGL(bpr_carry_kernel, dim3((unsigned)((n_win + 3) / 4)), dim3(256), 0, st, batch, n_nodes, F, sorted,
-                       (const float*)win_part, grad);
+                       (const float*)w.win_part, grad);
   }
   KGAT_CHECK_LAUNCH("bpr_carry");
   return KGAT_OK;

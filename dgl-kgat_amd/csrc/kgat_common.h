@@ -20,6 +20,29 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }  // float4 / int4 accesses
 
+// bits of a radix sort's keys: enough for every key in [0, max_key], at least 1, at most 31
+inline int bits_for(int64_t max_key) {
+  int b = 1;
+  while (b < 31 && ((int64_t)1 << b) <= max_key) ++b;
+  return b;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+// The blocks behind a launch's real work (block `first_block` on, `threads` each) clear zero[0 .. n_zero), n_zero a
+// multiple of 4: a zero fill rides beside launches that are chains of round trips on a few workgroups.
+__device__ __forceinline__ void zero_fill_behind(float* __restrict__ zero, int64_t n_zero, unsigned first_block,
+                                                 int threads) {
+  const int64_t n4 = n_zero / 4, stride = (int64_t)(gridDim.x - first_block) * threads;
+  float4* z = reinterpret_cast<float4*>(zero);
+  for (int64_t i = (int64_t)(blockIdx.x - first_block) * threads + threadIdx.x; i < n4; i += stride)
+    z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 // Carves 256-byte aligned regions out of a caller-provided workspace.
 struct Carver {
   char* base;

@@ -482,12 +482,6 @@ static inline unsigned blocks_for(int64_t n, int threads) {
   return (unsigned)((n + threads - 1) / threads);
 }
 
-static int bits_for(int64_t max_key) {
-  int b = 1;
-  while (b < 31 && ((int64_t)1 << b) <= max_key) ++b;
-  return b;
-}
-
 }  // namespace kgat
 
 using namespace kgat;

@@ -20,33 +20,22 @@
 #include <math.h>
 
 #include "kgat_adam_common.h"
+#include "kgat_lds_sort.h"
 
 namespace kgat {
 
 constexpr int kTrMaxDim = 128;    // d, k <= 128
 constexpr int kTrChunk = 64;      // samples per partial W-gradient block
 constexpr int kTrSmallSort = 8192;
+constexpr int kTrPosBits = 13;    // a position among kTrSmallSort
 constexpr int kTrMaxRel = 4096;   // relations (chunk table built by one workgroup, 4 keys per thread)
 constexpr int kTrSlotBits = 14;   // row_slot word = call tag << 14 | (first sorted position of the row's run + 1); 3 * batch <= 8192 < 2^14
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// ---- one-workgroup stable sort of n <= 8192 keys (< 2^19), payload = position in the input,
-// packed as key << 13 | position.  LSD radix sort, 9-bit digits (8 with the 64-bit packing), both buffers and the
-// counters in LDS: each of the 16 wavefronts owns a contiguous slice of the current order and its own column
-// of the 512 x 16 counter table, counts its digits (LDS atomics - counts do not depend on order),
-// a block scan turns the table into offsets in (digit, wavefront) order, and the wavefront walks
-// its slice 64 keys at a time ranking equal digits by lane with ballots - so equal keys keep
-// their order.  Also emits, for keys in [0, n_keys], offsets[v] = first sorted position whose key
+// ---- one-workgroup stable sort of n <= 8192 keys, payload = position in the input, packed as key << 13 | position
+// (LdsSort, kgat_lds_sort.h).  Also emits, for keys in [0, n_keys], offsets[v] = first sorted position whose key
 // is >= v (offsets == NULL: skipped).
 // keys_b / keys_c non-NULL: the key list is the interleaving (keys[i], keys_b[i], keys_c[i]) of
 // three arrays of n/3 entries (the three entity ids of every sample).
-constexpr int kSsWaves = 16;
-
 // PT: the packed (key, position) type - uint32_t for keys below 2^19 (64 KB of LDS for the two buffers), uint64_t for
 // any int32 key (128 KB: entity ids of graphs beyond 524,288 nodes, e.g. BASELINE configs[4]'s 10 M).
 struct SortJob {
@@ -65,7 +54,6 @@ struct SortJob {
 template <typename PT>
 __device__ __forceinline__ void small_sort_body(const SortJob& job) {
   const int32_t n = job.n, n_keys = job.n_keys;
-  const int key_bits = job.key_bits;
   const int32_t* __restrict__ keys = job.keys;
   const int32_t* __restrict__ keys_b = job.keys_b;
   const int32_t* __restrict__ keys_c = job.keys_c;
@@ -76,13 +64,9 @@ __device__ __forceinline__ void small_sort_body(const SortJob& job) {
   int2* __restrict__ chunks = job.chunks;
   // digits of 9 bits with the 32-bit packing (eighteen-bit entity ids: two passes instead of three), 8 with the
   // 64-bit one (its buffers leave 32 KB of LDS: 256 x 16 counters)
-  constexpr int DB = sizeof(PT) == 4 ? 9 : 8;
-  constexpr int NDIG = 1 << DB, CPT = NDIG * kSsWaves / 1024;   // counters per thread in the scan
-  __shared__ PT s_buf[2][kTrSmallSort];
-  __shared__ int32_t s_cnt[NDIG * kSsWaves];
-  __shared__ int32_t s_wsum[kSsWaves];
+  __shared__ LdsSort<PT, kTrSmallSort, sizeof(PT) == 4 ? 9 : 8, kTrPosBits> s_sort;
   const int tid = threadIdx.x, lane = tid % kWave, w = tid / kWave;
-  for (int32_t i = tid; i < n; i += 1024) {
+  for (int32_t i = tid; i < n; i += kLdsSortThreads) {
     int32_t key;
     if (keys_b) {
       const int32_t q = i / 3, v = i - 3 * q;
@@ -90,86 +74,27 @@ __device__ __forceinline__ void small_sort_body(const SortJob& job) {
     } else {
       key = keys[i];
     }
-    s_buf[0][i] = ((PT)(uint32_t)key << 13) | (PT)i;
+    s_sort.buf[0][i] = ((PT)(uint32_t)key << kTrPosBits) | (PT)i;
   }
-  const int32_t slice = ((n + kSsWaves * kWave - 1) / (kSsWaves * kWave)) * kWave;  // per wavefront, multiple of 64
-  const int32_t lo = w * slice, hi = lo + slice < n ? lo + slice : n;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  int cur = 0;
-  const int passes = (key_bits + DB - 1) / DB > 0 ? (key_bits + DB - 1) / DB : 1;
-  for (int pass = 0; pass < passes; ++pass) {
-    const int shift = 13 + DB * pass;
-    for (int i = tid; i < NDIG * kSsWaves; i += 1024) s_cnt[i] = 0;
-    __syncthreads();
-    for (int32_t i = lo + lane; i < hi; i += kWave) atomicAdd(&s_cnt[(uint32_t)((s_buf[cur][i] >> shift) & (PT)(NDIG - 1)) * kSsWaves + w], 1);
-    __syncthreads();
-    {  // exclusive scan of the counters in (digit, wavefront) order, CPT per thread
-      int32_t c[CPT];
-      int32_t mine = 0;
-#pragma unroll
-      for (int q = 0; q < CPT; ++q) { c[q] = s_cnt[CPT * tid + q]; mine += c[q]; }
-      int32_t inc = mine;
-#pragma unroll
-      for (int d = 1; d < kWave; d <<= 1) {
-        const int32_t up = __shfl_up(inc, d, kWave);
-        if (lane >= d) inc += up;
-      }
-      if (lane == kWave - 1) s_wsum[w] = inc;
-      __syncthreads();
-      int32_t base = inc - mine;
-      for (int q = 0; q < w; ++q) base += s_wsum[q];
-#pragma unroll
-      for (int q = 0; q < CPT; ++q) {
-        s_cnt[CPT * tid + q] = base;
-        base += c[q];
-      }
-    }
-    __syncthreads();
-    for (int32_t i0 = lo; i0 < hi; i0 += kWave) {
-      const int32_t i = i0 + lane;
-      const bool valid = i < hi;
-      const PT v = valid ? s_buf[cur][i] : (PT)0;
-      const uint32_t dgt = (uint32_t)((v >> shift) & (PT)(NDIG - 1));
-      uint64_t peers = __ballot(valid);
-#pragma unroll
-      for (int bit = 0; bit < DB; ++bit) {
-        const bool on = (dgt >> bit) & 1u;
-        const uint64_t bal = __ballot(on);
-        peers &= on ? bal : ~bal;
-      }
-      const int rank = __popcll(peers & lt_mask);
-      const int32_t basep = valid ? s_cnt[dgt * kSsWaves + w] : 0;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();  // every lane has its base before a leader moves it
-      if (valid) {
-        s_buf[cur ^ 1][basep + rank] = v;
-        if (rank == 0) s_cnt[dgt * kSsWaves + w] = basep + __popcll(peers);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  const PT* s = s_buf[cur];
-  for (int32_t p = tid; p <= n; p += 1024) {
+  const PT* s = s_sort.sort(n, job.key_bits);
+  for (int32_t p = tid; p <= n; p += kLdsSortThreads) {
     if (p < n) {
-      order[p] = (int32_t)(s[p] & 8191u);
-      if (sorted_keys) sorted_keys[p] = (int32_t)(s[p] >> 13);
-      if (job.inv) job.inv[(int32_t)(s[p] & 8191u)] = p;
+      order[p] = (int32_t)(s[p] & (kTrSmallSort - 1));
+      if (sorted_keys) sorted_keys[p] = (int32_t)(s[p] >> kTrPosBits);
+      if (job.inv) job.inv[(int32_t)(s[p] & (kTrSmallSort - 1))] = p;
       if (job.run_len) {
-        const PT key = s[p] >> 13;
+        const PT key = s[p] >> kTrPosBits;
         int32_t len = 0;
-        if (p == 0 || (s[p - 1] >> 13) != key) {
+        if (p == 0 || (s[p - 1] >> kTrPosBits) != key) {
           len = 1;
-          while (p + len < n && (s[p + len] >> 13) == key) ++len;
+          while (p + len < n && (s[p + len] >> kTrPosBits) == key) ++len;
         }
         job.run_len[p] = len;
       }
     }
     if (offsets) {
-      int32_t prev = p == 0 ? -1 : (int32_t)(s[p - 1] >> 13);
-      int32_t curk = p == n ? n_keys : (int32_t)(s[p] >> 13);
+      int32_t prev = p == 0 ? -1 : (int32_t)(s[p - 1] >> kTrPosBits);
+      int32_t curk = p == n ? n_keys : (int32_t)(s[p] >> kTrPosBits);
       curk = curk > n_keys ? n_keys : curk;
       prev = prev > n_keys ? n_keys : prev;
       for (int32_t v = prev + 1; v <= curk; ++v) offsets[v] = p;
@@ -178,11 +103,11 @@ __device__ __forceinline__ void small_sort_body(const SortJob& job) {
   if (chunk_ptr == nullptr) return;
   // chunk table of the per-relation gradient sums (n_keys <= kTrMaxRel): chunk_ptr[v] = first chunk
   // of key v, chunks[c] = (key, first sorted position); a chunk is <= kTrChunk positions of one key
-  int32_t* s_off = reinterpret_cast<int32_t*>(s_buf[cur ^ 1]);  // the other buffer is free now
+  int32_t* s_off = reinterpret_cast<int32_t*>(s_sort.other(s));  // the other buffer is free now
   __syncthreads();
-  for (int32_t p = tid; p <= n; p += 1024) {
-    int32_t prev = p == 0 ? -1 : (int32_t)(s[p - 1] >> 13);
-    int32_t curk = p == n ? n_keys : (int32_t)(s[p] >> 13);
+  for (int32_t p = tid; p <= n; p += kLdsSortThreads) {
+    int32_t prev = p == 0 ? -1 : (int32_t)(s[p - 1] >> kTrPosBits);
+    int32_t curk = p == n ? n_keys : (int32_t)(s[p] >> kTrPosBits);
     curk = curk > n_keys ? n_keys : curk;
     prev = prev > n_keys ? n_keys : prev;
     for (int32_t v = prev + 1; v <= curk; ++v) s_off[v] = p;
@@ -202,10 +127,10 @@ __device__ __forceinline__ void small_sort_body(const SortJob& job) {
       const int32_t up = __shfl_up(inc, d, kWave);
       if (lane >= d) inc += up;
     }
-    if (lane == kWave - 1) s_wsum[w] = inc;
+    if (lane == kWave - 1) s_sort.wsum[w] = inc;
     __syncthreads();
     int32_t base = inc - mine;
-    for (int q = 0; q < w; ++q) base += s_wsum[q];
+    for (int q = 0; q < w; ++q) base += s_sort.wsum[q];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int32_t v = 4 * tid + q;
@@ -225,17 +150,13 @@ __device__ __forceinline__ void small_sort_body(const SortJob& job) {
 // ran relation sort -> ... -> memset -> id sort in stream order: two one-workgroup launches of ~18 us and a 41 MB
 // memset on an otherwise idle chip.)
 template <typename PT>
-__global__ __launch_bounds__(1024) void small_sort_kernel(SortJob a, SortJob b, int n_jobs, float* __restrict__ zero,
-                                                          int64_t n_zero) {
+__global__ __launch_bounds__(kLdsSortThreads) void small_sort_kernel(SortJob a, SortJob b, int n_jobs,
+                                                                     float* __restrict__ zero, int64_t n_zero) {
   if ((int)blockIdx.x < n_jobs) {
     small_sort_body<PT>(blockIdx.x == 0 ? a : b);
     return;
   }
-  const int64_t n4 = n_zero / 4;
-  const int64_t stride = (int64_t)(gridDim.x - n_jobs) * 1024;
-  float4* z = reinterpret_cast<float4*>(zero);
-  for (int64_t i = (int64_t)(blockIdx.x - n_jobs) * 1024 + threadIdx.x; i < n4; i += stride)
-    z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  zero_fill_behind(zero, n_zero, (unsigned)n_jobs, kLdsSortThreads);
 }
 
 // ---- per-sample kernel: projections, loss head, its backward, grad_a W_r^T
@@ -902,13 +823,18 @@ __global__ __launch_bounds__(256) void transr_reduce_kernel(int n_first, int ny,
 //    and of the relation table add a relation's partials in chunk order (the reduction launch's order) on the way.
 // Launches per iteration: per-sample kernel (+ row tags) -> weight-gradient partials + loss -> Adam (+ gradient-row sums).
 
+// the most chunks a batch's chunk table can hold: one per started kTrChunk samples of every relation
+static size_t transr_max_chunks(int64_t batch, int n_rel) {
+  return (size_t)(batch > 0 ? batch : 1) / kTrChunk + (size_t)(n_rel > 0 ? n_rel : 0) + 1;
+}
+
 // per-batch block of the presort's output (offsets in bytes, 256-byte aligned)
 struct TrSortedLayout {
   size_t order, seg, chunk_ptr, chunks, sorted_ids, row_order, inv_pos, run_len, bytes;
 };
 static TrSortedLayout transr_sorted_layout(int64_t batch, int n_rel) {
   const size_t b = (size_t)(batch > 0 ? batch : 1);
-  const size_t n_part = b / kTrChunk + (size_t)(n_rel > 0 ? n_rel : 0) + 1;
+  const size_t n_part = transr_max_chunks(batch, n_rel);
   TrSortedLayout l;
   size_t w = 0;
   l.order = w; w += align_up(b * 4, 256);
@@ -932,7 +858,7 @@ struct TrPresortArgs {
 };
 
 template <typename PT>
-__global__ __launch_bounds__(1024) void transr_presort_kernel(TrPresortArgs a) {
+__global__ __launch_bounds__(kLdsSortThreads) void transr_presort_kernel(TrPresortArgs a) {
   const int32_t b = (int32_t)(blockIdx.x >> 1);
   if (b >= a.n_batches) return;
   unsigned char* blk = a.sorted + (size_t)b * a.lay.bytes;
@@ -1053,16 +979,75 @@ __global__ __launch_bounds__(256) void transr_adam_kernel(TrAdamArgs a, float w1
   }
 }
 
-static size_t transr_step_workspace_bytes(int64_t batch, int d, int k, int n_rel) {
+// ---- the workspaces.  Each is described once, as the carve of its pieces from `base`; over a null base the carve
+// yields the size (`bytes`) alone, so a size entry and the entry that uses the pointers cannot disagree.
+
+// what the per-sample kernel leaves for the launches behind it
+struct TrSampleArrays {
+  float *losses, *GA, *GR;
+  float *DX, *XS;   // DX: rows 3 b + v (transr_run) or the sorted positions (the KG phase's step)
+  float* part;      // W / relation gradient partials, n_part blocks of d k + k
+  int n_part;
+};
+static TrSampleArrays transr_take_sample_arrays(Carver& cv, int64_t batch, int d, int k, int n_rel) {
   const size_t b = (size_t)(batch > 0 ? batch : 1);
-  const size_t n_part = b / kTrChunk + (size_t)(n_rel > 0 ? n_rel : 0) + 1;
-  size_t w = 0;
-  w += align_up(b * 4, 256);                             // losses
-  w += align_up(3 * b * (size_t)k * 4, 256);             // GA
-  w += align_up(b * (size_t)k * 4, 256);                 // GR
-  w += 2 * align_up(3 * b * (size_t)d * 4, 256);         // DX (rows at their sorted positions), XS
-  w += align_up(n_part * ((size_t)d * k + k) * 4, 256);  // W / relation gradient partials
+  TrSampleArrays s;
+  s.n_part = (int)transr_max_chunks(batch, n_rel);
+  s.losses = cv.take<float>(b);
+  s.GA = cv.take<float>(3 * b * (size_t)k);
+  s.GR = cv.take<float>(b * (size_t)k);
+  s.DX = cv.take<float>(3 * b * (size_t)d);
+  s.XS = cv.take<float>(3 * b * (size_t)d);
+  s.part = cv.take<float>((size_t)s.n_part * ((size_t)d * k + k));
+  return s;
+}
+
+// transr_run's: the relation sort's outputs | the per-sample arrays | the id sort's outputs
+struct TrRunWorkspace {
+  int32_t *order, *seg, *chunk_ptr;
+  int2* chunks;
+  TrSampleArrays s;
+  int32_t *sorted_ids, *row_order;
+  size_t bytes;
+};
+static TrRunWorkspace transr_run_workspace(void* base, int64_t batch, int d, int k, int n_rel) {
+  const size_t b = (size_t)(batch > 0 ? batch : 1);
+  Carver cv(base);
+  TrRunWorkspace w;
+  w.order = cv.take<int32_t>(b);
+  w.seg = cv.take<int32_t>((size_t)n_rel + 2);
+  w.chunk_ptr = cv.take<int32_t>((size_t)n_rel + 2);
+  w.chunks = cv.take<int2>(transr_max_chunks(batch, n_rel));
+  w.s = transr_take_sample_arrays(cv, batch, d, k, n_rel);
+  w.sorted_ids = cv.take<int32_t>(3 * b);
+  w.row_order = cv.take<int32_t>(3 * b);
+  w.bytes = cv.off;
   return w;
+}
+
+// the KG phase's step's: the per-sample arrays (the sorts' outputs come in the presort's block)
+struct TrStepWorkspace {
+  TrSampleArrays s;
+  size_t bytes;
+};
+static TrStepWorkspace transr_step_workspace(void* base, int64_t batch, int d, int k, int n_rel) {
+  Carver cv(base);
+  TrStepWorkspace w;
+  w.s = transr_take_sample_arrays(cv, batch, d, k, n_rel);
+  w.bytes = cv.off;
+  return w;
+}
+
+// The per-sample launch: `blocks` workgroups of four samples (+ the KG phase's row-tag blocks behind them, with `mk`).
+static void transr_launch_sample(bool want_grad, unsigned blocks, hipStream_t st, int32_t B, int d, int k,
+                                 const int32_t* order, const int32_t* h, const int32_t* r, const int32_t* pos_t,
+                                 const int32_t* neg_t, const float* ent, const float* W_R, const float* rel,
+                                 float reg_lambda, const TrSampleArrays& s, const TrStepMarks& mk = TrStepMarks{}) {
+  const bool wlds = d <= kTrWLds && k <= kTrWLds;
+  const auto kernel = want_grad ? (wlds ? transr_sample_kernel<true, true> : transr_sample_kernel<true, false>)
+                                : (wlds ? transr_sample_kernel<false, true> : transr_sample_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, B, d, k, order, h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda,
+                     s.losses, s.GA, s.GR, s.DX, s.XS, mk);
 }
 
 }  // namespace kgat
@@ -1077,19 +1062,7 @@ int kgat_transr_supported(int64_t n_nodes, int d, int k, int n_rel, int64_t batc
 }
 
 size_t kgat_transr_workspace_bytes(int64_t batch, int d, int k, int n_rel) {
-  const size_t b = (size_t)(batch > 0 ? batch : 1);
-  const size_t n_part = b / kTrChunk + (size_t)(n_rel > 0 ? n_rel : 0) + 1;
-  size_t w = 0;
-  w += align_up(b * 4, 256);                       // order (relation-sorted samples)
-  w += 2 * align_up(((size_t)n_rel + 2) * 4, 256); // seg, chunk_ptr
-  w += align_up(n_part * 8, 256);                  // chunks
-  w += align_up(b * 4, 256);                       // losses
-  w += align_up(3 * b * (size_t)k * 4, 256);       // GA
-  w += align_up(b * (size_t)k * 4, 256);           // GR
-  w += 2 * align_up(3 * b * (size_t)d * 4, 256);   // DX, XS
-  w += align_up(n_part * ((size_t)d * k + k) * 4, 256);  // W / relation gradient partials
-  w += 2 * align_up(3 * b * 4, 256);               // sorted ids, row order
-  return w;
+  return transr_run_workspace(nullptr, batch, d, k, n_rel).bytes;
 }
 
 // stage bits of transr_run: FORWARD = relation sort + per-sample kernel (+ the weight-gradient partials) + the loss;
@@ -1111,34 +1084,20 @@ static int transr_run(int stage, int64_t n_nodes, int n_rel, int d, int k, int64
   KGAT_CHECK_ARG(!(stage & kTrForward) || (ent && W_R && rel && loss), "transr: null pointer");
   KGAT_CHECK_ARG(!(stage & kTrBackward) || !want_grad || (grad_ent && grad_W && grad_rel),
                  "transr: all three gradients or none");
-  if (workspace_bytes < kgat_transr_workspace_bytes(batch, d, k, n_rel)) {
+  const TrRunWorkspace w = transr_run_workspace(workspace, batch, d, k, n_rel);
+  if (workspace_bytes < w.bytes) {
     set_error("transr: workspace too small");
     return KGAT_E_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
   const int32_t B = (int32_t)batch;
-  const int n_part = B / kTrChunk + n_rel + 1;
-  Carver cv(workspace);
-  int32_t* order = cv.take<int32_t>((size_t)B);
-  int32_t* seg = cv.take<int32_t>((size_t)n_rel + 2);
-  int32_t* chunk_ptr = cv.take<int32_t>((size_t)n_rel + 2);
-  int2* chunks = cv.take<int2>((size_t)n_part);
-  float* losses = cv.take<float>((size_t)B);
-  float* GA = cv.take<float>((size_t)3 * B * k);
-  float* GR = cv.take<float>((size_t)B * k);
-  float* DX = cv.take<float>((size_t)3 * B * d);
-  float* XS = cv.take<float>((size_t)3 * B * d);
-  float* part = cv.take<float>((size_t)n_part * ((size_t)d * k + k));
-  int32_t* sorted_ids = cv.take<int32_t>((size_t)3 * B);
-  int32_t* row_order = cv.take<int32_t>((size_t)3 * B);
-
-  int rel_bits = 1, id_bits = 1;
-  while ((1 << rel_bits) < n_rel) ++rel_bits;
-  while ((1ll << id_bits) < n_nodes) ++id_bits;
+  const int n_part = w.s.n_part;
+  const int rel_bits = bits_for(n_rel - 1), id_bits = bits_for(n_nodes - 1);
   const bool fwd = (stage & kTrForward) != 0, bwd = (stage & kTrBackward) != 0 && want_grad;
-  const SortJob rel_job = {B, rel_bits, r, nullptr, nullptr, order, nullptr, (int32_t)n_rel, seg, chunk_ptr, chunks};
-  const SortJob id_job = {3 * B, id_bits, h, pos_t, neg_t, row_order, sorted_ids, 0, nullptr, nullptr, nullptr};
-  const TrScatterArgs sc = {3 * B, sorted_ids, row_order, DX, grad_ent, grad_scale};
+  const SortJob rel_job = {B, rel_bits, r, nullptr, nullptr, w.order, nullptr, (int32_t)n_rel, w.seg, w.chunk_ptr,
+                           w.chunks};
+  const SortJob id_job = {3 * B, id_bits, h, pos_t, neg_t, w.row_order, w.sorted_ids, 0, nullptr, nullptr, nullptr};
+  const TrScatterArgs sc = {3 * B, w.sorted_ids, w.row_order, w.s.DX, grad_ent, grad_scale};
   const TrScatterArgs no_sc = {0, nullptr, nullptr, nullptr, nullptr, nullptr};
   const unsigned scatter_blocks = (unsigned)((3 * B + 15) / 16);
   const int64_t n_zero = (int64_t)n_nodes * d;
@@ -1149,52 +1108,36 @@ static int transr_run(int stage, int64_t n_nodes, int n_rel, int d, int k, int64
     if (n_jobs == 0) return KGAT_OK;
     const unsigned zero_blocks = bwd ? 2u * (unsigned)device_cu_count() : 0u;
     if (bwd && id_bits > 19)  // entity ids beyond 2^19: the 64-bit packing (128 KB of LDS, one more radix pass per 8 id bits)
-      hipLaunchKernelGGL(small_sort_kernel<uint64_t>, dim3(n_jobs + zero_blocks), dim3(1024), 0, st, first, id_job, n_jobs,
-                         grad_ent, n_zero);
+      hipLaunchKernelGGL(small_sort_kernel<uint64_t>, dim3(n_jobs + zero_blocks), dim3(kLdsSortThreads), 0, st, first,
+                         id_job, n_jobs, grad_ent, n_zero);
     else
-      hipLaunchKernelGGL(small_sort_kernel<uint32_t>, dim3(n_jobs + zero_blocks), dim3(1024), 0, st, first, id_job, n_jobs,
-                         bwd ? grad_ent : (float*)nullptr, bwd ? n_zero : (int64_t)0);
+      hipLaunchKernelGGL(small_sort_kernel<uint32_t>, dim3(n_jobs + zero_blocks), dim3(kLdsSortThreads), 0, st, first,
+                         id_job, n_jobs, bwd ? grad_ent : (float*)nullptr, bwd ? n_zero : (int64_t)0);
     KGAT_CHECK_LAUNCH("transr_sort");
   }
   if (fwd) {
-    const unsigned sb = (unsigned)((B + 3) / 4);
-    if (!want_grad) {
-      if (d <= kTrWLds && k <= kTrWLds)
-        hipLaunchKernelGGL((transr_sample_kernel<false, true>), dim3(sb), dim3(256), 0, st, B, d, k, (const int32_t*)order, h,
-                           r, pos_t, neg_t, ent, W_R, rel, reg_lambda, losses, GA, GR, DX, XS);
-      else
-        hipLaunchKernelGGL((transr_sample_kernel<false, false>), dim3(sb), dim3(256), 0, st, B, d, k, (const int32_t*)order, h,
-                           r, pos_t, neg_t, ent, W_R, rel, reg_lambda, losses, GA, GR, DX, XS);
-      KGAT_CHECK_LAUNCH("transr_sample");
-      hipLaunchKernelGGL(transr_reduce_kernel, dim3(1), dim3(256), 0, st, 1, 1, B, d, k, 0, (const int32_t*)chunk_ptr,
-                         (const float*)part, (const float*)losses, (float*)nullptr, (float*)nullptr, loss,
-                         (const float*)nullptr, no_sc);
-      KGAT_CHECK_LAUNCH("transr_reduce");
-      return KGAT_OK;
-    }
-    if (d <= kTrWLds && k <= kTrWLds)
-      hipLaunchKernelGGL((transr_sample_kernel<true, true>), dim3(sb), dim3(256), 0, st, B, d, k, (const int32_t*)order, h, r,
-                         pos_t, neg_t, ent, W_R, rel, reg_lambda, losses, GA, GR, DX, XS);
-    else
-      hipLaunchKernelGGL((transr_sample_kernel<true, false>), dim3(sb), dim3(256), 0, st, B, d, k, (const int32_t*)order, h, r,
-                         pos_t, neg_t, ent, W_R, rel, reg_lambda, losses, GA, GR, DX, XS);
+    transr_launch_sample(want_grad, (unsigned)((B + 3) / 4), st, B, d, k, w.order, h, r, pos_t, neg_t, ent, W_R, rel,
+                         reg_lambda, w.s);
     KGAT_CHECK_LAUNCH("transr_sample");
-    // the weight-gradient partials, and beside them (whole step in one call) the entity-gradient scatter
-    const size_t lds = transr_stage_bytes(d, k);
-    // (set on every call: the attribute is per function AND per device, and a process-wide "already set" flag is
-    //  neither - ADVICE round 5; the call is a host-side table write)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(transr_wgrad_partial_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      set_error("transr: cannot reserve %zu bytes of LDS", lds);
-      return KGAT_E_HIP;
+    if (want_grad) {
+      // the weight-gradient partials, and beside them (whole step in one call) the entity-gradient scatter
+      const size_t lds = transr_stage_bytes(d, k);
+      // (set on every call: the attribute is per function AND per device, and a process-wide "already set" flag is
+      //  neither - ADVICE round 5; the call is a host-side table write)
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(transr_wgrad_partial_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        set_error("transr: cannot reserve %zu bytes of LDS", lds);
+        return KGAT_E_HIP;
+      }
+      hipLaunchKernelGGL(transr_wgrad_partial_kernel, dim3((unsigned)n_part + (bwd ? scatter_blocks : 0u)), dim3(256), lds,
+                         st, n_part, d, k, n_rel, (const int32_t*)w.seg, (const float*)w.s.XS, (const float*)w.s.GA,
+                         (const float*)w.s.GR, (const int32_t*)w.chunk_ptr, (const int2*)w.chunks, w.s.part,
+                         transr_stage_geom(d, k), bwd ? sc : no_sc);
+      KGAT_CHECK_LAUNCH("transr_wgrad_partial");
     }
-    hipLaunchKernelGGL(transr_wgrad_partial_kernel, dim3((unsigned)n_part + (bwd ? scatter_blocks : 0u)), dim3(256), lds, st,
-                       n_part, d, k, n_rel, (const int32_t*)seg, (const float*)XS, (const float*)GA, (const float*)GR,
-                       (const int32_t*)chunk_ptr, (const int2*)chunks, part, transr_stage_geom(d, k), bwd ? sc : no_sc);
-    KGAT_CHECK_LAUNCH("transr_wgrad_partial");
     if (!bwd) {  // the loss alone now (block n_rel of the reduction)
-      hipLaunchKernelGGL(transr_reduce_kernel, dim3(1), dim3(256), 0, st, 1, 1, B, d, k, 0, (const int32_t*)chunk_ptr,
-                         (const float*)part, (const float*)losses, (float*)nullptr, (float*)nullptr, loss,
+      hipLaunchKernelGGL(transr_reduce_kernel, dim3(1), dim3(256), 0, st, 1, 1, B, d, k, 0, (const int32_t*)w.chunk_ptr,
+                         (const float*)w.s.part, (const float*)w.s.losses, (float*)nullptr, (float*)nullptr, loss,
                          (const float*)nullptr, no_sc);
       KGAT_CHECK_LAUNCH("transr_reduce");
       return KGAT_OK;
@@ -1206,8 +1149,8 @@ static int transr_run(int stage, int64_t n_nodes, int n_rel, int d, int k, int64
   constexpr int kNy = 8;
   const unsigned red_blocks = ((unsigned)n_rel + 1) * kNy;
   hipLaunchKernelGGL(transr_reduce_kernel, dim3(red_blocks + (fwd ? 0u : scatter_blocks)), dim3(256), 0, st, (int)red_blocks,
-                     kNy, B, d, k, n_rel, (const int32_t*)chunk_ptr, (const float*)part, (const float*)losses, grad_W,
-                     grad_rel, fwd ? loss : (float*)nullptr, grad_scale, fwd ? no_sc : sc);
+                     kNy, B, d, k, n_rel, (const int32_t*)w.chunk_ptr, (const float*)w.s.part, (const float*)w.s.losses,
+                     grad_W, grad_rel, fwd ? loss : (float*)nullptr, grad_scale, fwd ? no_sc : sc);
   KGAT_CHECK_LAUNCH("transr_reduce");
   return KGAT_OK;
 }
@@ -1258,21 +1201,21 @@ int kgat_transr_presort_f32(int64_t n_nodes, int n_rel, int64_t n_batches, int64
     set_error("transr_presort: output buffer too small");
     return KGAT_E_WORKSPACE;
   }
-  int rel_bits = 1, id_bits = 1;
-  while ((1 << rel_bits) < n_rel) ++rel_bits;
-  while ((1ll << id_bits) < n_nodes) ++id_bits;
-  const TrPresortArgs a = {(int32_t)n_batches, (int32_t)batch, rel_bits, id_bits, n_rel, h, r, pos_t, neg_t,
+  const int id_bits = bits_for(n_nodes - 1);
+  const TrPresortArgs a = {(int32_t)n_batches, (int32_t)batch, bits_for(n_rel - 1), id_bits, n_rel, h, r, pos_t, neg_t,
                            static_cast<unsigned char*>(sorted), lay};
   if (id_bits > 19)
-    hipLaunchKernelGGL(transr_presort_kernel<uint64_t>, dim3((unsigned)(2 * n_batches)), dim3(1024), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(transr_presort_kernel<uint64_t>, dim3((unsigned)(2 * n_batches)), dim3(kLdsSortThreads), 0,
+                       as_stream(stream), a);
   else
-    hipLaunchKernelGGL(transr_presort_kernel<uint32_t>, dim3((unsigned)(2 * n_batches)), dim3(1024), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(transr_presort_kernel<uint32_t>, dim3((unsigned)(2 * n_batches)), dim3(kLdsSortThreads), 0,
+                       as_stream(stream), a);
   KGAT_CHECK_LAUNCH("transr_presort");
   return KGAT_OK;
 }
 
 size_t kgat_transr_step_workspace_bytes(int64_t batch, int d, int k, int n_rel) {
-  return transr_step_workspace_bytes(batch, d, k, n_rel);
+  return transr_step_workspace(nullptr, batch, d, k, n_rel).bytes;
 }
 
 int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t batch, const int32_t* h, const int32_t* r,
@@ -1297,13 +1240,15 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
                      reinterpret_cast<uintptr_t>(exp_avg_sq_host[t])) & 15) == 0,
                    "transr_adam_step: tensor %d: parameters and moments must be 16-byte aligned", t);
   }
-  if (workspace_bytes < transr_step_workspace_bytes(batch, d, k, n_rel)) {
+  const TrStepWorkspace w = transr_step_workspace(workspace, batch, d, k, n_rel);
+  const TrSampleArrays& ws = w.s;
+  if (workspace_bytes < w.bytes) {
     set_error("transr_adam_step: workspace too small");
     return KGAT_E_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
   const int32_t B = (int32_t)batch;
-  const int n_part = B / kTrChunk + n_rel + 1;
+  const int n_part = ws.n_part;
   const TrSortedLayout lay = transr_sorted_layout(batch, n_rel);
   const unsigned char* blk = static_cast<const unsigned char*>(sorted);
   const int32_t* order = reinterpret_cast<const int32_t*>(blk + lay.order);
@@ -1313,25 +1258,10 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
   const int32_t* sorted_ids = reinterpret_cast<const int32_t*>(blk + lay.sorted_ids);
   const int32_t* inv_pos = reinterpret_cast<const int32_t*>(blk + lay.inv_pos);
   const int32_t* run_len = reinterpret_cast<const int32_t*>(blk + lay.run_len);
-  Carver cv(workspace);
-  float* losses = cv.take<float>((size_t)B);
-  float* GA = cv.take<float>((size_t)3 * B * k);
-  float* GR = cv.take<float>((size_t)B * k);
-  float* DX = cv.take<float>((size_t)3 * B * d);
-  float* XS = cv.take<float>((size_t)3 * B * d);
-  float* part = cv.take<float>((size_t)n_part * ((size_t)d * k + k));
-
   const unsigned sb = (unsigned)((B + 3) / 4), mark_blocks = (unsigned)((3 * B + 255) / 256);
   const TrStepMarks mk = {inv_pos, sorted_ids, run_len, reinterpret_cast<unsigned long long*>(row_slot),
                           (unsigned long long)tag, (int)sb};
-  if (d <= kTrWLds && k <= kTrWLds)
-    hipLaunchKernelGGL((transr_sample_kernel<true, true>), dim3(sb + mark_blocks), dim3(256), 0, st, B, d, k, order, h, r,
-                       pos_t, neg_t, (const float*)ent, (const float*)W_R, (const float*)rel, reg_lambda, losses, GA, GR, DX,
-                       XS, mk);
-  else
-    hipLaunchKernelGGL((transr_sample_kernel<true, false>), dim3(sb + mark_blocks), dim3(256), 0, st, B, d, k, order, h, r,
-                       pos_t, neg_t, (const float*)ent, (const float*)W_R, (const float*)rel, reg_lambda, losses, GA, GR, DX,
-                       XS, mk);
+  transr_launch_sample(true, sb + mark_blocks, st, B, d, k, order, h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda, ws, mk);
   KGAT_CHECK_LAUNCH("transr_sample");
   const size_t lds = transr_stage_bytes(d, k);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(transr_wgrad_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1341,8 +1271,8 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
   }
   const int n_split = (d % 16 == 0 && k % 16 == 0) ? (d / 16 < 4 ? d / 16 : 4) : 1;
   hipLaunchKernelGGL(transr_wgrad_step_kernel, dim3((unsigned)(n_part * n_split + 1)), dim3(256), lds, st, n_part, n_split, B,
-                     d, k, n_rel, seg, (const float*)XS, (const float*)GA, (const float*)GR, chunk_ptr, chunks, part,
-                     (const float*)losses, loss, transr_stage_geom(d, k));
+                     d, k, n_rel, seg, (const float*)ws.XS, (const float*)ws.GA, (const float*)ws.GR, chunk_ptr, chunks,
+                     ws.part, (const float*)ws.losses, loss, transr_stage_geom(d, k));
   KGAT_CHECK_LAUNCH("transr_wgrad_step");
   TrAdamArgs a;
   const int64_t sizes[3] = {(int64_t)n_nodes * d, (int64_t)n_rel * d * k, (int64_t)n_rel * k};
@@ -1362,7 +1292,7 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
   a.d = d; a.k = k; a.dk = d * k;
   a.row_slot = reinterpret_cast<const unsigned long long*>(row_slot);
   a.tag = (unsigned long long)tag;
-  a.DXs = DX; a.run_len = run_len; a.part = part; a.chunk_ptr = chunk_ptr;
+  a.DXs = ws.DX; a.run_len = run_len; a.part = ws.part; a.chunk_ptr = chunk_ptr;
   hipLaunchKernelGGL(transr_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps);
   KGAT_CHECK_LAUNCH("transr_adam");

@@ -20,7 +20,10 @@ and a row passes when its error is within max(its floor, 2 x the restatement's l
 the loss when |L - L64| <= max(8 U, 2 x the restatement's) x |L64|.  The factor 2 is conftest.parity_8c's.
 
 The batch builders and the list of cases live here too: the host test (fp32 restatement against every bar, no GPU) and
-the device test walk the same cases."""
+the device test walk the same cases.
+
+At the end: the layout of the per-batch block that the KG phase's presort writes, restated (the host test tabulates it
+against the library's size entry, the device test decodes blocks with it), and what the block must hold, from numpy."""
 import functools
 import types
 
@@ -275,3 +278,61 @@ def bpr_case_data(n, F_, B, structured):
     batch = bpr_batch(n, B, structured)
     emb = torch.randn(n, F_, generator=torch.Generator().manual_seed(n + F_ + B))
     return batch, emb, bpr_ref(emb, *batch, 1e-5), bpr_ref(emb, *batch, 1e-5, dtype=torch.float32)
+
+
+# -- the presort's per-batch block (kgat_transr_presort_f32), restated
+CHUNK = 64       # samples per chunk of the weight-gradient partials
+
+
+def align256(nbytes):
+    return (int(nbytes) + 255) // 256 * 256
+
+
+def max_chunks(batch, n_rel):
+    """The most chunks a batch's chunk table can hold: one per started CHUNK samples of every relation."""
+    return batch // CHUNK + n_rel + 1
+
+
+def sorted_block_layout(batch, n_rel):
+    """name -> (byte offset, dtype, element count) of the pieces of one batch's block, and the block's size in bytes:
+    256-aligned pieces in this order."""
+    pieces = [("order", np.int32, batch), ("seg", np.int32, n_rel + 2), ("chunk_ptr", np.int32, n_rel + 2),
+              ("chunks", np.int32, 2 * max_chunks(batch, n_rel)), ("sorted_ids", np.int32, 3 * batch),
+              ("row_order", np.int32, 3 * batch), ("inv_pos", np.int32, 3 * batch), ("run_len", np.int32, 3 * batch)]
+    lay, off = {}, 0
+    for name, dtype, count in pieces:
+        lay[name] = (off, dtype, count)
+        off += align256(count * np.dtype(dtype).itemsize)
+    return lay, off
+
+
+def decode_sorted_block(block, batch, n_rel):
+    """The pieces of one batch's block (a uint8 numpy array of the block's size) as int32 arrays; `chunks` as (n, 2)."""
+    lay, nbytes = sorted_block_layout(batch, n_rel)
+    assert block.dtype == np.uint8 and block.size == nbytes
+    out = {name: block[off:off + 4 * count].view(np.int32) for name, (off, _, count) in lay.items()}
+    out["chunks"] = out["chunks"].reshape(-1, 2)
+    return types.SimpleNamespace(**out)
+
+
+def presort_expected(h, r, pos_t, neg_t, n_rel):
+    """What the presort must leave for one batch, from numpy's stable sorts (a stable sort's output is unique).  Only
+    the first chunk_ptr[n_rel] entries of `chunks`, and seg[0 .. n_rel], are defined."""
+    h, r, pos_t, neg_t = (np.asarray(t, np.int64) for t in (h, r, pos_t, neg_t))
+    order = np.argsort(r, kind="stable")
+    rs = r[order]
+    seg = np.searchsorted(rs, np.arange(n_rel + 1), side="left")
+    counts = np.bincount(r, minlength=n_rel)
+    n_chunks = (counts + CHUNK - 1) // CHUNK
+    chunk_ptr = np.concatenate([[0], np.cumsum(n_chunks)])
+    chunks = np.array([(v, seg[v] + CHUNK * j) for v in range(n_rel) for j in range(n_chunks[v])], np.int64).reshape(-1, 2)
+    ids = np.stack([h, pos_t, neg_t], 1).reshape(-1)
+    row_order = np.argsort(ids, kind="stable")
+    sorted_ids = ids[row_order]
+    inv_pos = np.empty_like(row_order)
+    inv_pos[row_order] = np.arange(len(ids))
+    starts = np.flatnonzero(np.concatenate([[True], sorted_ids[1:] != sorted_ids[:-1]]))
+    run_len = np.zeros(len(ids), np.int64)
+    run_len[starts] = np.diff(np.append(starts, len(ids)))
+    return types.SimpleNamespace(order=order, seg=seg, chunk_ptr=chunk_ptr, chunks=chunks, sorted_ids=sorted_ids,
+                                 row_order=row_order, inv_pos=inv_pos, run_len=run_len)
