@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kAttThreads) void att_score_mfma_kernel(
         for (int j = 0; j < 4; ++j)
           part[j] = fmaf(accT[t][c][j], att_tanh<ACC_TANH>(accH[t][c][j] + relv[c]), part[j]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) part[j] = row16_sum(part[j]);
+      for (int j = 0; j < 4; ++j) part[j] = lanes_sum<16>(part[j]);
       // lanes i = 0..3 of slot q write edges 4*q + i
       const float v = i == 0 ? part[0] : (i == 1 ? part[1] : (i == 2 ? part[2] : part[3]));
       const int32_t pe = t0 + t * 16 + 4 * q + i;
@@ -282,11 +282,7 @@ __global__ __launch_bounds__(256) void att_fold_head_small_kernel(
   const int32_t g_end = (int32_t)((int64_t)n_groups * (blockIdx.x + 1) / gridDim.x);
   int32_t g0 = g_begin;
   while (g0 < g_end) {  // workgroup-uniform loop over relation segments
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (gptr[mid] <= g0) lo = mid; else hi = mid;
-    }
+    int lo = segment_of(gptr, n_rel, g0);
     // (empty relations share their gptr value with the next one: take the last of them)
     while (lo + 1 < n_rel && gptr[lo + 1] <= g0) ++lo;
     const int r = lo;
@@ -340,11 +336,7 @@ __global__ __launch_bounds__(256) void att_fold_head_small_dk_kernel(
   const int32_t g_end = (int32_t)((int64_t)n_groups * (blockIdx.x + 1) / gridDim.x);
   int32_t g0 = g_begin;
   while (g0 < g_end) {  // workgroup-uniform loop over relation segments
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (gptr[mid] <= g0) lo = mid; else hi = mid;
-    }
+    int lo = segment_of(gptr, n_rel, g0);
     while (lo + 1 < n_rel && gptr[lo + 1] <= g0) ++lo;
     const int r = lo;
     const int32_t seg_end = gptr[r + 1] < g_end ? gptr[r + 1] : g_end;

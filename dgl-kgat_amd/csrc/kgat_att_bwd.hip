@@ -74,15 +74,7 @@ __global__ __launch_bounds__(256) void att_bwd_dense_kernel(int n_rel, const int
   const int32_t t0 = (int32_t)blockIdx.x * tpw;
   const int32_t t1 = t0 + tpw < n_tiles ? t0 + tpw : n_tiles;
   if (t0 >= t1) return;
-  int r;
-  {
-    int lo = 0, hi = n_rel;  // the relation of tile t0: last r with bptr[r] <= t0
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (bptr[mid] <= t0) lo = mid; else hi = mid;
-    }
-    r = lo;
-  }
+  int r = segment_of(bptr, n_rel, t0);  // the relation of tile t0
   int r_held = -1;
   floatx4_b acc[TPW];
   float rsum = 0.f;

@@ -46,14 +46,30 @@ __device__ __forceinline__ float att_tanh_scaled(float y) {
 }
 constexpr float kTwoLog2e = 2.8853900817779268f;
 
-// Sum over the 16 lanes of a DPP row (= one slot q of the MFMA layout); every lane gets the
-// total.  Four v_add_f32 with DPP operands, no LDS round trip.
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true));  // row_mirror
+// Sum over aligned groups of LANES lanes inside a DPP row; every lane gets its group's total.  log2(LANES)
+// v_add_f32 with DPP operands, no LDS round trip.  lanes_sum<16> is the sum over one slot q of the MFMA layout.
+template <int LANES>
+__device__ __forceinline__ float lanes_sum(float v) {
+  static_assert(LANES == 2 || LANES == 4 || LANES == 8 || LANES == 16, "a power-of-two part of a 16-lane row");
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));                   // quad_perm [1,0,3,2]
+  if (LANES >= 4) v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
+  if (LANES >= 8) v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
+  if (LANES >= 16) v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true)); // row_mirror
   return v;
+}
+
+// One node row as an MFMA fragment: lane group q takes floats 16m + 4q .. + 3 of row `row`, m = 0 .. D_/16 - 1, into
+// a[4m .. 4m + 3].  32-bit byte offsets from the table base (the launchers guarantee N * d * 4 < 4 GiB): one scalar
+// base + one VGPR offset per row instead of 64-bit address arithmetic per load.
+template <int D_>
+__device__ __forceinline__ void att_load_row_frag(float (&a)[D_ / 4], const float* __restrict__ ent, int32_t row, int q) {
+  const char* base = reinterpret_cast<const char*>(ent);
+  const uint32_t o = (uint32_t)row * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
+#pragma unroll
+  for (int m = 0; m < D_ / 16; ++m) {
+    const float4 v = *reinterpret_cast<const float4*>(base + o + m * 64);
+    a[4 * m + 0] = v.x; a[4 * m + 1] = v.y; a[4 * m + 2] = v.z; a[4 * m + 3] = v.w;
+  }
 }
 
 template <int D_, int TILES>

@@ -1,11 +1,17 @@
-// Persistent-wavefront attention-logit kernels (d == k <= 64): the one-kernel form
-// (att_score_persistent_kernel) and the split form (att_split_kernel, MODE_HEAD / MODE_TAIL);
-// overview in kgat_att.hip, measurements and the cost model in DESIGN.md 3.2 / NOTEBOOK.md 3.2.
+// Persistent attention-logit kernels (d == k): every wavefront or workgroup walks a contiguous range of tiles.
+//   att_score_persistent_kernel   one-kernel form, d <= 64: W_r in registers, 16-edge tiles
+//   att_split_kernel              split form, d <= 64: MODE_HEAD writes the G table per head group, MODE_TAIL the logits
+//   att_fold_head_kernel          folded form, d <= 64: V rows per head group (the per-edge dot is in kgat_att.hip)
+//   att_fold_head_lds_kernel      the same at d = 128: W_r in LDS, fp32 or three-bf16-piece products
+//   att_fold_fused_kernel         fused folded form, d <= 64: V rows stay in LDS, the wave walks the tile's positions
+//   att_fold_fused128_kernel      the same at d = 128: two fp16 pieces per operand
+// with the piece cuts of the bf16 / fp16 products between them; the tile walk they share is in kgat_att_tiles.h.
+// Overview in kgat_att.hip, measurements and the cost model in DESIGN.md 3.2 / NOTEBOOK.md 3.2.
 // Separate translation unit because it is built with -mllvm -amdgpu-mfma-vgpr-form=1 (MFMA
 // results in VGPRs, no v_accvgpr_read copies in the epilogue), which the LDS-staged chunk
 // kernels of kgat_att.hip do not want (it costs them occupancy).
 
-#include "kgat_att_common.h"
+#include "kgat_att_tiles.h"
 
 namespace kgat {
 
@@ -17,7 +23,7 @@ namespace kgat {
 // tiles ahead.  No LDS traffic and no barrier inside the tile loop; W_r is re-read from L2 only
 // when a wave's range crosses into the next relation.
 
-template <int D_, int ACC_TANH>
+template <int D_>
 __global__ __launch_bounds__(kAttThreads) void att_score_persistent_kernel(
     int n_rel, int64_t n_edges, const int32_t* __restrict__ rel_ptr, const int32_t* __restrict__ perm,
     const int32_t* __restrict__ src_g, const int32_t* __restrict__ dst_g,
@@ -27,59 +33,24 @@ __global__ __launch_bounds__(kAttThreads) void att_score_persistent_kernel(
   constexpr int K_ = D_;
   constexpr int KS = D_ / 4, KT = K_ / 16;
   __shared__ int32_t s_tptr[kAttMaxRelLds + 1];  // tile prefix per relation
-  const int tid = threadIdx.x;
-  for (int r = tid; r < n_rel; r += kAttThreads)
-    s_tptr[r + 1] = (rel_ptr[r + 1] - rel_ptr[r] + 15) >> 4;
-  __syncthreads();
-  if (tid == 0) {
-    int32_t run = 0;
-    s_tptr[0] = 0;
-    for (int r = 0; r < n_rel; ++r) {
-      run += s_tptr[r + 1];
-      s_tptr[r + 1] = run;
-    }
-  }
-  __syncthreads();
-  const int32_t n_tiles = s_tptr[n_rel];
-  const int lane = tid % kWave;
+  const int32_t n_tiles = att_tile_prefix<kAttThreads>(s_tptr, rel_ptr, n_rel, 4);
+  const int lane = threadIdx.x % kWave;
   const int i = lane & 15, q = lane >> 4;
   const int32_t* __restrict__ pos_or_perm = logits_csr ? pos_g : perm;
-  const int64_t n_waves = (int64_t)gridDim.x * (kAttThreads / kWave);
-  const int64_t wv = (int64_t)blockIdx.x * (kAttThreads / kWave) + tid / kWave;
-  const int32_t t_begin = (int32_t)((int64_t)n_tiles * wv / n_waves);
-  const int32_t t_end = (int32_t)((int64_t)n_tiles * (wv + 1) / n_waves);
-
-  // Edges whose type is outside [0, R) sit after rel_ptr[R] in perm: logit 0 (DGL's
-  // zero-initialised column); each wave clears its slice of that tail.
-  {
-    const int64_t tail0 = rel_ptr[n_rel];
-    const int64_t n_tail = n_edges - tail0;
-    for (int64_t p = tail0 + n_tail * wv / n_waves + lane; p < tail0 + n_tail * (wv + 1) / n_waves; p += kWave) {
-      logits[perm[p]] = 0.f;
-      if (logits_csr) logits_csr[pos_g[p]] = 0.f;
-    }
-  }
+  const AttWaveShare ws = att_wave_share<kAttThreads>();
+  const int32_t t_begin = (int32_t)ws.begin(n_tiles), t_end = (int32_t)ws.end(n_tiles);
+  att_zero_tail_wave<true>(rel_ptr[n_rel], n_edges, ws, lane, perm, pos_g, logits, logits_csr);
   if (t_begin >= t_end) return;
 
   float wreg[KS][KT];
   float relv[KT];
 
-  // Relation segments of this wave's tile range; all cursor values are wave-uniform scalars.
+  // Relation segments of this wave's tile range
   int32_t t = t_begin;
   while (t < t_end) {
-    int lo = 0, hi = n_rel;  // relation of tile t: largest r with s_tptr[r] <= t
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_tptr[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int r = __builtin_amdgcn_readfirstlane(lo);
-    const int32_t rbeg = __builtin_amdgcn_readfirstlane(rel_ptr[r]);
-    const int32_t rend = __builtin_amdgcn_readfirstlane(rel_ptr[r + 1]);
-    const int32_t tfirst = __builtin_amdgcn_readfirstlane(s_tptr[r]);
-    int32_t seg_end = __builtin_amdgcn_readfirstlane(s_tptr[r + 1]);
-    seg_end = seg_end < t_end ? seg_end : t_end;
-    const int32_t n_seg = seg_end - t;               // tiles of relation r owned by this wave
-    const int32_t pe0 = rbeg + ((t - tfirst) << 4);  // first edge of the first tile
+    const AttWaveCursor cur = att_wave_cursor(s_tptr, rel_ptr, n_rel, t, t_end, 4);
+    const int r = cur.r;
+    const int32_t rend = cur.rend, n_seg = cur.n_seg, pe0 = cur.item0;  // (pe0: first edge of the first tile)
 
     {  // W_r as B fragments: wreg[s][c] = W_r[16*(s>>2) + 4*q + (s&3)][16*c + i]
       const float* W = W_R + (size_t)r * D_ * K_;
@@ -91,8 +62,7 @@ __global__ __launch_bounds__(kAttThreads) void att_score_persistent_kernel(
       }
 #pragma unroll
       for (int c = 0; c < KT; ++c) {
-        relv[c] = rel[(size_t)r * K_ + 16 * c + i];
-        if (!ACC_TANH) relv[c] *= kTwoLog2e;  // tanh argument scale folded into one fma
+        relv[c] = rel[(size_t)r * K_ + 16 * c + i] * kTwoLog2e;  // tanh argument scale folded into one fma
       }
     }
 
@@ -115,8 +85,7 @@ __global__ __launch_bounds__(kAttThreads) void att_score_persistent_kernel(
       x.oe = perm[po];
       x.op = pos_or_perm[po];  // unconditional: a branch around a load makes the counted waits conservative
     };
-    // 32-bit byte offsets from the table base (the launcher guarantees N*d*4 < 4 GiB): one
-    // scalar base + one VGPR offset per row instead of 64-bit address arithmetic per load
+    // (att_load_row_frag for two rows at once: the loads of the tail and the head row alternate)
     auto load_a = [&](AFrag<D_, 1>& f, int32_t rs, int32_t rd) {
       const char* base = reinterpret_cast<const char*>(ent);
       const uint32_t os = (uint32_t)rs * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
@@ -149,12 +118,9 @@ __global__ __launch_bounds__(kAttThreads) void att_score_persistent_kernel(
       for (int cc = 0; cc < KT; ++cc)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          part[j] = fmaf(accT[cc][j],
-                         ACC_TANH ? tanhf(accH[cc][j] + relv[cc])
-                                  : att_tanh_scaled(fmaf(accH[cc][j], kTwoLog2e, relv[cc])),
-                         part[j]);
+          part[j] = fmaf(accT[cc][j], att_tanh_scaled(fmaf(accH[cc][j], kTwoLog2e, relv[cc])), part[j]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) part[j] = row16_sum(part[j]);
+      for (int j = 0; j < 4; ++j) part[j] = lanes_sum<16>(part[j]);
       const float v = i == 0 ? part[0] : (i == 1 ? part[1] : (i == 2 ? part[2] : part[3]));
       const int32_t pe = pe0 + (n << 4) + 4 * q + i;  // lanes i = 0..3 of slot q: edges 4q + i
       if (i < 4 && pe < rend) {
@@ -186,26 +152,21 @@ __global__ __launch_bounds__(kAttThreads) void att_score_persistent_kernel(
       x1 = x0;   // indices of tile n + 3
       x0 = x2;   // indices of tile n + 2
     }
-    t = seg_end;
+    t = cur.seg_end;
   }
 }
 
-template <int D_, int ACC_TANH>
+// The grid of a launch whose wavefronts split the tiles evenly: one resident workgroup per CU slot the kernel's
+// register budget admits, i.e. exactly the wavefronts that run concurrently (4 per workgroup, one per SIMD).
+template <auto Kernel>
+static unsigned att_resident_grid() {
+  return (unsigned)(device_cu_count() * resident_blocks_per_cu<Kernel>(kAttThreads));
+}
+
+template <int D_>
 static int launch_att_persistent(const AttArgs& a) {
-  // one resident workgroup per CU slot the kernel's register budget admits: the tile ranges
-  // are split evenly over exactly the wavefronts that run concurrently
-  static int blocks_per_cu = 0;
-  const int cus = device_cu_count();
-  if (blocks_per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, att_score_persistent_kernel<D_, ACC_TANH>,
-                                                     kAttThreads, 0) != hipSuccess || nb < 1)
-      nb = 1;
-    blocks_per_cu = nb > 8 ? 8 : nb;
-  }
-  const int per_cu = blocks_per_cu;
-  const unsigned grid = (unsigned)(cus * per_cu);  // 4 waves per block, one per SIMD
-  hipLaunchKernelGGL((att_score_persistent_kernel<D_, ACC_TANH>), dim3(grid), dim3(kAttThreads), 0, a.st,
+  hipLaunchKernelGGL((att_score_persistent_kernel<D_>), dim3(att_resident_grid<att_score_persistent_kernel<D_>>()),
+                     dim3(kAttThreads), 0, a.st,
                      a.n_rel, a.n_edges, a.rel_ptr, a.perm, a.src_g, a.dst_g, a.ent, a.W_R, a.rel, a.logits,
                      a.logits_csr, a.pos_g);
   KGAT_CHECK_LAUNCH("att_score_persistent");
@@ -233,55 +194,23 @@ __global__ __launch_bounds__(kAttThreads) void att_split_kernel(
   constexpr int K_ = D_;
   constexpr int KS = D_ / 4, KT = K_ / 16;
   __shared__ int32_t s_tptr[kAttMaxRelLds + 1];  // tile prefix per relation
-  const int tid = threadIdx.x;
-  for (int r = tid; r < n_rel; r += kAttThreads)
-    s_tptr[r + 1] = (seg_ptr[r + 1] - seg_ptr[r] + 15) >> 4;
-  __syncthreads();
-  if (tid == 0) {
-    int32_t run = 0;
-    s_tptr[0] = 0;
-    for (int r = 0; r < n_rel; ++r) {
-      run += s_tptr[r + 1];
-      s_tptr[r + 1] = run;
-    }
-  }
-  __syncthreads();
-  const int32_t n_tiles = s_tptr[n_rel];
-  const int lane = tid % kWave;
+  const int32_t n_tiles = att_tile_prefix<kAttThreads>(s_tptr, seg_ptr, n_rel, 4);
+  const int lane = threadIdx.x % kWave;
   const int i = lane & 15, q = lane >> 4;
   const int32_t* __restrict__ pos_or_perm = logits_csr ? pos_g : perm;
-  const int64_t n_waves = (int64_t)gridDim.x * (kAttThreads / kWave);
-  const int64_t wv = (int64_t)blockIdx.x * (kAttThreads / kWave) + tid / kWave;
-  const int32_t t_begin = (int32_t)((int64_t)n_tiles * wv / n_waves);
-  const int32_t t_end = (int32_t)((int64_t)n_tiles * (wv + 1) / n_waves);
-
-  if (MODE == MODE_TAIL) {  // unscored tail of the edge list: logit 0
-    const int64_t tail0 = seg_ptr[n_rel];
-    const int64_t n_tail = n_edges - tail0;
-    for (int64_t p = tail0 + n_tail * wv / n_waves + lane; p < tail0 + n_tail * (wv + 1) / n_waves; p += kWave) {
-      if (LOGITS_EID) logits[perm[p]] = 0.f;
-      if (logits_csr) logits_csr[pos_g[p]] = 0.f;
-    }
-  }
+  const AttWaveShare ws = att_wave_share<kAttThreads>();
+  const int32_t t_begin = (int32_t)ws.begin(n_tiles), t_end = (int32_t)ws.end(n_tiles);
+  if (MODE == MODE_TAIL)
+    att_zero_tail_wave<LOGITS_EID>(seg_ptr[n_rel], n_edges, ws, lane, perm, pos_g, logits, logits_csr);
   if (t_begin >= t_end) return;
 
   float wreg[KS][KT];
   float relv[KT];
   int32_t t = t_begin;
   while (t < t_end) {
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_tptr[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int r = __builtin_amdgcn_readfirstlane(lo);
-    const int32_t rbeg = __builtin_amdgcn_readfirstlane(seg_ptr[r]);
-    const int32_t rend = __builtin_amdgcn_readfirstlane(seg_ptr[r + 1]);
-    const int32_t tfirst = __builtin_amdgcn_readfirstlane(s_tptr[r]);
-    int32_t seg_end = __builtin_amdgcn_readfirstlane(s_tptr[r + 1]);
-    seg_end = seg_end < t_end ? seg_end : t_end;
-    const int32_t n_seg = seg_end - t;
-    const int32_t pe0 = rbeg + ((t - tfirst) << 4);
+    const AttWaveCursor cur = att_wave_cursor(s_tptr, seg_ptr, n_rel, t, t_end, 4);
+    const int r = cur.r;
+    const int32_t rend = cur.rend, n_seg = cur.n_seg, pe0 = cur.item0;
     {
       const float* W = W_R + (size_t)r * D_ * K_;
 #pragma unroll
@@ -328,13 +257,7 @@ __global__ __launch_bounds__(kAttThreads) void att_split_kernel(
     };
     struct Buf { float a[KS]; float g[KT][4]; };
     auto load_rows = [&](Buf& f, const LIdx& x) {
-      const char* base = reinterpret_cast<const char*>(ent);
-      const uint32_t o = (uint32_t)x.row * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
-#pragma unroll
-      for (int m = 0; m < D_ / 16; ++m) {
-        const float4 v = *reinterpret_cast<const float4*>(base + o + m * 64);
-        f.a[4 * m + 0] = v.x; f.a[4 * m + 1] = v.y; f.a[4 * m + 2] = v.z; f.a[4 * m + 3] = v.w;
-      }
+      att_load_row_frag<D_>(f.a, ent, x.row, q);
       if (MODE == MODE_TAIL) {  // the KT values of column slot i of group g sit together: one load per edge
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -370,7 +293,7 @@ __global__ __launch_bounds__(kAttThreads) void att_split_kernel(
 #pragma unroll
           for (int j = 0; j < 4; ++j) part[j] = fmaf(acc[cc][j], f.g[cc][j], part[j]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) part[j] = row16_sum(part[j]);
+        for (int j = 0; j < 4; ++j) part[j] = lanes_sum<16>(part[j]);
         const float v = i == 0 ? part[0] : (i == 1 ? part[1] : (i == 2 ? part[2] : part[3]));
         if (i < 4 && item0 + i < rend) {
           if (LOGITS_EID) logits[x.oe] = v;
@@ -417,24 +340,16 @@ __global__ __launch_bounds__(kAttThreads) void att_split_kernel(
       KGAT_SPLIT_STEP(b2, b1)
     }
 #undef KGAT_SPLIT_STEP
-    t = seg_end;
+    t = cur.seg_end;
   }
 }
 
 template <int D_, int MODE, bool LOGITS_EID>
 static int launch_att_split(const AttArgs& a, const int32_t* seg_ptr, const int32_t* row_idx) {
-  static int blocks_per_cu = 0;
-  const int cus = device_cu_count();
-  if (blocks_per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, att_split_kernel<D_, MODE, LOGITS_EID>, kAttThreads,
-                                                     0) != hipSuccess || nb < 1)
-      nb = 1;
-    blocks_per_cu = nb > 8 ? 8 : nb;
-  }
-  hipLaunchKernelGGL((att_split_kernel<D_, MODE, LOGITS_EID>), dim3((unsigned)(cus * blocks_per_cu)),
-                     dim3(kAttThreads), 0, a.st, a.n_rel, a.n_edges, seg_ptr, row_idx, a.gid, a.perm, a.pos_g,
-                     a.ent, a.W_R, a.rel, a.G_tab, a.logits, a.logits_csr);
+  hipLaunchKernelGGL((att_split_kernel<D_, MODE, LOGITS_EID>),
+                     dim3(att_resident_grid<att_split_kernel<D_, MODE, LOGITS_EID>>()), dim3(kAttThreads), 0, a.st,
+                     a.n_rel, a.n_edges, seg_ptr, row_idx, a.gid, a.perm, a.pos_g, a.ent, a.W_R, a.rel, a.G_tab, a.logits,
+                     a.logits_csr);
   KGAT_CHECK_LAUNCH("att_split");
   return KGAT_OK;
 }
@@ -469,25 +384,11 @@ __global__ __launch_bounds__(kAttThreads) void att_fold_head_kernel(
   constexpr int K_ = D_;
   constexpr int KS = D_ / 4, KT = K_ / 16;
   __shared__ int32_t s_tptr[kAttMaxRelLds + 1];  // tile prefix per relation
-  const int tid = threadIdx.x;
-  for (int r = tid; r < n_rel; r += kAttThreads) s_tptr[r + 1] = (gptr[r + 1] - gptr[r] + 15) >> 4;
-  __syncthreads();
-  if (tid == 0) {
-    int32_t run = 0;
-    s_tptr[0] = 0;
-    for (int r = 0; r < n_rel; ++r) {
-      run += s_tptr[r + 1];
-      s_tptr[r + 1] = run;
-    }
-  }
-  __syncthreads();
-  const int32_t n_tiles = s_tptr[n_rel];
-  const int lane = tid % kWave;
+  const int32_t n_tiles = att_tile_prefix<kAttThreads>(s_tptr, gptr, n_rel, 4);
+  const int lane = threadIdx.x % kWave;
   const int i = lane & 15, q = lane >> 4;
-  const int64_t n_waves = (int64_t)gridDim.x * (kAttThreads / kWave);
-  const int64_t wv = (int64_t)blockIdx.x * (kAttThreads / kWave) + tid / kWave;
-  const int32_t t_begin = (int32_t)((int64_t)n_tiles * wv / n_waves);
-  const int32_t t_end = (int32_t)((int64_t)n_tiles * (wv + 1) / n_waves);
+  const AttWaveShare ws = att_wave_share<kAttThreads>();
+  const int32_t t_begin = (int32_t)ws.begin(n_tiles), t_end = (int32_t)ws.end(n_tiles);
   if (t_begin >= t_end) return;
 
   float w1[KS][KT];      // W_r[krow(s, q)][16c + i]        (first product, as in the other kernels)
@@ -495,19 +396,9 @@ __global__ __launch_bounds__(kAttThreads) void att_fold_head_kernel(
   float relv[KT][4];     // e_r[16c + 4q + j] * 2 log2(e)
   int32_t t = t_begin;
   while (t < t_end) {
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_tptr[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int r = __builtin_amdgcn_readfirstlane(lo);
-    const int32_t rbeg = __builtin_amdgcn_readfirstlane(gptr[r]);
-    const int32_t rend = __builtin_amdgcn_readfirstlane(gptr[r + 1]);
-    const int32_t tfirst = __builtin_amdgcn_readfirstlane(s_tptr[r]);
-    int32_t seg_end = __builtin_amdgcn_readfirstlane(s_tptr[r + 1]);
-    seg_end = seg_end < t_end ? seg_end : t_end;
-    const int32_t n_seg = seg_end - t;
-    const int32_t g0 = rbeg + ((t - tfirst) << 4);
+    const AttWaveCursor cur = att_wave_cursor(s_tptr, gptr, n_rel, t, t_end, 4);
+    const int r = cur.r;
+    const int32_t rend = cur.rend, n_seg = cur.n_seg, g0 = cur.item0;
     {
       const float* W = W_R + (size_t)r * D_ * K_;
 #pragma unroll
@@ -538,15 +429,7 @@ __global__ __launch_bounds__(kAttThreads) void att_fold_head_kernel(
       return g_node[g];
     };
     struct Buf { float a[KS]; };
-    auto load_rows = [&](Buf& f, int32_t row) {
-      const char* base = reinterpret_cast<const char*>(ent);
-      const uint32_t o = (uint32_t)row * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
-#pragma unroll
-      for (int m = 0; m < D_ / 16; ++m) {
-        const float4 v = *reinterpret_cast<const float4*>(base + o + m * 64);
-        f.a[4 * m + 0] = v.x; f.a[4 * m + 1] = v.y; f.a[4 * m + 2] = v.z; f.a[4 * m + 3] = v.w;
-      }
-    };
+    auto load_rows = [&](Buf& f, int32_t row) { att_load_row_frag<D_>(f.a, ent, row, q); };
     auto tile = [&](int32_t n, const Buf& f) {
       floatx4 acc[KT];
 #pragma unroll
@@ -611,23 +494,14 @@ __global__ __launch_bounds__(kAttThreads) void att_fold_head_kernel(
       KGAT_FOLD_STEP(b2, b1)
     }
 #undef KGAT_FOLD_STEP
-    t = seg_end;
+    t = cur.seg_end;
   }
 }
 
 template <int D_>
 static int launch_att_fold_head(const AttArgs& a) {
-  static int blocks_per_cu = 0;
-  const int cus = device_cu_count();
-  if (blocks_per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, att_fold_head_kernel<D_>, kAttThreads, 0) != hipSuccess ||
-        nb < 1)
-      nb = 1;
-    blocks_per_cu = nb > 8 ? 8 : nb;
-  }
-  hipLaunchKernelGGL((att_fold_head_kernel<D_>), dim3((unsigned)(cus * blocks_per_cu)), dim3(kAttThreads), 0, a.st,
-                     a.n_rel, a.gptr, a.g_node, a.ent, a.W_R, a.rel, a.G_tab);
+  hipLaunchKernelGGL((att_fold_head_kernel<D_>), dim3(att_resident_grid<att_fold_head_kernel<D_>>()), dim3(kAttThreads),
+                     0, a.st, a.n_rel, a.gptr, a.g_node, a.ent, a.W_R, a.rel, a.G_tab);
   KGAT_CHECK_LAUNCH("att_fold_head");
   return KGAT_OK;
 }
@@ -682,12 +556,11 @@ __device__ __forceinline__ floatx4 mfma_bf16(const uintx4& a, const uintx4& b, c
                                                  0);
 }
 
-// fp16 pieces for the second product of the d <= 64 fused kernel (kAttF16Second, default 1 since round 4;
-// built and measured in round 3: W_r * 2^shift as three fp16 pieces, the tanh values * 2^14 as two, five piece
-// products).  Measured on the amazon-book graph, d = 64: stand-alone 0.1555 vs 0.1614 ms, inside the step 137.3 vs
-// 140.6 us; against fp64 max error 9.98e-7 / mean 1.09e-7 (three-bf16-piece form: 9.4e-7 / 1.23e-7; fp32 MFMA:
-// 1.48e-6 / 1.43e-7), every GPU test unchanged (tests/test_gpu_parity.py::test_att_fused_product_forms, incl. the
-// "small T" case that the 2^14 scale exists for).
+// fp16 pieces for the second product of the d <= 64 fused kernel's piece form (since round 4): W_r * 2^shift as
+// three fp16 pieces, the tanh values * 2^14 as two, five piece products.  Against three bf16 pieces on both
+// products, d = 64 on the amazon-book graph: 137.3 vs 140.6 us inside the step (-3.3 us) at equal error against fp64
+// (max 9.98e-7 vs 9.4e-7; fp32 MFMA 1.48e-6); tests/test_gpu_parity.py::test_att_fused_product_forms holds it, incl.
+// the "small T" case that the 2^14 scale exists for.  The bf16 second product went with that decision.
 // A value inside fp16's range is h + m + l with three round-to-nearest fp16 pieces EXACTLY (3 x 11 significand
 // bits), and h + m with a residual <= 2^-22 |x|.  What the format buys is the cut: the remainder x - float(h) is
 // ONE v_fma_mix_f32 per value (f16 operand taken straight from either half of the packed register), so a pair
@@ -792,42 +665,18 @@ __global__ __launch_bounds__(kFoldLdsThreads) void att_fold_head_lds_kernel(
   __shared__ __attribute__((aligned(16))) unsigned char s_img[X3 ? 3 * IMG : 16];
   __shared__ __attribute__((aligned(16))) float s_rel[K_];
   const int tid = threadIdx.x;
-  for (int r = tid; r < n_rel; r += kFoldLdsThreads) s_tptr[r + 1] = (gptr[r + 1] - gptr[r] + 15) >> 4;
-  __syncthreads();
-  if (tid == 0) {
-    int32_t run = 0;
-    s_tptr[0] = 0;
-    for (int r = 0; r < n_rel; ++r) {
-      run += s_tptr[r + 1];
-      s_tptr[r + 1] = run;
-    }
-  }
-  __syncthreads();
-  const int32_t n_tiles = s_tptr[n_rel];
+  const int32_t n_tiles = att_tile_prefix<kFoldLdsThreads>(s_tptr, gptr, n_rel, 4);
   const int lane = tid % kWave, w = tid / kWave;
   const int i = lane & 15, q = lane >> 4;
   const int32_t t_begin = (int32_t)((int64_t)n_tiles * blockIdx.x / gridDim.x);
   const int32_t t_end = (int32_t)((int64_t)n_tiles * (blockIdx.x + 1) / gridDim.x);
 
   struct Buf { float a[KS]; };
-  auto load_rows = [&](Buf& f, int32_t row) {
-    const char* base = reinterpret_cast<const char*>(ent);
-    const uint32_t o = (uint32_t)row * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
-#pragma unroll
-    for (int m = 0; m < D_ / 16; ++m) {
-      const float4 v = *reinterpret_cast<const float4*>(base + o + m * 64);
-      f.a[4 * m + 0] = v.x; f.a[4 * m + 1] = v.y; f.a[4 * m + 2] = v.z; f.a[4 * m + 3] = v.w;
-    }
-  };
+  auto load_rows = [&](Buf& f, int32_t row) { att_load_row_frag<D_>(f.a, ent, row, q); };
 
   int32_t t = t_begin;
   while (t < t_end) {  // workgroup-uniform loop over relation segments
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_tptr[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int r = lo;
+    const int r = segment_of(s_tptr, n_rel, t);
     const int32_t rbeg = gptr[r], rend = gptr[r + 1];
     const int32_t tfirst = s_tptr[r];
     int32_t seg_end = s_tptr[r + 1];
@@ -842,7 +691,7 @@ __global__ __launch_bounds__(kFoldLdsThreads) void att_fold_head_lds_kernel(
         const float x[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
         uintx4 h, m, l;
         split_bf16x3(x, h, m, l);
-        const int off = ROWB * row + 16 * (ch ^ (((row & 7) << 1) | ((row >> 3) & 1)));
+        const int off = att_img_offset(ROWB, row, ch);
         *reinterpret_cast<uintx4*>(s_img + off) = h;
         *reinterpret_cast<uintx4*>(s_img + IMG + off) = m;
         *reinterpret_cast<uintx4*>(s_img + 2 * IMG + off) = l;
@@ -1052,13 +901,10 @@ static int launch_att_fold_head_lds(const AttArgs& a) {
 // with their indices requested one chunk ahead; their tail rows are not (the row buffer is 64
 // registers), so tiles are capped and hub groups recompute V per `cap` positions instead.
 constexpr int kFusedThreads = 512;
-// kAttXcdRemap: every XCD a contiguous eighth of the workgroups' tile ranges (xcd_contiguous, kgat_common.h)
-// - neighbouring ranges, which share head nodes and relation tables, behind one L2.  Stand-alone within the noise at
-// d = 64 (0.172 vs 0.176 ms, round 3); in the step 0.4116 -> 0.4098 and 0.4121 -> 0.4107 ms on two boxes
-// (profiles/r04_step_ab_cache_policy.txt): default since round 4 for d <= 64.  2 % slower at d = 128
-// (kAtt128XcdRemap, off).
-constexpr int kAttXcdRemap = 1;
-constexpr int kAtt128XcdRemap = 0;
+// At d <= 64 every XCD takes a contiguous eighth of the workgroups' tile ranges (the PART of its prologue;
+// xcd_contiguous, kgat_common.h): neighbouring ranges, which share head nodes and relation tables, sit behind one
+// L2.  In the step 0.4116 -> 0.4098 ms (round 4, profiles/r04_step_ab_cache_policy.txt); 2 % slower at d = 128,
+// which keeps the block index.
 // (Round 4 also measured the packed position records - 4 bytes per edge, read once per step - and the head-group
 // node ids as non-temporal loads: with round-robin tile ranges the records gained 2.5 us per step (0.4178 -> 0.4153 ms),
 // with the XCD-contiguous ranges above they LOSE 1.2-1.6 us (0.4108 vs 0.4096, 0.4121 vs 0.4105:
@@ -1096,44 +942,23 @@ __global__ __launch_bounds__(kFusedThreads) void att_fold_fused_kernel(
   __shared__ uintx4 s_a[X3 ? 2 * 3 * NFRAG : 1];
   __shared__ __attribute__((aligned(16))) float s_v[NW][16 * LDV];
   __shared__ int32_t s_next;  // next unclaimed tile of the current relation segment
-constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step at equal error; 0: three bf16 pieces on both products)
-  constexpr bool F16B = X3 && kAttF16Second != 0;  // second product on fp16 pieces: W_r three, tanh values two
-  __shared__ unsigned s_wmax;                             // F16B: bits of max |W_r| of the current relation
+  __shared__ unsigned s_wmax;  // X3: bits of max |W_r| of the current relation (the second product's fp16 scale)
   const int tid = threadIdx.x;
   const int lane = tid % kWave, w = tid / kWave;
   const int i = lane & 15, q = lane >> 4;
   const int li = lane % LPE;
 
-  {  // relation ids outside [0, R): logit 0
-    const int64_t n_scored = rel_ptr[n_rel];
-    for (int64_t p = n_scored + (int64_t)blockIdx.x * kFusedThreads + tid; p < n_edges;
-         p += (int64_t)gridDim.x * kFusedThreads) {
-      if (LOGITS_EID) logits[perm[p]] = 0.f;
-      if (OUT >= 1 && logits_csr) logits_csr[pos_g[p]] = 0.f;
-      if (logits_g) logits_g[p] = 0.f;
-    }
-  }
-  const int32_t n_tiles = rel_tptr[n_rel];
-  // the workgroup's contiguous tile range: cost balanced (kgat_fold_tile_parts) or equal counts
-  const unsigned part = kAttXcdRemap ? xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int32_t t_begin = part_tptr ? part_tptr[part] : (int32_t)((int64_t)n_tiles * part / gridDim.x);
-  const int32_t t_end = part_tptr ? part_tptr[part + 1] : (int32_t)((int64_t)n_tiles * (part + 1) / gridDim.x);
+  KGAT_ATT_FUSED_PROLOGUE(kFusedThreads, xcd_contiguous(blockIdx.x, gridDim.x))
   float* vrow = s_v[w];
-  // measurement aid (kgat_att_score_fused_timed_f32): when this workgroup started and ended, in 100 MHz ticks
-  if (clocks && tid == 0) clocks[2 * part] = (long long)__builtin_amdgcn_s_memrealtime();
+  KGAT_ATT_FUSED_STAMP_START
 
   int32_t t = t_begin;
   while (t < t_end) {  // workgroup-uniform loop over relation segments
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (rel_tptr[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int r = lo;
+    const int r = segment_of(rel_tptr, n_rel, t);
     const int32_t rend = gptr[r + 1];
     int32_t seg_end = rel_tptr[r + 1];
     seg_end = seg_end < t_end ? seg_end : t_end;
-    if (F16B && tid == 0) s_wmax = 0u;  // (every wave has read the previous segment's value by now)
+    if (X3 && tid == 0) s_wmax = 0u;  // (every wave has read the previous segment's value by now)
     __syncthreads();  // every wave is done with the previous relation's W_r
     if (tid == 0) s_next = t;
     if (X3) {
@@ -1153,20 +978,16 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
           x[jj] = W[(16 * (2 * fs + (jj >> 2)) + 4 * fq + (jj & 3)) * K_ + 16 * fc + fi];
         split_bf16x3(x, h, m, l);
         s_a[0 * NFRAG + f] = h; s_a[1 * NFRAG + f] = m; s_a[2 * NFRAG + f] = l;
-        // second product, V^T = W T: A[row 16c2 + i][kk] = W[16c2 + i][kk]
+        // second product, V^T = W T: A[row 16c2 + i][kk] = W[16c2 + i][kk].  Its fp16 images need the relation's
+        // scale first: the maximum here, the images in a second pass below
         const float4 w0 = *reinterpret_cast<const float4*>(W + (16 * fc + fi) * K_ + 32 * fs + 4 * fq);
         const float4 w1 = *reinterpret_cast<const float4*>(W + (16 * fc + fi) * K_ + 32 * fs + 16 + 4 * fq);
         x[0] = w0.x; x[1] = w0.y; x[2] = w0.z; x[3] = w0.w;
         x[4] = w1.x; x[5] = w1.y; x[6] = w1.z; x[7] = w1.w;
-        if (F16B) {  // the fp16 images need the relation's scale first: second pass below
-          float mx = 0.f;
+        float mx = 0.f;
 #pragma unroll
-          for (int jj = 0; jj < 8; ++jj) mx = fmaxf(mx, fabsf(x[jj]));
-          atomicMax(&s_wmax, __float_as_uint(mx));
-        } else {
-          split_bf16x3(x, h, m, l);
-          s_a[3 * NFRAG + f] = h; s_a[4 * NFRAG + f] = m; s_a[5 * NFRAG + f] = l;
-        }
+        for (int jj = 0; jj < 8; ++jj) mx = fmaxf(mx, fabsf(x[jj]));
+        atomicMax(&s_wmax, __float_as_uint(mx));
       }
     } else {
       const float* W = W_R + (size_t)r * D_ * K_;
@@ -1176,8 +997,8 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
       }
     }
     __syncthreads();
-    int w_shift = 0;  // F16B: the second product runs on W_r * 2^w_shift; the logits are scaled back
-    if (F16B) {
+    int w_shift = 0;  // X3: the second product runs on W_r * 2^w_shift; the logits are scaled back
+    if (X3) {
       w_shift = __builtin_amdgcn_readfirstlane(f16_block_shift(s_wmax));
       const float* W = W_R + (size_t)r * D_ * K_;
       for (int f = tid; f < NFRAG; f += kFusedThreads) {
@@ -1207,35 +1028,13 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
       n = n < seg_end ? n : seg_end - 1;
       return tiles[n];
     };
-    struct CIdx { int32_t row_off, lg, oe, op; };
-    auto head_idx = [&](const int4& d) -> int32_t {
-      int32_t g = d.y + i;
-      g = g < rend ? g : rend - 1;
-      return g_node[g];
-    };
+    using CIdx = AttChunkIdx;
+    auto head_idx = [&](const int4& d) -> int32_t { return att_head_idx(d, i, rend, g_node); };
     auto chunk_idx = [&](const int4& d, int32_t p0) -> CIdx {
-      int32_t p = p0 + lane;
-      p = p < d.w ? p : d.w - 1;
-      CIdx c;
-      const uint32_t rec = (uint32_t)rec_g[p];
-      // byte offset of the source row: N * d * 4 < 4 GiB (checked by the caller), so the node id ends
-      // below bit 32 - ROW_SHIFT and the shift drops exactly the slot bits
-      c.row_off = (int32_t)(rec << ROW_SHIFT);
-      c.lg = (int32_t)(rec >> 28);
-      c.oe = LOGITS_EID ? perm[p] : 0;
-      c.op = (OUT >= 1 && logits_csr) ? pos_g[p] : 0;
-      return c;
+      return att_chunk_idx<ROW_SHIFT, OUT>(d, p0, lane, rec_g, perm, pos_g, logits_csr);
     };
     struct HBuf { float a[KS]; };
-    auto load_head = [&](HBuf& f, int32_t row) {
-      const char* base = reinterpret_cast<const char*>(ent);
-      const uint32_t o = (uint32_t)row * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
-#pragma unroll
-      for (int m = 0; m < D_ / 16; ++m) {
-        const float4 v = *reinterpret_cast<const float4*>(base + o + m * 64);
-        f.a[4 * m + 0] = v.x; f.a[4 * m + 1] = v.y; f.a[4 * m + 2] = v.z; f.a[4 * m + 3] = v.w;
-      }
-    };
+    auto load_head = [&](HBuf& f, int32_t row) { att_load_row_frag<D_>(f.a, ent, row, q); };
     struct EBuf { float4 r[LPE][VPL]; };
     const char* eb = reinterpret_cast<const char*>(ent) + li * 16;
     auto load_edges = [&](EBuf& e, const CIdx& c) {
@@ -1289,47 +1088,31 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
       for (int c = 0; c < KT; ++c)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          // F16B: the tanh values leave as T * 2^14 (the same rounding, scaled: a power of two), so that the low
+          // X3: the tanh values leave as T * 2^14 (the same rounding, scaled: a power of two), so that the low
           // piece of a small |T| is still a normal fp16 number (unscaled, |T| ~ 1e-3 keeps 14 bits, not 22)
           const float y = fmaf(acc[c][j], kTwoLog2e, relv[c][j]);
-          acc[c][j] = F16B ? fmaf(-32768.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(y) + 1.0f), 16384.0f)
-                           : att_tanh_scaled(y);
+          acc[c][j] = X3 ? fmaf(-32768.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(y) + 1.0f), 16384.0f)
+                         : att_tanh_scaled(y);
         }
       if (X3) {
         const uintx4* fa = s_a + 3 * NFRAG + lane;
 #pragma unroll
         for (int s = 0; s < S3; ++s) {
           float x[8];
-          uintx4 bh, bm, bl;
+          uintx4 bh, bm;
 #pragma unroll
           for (int jj = 0; jj < 8; ++jj) x[jj] = acc[2 * s + (jj >> 2)][jj & 3];
-          if (F16B) {
-            split_f16x2(x, bh, bm);  // |tanh| * 2^14 < 16,384: inside fp16's range
+          split_f16x2(x, bh, bm);  // |tanh| * 2^14 < 16,384: inside fp16's range
 #pragma unroll
-            for (int c2 = 0; c2 < KT; ++c2) {  // five piece products, smallest first
-              const uintx4 ah = fa[0 * NFRAG + (c2 * S3 + s) * kWave];
-              const uintx4 am = fa[1 * NFRAG + (c2 * S3 + s) * kWave];
-              const uintx4 al = fa[2 * NFRAG + (c2 * S3 + s) * kWave];
-              v[c2] = mfma_f16(al, bh, v[c2]);
-              v[c2] = mfma_f16(am, bm, v[c2]);
-              v[c2] = mfma_f16(am, bh, v[c2]);
-              v[c2] = mfma_f16(ah, bm, v[c2]);
-              v[c2] = mfma_f16(ah, bh, v[c2]);
-            }
-            continue;
-          }
-          split_bf16x3(x, bh, bm, bl);
-#pragma unroll
-          for (int c2 = 0; c2 < KT; ++c2) {
+          for (int c2 = 0; c2 < KT; ++c2) {  // five piece products, smallest first
             const uintx4 ah = fa[0 * NFRAG + (c2 * S3 + s) * kWave];
             const uintx4 am = fa[1 * NFRAG + (c2 * S3 + s) * kWave];
             const uintx4 al = fa[2 * NFRAG + (c2 * S3 + s) * kWave];
-            v[c2] = mfma_bf16(al, bh, v[c2]);
-            v[c2] = mfma_bf16(ah, bl, v[c2]);
-            v[c2] = mfma_bf16(am, bm, v[c2]);
-            v[c2] = mfma_bf16(am, bh, v[c2]);
-            v[c2] = mfma_bf16(ah, bm, v[c2]);
-            v[c2] = mfma_bf16(ah, bh, v[c2]);
+            v[c2] = mfma_f16(al, bh, v[c2]);
+            v[c2] = mfma_f16(am, bm, v[c2]);
+            v[c2] = mfma_f16(am, bh, v[c2]);
+            v[c2] = mfma_f16(ah, bm, v[c2]);
+            v[c2] = mfma_f16(ah, bh, v[c2]);
           }
         }
       } else {
@@ -1346,15 +1129,14 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
           }
       }
       // v[c2][j] = V[group i][16c2 + 4q + j] -> the wave's LDS patch, row = group
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the previous tile's reads are done
+      att_store_v_patch([&] {
 #pragma unroll
-      for (int c2 = 0; c2 < KT; ++c2) {
-        float4 o;
-        o.x = v[c2][0]; o.y = v[c2][1]; o.z = v[c2][2]; o.w = v[c2][3];
-        *reinterpret_cast<float4*>(vrow + i * LDV + 16 * c2 + 4 * q) = o;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+        for (int c2 = 0; c2 < KT; ++c2) {
+          float4 o;
+          o.x = v[c2][0]; o.y = v[c2][1]; o.z = v[c2][2]; o.w = v[c2][3];
+          *reinterpret_cast<float4*>(vrow + i * LDV + 16 * c2 + 4 * q) = o;
+        }
+      });
     };
     auto edge_phase = [&](const EBuf& e, const CIdx& c, int32_t p0, int32_t pe) {
       float mine = 0.f;
@@ -1370,13 +1152,10 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
           d = fmaf(e.r[s][v].z, b.z, d);
           d = fmaf(e.r[s][v].w, b.w, d);
         }
-        d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0xB1, 0xF, 0xF, true));
-        if (LPE >= 4) d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x4E, 0xF, 0xF, true));
-        if (LPE >= 8) d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x141, 0xF, 0xF, true));
-        if (LPE >= 16) d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x140, 0xF, 0xF, true));
+        d = lanes_sum<LPE>(d);
         mine = li == s ? d : mine;
       }
-      if (F16B) mine = ldexpf(mine, -w_shift - 14);  // (V rows are those of (W_r * 2^w_shift) (T * 2^14))
+      if (X3) mine = ldexpf(mine, -w_shift - 14);  // (V rows are those of (W_r * 2^w_shift) (T * 2^14))
       if (p0 + lane < pe) {
         if (LOGITS_EID) logits[c.oe] = mine;
         if (OUT >= 1 && logits_csr) logits_csr[c.op] = mine;
@@ -1456,10 +1235,7 @@ constexpr int kAttF16Second = 1;  // default since round 4 (-3.3 us in the step 
     }
     t = seg_end;
   }
-  if (clocks) {
-    __syncthreads();
-    if (tid == 0) clocks[2 * part + 1] = (long long)__builtin_amdgcn_s_memrealtime();
-  }
+  KGAT_ATT_FUSED_EPILOGUE
 }
 
 // Where the logits go -> the fused kernels' OUT, as an integral_constant: edge-id order asked for 2, else CSR order 1,
@@ -1531,8 +1307,7 @@ __global__ __launch_bounds__(kFused128Threads) void att_fold_fused128_kernel(
   constexpr int D_ = 128, K_ = 128, KS = D_ / 4, KT = K_ / 16, NW = kFused128Threads / kWave;
   constexpr int S3 = D_ / 32, ROWB = D_ * 2, IMG = D_ * ROWB;
   constexpr int LPE = 8, VPL = D_ / (4 * LPE);
-constexpr int kF128Passes = 2;
-  constexpr int NPASS = kF128Passes, HALF = LPE / NPASS;  // row-gather passes per 64-position chunk
+  constexpr int NPASS = 2, HALF = LPE / NPASS;  // row-gather passes per 64-position chunk
   constexpr bool LOGITS_EID = OUT == 2;
   constexpr int ROW_SHIFT = 9;  // 512-byte rows
   __shared__ __attribute__((aligned(16))) unsigned char s_img[2 * IMG];   // W_r 2^shift: fp16 pieces h, l
@@ -1544,41 +1319,16 @@ constexpr int kF128Passes = 2;
   const int i = lane & 15, q = lane >> 4;
   const int li = lane % LPE;
 
-  {  // relation ids outside [0, R): logit 0
-    const int64_t n_scored = rel_ptr[n_rel];
-    for (int64_t p = n_scored + (int64_t)blockIdx.x * kFused128Threads + tid; p < n_edges;
-         p += (int64_t)gridDim.x * kFused128Threads) {
-      if (LOGITS_EID) logits[perm[p]] = 0.f;
-      if (OUT >= 1 && logits_csr) logits_csr[pos_g[p]] = 0.f;
-      if (logits_g) logits_g[p] = 0.f;
-    }
-  }
-  const int32_t n_tiles = rel_tptr[n_rel];
-  const unsigned part = kAtt128XcdRemap ? xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int32_t t_begin = part_tptr ? part_tptr[part] : (int32_t)((int64_t)n_tiles * part / gridDim.x);
-  const int32_t t_end = part_tptr ? part_tptr[part + 1] : (int32_t)((int64_t)n_tiles * (part + 1) / gridDim.x);
+  KGAT_ATT_FUSED_PROLOGUE(kFused128Threads, blockIdx.x)
   float* vrow = s_v[w];
-  if (clocks && tid == 0) clocks[2 * part] = (long long)__builtin_amdgcn_s_memrealtime();   // (measurement aid)
+  KGAT_ATT_FUSED_STAMP_START
 
   struct HBuf { float a[KS]; };
-  auto load_head = [&](HBuf& f, int32_t row) {
-    const char* base = reinterpret_cast<const char*>(ent);
-    const uint32_t o = (uint32_t)row * (uint32_t)(D_ * 4) + (uint32_t)(q * 16);
-#pragma unroll
-    for (int m = 0; m < D_ / 16; ++m) {
-      const float4 v = *reinterpret_cast<const float4*>(base + o + m * 64);
-      f.a[4 * m + 0] = v.x; f.a[4 * m + 1] = v.y; f.a[4 * m + 2] = v.z; f.a[4 * m + 3] = v.w;
-    }
-  };
+  auto load_head = [&](HBuf& f, int32_t row) { att_load_row_frag<D_>(f.a, ent, row, q); };
 
   int32_t t = t_begin;
   while (t < t_end) {  // workgroup-uniform loop over relation segments
-    int lo = 0, hi = n_rel;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (rel_tptr[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int r = lo;
+    const int r = segment_of(rel_tptr, n_rel, t);
     const int32_t rend = gptr[r + 1];
     int32_t seg_end = rel_tptr[r + 1];
     seg_end = seg_end < t_end ? seg_end : t_end;
@@ -1607,7 +1357,7 @@ constexpr int kF128Passes = 2;
                             ldexpf(w1.x, w_shift), ldexpf(w1.y, w_shift), ldexpf(w1.z, w_shift), ldexpf(w1.w, w_shift)};
         uintx4 h, l;
         split_f16x2(x, h, l);
-        const int off = ROWB * row + 16 * (ch ^ (((row & 7) << 1) | ((row >> 3) & 1)));
+        const int off = att_img_offset(ROWB, row, ch);
         *reinterpret_cast<uintx4*>(s_img + off) = h;
         *reinterpret_cast<uintx4*>(s_img + IMG + off) = l;
       }
@@ -1620,22 +1370,10 @@ constexpr int kF128Passes = 2;
       return make_int4(__builtin_amdgcn_readfirstlane(d.x), __builtin_amdgcn_readfirstlane(d.y),
                        __builtin_amdgcn_readfirstlane(d.z), __builtin_amdgcn_readfirstlane(d.w));
     };
-    auto head_idx = [&](const int4& d) -> int32_t {
-      int32_t g = d.y + i;
-      g = g < rend ? g : rend - 1;
-      return g_node[g];
-    };
-    struct CIdx { int32_t row_off, lg, oe, op; };
+    auto head_idx = [&](const int4& d) -> int32_t { return att_head_idx(d, i, rend, g_node); };
+    using CIdx = AttChunkIdx;
     auto chunk_idx = [&](const int4& d, int32_t p0) -> CIdx {
-      int32_t p = p0 + lane;
-      p = p < d.w ? p : d.w - 1;
-      CIdx c;
-      const uint32_t rec = (uint32_t)rec_g[p];
-      c.row_off = (int32_t)(rec << ROW_SHIFT);
-      c.lg = (int32_t)(rec >> 28);
-      c.oe = LOGITS_EID ? perm[p] : 0;
-      c.op = (OUT >= 1 && logits_csr) ? pos_g[p] : 0;
-      return c;
+      return att_chunk_idx<ROW_SHIFT, OUT>(d, p0, lane, rec_g, perm, pos_g, logits_csr);
     };
 
     // the two chained products of one tile: V rows of the tile's 16 groups -> the wave's LDS patch
@@ -1749,15 +1487,14 @@ constexpr int kF128Passes = 2;
       // v[c2][j] = V[group i][16c2 + 4q + j] -> the wave's patch, row = group slot; the 16-byte chunks
       // of a row are swizzled by the slot's parity (chunk ^ 8) so that the edge phase's reads of two
       // different slots by one 16-lane group fall into different bank halves
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the previous tile's reads are done
+      att_store_v_patch([&] {
 #pragma unroll
-      for (int c2 = 0; c2 < KT; ++c2) {
-        float4 o;
-        o.x = v[c2][0]; o.y = v[c2][1]; o.z = v[c2][2]; o.w = v[c2][3];
-        *reinterpret_cast<float4*>(vrow + i * D_ + 4 * ((4 * c2 + q) ^ ((i & 1) << 3))) = o;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+        for (int c2 = 0; c2 < KT; ++c2) {
+          float4 o;
+          o.x = v[c2][0]; o.y = v[c2][1]; o.z = v[c2][2]; o.w = v[c2][3];
+          *reinterpret_cast<float4*>(vrow + i * D_ + 4 * ((4 * c2 + q) ^ ((i & 1) << 3))) = o;
+        }
+      });
     };
 
     // 64 positions starting at p0, their rows gathered in NPASS passes (1: all 8 steps of the 8-lane
@@ -1788,9 +1525,7 @@ constexpr int kF128Passes = 2;
             d = fmaf(rowv[s][v].z, b.z, d);
             d = fmaf(rowv[s][v].w, b.w, d);
           }
-          d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0xB1, 0xF, 0xF, true));
-          d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x4E, 0xF, 0xF, true));
-          d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x141, 0xF, 0xF, true));
+          d = lanes_sum<LPE>(d);
           mine = li == h * HALF + s ? d : mine;
         }
       }
@@ -1835,10 +1570,7 @@ constexpr int kF128Passes = 2;
     }
     t = seg_end;
   }
-  if (clocks) {
-    __syncthreads();
-    if (tid == 0) clocks[2 * part + 1] = (long long)__builtin_amdgcn_s_memrealtime();
-  }
+  KGAT_ATT_FUSED_EPILOGUE
 }
 
 static int launch_att_fold_fused128(const AttArgs& a) {
@@ -1865,7 +1597,7 @@ int launch_att_split_any(int d, const AttArgs& a) {
 }
 
 int launch_att_persistent_any(int d, const AttArgs& a) {
-  return dispatch_width(AttWidths{}, d, [&](auto w) { return launch_att_persistent<decltype(w)::value, 0>(a); });
+  return dispatch_width(AttWidths{}, d, [&](auto w) { return launch_att_persistent<decltype(w)::value>(a); });
 }
 
 }  // namespace kgat

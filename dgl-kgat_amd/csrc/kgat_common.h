@@ -68,6 +68,31 @@ inline int device_cu_count() {
   return cached[dev];
 }
 
+// Workgroups per compute unit of a persistent launch of `Kernel` with `threads` threads: what the kernel's registers
+// and LDS admit, at most 8.  The occupancy query is made once per kernel instantiation.
+template <auto Kernel>
+inline int resident_blocks_per_cu(int threads) {
+  static int cached = 0;
+  if (cached == 0) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, threads, 0) != hipSuccess || nb < 1) nb = 1;
+    cached = nb > 8 ? 8 : nb;
+  }
+  return cached;
+}
+
+// The segment that holds item t: the largest r in [0, n) with prefix[r] <= t (prefix non-decreasing, prefix[0] <= t).
+// Among empty segments, which share their prefix value with the next one, that is the last.
+template <typename T>
+__device__ __forceinline__ int segment_of(const int32_t* prefix, int n, T t) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (prefix[mid] <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs (observed placement, a speed matter only: blocks b and
 // b + 8 share an L2; MI355X_MICROARCH.md, Workgroup dispatch).  The work item of block b out of n such
 // that the blocks of one XCD take a CONTIGUOUS eighth of the items (bijective for any n).  Used by the fused

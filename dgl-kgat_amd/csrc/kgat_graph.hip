@@ -401,12 +401,8 @@ __global__ void att_pack_records_kernel(int64_t n_edges, int n_rel, const int32_
   if (p >= n_edges) return;
   uint32_t rec = (uint32_t)src_g[p];
   if (p < rel_ptr[n_rel]) {
-    int lo = 0, hi = n_rel;  // relation of position p: largest r with rel_ptr[r] <= p
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (rel_ptr[mid] <= p) lo = mid; else hi = mid;
-    }
-    rec |= (uint32_t)((gid[p] - gptr[lo]) & (kGroupsPerTile - 1)) << 28;   // the slot of 16 groups in the top 4 bits
+    const int r = segment_of(rel_ptr, n_rel, p);  // relation of position p
+    rec |= (uint32_t)((gid[p] - gptr[r]) & (kGroupsPerTile - 1)) << 28;   // the slot of 16 groups in the top 4 bits
   }
   rec_g[p] = (int32_t)rec;
 }
@@ -433,11 +429,7 @@ __device__ __forceinline__ int fold_base_tile(int n_rel, const int32_t* __restri
                                               const int32_t* __restrict__ gptr,
                                               const int32_t* __restrict__ gstart, int32_t b,
                                               int32_t& g0, int32_t& pb, int32_t& pe) {
-  int lo = 0, hi = n_rel;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (bptr[mid] <= b) lo = mid; else hi = mid;
-  }
+  const int lo = segment_of(bptr, n_rel, b);
   g0 = gptr[lo] + (b - bptr[lo]) * kGroupsPerTile;
   const int32_t g1 = g0 + kGroupsPerTile < gptr[lo + 1] ? g0 + kGroupsPerTile : gptr[lo + 1];
   pb = gstart[g0];
