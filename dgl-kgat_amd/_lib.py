@@ -135,6 +135,13 @@ SIGNATURES = {
     "kgat_transr_adam_step_f32": (_i32, [_i64, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, _p, _p, C.c_uint64,
                                          _p, _sz, _p]),
+    # BPR-MF pretraining as three-launch iterations: reference models.py:170-178, kgat.py:150-168 (ABI 16, additive)
+    "kgat_mf_supported": (_i32, [_i64, _i32, _i64]),
+    "kgat_mf_sorted_bytes": (_sz, [_i64]),
+    "kgat_mf_presort_f32": (_i32, [_i64, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "kgat_mf_step_workspace_bytes": (_sz, [_i64, _i32]),
+    "kgat_mf_adam_step_f32": (_i32, [_i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_float, _p, _p, C.c_uint64, _p, _sz, _p]),
     "kgat_adam_max_tensors": (_i32, []),
     "kgat_adam_step_f32": (_i32, [_i32, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _i32, _p]),
     # global-norm gradient clipping: reference kgat.py:32,162 (ABI 16, additive)

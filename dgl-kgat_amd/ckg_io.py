@@ -45,6 +45,32 @@ def write_table(path, names, data):
                comments="")
 
 
+def save_pretrain(path, user_embed, item_embed):
+    """BPR-MF embeddings in the layout of the KGAT release's ``pretrain/<dataset>/mf.npz``: an ``.npz`` with float32
+    arrays ``user_embed`` (n_users, d) and ``item_embed`` (n_items, d).  (numpy appends ``.npz`` to a path without it.)"""
+    ue, ie = _pretrain_pair(np.asarray(user_embed, dtype=np.float32), np.asarray(item_embed, dtype=np.float32), path)
+    np.savez(path, user_embed=ue, item_embed=ie)
+
+
+def load_pretrain(path):
+    """``(user_embed, item_embed)`` of an ``mf.npz`` (save_pretrain) as float32 arrays; other keys are ignored, a missing
+    key, an array that is not 2-D, or two different widths raise ValueError."""
+    with np.load(path) as z:
+        missing = [k for k in ("user_embed", "item_embed") if k not in z.files]
+        if missing:
+            raise ValueError("%s: no array %s (found %s)" % (path, " / ".join(missing), sorted(z.files)))
+        ue, ie = z["user_embed"], z["item_embed"]
+    return _pretrain_pair(np.asarray(ue, dtype=np.float32), np.asarray(ie, dtype=np.float32), path)
+
+
+def _pretrain_pair(ue, ie, path):
+    if ue.ndim != 2 or ie.ndim != 2:
+        raise ValueError("%s: user_embed and item_embed must be 2-D, got shapes %s and %s" % (path, ue.shape, ie.shape))
+    if ue.shape[1] != ie.shape[1]:
+        raise ValueError("%s: user_embed is %d wide, item_embed %d" % (path, ue.shape[1], ie.shape[1]))
+    return np.ascontiguousarray(ue), np.ascontiguousarray(ie)
+
+
 def _uv_triplets(uv, offset_rel, n_uv_rel, symmetric=True):
     """dataset.py:165-185: [u, R, v] rows, then (symmetric) the reversed [v, R + n_uv_rel, u] rows."""
     rel = np.zeros(len(uv), np.int32) if uv.shape[1] == 2 else uv[:, 2]

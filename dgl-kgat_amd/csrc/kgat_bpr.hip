@@ -13,6 +13,11 @@
 //             reproducible; scaled by the incoming gradient read from device memory (no host synchronisation, no
 //             separate multiply pass)
 //   loss = -mean_b logsigmoid(<s,p> - <s,n>) + lambda (mean_b |s|^2/2 + mean_b |p|^2/2 + mean_b |n|^2/2)
+// Below them, BPR-MF pretraining (the same loss with the embedding table as the readout) as three-launch iterations
+// without a dense gradient: kgat_mf_presort_f32 + kgat_mf_adam_step_f32, on the kernels' shared bodies.
+#include <math.h>
+
+#include "kgat_adam_common.h"
 #include "kgat_lds_sort.h"
 
 namespace kgat {
@@ -59,19 +64,24 @@ __global__ __launch_bounds__(256) void bpr_sample_kernel(int64_t batch, int64_t 
   }
 }
 
-// loss = -mean(part[0:B]) + lambda (mean(part[B:2B]) + mean(part[2B:3B]) + mean(part[3B:4B])), fixed order
-__global__ __launch_bounds__(1024) void bpr_reduce_kernel(int64_t batch, const float* __restrict__ part,
-                                                          float reg_lambda, float* __restrict__ loss) {
+// loss = -mean(part[0:B]) + lambda (mean(part[B:2B]) + mean(part[2B:3B]) + mean(part[3B:4B])), fixed order: the sums
+// of 1,024 threads in sixteen wavefronts.  A block of THREADS < 1,024 threads (the fused MF iteration's, where the
+// reduction rides in a launch of 256-thread blocks) plays the sixteen wavefronts in turn: the same additions.
+template <int THREADS>
+__device__ __forceinline__ void bpr_reduce_body(int64_t batch, const float* __restrict__ part, float reg_lambda,
+                                                float* __restrict__ loss) {
   __shared__ float s_red[4][16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int64_t i = threadIdx.x; i < batch; i += 1024)
+  const int lane = threadIdx.x & 63;
+  for (int w = threadIdx.x >> 6; w < 16; w += THREADS / 64) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = w * 64 + lane; i < batch; i += 1024)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] += part[k * batch + i];
+      for (int k = 0; k < 4; ++k) acc[k] += part[k * batch + i];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    acc[k] = wave_sum(acc[k]);
-    if (lane == 0) s_red[k][w] = acc[k];
+    for (int k = 0; k < 4; ++k) {
+      acc[k] = wave_sum(acc[k]);
+      if (lane == 0) s_red[k][w] = acc[k];
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -84,6 +94,11 @@ __global__ __launch_bounds__(1024) void bpr_reduce_kernel(int64_t batch, const f
     }
     loss[0] = -t[0] + reg_lambda * (t[1] + t[2] + t[3]);
   }
+}
+
+__global__ __launch_bounds__(1024) void bpr_reduce_kernel(int64_t batch, const float* __restrict__ part,
+                                                          float reg_lambda, float* __restrict__ loss) {
+  bpr_reduce_body<1024>(batch, part, reg_lambda, loss);
 }
 
 __global__ __launch_bounds__(256) void bpr_keys_kernel(int64_t batch, const int32_t* __restrict__ u,
@@ -115,16 +130,18 @@ struct BprSample {   // what the window's lane l knows about sorted position bas
   bool ok;
 };
 
-__global__ __launch_bounds__(256) void bpr_window_kernel(int64_t batch, int64_t n_nodes, int F,
-                                                         const float* __restrict__ emb, int64_t stride,
-                                                         const int32_t* __restrict__ u, const int32_t* __restrict__ p,
-                                                         const int32_t* __restrict__ n, const float* __restrict__ coef,
-                                                         float reg_lambda, const float* __restrict__ grad_scale,
-                                                         const int32_t* __restrict__ sorted,
-                                                         const int32_t* __restrict__ order, float* __restrict__ grad,
-                                                         float* __restrict__ partials) {
+// COMPACT (the fused MF iteration, below): a row completed inside the window goes to row `sorted position of the run's
+// head` of a 3 B x F buffer instead of row `id` of the dense gradient; the pieces of crossing runs as ever.
+template <bool COMPACT>
+__device__ __forceinline__ void bpr_window_body(int64_t w, int64_t batch, int64_t n_nodes, int F,
+                                                const float* __restrict__ emb, int64_t stride,
+                                                const int32_t* __restrict__ u, const int32_t* __restrict__ p,
+                                                const int32_t* __restrict__ n, const float* __restrict__ coef,
+                                                float reg_lambda, const float* __restrict__ grad_scale,
+                                                const int32_t* __restrict__ sorted,
+                                                const int32_t* __restrict__ order, float* __restrict__ grad,
+                                                float* __restrict__ partials) {
   const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t total = 3 * batch;
   const int64_t base = w * kBprWin;
   if (base >= total) return;
@@ -156,12 +173,13 @@ __global__ __launch_bounds__(256) void bpr_window_kernel(int64_t batch, int64_t 
     const int c = live ? c0 + lane * 4 : 0;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     int32_t cur = __shfl(me.key, 0, 64);
+    int64_t head = base;   // the sorted position at which the current run enters the window
     bool first_piece = true;
     auto flush = [&](bool last_piece) {
       if ((uint64_t)cur >= (uint64_t)n_nodes) return;              // ids outside the table carry nothing
       const bool starts = !(first_piece && prev_key == cur), ends = !(last_piece && next_key == cur);
       if (!live) return;
-      if (starts && ends) *reinterpret_cast<float4*>(grad + (size_t)cur * F + c) = acc;
+      if (starts && ends) *reinterpret_cast<float4*>(grad + (size_t)(COMPACT ? head : (int64_t)cur) * F + c) = acc;
       else *reinterpret_cast<float4*>(partials + ((size_t)w * 2 + (starts ? 1 : 0)) * F + c) = acc;
     };
     constexpr int RB = 8;   // positions whose rows are in flight together
@@ -189,6 +207,7 @@ __global__ __launch_bounds__(256) void bpr_window_kernel(int64_t batch, int64_t 
           flush(false);
           acc = make_float4(0.f, 0.f, 0.f, 0.f);
           cur = kt[t];
+          head = base + t0 + t;
           first_piece = false;
         }
         if (!okt[t]) continue;   // (a sample with an id outside the table: the forward made the loss NaN)
@@ -201,6 +220,18 @@ __global__ __launch_bounds__(256) void bpr_window_kernel(int64_t batch, int64_t 
     }
     flush(true);
   }
+}
+
+__global__ __launch_bounds__(256) void bpr_window_kernel(int64_t batch, int64_t n_nodes, int F,
+                                                         const float* __restrict__ emb, int64_t stride,
+                                                         const int32_t* __restrict__ u, const int32_t* __restrict__ p,
+                                                         const int32_t* __restrict__ n, const float* __restrict__ coef,
+                                                         float reg_lambda, const float* __restrict__ grad_scale,
+                                                         const int32_t* __restrict__ sorted,
+                                                         const int32_t* __restrict__ order, float* __restrict__ grad,
+                                                         float* __restrict__ partials) {
+  bpr_window_body<false>((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), batch, n_nodes, F, emb, stride, u, p, n, coef,
+                         reg_lambda, grad_scale, sorted, order, grad, partials);
 }
 
 // the runs that cross window edges: the wavefront of the window in which such a run begins (its last piece, slot 1)
@@ -265,18 +296,14 @@ constexpr int kSliceSortMaxLists = 16;
 constexpr int kSlicePosBits = 17;    // index among the 3B <= 65,536 ids
 constexpr int kSliceDigitBits = 9;   // 18-bit ids (the CKGs of the reference's datasets) in TWO passes; eight bits took three
 
-__global__ __launch_bounds__(kLdsSortThreads) void bpr_sort_zero_kernel(
-    int32_t batch, int32_t n_lists, int64_t n_nodes, int key_bits, const int32_t* __restrict__ u,
-    const int32_t* __restrict__ p, const int32_t* __restrict__ n, uint64_t* __restrict__ lists, float* __restrict__ zero,
-    int64_t n_zero) {
-  if ((int32_t)blockIdx.x >= n_lists) {
-    zero_fill_behind(zero, n_zero, (unsigned)n_lists, kLdsSortThreads);
-    return;
-  }
+// slice `slice` of one batch's role-major id list, sorted into lists[slice * kSliceSort ...)
+__device__ __forceinline__ void bpr_slice_sort_body(int32_t slice, int32_t batch, int64_t n_nodes, int key_bits,
+                                                    const int32_t* __restrict__ u, const int32_t* __restrict__ p,
+                                                    const int32_t* __restrict__ n, uint64_t* __restrict__ lists) {
   __shared__ LdsSort<uint64_t, kSliceSort, kSliceDigitBits, kSlicePosBits> s_sort;
   const int tid = threadIdx.x;
   const int32_t total = 3 * batch;
-  const int32_t g0 = (int32_t)blockIdx.x * kSliceSort;
+  const int32_t g0 = slice * kSliceSort;
   const int32_t cnt = total - g0 < kSliceSort ? total - g0 : kSliceSort;
   for (int32_t i = tid; i < cnt; i += kLdsSortThreads) {
     const int32_t gi = g0 + i;
@@ -289,19 +316,22 @@ __global__ __launch_bounds__(kLdsSortThreads) void bpr_sort_zero_kernel(
   for (int32_t i = tid; i < cnt; i += kLdsSortThreads) lists[g0 + i] = s[i];
 }
 
+__global__ __launch_bounds__(kLdsSortThreads) void bpr_sort_zero_kernel(
+    int32_t batch, int32_t n_lists, int64_t n_nodes, int key_bits, const int32_t* __restrict__ u,
+    const int32_t* __restrict__ p, const int32_t* __restrict__ n, uint64_t* __restrict__ lists, float* __restrict__ zero,
+    int64_t n_zero) {
+  if ((int32_t)blockIdx.x >= n_lists) {
+    zero_fill_behind(zero, n_zero, (unsigned)n_lists, kLdsSortThreads);
+    return;
+  }
+  bpr_slice_sort_body((int32_t)blockIdx.x, batch, n_nodes, key_bits, u, p, n, lists);
+}
+
 // the place of every id among all ids (see above); thread t = position t of the concatenated sorted slices
 // (NL: the slices the search is unrolled over - 8 at the CF step's batch, 30,720 ids in eight slices)
 template <int NL>
-__global__ __launch_bounds__(256) void bpr_merge_kernel(int32_t total, int32_t n_lists, const uint64_t* __restrict__ lists,
-                                                        int32_t* __restrict__ order, int32_t* __restrict__ sorted,
-                                                        float* __restrict__ zero, int64_t n_zero) {
-  // the blocks behind the merge's own: the second part of the gradient's zero fill (see kgat_bpr_grad_f32)
-  const int32_t merge_blocks = (total + 255) / 256;
-  if ((int32_t)blockIdx.x >= merge_blocks) {
-    zero_fill_behind(zero, n_zero, (unsigned)merge_blocks, 256);
-    return;
-  }
-  const int32_t t = (int32_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void bpr_merge_body(int32_t t, int32_t total, int32_t n_lists, const uint64_t* __restrict__ lists,
+                                               int32_t* __restrict__ order, int32_t* __restrict__ sorted) {
   if (t >= total) return;
   const uint64_t v = lists[t];
   const uint64_t key = v >> kSlicePosBits;
@@ -342,6 +372,19 @@ __global__ __launch_bounds__(256) void bpr_merge_kernel(int32_t total, int32_t n
   sorted[pos] = (int32_t)key;
 }
 
+template <int NL>
+__global__ __launch_bounds__(256) void bpr_merge_kernel(int32_t total, int32_t n_lists, const uint64_t* __restrict__ lists,
+                                                        int32_t* __restrict__ order, int32_t* __restrict__ sorted,
+                                                        float* __restrict__ zero, int64_t n_zero) {
+  // the blocks behind the merge's own: the second part of the gradient's zero fill (see kgat_bpr_grad_f32)
+  const int32_t merge_blocks = (total + 255) / 256;
+  if ((int32_t)blockIdx.x >= merge_blocks) {
+    zero_fill_behind(zero, n_zero, (unsigned)merge_blocks, 256);
+    return;
+  }
+  bpr_merge_body<NL>((int32_t)blockIdx.x * 256 + threadIdx.x, total, n_lists, lists, order, sorted);
+}
+
 // The workspace of both entries: per-sample partials (4 B floats) | keys, order (3 B int32 each) | the window partials
 // of the gradient (two rows of F floats per 32 sorted positions) | sort scratch: the slice sort's packed lists + its
 // sorted keys (up to kSliceSort * kSliceSortMaxLists ids), or the device radix sort's, whichever is larger.  Carved
@@ -372,6 +415,236 @@ static BprWorkspace bpr_workspace(void* base, int64_t batch, int F) {
   }
   const size_t radix = radix_sort_workspace_bytes(3 * batch);
   w.bytes = cv.off + (cs.off > radix ? cs.off : radix) + 256;
+  return w;
+}
+
+// ---------------------------------------------------------------------------------------------
+// BPR-MF pretraining as a sequence of three-launch iterations (reference kgat.py:150-168 with the embedding table itself
+// as the readout: get_loss -> backward -> optimizer.step -> zero_grad; ~640 iterations per epoch at the amazon-book
+// shape and the authors' MF batch of 1,024).  The treatment the KG phase got in kgat_transr.hip (transr_adam_step):
+//  * the sort of a batch's 3 B row ids depends on nothing but the ids, and a phase's batches are drawn up front: ONE
+//    launch sorts them all (mf_presort_kernel: a workgroup per batch, the shared LdsSort), role-major and stable - the
+//    order the slice sort + rank merge above produce - and leaves sorted ids, order and run lengths per batch; beyond
+//    8,192 ids per batch (up to 65,536: the reference's CF batch of 10,240) the slice sort + rank merge themselves, over
+//    all batches at once, and a third launch for the run lengths;
+//  * no dense gradient.  At most 3 B of the N rows have one, and torch's dense Adam moves every row all the same: the
+//    window kernel (bpr_window_body<true>: the additions of bpr_window_kernel) writes a row completed inside its window
+//    at the sorted position of the run's head in a 3 B x F buffer, pieces of crossing runs into the window's two partial
+//    slots as ever; workgroups behind the windows tag the batch's rows in `row_slot` (one 64-bit word per node: call
+//    tag << 17 | head position + 1; a stale word carries an older tag, so nothing is ever cleared), and the last
+//    workgroup reduces the loss (bpr_reduce_body).  The Adam launch streams p, m, v of every row and takes g = 0 unless
+//    the row's word carries this call's tag - then the row's compact sum, or for a crossing run its pieces in window
+//    order (bpr_carry_kernel's order).  Gone: the N x F zero fill, the N x F gradient read, the sort and the merge in
+//    front of every iteration, the carry launch.  Same arithmetic on the same values: the bits of kgat_bpr_loss_f32 +
+//    kgat_bpr_grad_f32 + kgat_adam_step_f32.
+// Every gradient row is a function of the OLD table, so the window launch must end before a parameter moves: the Adam
+// launch cannot merge into it.
+constexpr int kMfSmallSort = 8192;   // 3 B ids in one workgroup's LDS
+constexpr int kMfPosBits = 13;       // a position among kMfSmallSort
+constexpr int kMfMaxIds = kSliceSort * kSliceSortMaxLists;   // 3 B ids by slice sort + rank merge
+constexpr int kMfSlotBits = 17;      // row_slot word = call tag << 17 | (sorted position of the run's head + 1 <= 65,536)
+constexpr int kMfMaxF = 256;
+
+// per-batch block of the presort's output (offsets in bytes, 256-byte aligned)
+// (+ beyond kMfSmallSort ids: the slice sort's packed lists, scratch of the presort)
+struct MfSortedLayout {
+  size_t sorted_ids, order, run_len, lists, bytes;
+};
+static MfSortedLayout mf_sorted_layout(int64_t batch) {
+  const size_t ids = 3 * (size_t)(batch > 0 ? batch : 1);
+  const size_t piece = align_up(ids * 4, 256);
+  return MfSortedLayout{0, piece, 2 * piece, 3 * piece, 3 * piece + (ids > (size_t)kMfSmallSort ? align_up(ids * 8, 256) : 0)};
+}
+
+struct MfPresortArgs {
+  int32_t batch;
+  int key_bits;
+  int64_t n_nodes;
+  const int32_t *u, *p, *n;   // n_batches x batch each
+  unsigned char* sorted;
+  MfSortedLayout lay;
+};
+
+// PT: uint32_t while every key (ids, and n_nodes for an id outside the table) is below 2^19, else uint64_t
+template <typename PT>
+__global__ __launch_bounds__(kLdsSortThreads) void mf_presort_kernel(MfPresortArgs a) {
+  __shared__ LdsSort<PT, kMfSmallSort, sizeof(PT) == 4 ? 9 : 8, kMfPosBits> s_sort;
+  const int tid = threadIdx.x;
+  const int32_t total = 3 * a.batch;
+  const size_t o = (size_t)blockIdx.x * a.batch;
+  unsigned char* blk = a.sorted + (size_t)blockIdx.x * a.lay.bytes;
+  int32_t* __restrict__ sorted_ids = reinterpret_cast<int32_t*>(blk + a.lay.sorted_ids);
+  int32_t* __restrict__ order = reinterpret_cast<int32_t*>(blk + a.lay.order);
+  int32_t* __restrict__ run_len = reinterpret_cast<int32_t*>(blk + a.lay.run_len);
+  for (int32_t i = tid; i < total; i += kLdsSortThreads) {
+    const int32_t role = i / a.batch, b = i - role * a.batch;
+    const int32_t id = role == 0 ? a.u[o + b] : (role == 1 ? a.p[o + b] : a.n[o + b]);
+    // (ids outside [0, N) sort as N, behind every real row: bpr_sort_zero_kernel's key)
+    const PT key = (uint64_t)(uint32_t)id >= (uint64_t)a.n_nodes ? (PT)a.n_nodes : (PT)id;
+    s_sort.buf[0][i] = (key << kMfPosBits) | (PT)i;
+  }
+  const PT* s = s_sort.sort(total, a.key_bits);
+  for (int32_t q = tid; q < total; q += kLdsSortThreads) {
+    const PT key = s[q] >> kMfPosBits;
+    sorted_ids[q] = (int32_t)key;
+    order[q] = (int32_t)(s[q] & (PT)(kMfSmallSort - 1));
+    int32_t len = 0;   // the length of the run that STARTS at q, 0 elsewhere
+    if (q == 0 || (s[q - 1] >> kMfPosBits) != key) {
+      len = 1;
+      while (q + len < total && (s[q + len] >> kMfPosBits) == key) ++len;
+    }
+    run_len[q] = len;
+  }
+}
+
+// The same block for 8,192 < 3 B <= 65,536 ids in three launches over all batches (blockIdx.y = the batch): the slice
+// sort, the rank merge (kgat_bpr_grad_f32's two, without the zero fill), and the run lengths - the head of a run finds
+// the run's end by a binary search of the sorted ids.
+__global__ __launch_bounds__(kLdsSortThreads) void mf_slice_sort_kernel(MfPresortArgs a) {
+  const size_t o = (size_t)blockIdx.y * a.batch;
+  unsigned char* blk = a.sorted + (size_t)blockIdx.y * a.lay.bytes;
+  bpr_slice_sort_body((int32_t)blockIdx.x, a.batch, a.n_nodes, a.key_bits, a.u + o, a.p + o, a.n + o,
+                      reinterpret_cast<uint64_t*>(blk + a.lay.lists));
+}
+
+template <int NL>
+__global__ __launch_bounds__(256) void mf_merge_kernel(MfPresortArgs a, int32_t n_lists) {
+  unsigned char* blk = a.sorted + (size_t)blockIdx.y * a.lay.bytes;
+  bpr_merge_body<NL>((int32_t)blockIdx.x * 256 + threadIdx.x, 3 * a.batch, n_lists,
+                     reinterpret_cast<const uint64_t*>(blk + a.lay.lists), reinterpret_cast<int32_t*>(blk + a.lay.order),
+                     reinterpret_cast<int32_t*>(blk + a.lay.sorted_ids));
+}
+
+__global__ __launch_bounds__(256) void mf_run_len_kernel(MfPresortArgs a) {
+  unsigned char* blk = a.sorted + (size_t)blockIdx.y * a.lay.bytes;
+  const int32_t* __restrict__ sorted_ids = reinterpret_cast<const int32_t*>(blk + a.lay.sorted_ids);
+  int32_t* __restrict__ run_len = reinterpret_cast<int32_t*>(blk + a.lay.run_len);
+  const int32_t total = 3 * a.batch;
+  const int32_t q = (int32_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= total) return;
+  const int32_t key = sorted_ids[q];
+  int32_t len = 0;
+  if (q == 0 || sorted_ids[q - 1] != key) {
+    int32_t lo = q + 1, hi = total;   // the first position behind q whose id is larger
+    while (lo < hi) {
+      const int32_t mid = (lo + hi) >> 1;
+      if (sorted_ids[mid] <= key) lo = mid + 1; else hi = mid;
+    }
+    len = lo - q;
+  }
+  run_len[q] = len;
+}
+
+struct MfStepArgs {
+  int64_t batch, n_nodes;
+  int F;
+  const float* emb;
+  const int32_t *u, *p, *n;
+  const float *coef, *part;
+  float reg_lambda;
+  const int32_t *sorted_ids, *order, *run_len;
+  float *compact, *partials, *loss;
+  unsigned long long* row_slot;
+  unsigned long long tag;
+  int win_blocks, tag_blocks;
+};
+
+// second launch of an iteration: blocks [0, win_blocks) the windows, the next tag_blocks the row tags (one thread per
+// sorted position: the head of a run of a real row writes the row's word), the last block the loss
+__global__ __launch_bounds__(256) void mf_window_kernel(MfStepArgs a) {
+  const int bx = (int)blockIdx.x;
+  if (bx < a.win_blocks) {
+    bpr_window_body<true>((int64_t)bx * 4 + (threadIdx.x >> 6), a.batch, a.n_nodes, a.F, a.emb, a.F, a.u, a.p, a.n, a.coef,
+                          a.reg_lambda, nullptr, a.sorted_ids, a.order, a.compact, a.partials);
+  } else if (bx < a.win_blocks + a.tag_blocks) {
+    const int64_t q = (int64_t)(bx - a.win_blocks) * 256 + threadIdx.x;
+    if (q < 3 * a.batch && a.run_len[q] > 0) {
+      const int32_t key = a.sorted_ids[q];
+      if ((uint64_t)key < (uint64_t)a.n_nodes) a.row_slot[key] = (a.tag << kMfSlotBits) | (unsigned long long)(q + 1);
+    }
+  } else {
+    bpr_reduce_body<256>(a.batch, a.part, a.reg_lambda, a.loss);
+  }
+}
+
+// third launch: dense Adam over the table, the gradient through row_slot.  4,096 elements per workgroup, 16 bytes per
+// lane and stream, as adam_kernel.
+struct MfAdamArgs {
+  float *p, *m, *v;
+  int64_t n;
+  int F;
+  int32_t total;   // 3 B
+  const unsigned long long* row_slot;
+  unsigned long long tag;
+  const float *compact, *partials;
+  const int32_t* run_len;
+  float step_size, bc2_sqrt;
+};
+
+__global__ __launch_bounds__(256) void mf_adam_kernel(MfAdamArgs a, float w1, float beta2, float w2, float eps) {
+  const int64_t base = (int64_t)blockIdx.x * 4096;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    const int64_t i = base + (int64_t)q4 * 1024 + threadIdx.x * 4;
+    if (i >= a.n) break;   // (n is a multiple of 4: F is)
+    float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t row = i / a.F;
+    const int c = (int)(i - row * a.F);
+    const unsigned long long slot = a.row_slot[row];
+    const int32_t q = (int32_t)(slot & ((1ull << kMfSlotBits) - 1ull)) - 1;
+    if ((slot >> kMfSlotBits) == a.tag && q >= 0 && q < a.total) {
+      int32_t len = a.run_len[q];
+      len = len < 1 ? 1 : (len > a.total - q ? a.total - q : len);
+      const int32_t w = q / kBprWin, last = (q + len - 1) / kBprWin;
+      if (last == w) {
+        gg = *reinterpret_cast<const float4*>(a.compact + (size_t)q * a.F + c);
+      } else {
+        // bpr_carry_kernel's order: the piece in the window where the run begins, then the following windows' first
+        // pieces in window order, eight requested together
+        gg = *reinterpret_cast<const float4*>(a.partials + ((size_t)w * 2 + 1) * a.F + c);
+        const int32_t n_follow = last - w;
+        for (int32_t j0 = 0; j0 < n_follow; j0 += 8) {
+          float4 x[8];
+#pragma unroll
+          for (int t = 0; t < 8; ++t) {
+            const int32_t wj = w + 1 + (j0 + t < n_follow ? j0 + t : n_follow - 1);
+            x[t] = *reinterpret_cast<const float4*>(a.partials + ((size_t)wj * 2 + 0) * a.F + c);
+          }
+#pragma unroll
+          for (int t = 0; t < 8; ++t)
+            if (j0 + t < n_follow) { gg.x += x[t].x; gg.y += x[t].y; gg.z += x[t].z; gg.w += x[t].w; }
+        }
+      }
+    }
+    float4 pp = *reinterpret_cast<const float4*>(a.p + i);
+    float4 mm = *reinterpret_cast<const float4*>(a.m + i);
+    float4 vv = *reinterpret_cast<const float4*>(a.v + i);
+    adam_one(pp.x, gg.x, mm.x, vv.x, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
+    adam_one(pp.y, gg.y, mm.y, vv.y, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
+    adam_one(pp.z, gg.z, mm.z, vv.z, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
+    adam_one(pp.w, gg.w, mm.w, vv.w, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
+    *reinterpret_cast<float4*>(a.p + i) = pp;
+    *reinterpret_cast<float4*>(a.m + i) = mm;
+    *reinterpret_cast<float4*>(a.v + i) = vv;
+  }
+}
+
+// the iteration's workspace: per-sample partials (4 B floats) | coef (B) | the compact gradient rows (3 B x F) | the
+// windows' partial rows (two of F floats per 32 sorted positions)
+struct MfStepWorkspace {
+  float *part, *coef, *compact, *win_part;
+  size_t bytes;
+};
+static MfStepWorkspace mf_step_workspace(void* base, int64_t batch, int F) {
+  if (batch < 1) batch = 1;
+  if (F < 4) F = 4;
+  MfStepWorkspace w;
+  Carver cv(base);
+  w.part = cv.take<float>((size_t)batch * 4);
+  w.coef = cv.take<float>((size_t)batch);
+  w.compact = cv.take<float>((size_t)batch * 3 * (size_t)F);
+  w.win_part = cv.take<float>((size_t)((3 * batch + kBprWin - 1) / kBprWin) * 2 * (size_t)F);
+  w.bytes = cv.off;
   return w;
 }
 
@@ -462,6 +735,111 @@ int kgat_bpr_grad_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
                        (const float*)w.win_part, grad);
   }
   KGAT_CHECK_LAUNCH("bpr_carry");
+  return KGAT_OK;
+}
+
+int kgat_mf_supported(int64_t n_nodes, int F, int64_t batch) {
+  return F >= 4 && F % 4 == 0 && F <= kMfMaxF && batch > 0 && 3 * batch <= kMfMaxIds && n_nodes > 0 && n_nodes < INT32_MAX;
+}
+
+size_t kgat_mf_sorted_bytes(int64_t batch) { return mf_sorted_layout(batch).bytes; }
+
+int kgat_mf_presort_f32(int64_t n_nodes, int64_t n_batches, int64_t batch, const int32_t* u, const int32_t* p,
+                        const int32_t* n, void* sorted, size_t sorted_bytes, kgat_stream_t stream) {
+  KGAT_CHECK_ARG(n_batches >= 0 && n_batches < (1 << 30), "mf_presort: bad batch count");
+  if (!kgat_mf_supported(n_nodes, 4, batch)) {
+    set_error("mf_presort: needs 1 <= batch <= %d, 1 <= n_nodes < 2^31 (batch=%lld n_nodes=%lld)", kMfMaxIds / 3,
+              (long long)batch, (long long)n_nodes);
+    return KGAT_E_UNSUPPORTED;
+  }
+  if (n_batches == 0) return KGAT_OK;
+  KGAT_CHECK_ARG(u && p && n && sorted, "mf_presort: null pointer");
+  const MfSortedLayout lay = mf_sorted_layout(batch);
+  if (sorted_bytes < (size_t)n_batches * lay.bytes) {
+    set_error("mf_presort: output buffer too small");
+    return KGAT_E_WORKSPACE;
+  }
+  const int key_bits = bits_for(n_nodes);   // (the key of an id outside the table is n_nodes itself)
+  const MfPresortArgs a = {(int32_t)batch, key_bits, n_nodes, u, p, n, static_cast<unsigned char*>(sorted), lay};
+  if (3 * batch > kMfSmallSort) {
+    const int32_t total = (int32_t)(3 * batch), n_lists = (total + kSliceSort - 1) / kSliceSort;
+    const unsigned nb = (unsigned)n_batches;   // (gridDim.y <= 65,535)
+    KGAT_CHECK_ARG(n_batches <= 65535, "mf_presort: at most 65,535 batches of more than %d ids per call", kMfSmallSort);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(mf_slice_sort_kernel, dim3((unsigned)n_lists, nb), dim3(kLdsSortThreads), 0, st, a);
+    KGAT_CHECK_LAUNCH("mf_slice_sort");
+    const unsigned merge_blocks = (unsigned)((total + 255) / 256);
+    if (n_lists <= 8) hipLaunchKernelGGL(mf_merge_kernel<8>, dim3(merge_blocks, nb), dim3(256), 0, st, a, n_lists);
+    else hipLaunchKernelGGL(mf_merge_kernel<kSliceSortMaxLists>, dim3(merge_blocks, nb), dim3(256), 0, st, a, n_lists);
+    KGAT_CHECK_LAUNCH("mf_merge");
+    hipLaunchKernelGGL(mf_run_len_kernel, dim3(merge_blocks, nb), dim3(256), 0, st, a);
+    KGAT_CHECK_LAUNCH("mf_run_len");
+    return KGAT_OK;
+  }
+  if (key_bits > 32 - kMfPosBits)
+    hipLaunchKernelGGL(mf_presort_kernel<uint64_t>, dim3((unsigned)n_batches), dim3(kLdsSortThreads), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(mf_presort_kernel<uint32_t>, dim3((unsigned)n_batches), dim3(kLdsSortThreads), 0, as_stream(stream), a);
+  KGAT_CHECK_LAUNCH("mf_presort");
+  return KGAT_OK;
+}
+
+size_t kgat_mf_step_workspace_bytes(int64_t batch, int F) { return mf_step_workspace(nullptr, batch, F).bytes; }
+
+int kgat_mf_adam_step_f32(int64_t n_nodes, int F, int64_t batch, const int32_t* u, const int32_t* p, const int32_t* n,
+                          const void* sorted, float* emb, float* exp_avg, float* exp_avg_sq, int64_t step, double lr,
+                          double beta1, double beta2, double eps, float reg_lambda, float* loss, uint64_t* row_slot,
+                          uint64_t tag, void* workspace, size_t workspace_bytes, kgat_stream_t stream) {
+  if (!kgat_mf_supported(n_nodes, F, batch)) {
+    set_error("mf_adam_step: needs F a multiple of 4 and <= %d, 1 <= batch <= %d, 1 <= n_nodes < 2^31 (F=%d batch=%lld n_nodes=%lld)",
+              kMfMaxF, kMfMaxIds / 3, F, (long long)batch, (long long)n_nodes);
+    return KGAT_E_UNSUPPORTED;
+  }
+  KGAT_CHECK_ARG(u && p && n && sorted && emb && exp_avg && exp_avg_sq && loss && row_slot && workspace,
+                 "mf_adam_step: null pointer");
+  KGAT_CHECK_ARG(step >= 1, "mf_adam_step: the step count after this step must be >= 1");
+  KGAT_CHECK_ARG(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "mf_adam_step: bad hyperparameter");
+  KGAT_CHECK_ARG(tag >= 1 && tag < (1ull << (64 - kMfSlotBits)), "mf_adam_step: tag must be in [1, 2^47)");
+  KGAT_CHECK_ARG(aligned16(emb) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(sorted) && aligned16(workspace),
+                 "mf_adam_step: the table, its moments, the sorted block and the workspace must be 16-byte aligned");
+  const MfStepWorkspace w = mf_step_workspace(workspace, batch, F);
+  if (workspace_bytes < w.bytes) {
+    set_error("mf_adam_step: workspace too small");
+    return KGAT_E_WORKSPACE;
+  }
+  const int64_t n_elem = n_nodes * F;
+  const int64_t adam_blocks = (n_elem + 4095) / 4096;
+  KGAT_CHECK_ARG(adam_blocks < ((int64_t)1 << 31), "mf_adam_step: too many elements");
+  hipStream_t st = as_stream(stream);
+  const MfSortedLayout lay = mf_sorted_layout(batch);
+  const unsigned char* blk = static_cast<const unsigned char*>(sorted);
+  const int32_t* sorted_ids = reinterpret_cast<const int32_t*>(blk + lay.sorted_ids);
+  const int32_t* order = reinterpret_cast<const int32_t*>(blk + lay.order);
+  const int32_t* run_len = reinterpret_cast<const int32_t*>(blk + lay.run_len);
+  hipLaunchKernelGGL(bpr_sample_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, batch, n_nodes, F,
+                     (const float*)emb, (int64_t)F, u, p, n, w.part, w.coef);
+  KGAT_CHECK_LAUNCH("mf_sample");
+  const int64_t n_win = (3 * batch + kBprWin - 1) / kBprWin;
+  MfStepArgs a;
+  a.batch = batch; a.n_nodes = n_nodes; a.F = F; a.emb = emb; a.u = u; a.p = p; a.n = n;
+  a.coef = w.coef; a.part = w.part; a.reg_lambda = reg_lambda;
+  a.sorted_ids = sorted_ids; a.order = order; a.run_len = run_len;
+  a.compact = w.compact; a.partials = w.win_part; a.loss = loss;
+  a.row_slot = reinterpret_cast<unsigned long long*>(row_slot);
+  a.tag = (unsigned long long)tag;
+  a.win_blocks = (int)((n_win + 3) / 4);
+  a.tag_blocks = (int)((3 * batch + 255) / 256);
+  hipLaunchKernelGGL(mf_window_kernel, dim3((unsigned)(a.win_blocks + a.tag_blocks + 1)), dim3(256), 0, st, a);
+  KGAT_CHECK_LAUNCH("mf_window");
+  MfAdamArgs ad;
+  ad.p = emb; ad.m = exp_avg; ad.v = exp_avg_sq; ad.n = n_elem; ad.F = F; ad.total = (int32_t)(3 * batch);
+  ad.row_slot = a.row_slot; ad.tag = a.tag; ad.compact = w.compact; ad.partials = w.win_part; ad.run_len = run_len;
+  // torch.optim.adam: python floats (double), then fp32 in the kernels (as kgat_adam_step_f32)
+  ad.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
+  ad.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
+  hipLaunchKernelGGL(mf_adam_kernel, dim3((unsigned)adam_blocks), dim3(256), 0, st, ad, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), (float)eps);
+  KGAT_CHECK_LAUNCH("mf_adam");
   return KGAT_OK;
 }
 

@@ -607,6 +607,129 @@ class KGATPropagation(nn.Module):
                 s_["step"].fill_(float(t))
         return losses
 
+    # -- BPR-MF pretraining (the KGAT paper initialises its runs from MF embeddings: the release's pretrain/<dataset>/mf.npz)
+    def _mf_kernels_apply(self, batch):
+        """The BPR kernels can run on the table itself: fp32 on the GPU, 16-byte aligned, a width they take."""
+        ent = self.entity_embed.weight
+        return (ent.is_cuda and ent.dtype == torch.float32 and ent.is_contiguous() and ent.shape[1] % 4 == 0 and
+                ent.data_ptr() % 16 == 0 and 1 <= batch < (1 << 29))
+
+    def mf_step(self, u, p, n, optimizer, reg_lambda=None):
+        """One iteration of BPR-MF pretraining: ``get_loss(entity_embed.weight, u, p, n)`` (reference models.py:170-178 with
+        the embedding table as the readout) -> backward -> optimizer.step -> zero_grad, without the autograd bookkeeping:
+        on the GPU in fp32 kgat_bpr_loss_f32 + kgat_bpr_grad_f32 write the loss and the dense gradient into buffers kept
+        with the model, the gradient becomes the table's ``.grad``, ``optimizer.step()`` runs (any torch optimiser), the
+        gradient is dropped.  The same kernels on the same data as ``get_loss(...).backward()``: the same bits.
+        ``reg_lambda=None``: the model's ``reg_lambda_gnn``.  CPU / float64 modules, a table the kernels do not take
+        (width not a multiple of 4, not 16-byte aligned): the torch operators.  Returns the loss (a 0-dim device tensor).
+        As ``kg_step``, this leaves EVERY parameter's ``.grad`` None: call it between complete steps."""
+        from . import ops
+        ent = self.entity_embed.weight
+        lam = self._reg_lambda_gnn if reg_lambda is None else reg_lambda
+        if u.dim() != 1 or p.shape != u.shape or n.shape != u.shape:
+            raise ValueError("mf_step: u, p, n must share one (batch,) shape")
+        if not self._mf_kernels_apply(u.numel()):
+            keep = self._reg_lambda_gnn
+            self._reg_lambda_gnn = lam
+            try:   # (a GPU table the kernels refuse - unaligned, odd width - takes the torch restatement)
+                loss = self.get_loss(ent, u.long(), p.long(), n.long(), fused=False if ent.is_cuda else None)
+            finally:
+                self._reg_lambda_gnn = keep
+            loss.backward()
+            optimizer.step()
+            optimizer.zero_grad()
+            return loss.detach()
+        ids = [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in (u, p, n)]
+        b = ids[0].numel()
+        buf = getattr(self, "_mf_buffers", None)
+        if buf is None or buf[0].shape != ent.shape or buf[0].device != ent.device or buf[1] != b:
+            buf = self._mf_buffers = [torch.empty_like(ent), b,
+                                      (torch.empty((), dtype=torch.float32, device=ent.device),
+                                       torch.empty(b, dtype=torch.float32, device=ent.device),
+                                       ops._workspace(ops._lib.load().kgat_bpr_workspace_bytes(b, ent.shape[1]), ent.device))]
+        with torch.no_grad():
+            e = ent.detach()
+            loss, coef, ws = ops.bpr_loss(e, *ids, lam, out=buf[2])
+            ent.grad = ops.bpr_grad(e, *ids, coef, lam, workspace=ws, out=buf[0])
+        for p_ in self.parameters():       # (parameters the MF loss does not reach have no gradient in this phase)
+            if p_ is not ent:
+                p_.grad = None
+        optimizer.step()
+        ent.grad = None
+        return loss
+
+    def mf_phase(self, u, p, n, optimizer, reg_lambda=None):
+        """BPR-MF pretraining over batches drawn up front: u, p, n are (n_iterations, batch) id tensors (int64 or int32;
+        contiguous int32 is used as it is); iteration i is ``mf_step(u[i], p[i], n[i])``.  Returns the n_iterations losses
+        as a device tensor (no host round trip per iteration).
+
+        With ``FusedAdam`` on the GPU, the table in fp32 and 16-byte aligned, and a size ``ops.mf_supported`` takes (width
+        a multiple of 4 up to 256, 3 * batch <= 65536: batch <= 21845, which covers the authors' MF batch of 1,024 and the
+        reference's CF batch of 10,240): every batch is sorted up front (kgat_mf_presort_f32: one launch up to batch 2,730,
+        three beyond), then an iteration is ONE library call of three launches
+        (kgat_mf_adam_step_f32: per-sample kernel, window sums into a compact buffer + row tags + loss, Adam on the table
+        without a dense gradient) - the bits of ``mf_step`` and of the autograd + torch.optim.Adam sequence.  Any other
+        optimiser or size loops over ``mf_step``.  Parameters the MF
+        loss does not reach get no update, and on the fused route their ``.grad`` is left alone."""
+        from . import ops
+        from .optim import FusedAdam
+        ent = self.entity_embed.weight
+        if u.dim() != 2 or p.shape != u.shape or n.shape != u.shape:
+            raise ValueError("mf_phase: u, p, n must share one (n_iterations, batch) shape")
+        n_it, b = u.shape
+        lam = self._reg_lambda_gnn if reg_lambda is None else reg_lambda
+        fused = (n_it > 0 and isinstance(optimizer, FusedAdam) and self._mf_kernels_apply(b) and
+                 ops.mf_supported(ent.shape[0], ent.shape[1], b))
+        hyper = optimizer.kg_state((ent,)) if fused else None
+        if hyper is None:
+            if n_it == 0:
+                return torch.zeros(0, dtype=torch.float32, device=ent.device)
+            # (mf_step may hand back its persistent loss buffer: copy it before the next iteration overwrites it)
+            return torch.stack([self.mf_step(u[i], p[i], n[i], optimizer, lam).clone() for i in range(n_it)])
+        ids = [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in (u, p, n)]
+        st = getattr(self, "_mf_phase_state", None)
+        key = (ent.shape[0], ent.shape[1], b, str(ent.device))
+        if st is None or st.key != key:
+            st = self._mf_phase_state = ops.MFAdamState(*key[:3], ent.device)
+        losses = torch.empty(n_it, dtype=torch.float32, device=ent.device)
+        with torch.no_grad():
+            sorted_all, stride = ops.mf_presort(*ids, ent.shape[0])
+            state = optimizer.state[ent]
+            step = int(state["step"])
+            e_ = ent.detach()
+            lr, b1, b2, eps = hyper
+            for i in range(n_it):
+                step += 1
+                ops.mf_adam_step(ids[0][i], ids[1][i], ids[2][i], sorted_all[i * stride:(i + 1) * stride], e_,
+                                 state["exp_avg"], state["exp_avg_sq"], step, lr, b1, b2, eps, lam, losses[i:i + 1], st)
+            state["step"].fill_(float(step))
+        return losses
+
+    def load_pretrained(self, user_embed, item_embed, n_users):
+        """Initialise from BPR-MF embeddings (the layout of the KGAT release's pretrain/<dataset>/mf.npz, ckg_io.load_pretrain):
+        ``user_embed`` (n_users, d) goes to rows [0, n_users) of the entity table, ``item_embed`` (n_items, d) to rows
+        [n_users, n_users + n_items) - the node layout of ckg_io: users first, then the items, then the attribute entities,
+        whose rows stay as they are."""
+        ent = self.entity_embed.weight
+        ue, ie = torch.as_tensor(user_embed), torch.as_tensor(item_embed)
+        if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != ent.shape[1] or ie.shape[1] != ent.shape[1]:
+            raise ValueError("load_pretrained: embeddings must be (rows, %d), got %s and %s"
+                             % (ent.shape[1], tuple(ue.shape), tuple(ie.shape)))
+        if ue.shape[0] != int(n_users) or n_users + ie.shape[0] > ent.shape[0]:
+            raise ValueError("load_pretrained: %d user rows for n_users = %d, %d item rows, %d table rows"
+                             % (ue.shape[0], n_users, ie.shape[0], ent.shape[0]))
+        with torch.no_grad():
+            ent[:n_users].copy_(ue.to(device=ent.device, dtype=ent.dtype))
+            ent[n_users:n_users + ie.shape[0]].copy_(ie.to(device=ent.device, dtype=ent.dtype))
+
+    def pretrained_embeddings(self, n_users, n_items):
+        """The user and item blocks of the entity table as float32 CPU numpy arrays (for ckg_io.save_pretrain)."""
+        ent = self.entity_embed.weight.detach()
+        if n_users < 0 or n_items < 0 or n_users + n_items > ent.shape[0]:
+            raise ValueError("pretrained_embeddings: %d users + %d items exceed the table's %d rows" % (n_users, n_items, ent.shape[0]))
+        t = ent[:n_users + n_items].to(device="cpu", dtype=torch.float32).numpy()
+        return t[:n_users].copy(), t[n_users:].copy()
+
     # -- link prediction with the TransR embedding (kg_eval.py)
     def kg_rank(self, h, r, t, known=None, side="tail", candidates=None):
         """Filtered ranks of the triples under the TransR score (kg_eval.kg_rank): KGRanks(lt, eq, rank)."""

@@ -1630,9 +1630,10 @@ def transr_rank(Q, t, P, n2, c0, filter_ptr, filter_ids):
     return lt, eq
 
 
-def bpr_loss(emb, u, p, n, reg_lambda):
+def bpr_loss(emb, u, p, n, reg_lambda, out=None):
     """BPR loss of reference models.py:170-178 on the readout (kgat_bpr_loss_f32).  Returns (loss (0-dim), coef (B,),
-    workspace) - the last two feed bpr_grad."""
+    workspace) - the last two feed bpr_grad.  `out` = such a triple of an earlier call with the same batch and width:
+    its buffers are written again."""
     if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
         raise KGATLibraryError("bpr_loss: `emb` must be a float32 HIP matrix with unit column stride")
     u, p, n = (_need(t, torch.int32, name) for t, name in ((u, "u"), (p, "p"), (n, "n")))
@@ -1640,9 +1641,13 @@ def bpr_loss(emb, u, p, n, reg_lambda):
     if p.numel() != b or n.numel() != b or b < 1:
         raise ValueError("bpr_loss: the three id lists must have one common, non-zero length")
     lib = _lib.load()
-    loss = torch.empty((), dtype=torch.float32, device=emb.device)
-    coef = torch.empty(b, dtype=torch.float32, device=emb.device)
-    ws = _workspace(lib.kgat_bpr_workspace_bytes(b, emb.shape[1]), emb.device)
+    if out is not None:
+        loss, coef, ws = out
+        _need(coef, torch.float32, "coef", (b,))
+    else:
+        loss = torch.empty((), dtype=torch.float32, device=emb.device)
+        coef = torch.empty(b, dtype=torch.float32, device=emb.device)
+        ws = _workspace(lib.kgat_bpr_workspace_bytes(b, emb.shape[1]), emb.device)
     with _timed("bpr_loss", (b, emb.shape[1])):
         check(lib.kgat_bpr_loss_f32(emb.shape[0], emb.shape[1], _ptr(emb), emb.stride(0), b, _ptr(u), _ptr(p), _ptr(n),
                                     float(reg_lambda), _ptr(loss), _ptr(coef), _ptr(ws), ws.numel(), _stream(emb)),
@@ -1650,11 +1655,12 @@ def bpr_loss(emb, u, p, n, reg_lambda):
     return loss, coef, ws
 
 
-def bpr_grad(emb, u, p, n, coef, reg_lambda, grad_scale=None, workspace=None):
-    """d loss / d emb, dense (N, F), scaled by the device scalar `grad_scale` (kgat_bpr_grad_f32)."""
+def bpr_grad(emb, u, p, n, coef, reg_lambda, grad_scale=None, workspace=None, out=None):
+    """d loss / d emb, dense (N, F), scaled by the device scalar `grad_scale` (kgat_bpr_grad_f32); into `out` if given."""
     lib = _lib.load()
     b = u.numel()
-    grad = torch.empty((emb.shape[0], emb.shape[1]), dtype=torch.float32, device=emb.device)
+    grad = torch.empty((emb.shape[0], emb.shape[1]), dtype=torch.float32, device=emb.device) if out is None else \
+        _need(out, torch.float32, "out", (emb.shape[0], emb.shape[1]))
     if grad_scale is not None:
         grad_scale = _need(grad_scale.reshape(1), torch.float32, "grad_scale")
     ws = workspace if workspace is not None else _workspace(lib.kgat_bpr_workspace_bytes(b, emb.shape[1]), emb.device)
@@ -1663,6 +1669,55 @@ def bpr_grad(emb, u, p, n, coef, reg_lambda, grad_scale=None, workspace=None):
                                     _ptr(coef), float(reg_lambda), _ptr(grad_scale), _ptr(grad), _ptr(ws), ws.numel(),
                                     _stream(emb)), "kgat_bpr_grad_f32")
     return grad
+
+
+# ---------------------------------------------------------------- BPR-MF pretraining (kgat_mf_*)
+def mf_supported(n_nodes, F, batch):
+    """Sizes of the fused MF iteration: F a multiple of 4 up to 256, 3 * batch <= 65536, n_nodes < 2^31."""
+    return bool(_lib.load().kgat_mf_supported(int(n_nodes), int(F), int(batch)))
+
+
+def mf_presort(u, p, n, n_nodes):
+    """The sorts of a whole MF phase's batches up front (kgat_mf_presort_f32; one launch up to batch 2,730, three beyond): u, p, n are (n_batches, batch)
+    int32 tensors; returns (sorted, stride) - batch b's block is sorted[b * stride:(b + 1) * stride]."""
+    u = _need(u, torch.int32, "u")
+    if u.dim() != 2:
+        raise ValueError("u must be (n_batches, batch)")
+    for name, t in (("p", p), ("n", n)):
+        _need(t, torch.int32, name, u.shape)
+    lib = _lib.load()
+    nb, b = u.shape
+    stride = int(lib.kgat_mf_sorted_bytes(b))
+    out = torch.empty(max(nb * stride, 256), dtype=torch.uint8, device=u.device)
+    with _timed("mf_presort", (nb, b)):
+        check(lib.kgat_mf_presort_f32(int(n_nodes), nb, b, _ptr(u), _ptr(p), _ptr(n), _ptr(out), out.numel(), _stream(u)),
+              "kgat_mf_presort_f32")
+    return out, stride
+
+
+class MFAdamState:
+    """What a sequence of kgat_mf_adam_step_f32 calls keeps between calls: the step workspace, the row_slot words (zero
+    once, never cleared: a word is valid for the call whose tag it carries) and the tag counter."""
+
+    def __init__(self, n_nodes, F, batch, device):
+        lib = _lib.load()
+        self.key = (int(n_nodes), int(F), int(batch), str(device))
+        self.workspace = _workspace(lib.kgat_mf_step_workspace_bytes(batch, F), device)
+        self.row_slot = torch.zeros(int(n_nodes), dtype=torch.int64, device=device)
+        self.tag = 0
+
+
+def mf_adam_step(u, p, n, sorted_block, emb, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, reg_lambda, loss_out, state):
+    """One MF iteration (kgat_mf_adam_step_f32): BPR loss of the batch on the table `emb` into `loss_out` (a 1-element
+    fp32 view) and the Adam step on `emb` in place; `step`: the step count after this step.  Shapes and dtypes are the
+    caller's responsibility here (KGATPropagation.mf_phase validates them once per phase)."""
+    state.tag += 1
+    check(_lib.load().kgat_mf_adam_step_f32(emb.shape[0], emb.shape[1], u.numel(), u.data_ptr(), p.data_ptr(), n.data_ptr(),
+                                            sorted_block.data_ptr(), emb.data_ptr(), exp_avg.data_ptr(),
+                                            exp_avg_sq.data_ptr(), int(step), float(lr), float(beta1), float(beta2),
+                                            float(eps), float(reg_lambda), loss_out.data_ptr(), state.row_slot.data_ptr(),
+                                            state.tag, state.workspace.data_ptr(), state.workspace.numel(), _stream(emb)),
+          "kgat_mf_adam_step_f32")
 
 
 # ---------------------------------------------------------------- global-norm gradient clipping (kgat.py:32,162)

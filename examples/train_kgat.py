@@ -21,6 +21,9 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
   python examples/train_kgat.py --synthetic 1.0 --grad_norm 1.0          # clip the CF gradient's global norm (kgat.py:32,162)
   python examples/train_kgat.py --planted --epochs 6 --kg_eval 2000 --kg_holdout 0.1   # + filtered MRR / MR / Hits@10 of
                                                                           # held-out KG triples under the TransR score
+  python examples/train_kgat.py --planted --pretrain_epochs 5 --pretrain_lr 0.1 --pretrain_save mf.npz --epochs 3
+                                                                          # BPR-MF pretraining of the table first (the paper's
+                                                                          # initialisation); --pretrain_load mf.npz reuses it
 
 ``--gpus N``: one process per GPU (started here as a child ``torch.distributed.run``),
 parameters replicated, the training graph sharded by destination range.  Every rank draws the same
@@ -217,7 +220,25 @@ def parse_args(argv=None):
     ap.add_argument("--kg_holdout", type=float, default=0.0, metavar="F",
                     help="hold a fraction F of the item-KG triples (never an interaction; a triple leaves with its "
                          "reverse twin) out of the KG phase and of the propagation graphs, for --kg_eval to rank")
+    ap.add_argument("--pretrain_epochs", type=int, default=0, metavar="N",
+                    help="BPR-MF pretraining of the embedding table before the first KGAT epoch (the KGAT paper "
+                         "initialises every run from MF embeddings): N epochs of KGATPropagation.mf_phase with an Adam of "
+                         "its own.  0 = off")
+    ap.add_argument("--pretrain_batch_size", type=int, default=1024, help="MF batch (the authors' 1,024; the fused "
+                    "iteration takes up to 21,845, larger batches run launch by launch)")
+    ap.add_argument("--pretrain_lr", type=float, default=None, help="MF learning rate (default: --lr)")
+    ap.add_argument("--pretrain_regs", type=float, default=None,
+                    help="MF regulariser (default: the CF phase's, the model's reg_lambda_gnn)")
+    ap.add_argument("--pretrain_save", default=None, metavar="PATH",
+                    help="write the user / item rows after pretraining as an mf.npz (ckg_io.save_pretrain: the layout of "
+                         "the KGAT release's pretrain/<dataset>/mf.npz)")
+    ap.add_argument("--pretrain_load", default=None, metavar="PATH",
+                    help="initialise the user / item rows from an mf.npz (before --pretrain_epochs, if both are given)")
     args = ap.parse_args(argv)
+    if args.pretrain_epochs < 0 or args.pretrain_batch_size < 1:
+        ap.error("--pretrain_epochs takes a number of epochs >= 0, --pretrain_batch_size a batch >= 1")
+    if (args.pretrain_epochs or args.pretrain_load or args.pretrain_save) and args.gpus > 1:
+        ap.error("pretraining (--pretrain_epochs / --pretrain_load / --pretrain_save) runs on one GPU")
     if args.kg_eval < 0:
         ap.error("--kg_eval takes a number of triples >= 0")
     if not 0.0 <= args.kg_holdout < 1.0:
@@ -406,9 +427,48 @@ def _run(args, argv):
             kg_evaluate(rec)
 
     history = []
+    if args.pretrain_epochs or args.pretrain_load or args.pretrain_save:
+        # ---- BPR-MF pretraining of the embedding table (the KGAT paper's initialisation; the authors ship its result as
+        # pretrain/<dataset>/mf.npz): get_loss on the raw table -> backward -> Adam, batches drawn as the CF phase's
+        def evaluate_table(rec):
+            emb = model.entity_embed.weight.detach()
+            for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict)):
+                rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
+                    emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
+            return "test recall@20 %.5f ndcg@20 %.5f | valid recall@20 %.5f" % (
+                rec["test_recall"], rec["test_ndcg"], rec["valid_recall"])
+
+        pre = {"loaded": args.pretrain_load, "saved": args.pretrain_save, "epochs": []}
+        if args.pretrain_load:
+            model.load_pretrained(*ckg_io.load_pretrain(args.pretrain_load), ds.n_users)
+            say("Pretrain   | user / item rows from %s" % args.pretrain_load)
+        pre["before"] = {}
+        say("Pretrain 0000 | raw table: %s" % evaluate_table(pre["before"]))
+        if args.pretrain_epochs:
+            # an Adam of its own: the KGAT optimiser starts with clean moments
+            mf_opt = K.FusedAdam([model.entity_embed.weight], lr=args.lr if args.pretrain_lr is None else args.pretrain_lr)
+            model.train()
+        for ep in range(1, args.pretrain_epochs + 1):
+            t0 = clock()
+            n_it, bs = cap(n_pairs // args.pretrain_batch_size + 1), min(args.pretrain_batch_size, n_pairs)
+            idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
+            u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
+            n_all = torch.randint(off, off + ds.n_items, (n_it, bs), device=dev, dtype=torch.int32)
+            total = model.mf_phase(u_all, p_all, n_all, mf_opt, reg_lambda=args.pretrain_regs).sum()
+            rec = {"epoch": ep, "mf_s": clock() - t0, "mf_iters": n_it}
+            rec["mf_loss"] = float(total) / n_it
+            say("Pretrain %04d | MF %.4fs (%d it, %.4f ms/it) mf_loss %.4f | %s" % (
+                ep, rec["mf_s"], n_it, 1e3 * rec["mf_s"] / n_it, rec["mf_loss"], evaluate_table(rec)))
+            pre["epochs"].append(rec)
+            del idx, u_all, p_all, n_all
+        if args.pretrain_save:
+            ckg_io.save_pretrain(args.pretrain_save, *model.pretrained_embeddings(ds.n_users, ds.n_items))
+            say("Pretrain   | user / item rows written to %s" % args.pretrain_save)
+        history.append({"epoch": 0, "pretrain": pre})
     if args.eval_before:
         model.eval()
-        history.append({"epoch": 0})
+        if not history:
+            history.append({"epoch": 0})
         say("Epoch 0000 | (untrained)")
         evaluate(history[-1])
     for epoch in range(1, args.epochs + 1):

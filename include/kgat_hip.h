@@ -963,6 +963,48 @@ int kgat_bpr_grad_f32(int64_t n_nodes, int F, const float* emb, int64_t emb_stri
                       const int32_t* p, const int32_t* n, const float* coef, float reg_lambda, const float* grad_scale,
                       float* grad, void* workspace, size_t workspace_bytes, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- BPR-MF pretraining (ABI 16, additive)
+ * The KGAT paper initialises its runs from BPR-MF embeddings: the loss of reference models.py:170-178 with the
+ * embedding table itself as the readout, trained by the loop of reference kgat.py:150-168 (sample a batch, get_loss,
+ * backward, optimizer.step, zero_grad).  Here that loop is a sequence of three-launch iterations without a dense
+ * gradient, as the KG phase's (kgat_transr_presort_f32 / kgat_transr_adam_step_f32 above).
+ *
+ * kgat_mf_supported: F a multiple of 4 in [4, 256], 1 <= batch with 3 * batch <= 65536 (batch <= 21845),
+ * 1 <= n_nodes < 2^31.  Other sizes: KGAT_E_UNSUPPORTED from both entries (the Python layer then runs
+ * kgat_bpr_loss_f32 + kgat_bpr_grad_f32 + the optimiser per iteration).
+ *
+ * kgat_mf_presort_f32: the batches of a whole phase - u, p, n as n_batches x batch row-major arrays - sorted up front,
+ * by ONE launch while 3 * batch <= 8192 (batch <= 2730: a workgroup per batch sorts in LDS), beyond it by three (the
+ * slice sort and rank merge of kgat_bpr_grad_f32 over all batches, then the run lengths; at most 65,535 batches per
+ * call): per batch the stable sort of its 3 x batch row ids taken role-major (i = role * batch + b; ids outside
+ * [0, n_nodes) sort as n_nodes), i.e. the order kgat_bpr_grad_f32 sorts them into.  Batch b's result is the block of
+ * kgat_mf_sorted_bytes(batch) bytes at sorted + b * that: sorted ids | order | run lengths (at the head of each run of
+ * equal ids, 0 elsewhere), 3 x batch int32 each, 256-byte aligned (+ 8 x 3 x batch bytes of sort scratch beyond 8192 ids).
+ *
+ * kgat_mf_adam_step_f32: one iteration on batch arrays u, p, n (batch ids each) and that batch's `sorted` block: the
+ * loss (1 float at `loss`) and the step of torch.optim.Adam on emb (n_nodes x F, contiguous), updated IN PLACE with
+ * its moments exp_avg / exp_avg_sq (device pointers); `step` is the step count AFTER this step.  Dense semantics as
+ * kgat_adam_step_f32 (every row of the table moves), without the n_nodes x F gradient and its zero fill.  Launches:
+ * (1) the per-sample kernel of kgat_bpr_loss_f32; (2) the window kernel of kgat_bpr_grad_f32 writing into a compact
+ * 3 x batch x F buffer - a run of equal ids completed inside its window of 32 sorted positions at the position of the
+ * run's head, the pieces of a run that crosses window edges in the window's two partial slots -, beside it workgroups
+ * that tag the batch's rows in `row_slot` (n_nodes 64-bit words owned by the caller - zero before the first call,
+ * never to be cleared - a word is valid for the call whose `tag` it carries: pass a tag in [1, 2^47) that differs from
+ * every earlier call's on the same row_slot) and the ordered loss reduction; (3) Adam over every row, g = 0 for an
+ * untagged row, else the row's compact sum, or its pieces added in window order starting from the piece in the window
+ * where the run begins.  The order of every addition is that of kgat_bpr_loss_f32 / kgat_bpr_grad_f32 (grad_scale
+ * NULL) followed by kgat_adam_step_f32: the same bits, i.e. those of the reference's loss.backward();
+ * optimizer.step().  emb, the moments, `sorted` and the workspace 16-byte aligned (else KGAT_E_BADARG). */
+int kgat_mf_supported(int64_t n_nodes, int F, int64_t batch);
+size_t kgat_mf_sorted_bytes(int64_t batch);
+int kgat_mf_presort_f32(int64_t n_nodes, int64_t n_batches, int64_t batch, const int32_t* u, const int32_t* p,
+                        const int32_t* n, void* sorted, size_t sorted_bytes, kgat_stream_t stream);
+size_t kgat_mf_step_workspace_bytes(int64_t batch, int F);
+int kgat_mf_adam_step_f32(int64_t n_nodes, int F, int64_t batch, const int32_t* u, const int32_t* p, const int32_t* n,
+                          const void* sorted, float* emb, float* exp_avg, float* exp_avg_sq, int64_t step, double lr,
+                          double beta1, double beta2, double eps, float reg_lambda, float* loss, uint64_t* row_slot,
+                          uint64_t tag, void* workspace, size_t workspace_bytes, kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- TransR link prediction (ABI 16, additive)
  * The filtered rank of a triple's true tail (head) among the entities under the score of reference models.py:120-126,
  * |u_h + u_r - u_t|^2 with the normalisation of the training kernel (u = a / max(|a|, 1e-12), a = e W_r).
