@@ -28,6 +28,7 @@ SOURCES = {
     "kgat_transr_rank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_eval.hip": [],
     "kgat_eval_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "kgat_eval_rank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_optim.hip": [],
     "kgat_bpr.hip": [],
     "kgat_sage.hip": [],
@@ -184,6 +185,13 @@ SIGNATURES = {
     "kgat_eval_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "kgat_eval_topk_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _sz, _p, _p, _p]),
     "kgat_eval_metrics_at_ks": (_i32, [_i64, _i32, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    # exact ranks of the held-out items at any depth and their metrics (ABI 16, additive)
+    "kgat_eval_rank_supported": (_i32, [_i32]),
+    "kgat_eval_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64, _i64]),
+    "kgat_eval_rank_f32": (_i32, [_i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i32, _p, _sz, _p, _p,
+                                  _p]),
+    "kgat_eval_rank_metrics_workspace_bytes": (_sz, [_i64]),
+    "kgat_eval_rank_metrics": (_i32, [_i64, _i64, _p, _p, _p, _i64, _p, _i32, _p, _p, _p, _sz, _p, _p, _p]),
     "kgat_edge_norm_f32": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p]),
     "kgat_edge_dropout_f32": (_i32, [_i64, _p, _p, C.c_float, C.c_uint64, _p, _p]),
     # TransR link prediction: projection + filtered rank counts (ABI 16, additive)

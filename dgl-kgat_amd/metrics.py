@@ -15,6 +15,10 @@ index first).  ``calc_recall_ndcg_sorted`` is the batched matmul + full stable s
 cut-offs up to 128 - from one sweep at the largest cut-off (``kgat_eval_topk_f32`` +
 ``kgat_eval_metrics_at_ks``, csrc/kgat_eval_topk.hip); ``recommend`` returns the K best unseen
 items of a list of users with their scores.
+
+``rank_items`` gives the exact rank of every held-out item at any depth and ``calc_rank_metrics`` the metrics that
+follow from it - the four above at any cut-off up to the number of items, MRR, MAP, AUC and the mean rank - from one
+counting sweep (``kgat_eval_rank_f32`` + ``kgat_eval_rank_metrics``, csrc/kgat_eval_rank.hip): no list, so no K.
 """
 import numpy as np
 import torch
@@ -157,6 +161,81 @@ def calc_metrics(embedding, train_user_dict, test_user_dict, all_item_id_range, 
         return {name: out[:, :, m] for m, name in enumerate(METRIC_NAMES)}
     mean = (out.sum(0) / plan.n_users).cpu().numpy()
     return {name: mean[:, m].copy() for m, name in enumerate(METRIC_NAMES)}
+
+
+RANK_SCALAR_NAMES = ("mrr", "map", "auc", "mean_rank")
+
+
+def _rank_inputs(embedding, train_user_dict, test_user_dict, all_item_id_range, plan, mode, what):
+    if mode not in ("mask", "drop"):
+        raise ValueError("%s: mode must be 'mask' or 'drop', got %r" % (what, mode))
+    emb = _device_rows(embedding, what)
+    if plan is None:
+        plan = EvalPlan(train_user_dict, test_user_dict, all_item_id_range, embedding.device)
+    if plan.n_users == 0:
+        raise ZeroDivisionError("no test users")   # (metric.py:65 divides by len(test_user_dict))
+    if plan.max_node_id >= embedding.shape[0]:
+        raise IndexError("user / item node id %d outside the embedding's %d rows" % (plan.max_node_id,
+                                                                                    embedding.shape[0]))
+    return emb, plan
+
+
+def rank_items(embedding, train_user_dict, test_user_dict, all_item_id_range, plan=None, mode="mask"):
+    """Where every held-out item landed: ``(ranks, ptr)`` - ``ranks`` an int64 device tensor with the 1-based rank of
+    every test entry in the order of the plan's test CSR (per user the item positions ascending, duplicates kept), ``ptr``
+    that CSR's pointer (user ``j`` of the plan owns ``ranks[ptr[j]:ptr[j + 1]]``).  The order is the evaluation's:
+    score descending, equal scores by item position, so ``rank <= K`` exactly when ``kgat_eval_topk_f32`` lists the
+    item at place ``rank - 1``.  ``mode="mask"`` is the reference's rule (``metric.py:50``: a training item competes at
+    score 0.0); ``mode="drop"`` ranks among the items the user has not trained on, and a test entry that is itself a
+    training item is not ranked: 0.  Inputs, checks and exceptions as ``calc_metrics``; no limit on a list's length."""
+    from . import ops
+    emb, plan = _rank_inputs(embedding, train_user_dict, test_user_dict, all_item_id_range, plan, mode, "rank_items")
+    with torch.no_grad():
+        above = ops.eval_rank(emb, plan.user_ids, plan.item_ids, plan.train_ptr, plan.train_items, plan.test_ptr,
+                              plan.test_items, drop_train=mode == "drop")
+    return above.long() + 1, plan.test_ptr
+
+
+def calc_rank_metrics(embedding, train_user_dict, test_user_dict, all_item_id_range, Ks=(20, 100, 500), plan=None,
+                      mode="mask", return_per_user=False):
+    """recall, ndcg, precision and hit ratio at every cut-off of ``Ks`` (ascending, distinct, at most 64, each within
+    1..n_items - no 128) and MRR, MAP, AUC and the mean rank, from the exact ranks of the held-out items
+    (``rank_items``): one item layout pass, one counting sweep, one metrics launch.  The four metrics at a cut-off are
+    ``calc_metrics``'s (a duplicated test item hits once and counts twice in recall's denominator, ``metric.py:24,61``);
+    over a user's T distinct ranked test items with 0-based ranks a_0 < ... < a_{T-1} among C candidates,
+    mrr = 1 / (a_0 + 1), map = mean_j (j + 1) / (a_j + 1), auc = 1 - sum_j (a_j - j) / (T (C - T)) - the share of
+    (held-out, other) pairs ranked the right way round - and mean_rank = mean_j (a_j + 1); a user without a ranked
+    item has 0 in all four.  ``mode`` as ``rank_items``.  Returns a dict: ``recall`` / ``ndcg`` / ``precision`` /
+    ``hit_ratio`` float64 arrays of ``len(Ks)`` and ``mrr`` / ``map`` / ``auc`` / ``mean_rank`` floats - means over the
+    test users, as ``calc_metrics`` - or, with ``return_per_user``, ``(n_users, len(Ks))`` and ``(n_users,)`` tensors.
+    Checks and exceptions as ``calc_metrics``; a cut-off above the number of items or a list that does not ascend
+    raises ``ValueError``."""
+    from . import ops
+    Ks = [int(k) for k in Ks]
+    if not 1 <= len(Ks) <= ops.EVAL_RANK_MAX_KS:
+        raise ValueError("calc_rank_metrics: 1 to %d cut-offs, got %d" % (ops.EVAL_RANK_MAX_KS, len(Ks)))
+    if Ks[0] < 1 or any(b <= a for a, b in zip(Ks, Ks[1:])):
+        raise ValueError("calc_rank_metrics: the cut-offs must be positive, ascending and distinct: %r" % (Ks,))
+    n_items = plan.n_items if plan is not None else int(np.asarray(all_item_id_range).size)
+    if Ks[-1] > n_items:
+        raise ValueError("calc_rank_metrics: cut-off %d is beyond the %d items" % (Ks[-1], n_items))
+    emb, plan = _rank_inputs(embedding, train_user_dict, test_user_dict, all_item_id_range, plan, mode,
+                             "calc_rank_metrics")
+    drop = mode == "drop"
+    with torch.no_grad():
+        above = ops.eval_rank(emb, plan.user_ids, plan.item_ids, plan.train_ptr, plan.train_items, plan.test_ptr,
+                              plan.test_items, drop_train=drop)
+        n_cand = (plan.n_items - (plan.train_ptr[1:] - plan.train_ptr[:-1])).contiguous() if drop else plan.n_items
+        at_k, scalar = ops.eval_rank_metrics(above, plan.test_ptr, plan.test_items, n_cand, Ks, n_items=plan.n_items)
+    if return_per_user:
+        out = {name: at_k[:, :, m] for m, name in enumerate(METRIC_NAMES)}
+        out.update({name: scalar[:, m] for m, name in enumerate(RANK_SCALAR_NAMES)})
+        return out
+    mean = (at_k.sum(0) / plan.n_users).cpu().numpy()
+    smean = (scalar.sum(0) / plan.n_users).cpu().numpy()
+    out = {name: mean[:, m].copy() for m, name in enumerate(METRIC_NAMES)}
+    out.update({name: float(smean[m]) for m, name in enumerate(RANK_SCALAR_NAMES)})
+    return out
 
 
 def recommend(embedding, user_ids, all_item_id_range, K, seen=None):

@@ -1511,6 +1511,95 @@ def eval_metrics_at_ks(topk, test_ptr, test_items, ks):
     return out
 
 
+def eval_rank_supported(F):
+    return bool(_lib.load().kgat_eval_rank_supported(int(F)))
+
+
+def eval_rank(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, test_items, drop_train=False,
+              want_scores=False):
+    """The number of candidates that rank before every test entry (reference metric.py:48-51 read from the other side:
+    the place of each held-out item in the descending sort, at any depth) - kgat_eval_items_kmajor_f32 +
+    kgat_eval_rank_f32.  Arguments as eval_recall_ndcg; drop_train as eval_topk (False: a training item is a candidate
+    at score 0.0; True: it is none, and a test entry that is a training item gets -1).  Returns (above[, scores]) -
+    int32 (n_test,) in test-CSR order, the rank is above + 1, and the float32 scores of the test entries."""
+    if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
+        raise KGATLibraryError("eval_rank: `emb` must be a float32 HIP matrix with unit column stride")
+    F, stride = emb.shape[1], emb.stride(0)
+    user_ids = _need(user_ids, torch.int32, "user_ids")
+    item_ids = _need(item_ids, torch.int32, "item_ids")
+    n_users, n_items = user_ids.numel(), item_ids.numel()
+    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
+    test_ptr = _need(test_ptr, torch.int32, "test_ptr", (n_users + 1,))
+    train_items = _need(train_items, torch.int32, "train_items")
+    test_items = _need(test_items, torch.int32, "test_items")
+    n_train, n_test = train_items.numel(), test_items.numel()
+    lib = _lib.load()
+    if not lib.kgat_eval_rank_supported(F):
+        raise KGATLibraryError("eval_rank: F = %d outside the kernel's range" % F)
+    dev = emb.device
+    above = torch.zeros(n_test, dtype=torch.int32, device=dev)
+    scores = torch.zeros(n_test, dtype=torch.float32, device=dev) if want_scores else None
+    if n_users == 0 or n_test == 0:
+        return (above, scores) if want_scores else above
+    itemT = torch.empty(max(int(lib.kgat_eval_items_elems(n_items, F)), 1), dtype=torch.float32, device=dev)
+    ws = _workspace(lib.kgat_eval_rank_workspace_bytes(n_users, n_items, F, n_train, n_test), dev)
+    with _timed("eval_items_kmajor", (n_items, F)):
+        check(lib.kgat_eval_items_kmajor_f32(n_items, F, _ptr(emb), stride, _ptr(item_ids), _ptr(itemT), _stream(emb)),
+              "kgat_eval_items_kmajor_f32")
+    with _timed("eval_rank", (n_users, n_items, F, n_test)):
+        check(lib.kgat_eval_rank_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
+                                     _ptr(train_ptr), _ptr(train_items), n_train, _ptr(test_ptr), _ptr(test_items),
+                                     n_test, 1 if drop_train else 0, _ptr(ws), ws.numel(), _ptr(above),
+                                     _ptr(scores) if want_scores else None, _stream(emb)), "kgat_eval_rank_f32")
+    return (above, scores) if want_scores else above
+
+
+EVAL_RANK_MAX_KS = 64
+
+
+def eval_rank_metrics(above, test_ptr, test_items, n_candidates, ks, n_items=None):
+    """recall / ndcg / precision / hit ratio at the ascending cut-offs `ks` (at most 64, each within 1..n_items) and
+    mrr / ap / auc / mean rank per user from eval_rank's counts - kgat_eval_rank_metrics.  `n_candidates`: the number
+    of items a user's test entries were ranked among - an int (every user: n_items, the mask rule) or int32
+    (n_users,) (n_items - |train(u)| under drop_train); `n_items` defaults to the largest of them.  Returns
+    (at_k, scalar): float64 (n_users, len(ks), 4) and (n_users, 4)."""
+    if above.dtype != torch.int32 or not above.is_cuda or above.dim() != 1 or not above.is_contiguous():
+        raise KGATLibraryError("eval_rank_metrics: `above` must be a contiguous int32 HIP vector")
+    test_ptr = _need(test_ptr, torch.int32, "test_ptr")
+    n_users = test_ptr.numel() - 1
+    if n_users < 0:
+        raise ValueError("eval_rank_metrics: test_ptr is empty")
+    test_items = _need(test_items, torch.int32, "test_items", (above.numel(),))
+    if not isinstance(n_candidates, torch.Tensor):
+        n_items = int(n_candidates) if n_items is None else int(n_items)
+        n_candidates = torch.full((n_users,), int(n_candidates), dtype=torch.int32, device=above.device)
+    n_candidates = _need(n_candidates, torch.int32, "n_candidates", (n_users,))
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= EVAL_RANK_MAX_KS:
+        raise ValueError("eval_rank_metrics: 1 to %d cut-offs, got %d" % (EVAL_RANK_MAX_KS, len(ks)))
+    if any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1:
+        raise ValueError("eval_rank_metrics: the cut-offs must be positive and ascend: %r" % (ks,))
+    import ctypes
+    import numpy as np
+    dev = above.device
+    if n_items is None:
+        n_items = int(n_candidates.max()) if n_users else ks[-1]
+    if ks[-1] > n_items:
+        raise ValueError("eval_rank_metrics: cut-off %d is beyond the %d items" % (ks[-1], n_items))
+    disc = torch.as_tensor(1.0 / np.log2(np.arange(2, ks[-1] + 2)), dtype=torch.float64, device=dev)
+    at_k = torch.zeros((n_users, len(ks), 4), dtype=torch.float64, device=dev)
+    scalar = torch.zeros((n_users, 4), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    ws = _workspace(lib.kgat_eval_rank_metrics_workspace_bytes(above.numel()), dev)
+    ks_host = (ctypes.c_int32 * len(ks))(*ks)
+    with _timed("eval_rank_metrics", (n_users, above.numel(), len(ks))):
+        check(lib.kgat_eval_rank_metrics(n_users, n_items, _ptr(above), _ptr(test_ptr), _ptr(test_items), above.numel(),
+                                         _ptr(n_candidates), len(ks), ctypes.cast(ks_host, ctypes.c_void_p), _ptr(disc),
+                                         _ptr(ws), ws.numel(), _ptr(at_k), _ptr(scalar), _stream(above)),
+              "kgat_eval_rank_metrics")
+    return at_k, scalar
+
+
 # ---------------------------------------------------------------- TransR link prediction (models.py:120-126)
 def transr_project_supported(d, k):
     return bool(_lib.load().kgat_transr_project_supported(int(d), int(k)))

@@ -160,6 +160,16 @@ def _cutoffs(text):
     return ks
 
 
+def _rank_cutoffs(text):
+    try:
+        ks = [int(x) for x in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("a comma-separated list of integers, e.g. 20,200,1000")
+    if not 1 <= len(ks) <= 64 or ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise argparse.ArgumentTypeError("1 to 64 ascending, distinct cut-offs >= 1")
+    return ks
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_dir", default=None)
@@ -205,6 +215,15 @@ def parse_args(argv=None):
                     help="evaluation cut-offs, ascending (the KGAT paper's table: 20,40,60,80,100; at most 8, each <= "
                          "128).  The default keeps recall@20 / ndcg@20; a longer list logs recall, ndcg, precision and "
                          "hit ratio at every cut-off (metrics.calc_metrics)")
+    # (both absent from the namespace unless given: a run without them has the arguments - and the --log_json "args" -
+    #  it had before they existed; read with getattr below)
+    ap.add_argument("--rank_metrics", type=int, choices=(0, 1), default=argparse.SUPPRESS,
+                    help="1: at every evaluation also rank EVERY held-out item (metrics.calc_rank_metrics: one counting "
+                         "sweep, no list, so no 128) and log a rank_metrics line - recall, ndcg, precision and hit ratio "
+                         "at --rank_Ks, MRR, MAP, AUC and the mean rank")
+    ap.add_argument("--rank_Ks", type=_rank_cutoffs, default=argparse.SUPPRESS, metavar="K[,K...]",
+                    help="cut-offs of --rank_metrics, ascending, any depth (default 20,200,1000; cut-offs beyond the "
+                         "number of items are left out)")
     ap.add_argument("--grad_digest", action="store_true",
                     help="print |grad| sums of the first CF step (to compare an N-GPU run with the one-GPU run)")
     ap.add_argument("--explain", type=int, default=0, metavar="N",
@@ -410,6 +429,19 @@ def _run(args, argv):
             for name, g, seen, held in (("valid", train_g, train_dict, valid_dict), ("test", test_g, train_valid_dict, test_dict)):
                 g.edata["w"] = model.compute_attention(g)
                 emb = model.gnn(g, g.ndata["id"])
+                if getattr(args, "rank_metrics", 0):
+                    rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
+                    rank_Ks = [k for k in rank_Ks if k <= plans[name].n_items] or [plans[name].n_items]
+                    m = metrics.calc_rank_metrics(emb, seen, held, ds.item_id_range, Ks=rank_Ks, plan=plans[name])
+                    for metric in metrics.RANK_SCALAR_NAMES:
+                        rec["%s_%s" % (name, metric)] = float(m[metric])
+                    for j, k in enumerate(rank_Ks):
+                        for metric in metrics.METRIC_NAMES:
+                            rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                    say("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f | %s" % (
+                        name, m["auc"], m["mrr"], m["map"], m["mean_rank"],
+                        " ".join("recall@%d %.5f ndcg@%d %.5f" % (k, m["recall"][j], k, m["ndcg"][j])
+                                 for j, k in enumerate(rank_Ks))))
                 if args.Ks == [20]:
                     rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
                         emb, seen, held, ds.item_id_range, K=20, plan=plans[name])

@@ -855,6 +855,46 @@ int kgat_eval_metrics_at_ks(int64_t n_users, int K, const int32_t* topk_items, c
                             const int32_t* test_items, int n_ks, const int32_t* ks, const double* disc, double* out,
                             kgat_stream_t stream);
 
+/* (ABI 16, additive) The exact rank of every held-out item, at any depth: no candidate buffer, so no K.
+ * kgat_eval_rank_f32 takes the inputs of kgat_eval_topk_f32 (itemT from kgat_eval_items_kmajor_f32; the train CSR
+ * ascending and de-duplicated, n_train = train_ptr[n_users] entries) and the test CSR (ascending positions, duplicates
+ * kept, n_test = test_ptr[n_users] entries).  With
+ *   s'(u,i) = 0.0f if drop_train == 0 and i is a training item of u (metric.py:50), else score(u,i)   (metric.py:48)
+ *   candidates(u) = every item position (drop_train == 0, "mask") | the positions not in train(u) ("drop")
+ * above[e] (int32, n_test entries in test-CSR order) for the entry e of user u at item position t is
+ *   #{ i in candidates(u), i != t : s'(u,i) > s'(u,t) or (s'(u,i) == s'(u,t) and i < t) }
+ * - IEEE compares, -0 equal to +0, the lower position first: the total order of kgat_eval_topk_f32, whose scores
+ * score(u,i) has bit for bit (the same v_mfma_f32_32x32x2_f32 chain, k order and zero padding: above[e] < K  <=>
+ * topk_items[u][above[e]] == t).  The rank is above + 1.  In drop mode a test entry that is a training item is never
+ * ranked: above = -1.  A duplicated test entry gets the same value twice.  target_score (optional, fp32, n_test): s'(u,t).
+ * No limit on a user's list length: the lists are processed in groups of 16 thresholds.
+ * kgat_eval_rank_supported(F): the widths of kgat_eval_topk_supported at K = 32 (F <= ~1100).  Errors before any
+ * device work: bad sizes / null pointers KGAT_E_BADARG, F outside the range KGAT_E_UNSUPPORTED, workspace_bytes <
+ * kgat_eval_rank_workspace_bytes KGAT_E_WORKSPACE (the slot table and one fp32 score per train and test entry).
+ * Item segments add integer counts into the zeroed output: exact, order-independent, bitwise reproducible.
+ * kgat_eval_rank_metrics: per user, over the DISTINCT test items with above >= 0, their 0-based ranks in ascending
+ * order a_0 < ... < a_{T-1}, and C = n_candidates[u] (device int32: n_items, or n_items - |train(u)| in drop mode):
+ *   out_at_k[u][j] = { recall = hits / |test list with duplicates| (metric.py:5-7,24,61; 0 for an empty list),
+ *     ndcg = sum of disc[a] over the hits / sum of disc[0 .. hits) (metric.py:23-34, method 1), precision = hits / ks[j],
+ *     hit ratio = 1 if any hit }, hits = #{ a < ks[j] }  - n_users x n_ks x 4 doubles, the definitions of
+ *     kgat_eval_metrics_at_ks, for 1 <= n_ks <= 64 cut-offs ks[j] (a HOST array, ascending, 1 <= ks[j] <= n_items);
+ *     disc[ks[n_ks - 1]] = 1 / log2(r + 2) in fp64, host-computed, summed in ascending rank order.
+ *   out_scalar[u] = { mrr = 1 / (a_0 + 1), ap = (1/T) sum_j (j + 1) / (a_j + 1),
+ *     auc = 1 - sum_j (a_j - j) / (T (C - T)) (0 when C == T), mean_rank = (1/T) sum_j (a_j + 1) }; all 0 when T == 0.
+ * workspace: kgat_eval_rank_metrics_workspace_bytes(n_test) (the users' ranks, compacted and in ascending order). */
+int kgat_eval_rank_supported(int F);
+size_t kgat_eval_rank_workspace_bytes(int64_t n_users, int64_t n_items, int F, int64_t n_train, int64_t n_test);
+int kgat_eval_rank_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
+                       int64_t emb_stride, const float* itemT, const int32_t* train_ptr, const int32_t* train_items,
+                       int64_t n_train, const int32_t* test_ptr, const int32_t* test_items, int64_t n_test,
+                       int drop_train, void* workspace, size_t workspace_bytes, int32_t* above, float* target_score,
+                       kgat_stream_t stream);
+size_t kgat_eval_rank_metrics_workspace_bytes(int64_t n_test);
+int kgat_eval_rank_metrics(int64_t n_users, int64_t n_items, const int32_t* above, const int32_t* test_ptr,
+                           const int32_t* test_items, int64_t n_test, const int32_t* n_candidates, int n_ks,
+                           const int32_t* ks, const double* disc, void* workspace, size_t workspace_bytes,
+                           double* out_at_k, double* out_scalar, kgat_stream_t stream);
+
 /* ---------------------------------------------------------------- edge weights without attention, node dropout (ABI 15)
  * kgat_edge_norm_f32: the weights g.edata['w'] that reference models.py:63 multiplies by when kgat.py:27,139-145 runs
  * with --use_attention False (there nothing ever writes them; the adjacency meant is the Laplacian the commented-out
