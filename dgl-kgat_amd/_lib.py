@@ -34,6 +34,7 @@ SOURCES = {
     "kgat_sage.hip": [],
     "kgat_edge_weights.hip": [],
     "kgat_att_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "kgat_gat.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -199,6 +200,14 @@ SIGNATURES = {
     "kgat_transr_project_f32": (_i32, [_i64, _i64, _i32, _i32, _p, _p, _i64, _p, _p, C.c_float, _p, _p, _p]),
     "kgat_transr_rank_supported": (_i32, [_i32]),
     "kgat_transr_rank_f32": (_i32, [_i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    # dgl.nn.pytorch.conv.GATConv's aggregation (u_add_v, leaky_relu, edge_softmax, u_mul_e -> sum) in one walk, and
+    # its backward (ABI 16, additive)
+    "kgat_gat_supported": (_i32, [_i32, _i32]),
+    "kgat_gat_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "kgat_gat_fwd_f32": (_i32, [_i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, C.c_float, C.c_float, C.c_uint64,
+                                _p, _p, _p, _p, _sz, _p]),
+    "kgat_gat_bwd_f32": (_i32, [_i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                C.c_float, C.c_float, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

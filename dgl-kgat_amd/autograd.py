@@ -9,6 +9,8 @@
   "graphsage"); backward over the reversed graph's CSR.
 * ``max_reduce`` - update_all(u_mul_e | copy_src, max) (kgat_spmm_umule_max_f32).  Forward only: it lives here to refuse,
   in one place, inputs that would need a backward.
+* ``gat_aggregate`` - the message passing of DGL's GATConv (kgat_gat_fwd_f32 / kgat_gat_bwd_f32): logits, destination softmax,
+  attention dropout and the weighted sum per head in one walk; backward towards ft, el and er.
 * ``kgat_attention`` - the fused attention (logits + destination softmax, models.py:135-154) as one unit that
   differentiates towards the entity table, W_R and the relation embeddings.
 """
@@ -475,3 +477,81 @@ def gnn_train(g, h0, weights, slope=0.01, drop_p=0.0, seed=0, forms=None, edge_d
             flat.append(w)
     return _GNNTrain.apply(g, float(slope), float(drop_p), int(seed), forms, (float(edge_drop_p), int(edge_seed)), h0,
                            *flat)
+
+
+class _GATAggregate(torch.autograd.Function):
+    """GATConv's aggregation (kgat_gat_fwd_f32) and its backward (kgat_gat_bwd_f32).  Saved: ft, el, er, out and the
+    (N, H) row maximum and denominator; nothing edge-sized."""
+
+    @staticmethod
+    def forward(ctx, ft, el, er, g, slope, p, seed):
+        st = g._st
+        ftc, elc, erc = ft.detach().contiguous(), el.detach().contiguous(), er.detach().contiguous()
+        out, m, l = ops.gat_forward(st.csr(ftc.device), ftc, elc, erc, slope, p, seed)
+        ctx.g, ctx.slope, ctx.p, ctx.seed = g, slope, p, seed
+        ctx.save_for_backward(ftc, elc, erc, m, l, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        ft, el, er, m, l, out = ctx.saved_tensors
+        st = ctx.g._st
+        dev = g_out.device
+        g_ft, g_el, g_er = ops.gat_backward(st.csr(dev), st.csr_rev(dev), ft, el, er, m, l, out, g_out.contiguous(),
+                                            ctx.slope, ctx.p, ctx.seed)
+        need = ctx.needs_input_grad
+        return (g_ft if need[0] else None, g_el if need[1] else None, g_er if need[2] else None, None, None, None, None)
+
+
+def _gat_restated(st, ft, el, er, slope, p, seed):
+    """The aggregation restated in torch operators over the COO (under torch's autograd), for (H, F) outside
+    ops.gat_supported: the same values to rounding, in the kernel's order - the weighted sum of exp(s - m) first, one
+    division by the denominator per output element.  torch's scatter adds are unordered atomics, so the arithmetic runs in
+    fp64 (forward and, through the casts, backward) and the results are rounded to fp32 once: their order then shows in
+    the last bit at most, where in fp32 it showed as several ulps on a hub's gradient."""
+    dev = ft.device
+    n, H, _ = ft.shape
+    src, dst = (t.long() for t in st.coo(dev))
+    ft64, el64, er64 = ft.double(), el.double(), er.double()
+    s = torch.nn.functional.leaky_relu(el64[src] + er64[dst], slope)
+    m = torch.full((n, H), float("-inf"), dtype=torch.float64, device=dev).scatter_reduce(
+        0, dst.unsqueeze(1).expand(-1, H), s.detach(), "amax")
+    pe = torch.exp(s - m[dst])
+    l = torch.zeros((n, H), dtype=torch.float64, device=dev).index_add(0, dst, pe)
+    if p > 0:
+        keep = torch.as_tensor(ops.dropout_keep_mask(seed, src.numel(), H, p), device=dev)
+        cpe = pe * keep.to(pe.dtype) * (1.0 / (1.0 - p))
+    else:
+        cpe = pe
+    num = torch.zeros_like(ft64).index_add(0, dst, cpe.unsqueeze(-1) * ft64[src])
+    return (num / torch.where(l > 0, l, torch.ones_like(l)).unsqueeze(-1)).to(ft.dtype)  # (rows without in-edges: 0 / 1)
+
+
+def gat_aggregate(g, ft, el, er, negative_slope=0.2, attn_drop=0.0, seed=0):
+    """rst[v,h,:] = sum_{e:u->v} attn_drop(a)[e,h] * ft[u,h,:] with a = edge_softmax(leaky_relu(el[u] + er[v])) per
+    head: the message passing of DGL's GATConv as one differentiable unit (gradients to ft, el and er).  ft (N, H, F),
+    el, er (N, H) float32.  The attention is never formed as an edge tensor; attn_drop keeps edge e, head h iff
+    ops.dropout_keep_mask(seed, E, H, attn_drop)[e, h]."""
+    if ft.dim() != 3 or tuple(el.shape) != tuple(ft.shape[:2]) or tuple(er.shape) != tuple(ft.shape[:2]):
+        raise ValueError("gat_aggregate: ft must be (N, H, F) and el, er (N, H); got %s, %s, %s"
+                         % (tuple(ft.shape), tuple(el.shape), tuple(er.shape)))
+    if ft.shape[0] != g.number_of_nodes():
+        raise ValueError("node feature has %d rows, graph has %d nodes" % (ft.shape[0], g.number_of_nodes()))
+    if g.partition is not None:
+        from .graph import DGLError
+        raise DGLError("gat_aggregate on a partitioned graph is not supported: a shard holds only part of a source's "
+                       "out-edges; use the unsharded graph")
+    for name, t in (("ft", ft), ("el", el), ("er", er)):
+        if not t.is_cuda:
+            raise ops.KGATLibraryError("%s is on %s: the graph attention only runs on a HIP device (no CPU "
+                                       "implementation exists in this package)" % (name, t.device))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    if not 0.0 <= float(attn_drop) < 1.0:
+        raise ValueError("gat_aggregate: attn_drop must be in [0, 1), got %r" % (attn_drop,))
+    if not 0.0 <= float(negative_slope) <= 1.0:
+        raise ValueError("gat_aggregate: negative_slope must be in [0, 1], got %r" % (negative_slope,))
+    if ops.gat_supported(ft.shape[1], ft.shape[2]):
+        return _GATAggregate.apply(ft, el, er, g, float(negative_slope), float(attn_drop), int(seed))
+    return _gat_restated(g._st, ft, el, er, float(negative_slope), float(attn_drop), int(seed))

@@ -1,6 +1,6 @@
 """Make this package answer to the module names the reference imports
 (``import dgl``, ``import dgl.function as fn``, ``from dgl.nn.pytorch.softmax import
-edge_softmax``, ``from dgl.nn.pytorch.conv import SAGEConv`` - models.py:4-6, dataset.py:3),
+edge_softmax``, ``from dgl.nn.pytorch.conv import SAGEConv`` - models.py:4-6, dataset.py:3 - and ``GATConv`` beside it),
 so reference-style model code runs over the HIP kernels without edits."""
 import sys
 import types
@@ -11,6 +11,7 @@ def install_as_dgl(force=False):
         raise RuntimeError("a real `dgl` is already imported; pass force=True to shadow it")
     import dgl_kgat_amd as pkg
     from . import function, graph, softmax
+    from .gat_layer import GATConv
     from .sage_layer import SAGEConv
 
     dgl = types.ModuleType("dgl")
@@ -21,6 +22,7 @@ def install_as_dgl(force=False):
     pt = types.ModuleType("dgl.nn.pytorch")
     conv = types.ModuleType("dgl.nn.pytorch.conv")
     conv.SAGEConv = SAGEConv  # models.py:6; the graphsage branch (sage_layer.py)
+    conv.GATConv = GATConv    # the plain graph-attention baseline (gat_layer.py)
     nn.pytorch, pt.softmax, pt.conv = pt, softmax, conv
     dgl.nn = nn
     mods = {"dgl": dgl, "dgl.function": function, "dgl.nn": nn, "dgl.nn.pytorch": pt,

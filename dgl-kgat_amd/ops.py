@@ -826,6 +826,66 @@ def spmm_max4(indptr, col, row_of, X, w=None, eid=None, want_arg=True, rows=None
     return out.view(n_rows, Q, 4), arg_edge, arg_slot
 
 
+def gat_supported(H, F):
+    """The (heads, features per head) kgat_gat_fwd_f32 / kgat_gat_bwd_f32 cover: H F in {16, 32, 64, 128}, F % 4 == 0."""
+    return bool(_lib.load().kgat_gat_supported(int(H), int(F)))
+
+
+def _gat_operands(csr, ft, el, er):
+    ft = _need(ft, torch.float32, "ft")
+    if ft.dim() != 3:
+        raise ValueError("ft must be (N, H, F), got %s" % (tuple(ft.shape),))
+    n, H, F = ft.shape
+    el = _need(el, torch.float32, "el", (n, H))
+    er = _need(er, torch.float32, "er", (n, H))
+    indptr = _need(csr.indptr, torch.int32, "indptr", (n + 1,))
+    col = _need(csr.col, torch.int32, "col")
+    row_of = _need(csr.row_of, torch.int32, "row_of", col.shape)
+    eid = _need(csr.eid, torch.int32, "eid", col.shape)
+    return ft, el, er, (n, col.numel(), H, F), (indptr, col, row_of, eid)
+
+
+def _gat_workspace(n, e, H, F, backward, device):
+    return _workspace(_lib.load().kgat_gat_workspace_bytes(n, e, H, F, int(backward)), device)
+
+
+def gat_forward(csr, ft, el, er, negative_slope=0.2, drop_p=0.0, seed=0):
+    """(out, m, l) of kgat_gat_fwd_f32: GATConv's aggregation over the destination-major `csr` (indptr, col, eid,
+    row_of) - out[v,h,:] = sum_{e->v} c a ft[src e, h, :] with a the destination softmax of
+    leaky_relu(el[src] + er[dst]) per head and c the attention dropout's factor
+    (dropout_keep_mask(seed, E, H, drop_p)[edge id, h]) - plus the row maximum m and the denominator l (N, H) the
+    backward recomputes a from.  ft (N, H, F), el, er (N, H) float32; (H, F) as gat_supported."""
+    ft, el, er, (n, e, H, F), graph = _gat_operands(csr, ft, el, er)
+    out = torch.empty_like(ft)
+    m, l = torch.empty_like(el), torch.empty_like(el)
+    ws = _gat_workspace(n, e, H, F, False, ft.device)
+    with _timed("gat_fwd", (e, n, H, F)):
+        check(_lib.load().kgat_gat_fwd_f32(n, e, H, F, *[_ptr(t) for t in graph], _ptr(ft), _ptr(el), _ptr(er),
+                                           float(negative_slope), float(drop_p), int(seed) & (2 ** 64 - 1), _ptr(out),
+                                           _ptr(m), _ptr(l), _ptr(ws), ws.numel(), _stream(ft)), "kgat_gat_fwd_f32")
+    return out, m, l
+
+
+def gat_backward(csr, csr_rev, ft, el, er, m, l, out, g_out, negative_slope=0.2, drop_p=0.0, seed=0):
+    """(g_ft, g_el, g_er) of kgat_gat_bwd_f32 from what gat_forward returned and the gradient at `out`: one walk over
+    `csr` and one over the reversed graph's `csr_rev`, the attention recomputed from m and l in both."""
+    ft, el, er, (n, e, H, F), graph = _gat_operands(csr, ft, el, er)
+    m = _need(m, torch.float32, "m", el.shape)
+    l = _need(l, torch.float32, "l", el.shape)
+    out = _need(out, torch.float32, "out", ft.shape)
+    g_out = _need(g_out, torch.float32, "g_out", ft.shape)
+    rev = (_need(csr_rev.indptr, torch.int32, "rev.indptr", (n + 1,)), _need(csr_rev.col, torch.int32, "rev.col", (e,)),
+           _need(csr_rev.row_of, torch.int32, "rev.row_of", (e,)), _need(csr_rev.eid, torch.int32, "rev.eid", (e,)))
+    g_ft, g_el, g_er = torch.empty_like(ft), torch.empty_like(el), torch.empty_like(el)
+    ws = _gat_workspace(n, e, H, F, True, ft.device)
+    with _timed("gat_bwd", (e, n, H, F)):
+        check(_lib.load().kgat_gat_bwd_f32(n, e, H, F, *[_ptr(t) for t in graph + rev], _ptr(ft), _ptr(el), _ptr(er),
+                                           _ptr(m), _ptr(l), _ptr(out), _ptr(g_out), float(negative_slope),
+                                           float(drop_p), int(seed) & (2 ** 64 - 1), _ptr(g_ft), _ptr(g_el), _ptr(g_er),
+                                           _ptr(ws), ws.numel(), _stream(ft)), "kgat_gat_bwd_f32")
+    return g_ft, g_el, g_er
+
+
 REDUCE ={"sum": 0, "mean": 1}
 ACT = {None: 0, "none": 0, "relu": 1}
 

@@ -1081,6 +1081,45 @@ int kgat_transr_rank_f32(int64_t n_q, int64_t n_c, int64_t c0, int k, const floa
                          const float* n2, const int32_t* filter_ptr, const int32_t* filter_ids, int64_t n_filter,
                          int32_t* lt, int32_t* eq, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- multi-head graph attention (additive within ABI 16)
+ * The aggregation of dgl.nn.pytorch.conv.GATConv (DGL 0.4.x, homogeneous graph) and its backward: what
+ *   graph.apply_edges(fn.u_add_v('el', 'er', 'e')); e = leaky_relu(e); a = edge_softmax(graph, e)
+ *   graph.update_all(fn.u_mul_e('ft', 'a', 'm'), fn.sum('m', 'ft'))              (a = attn_drop(a) in between)
+ * computes, in one walk over the destination-major CSR with no edge-sized tensor.  ft [N x H x F], el, er [N x H]:
+ *   z[e,h] = el[src e, h] + er[dst e, h];  s = z > 0 ? z : negative_slope z;  m[v,h] = max_{e -> v} s;
+ *   p = exp(s - m[dst e, h]);  l[v,h] = sum_{e -> v} p  (dropped edges included, as DGL);
+ *   out[v,h,:] = (sum_{e -> v} c[e,h] p ft[src e, h, :]) / l[v,h]   - one correctly rounded division per element;
+ * c[e,h] = 0 or 1 / (1 - drop_p): edge e, head h is kept iff the counter hash of the training entries over element
+ * (row = edge id, d = H, col = h) says so (ops.dropout_keep_mask(seed, E, H, drop_p)[e, h]); eid maps CSR position ->
+ * edge id and is required with drop_p > 0.  Rows without in-edges: out = 0, l = 0.  m, l [N x H] are outputs of the
+ * forward and inputs of the backward.  m is formed without a rescale: leaky_relu (0 <= negative_slope <= 1) and the
+ * fp32 add are monotone, so m = leaky_relu(max_u el[u,h] + er[v,h]) - kgat_spmm_umule_max_f32 on el, then one pass.
+ *
+ * kgat_gat_bwd_f32: with sg[v,h] = <g_out[v,h,:], out[v,h,:]>, gamma = <g_out[v,h,:], ft[u,h,:]>, a = p / l,
+ *   g_z = a (c gamma - sg[v,h]) (z > 0 ? 1 : negative_slope)
+ *   g_er[v,h] = sum_{e -> v} g_z;   g_el[u,h] = sum_{u -> e} g_z;   g_ft[u,h,:] = sum_{u -> e} c a g_out[dst e, h, :]
+ * one walk over the forward CSR (g_er) and one over the reversed CSR (rev_*: rows = sources, col = destinations,
+ * rev_eid the edge ids; g_ft, g_el), each recomputing a from m and l; nothing edge-sized is stored.
+ *
+ * All walks use the sum kernel's tile decomposition with partials combined in run and tile order: no atomics, bitwise
+ * reproducible.  (H, F) with H F in {16, 32, 64, 128} and F % 4 == 0 (kgat_gat_supported), others KGAT_E_UNSUPPORTED.
+ * The whole graph per call: indptr [N + 1], col / row_of / eid [E].  ft, out, g_out, g_ft, el, m and the workspace
+ * 16-byte aligned; n_edges * H < 2^32.  Null pointer, negative size, slope or probability out of range:
+ * KGAT_E_BADARG; workspace below kgat_gat_workspace_bytes(n_nodes, n_edges, H, F, backward = 0 | 1): KGAT_E_WORKSPACE.
+ * Every check precedes any device work. */
+int kgat_gat_supported(int H, int F);
+size_t kgat_gat_workspace_bytes(int64_t n_nodes, int64_t n_edges, int H, int F, int backward);
+int kgat_gat_fwd_f32(int64_t n_nodes, int64_t n_edges, int H, int F, const int32_t* indptr, const int32_t* col,
+                     const int32_t* row_of, const int32_t* eid, const float* ft, const float* el, const float* er,
+                     float negative_slope, float drop_p, uint64_t seed, float* out, float* m, float* l, void* workspace,
+                     size_t workspace_bytes, kgat_stream_t stream);
+int kgat_gat_bwd_f32(int64_t n_nodes, int64_t n_edges, int H, int F, const int32_t* indptr, const int32_t* col,
+                     const int32_t* row_of, const int32_t* eid, const int32_t* rev_indptr, const int32_t* rev_col,
+                     const int32_t* rev_row_of, const int32_t* rev_eid, const float* ft, const float* el, const float* er,
+                     const float* m, const float* l, const float* out, const float* g_out, float negative_slope,
+                     float drop_p, uint64_t seed, float* g_ft, float* g_el, float* g_er, void* workspace,
+                     size_t workspace_bytes, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
