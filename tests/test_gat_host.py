@@ -1,5 +1,6 @@
 """Host-side checks of the graph-attention layer (no GPU): the four ABI entries and their argument refusals, the
-parameters and state_dict of GATConv, the dgl shim, and the CPU refusals."""
+parameters and state_dict of GATConv, the dgl shim, the CPU refusals, and what the GPU tests' helpers claim: the
+restatement, the per-element metric and the rows the planted graph holds."""
 import ctypes as C
 import os
 import re
@@ -205,6 +206,74 @@ def test_cpu_tensors_and_other_refusals():
     # the (E, H) refusal of edge_softmax stays
     with pytest.raises(NotImplementedError):
         K.edge_softmax(_ring(), torch.randn(5, 4))
+
+
+@pytest.mark.parametrize("hf, te", [(16, 256), (32, 256), (64, 256), (128, 128)])
+def test_planted_graph_holds_every_finish_case(hf, te):
+    """What tests/test_gpu_gat_shapes.py relies on: from indptr and the tile size alone, the (tile, slot) that owns each
+    row and the number of tiles its chain runs on, as gat_finish_kernel derives them."""
+    deg = _gat_ref.planted_degrees(te)
+    src, dst = _gat_ref.graph_from_degrees(deg, 3)
+    n, e = len(deg), int(deg.sum())
+    assert _lib.load().kgat_spmm_tile_edges(e, hf) == te                  # the tile the call takes is the one assumed
+    assert len(src) == e and np.array_equal(np.bincount(dst, minlength=n), deg) and src.min() >= 0 and src.max() < n
+    assert not np.array_equal(dst, np.sort(dst))                          # edge ids are shuffled
+    assert deg[0] == 0 and deg[-1] == 0 and (deg[1:-1] == 0).sum() >= 6
+    indptr = np.concatenate([[0], np.cumsum(deg)])
+    owners = _gat_ref.row_owners(indptr, te)
+    for slot in (0, 1):
+        have = {k for (_, s, k) in owners.values() if s == slot}
+        assert have >= set(_gat_ref.CHAINS) | {0}, (slot, have)
+    ends = indptr[1:][deg > 0]
+    assert deg[1] == te and indptr[1] == 0                                # a row that is exactly tile 0
+    assert any(deg[i] == deg[i + 1] == te // 2 and indptr[i] % te == 0 for i in range(n - 1))
+    single = np.nonzero(deg == 1)[0]
+    assert any(indptr[r] % te == 0 and deg[r - 1] == 1 for r in single)   # single-edge rows on both sides of a tile edge
+    assert any(k >= _gat_ref.LONG_CHAIN and indptr[r + 1] % te == 0 for r, (_, s, k) in owners.items())
+    assert any(k == 2 and indptr[r] % te == 0 and indptr[r + 1] % te == 0 for r, (_, s, k) in owners.items())
+    assert (ends % te == 0).sum() >= 5
+    assert e % te == 1 and deg[-2] == 1                                   # the last tile holds one edge, a row of its own
+    # a wavefront of the finish holds 64 / LPR consecutive (tile, slot) items: one of them has a short and a long chain
+    spw = 64 // (hf // 4)
+    items = {2 * b + s: k for (b, s, k) in owners.values() if s >= 0}
+    mixed = [w for w in range(0, 2 * -(-e // te), spw)
+             if any(items.get(i, -1) >= _gat_ref.LONG_CHAIN for i in range(w, w + spw))
+             and any(0 <= items.get(i, -1) < _gat_ref.LONG_CHAIN for i in range(w, w + spw))]
+    assert mixed, "no wavefront with a short and a long chain"
+    if spw > 2:                                                           # (two items are one tile: its first row ends inside it)
+        assert any(any(1 <= items.get(i, -1) < _gat_ref.LONG_CHAIN for i in range(w, w + spw)) for w in mixed)
+
+
+def test_per_element_metric():
+    """term_scales against a loop over the edges, and scaled_error's two halves."""
+    rng = np.random.default_rng(4)
+    n, e, H, F, slope, p = 7, 30, 2, 3, 0.2, 0.5
+    src, dst = rng.integers(0, n - 1, e), rng.integers(1, n, e)          # node 6 has no out-edges, node 0 no in-edges
+    ft, el, er, g = (rng.standard_normal(s) for s in ((n, H, F), (n, H), (n, H), (n, H, F)))
+    keep = rng.random((e, H)) < 0.5
+    t = [torch.as_tensor(x) for x in (ft, el, er, g)]
+    S = [x.numpy() for x in _gat_ref.term_scales(torch.as_tensor(src), torch.as_tensor(dst), n, *t, slope, torch.as_tensor(keep), p)]
+    out = _gat_ref.gat_aggregate(torch.as_tensor(src), torch.as_tensor(dst), n, *t[:3], slope, torch.as_tensor(keep), p).numpy()
+    want = [np.zeros((n, H, F)), np.zeros((n, H, F)), np.zeros((n, H)), np.zeros((n, H))]
+    for h in range(H):
+        z = el[src, h] + er[dst, h]
+        s = np.where(z > 0, z, slope * z)
+        for i in range(e):
+            u, v = src[i], dst[i]
+            a = np.exp(s[i]) / np.exp(s[dst == v]).sum()
+            c = keep[i, h] / (1 - p)
+            want[0][v, h] += c * a * np.abs(ft[u, h])
+            want[1][u, h] += c * a * np.abs(g[v, h])
+            t_ = a * (c * np.abs(g[v, h] * ft[u, h]).sum() + np.abs(g[v, h] * out[v, h]).sum()) * (1.0 if z[i] > 0 else slope)
+            want[2][u, h] += t_
+            want[3][v, h] += t_
+    for a, b in zip(S, want):
+        assert np.allclose(a, b, rtol=1e-12, atol=0)
+    assert (S[0][0] == 0).all() and (S[3][0] == 0).all() and (S[1][6] == 0).all() and (S[2][6] == 0).all()
+    assert _gat_ref.scaled_error([1.0, 0.0, 2.5], [1.0, 0.0, 2.0], [4.0, 0.0, 2.0]) == 0.25
+    assert _gat_ref.scaled_error([0.0], [0.0], [0.0]) == 0.0
+    with pytest.raises(AssertionError):
+        _gat_ref.scaled_error([1.0, 1e-30], [1.0, 0.0], [1.0, 0.0])      # a value where no term exists
 
 
 def test_restatement_is_the_per_node_softmax():
