@@ -21,8 +21,9 @@
 // The order is total - (score descending, position ascending) - so the result does not depend on how
 // items were cut into tiles and segments: bitwise reproducible, equal to a stable descending sort.
 //
-// Launch 2's body is kgat_eval_sweep_body.h and the plan kgat_eval_common.h: kgat_eval_topk.hip (ranked lists with
-// scores for K up to 128, metrics at several cut-offs) sweeps with the same text over a larger candidate buffer.
+// Launch 2's body is kgat_eval_sweep_body.h around the tile walk of kgat_eval_walk.h; the plan and the launch are
+// kgat_eval_common.h's.  kgat_eval_topk.hip (ranked lists with scores for K up to 128, metrics at several cut-offs)
+// includes the same body over a larger candidate buffer, kgat_eval_rank.hip (exact ranks) the same walk.
 #include "kgat_eval_common.h"
 
 namespace kgat {
@@ -101,44 +102,13 @@ __global__ __launch_bounds__(256) void eval_merge_kernel(
   }
 }
 
-// The sweep at K <= 32 (declared in kgat_eval_common.h: kgat_eval_topk_f32 launches it too): the segments' partial
-// lists of every user into part_s / part_i [n_users][pl.n_lists][K]; tau_shared [n_users].
+// The sweep at K <= 32 (declared in kgat_eval_common.h: kgat_eval_topk_f32 launches it too).
 int eval_sweep_launch(const char* who, int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
                       int64_t emb_stride, const float* itemT, const int32_t* train_ptr, const int32_t* train_items, int K,
                       const EvalPlanH& pl, float* part_s, int32_t* part_i, unsigned* tau_shared, hipStream_t st) {
-  const int FP2 = eval_fp2(F);
-  const int nw = pl.nw;
-  for (int y = 0; y < pl.n_lists; ++y)   // (the kernel addresses a segment's fragments with 32-bit offsets)
-    KGAT_CHECK_ARG((int64_t)(pl.bounds.b[y + 1] - pl.bounds.b[y]) * FP2 * 256 < ((int64_t)1 << 32),
-                   "%s: a segment of %d tiles is beyond 4 GB of fragments", who, pl.bounds.b[y + 1] - pl.bounds.b[y]);
-  const int kg = eval_reg_kg(F);
-  const bool reg = kg > 0;
-  const size_t lds = EvalLds::per_wave_bytes(FP2, reg) * nw;
-  const unsigned gx = (unsigned)((n_users + 32 * nw - 1) / (32 * nw));
-#define KGAT_EVAL_LAUNCH(NW, KG_)                                                                                     \
-  do {                                                                                                                \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(eval_topk_kernel<NW, KG_>),                                 \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {                    \
-      set_error("%s: cannot reserve %zu bytes of LDS", who, lds);                                                     \
-      return KGAT_E_HIP;                                                                                              \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((eval_topk_kernel<NW, KG_>), dim3(gx, (unsigned)pl.n_lists), dim3(NW * 64), lds, st, n_users,  \
-                       user_ids, n_items, FP2, F, pl.bounds, emb, emb_stride, itemT,                                  \
-                       train_ptr, train_items, K, part_s, part_i, pl.n_lists > 1 ? tau_shared : nullptr);             \
-  } while (0)
-  if (pl.n_lists > 1 && hipMemsetAsync(tau_shared, 0, (size_t)n_users * 4, st) != hipSuccess) {
-    set_error("%s: cannot clear the shared thresholds", who);
-    return KGAT_E_HIP;
-  }
-  // ONE launch over (user blocks) x (item segments)
-  if (kg == 6) KGAT_EVAL_LAUNCH(4, 6);
-  else if (kg == 11) KGAT_EVAL_LAUNCH(4, 11);
-  else if (kg == 16) KGAT_EVAL_LAUNCH(4, 16);
-  else if (kg == 22) KGAT_EVAL_LAUNCH(4, 22);
-  else if (nw == 4) KGAT_EVAL_LAUNCH(4, 0);
-  else if (nw == 2) KGAT_EVAL_LAUNCH(2, 0);
-  else KGAT_EVAL_LAUNCH(1, 0);
-#undef KGAT_EVAL_LAUNCH
+  const auto kernel = eval_with_form<4>(eval_reg_kg(F), pl.nw, [](auto NW, auto KG) { return &eval_topk_kernel<NW(), KG()>; });
+  KGAT_RETURN_IF(eval_lists_sweep(who, kernel, kEvalCap, n_users, user_ids, n_items, F, emb, emb_stride, itemT, train_ptr,
+                                  train_items, K, pl, EvalListsWs{part_s, part_i, tau_shared}, st));
   KGAT_CHECK_LAUNCH("eval_topk");
   return KGAT_OK;
 }
@@ -177,8 +147,7 @@ int kgat_eval_items_kmajor_f32(int64_t n_items, int F, const float* emb, int64_t
 
 size_t kgat_eval_workspace_bytes(int64_t n_users, int64_t n_items, int F, int K) {
   if (n_users <= 0 || n_items <= 0 || !kgat_eval_supported(F, K)) return 256;
-  const EvalPlanH pl = eval_plan(n_users, n_items, F);
-  return 2 * align_up((size_t)n_users * pl.n_lists * K * 4, 256) + align_up((size_t)n_users * 4, 256) + 256;
+  return eval_lists_workspace_bytes(n_users, eval_plan(n_users, n_items, F), K);
 }
 
 int kgat_eval_recall_ndcg_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
@@ -201,16 +170,13 @@ int kgat_eval_recall_ndcg_f32(int64_t n_users, const int32_t* user_ids, int64_t 
     return KGAT_E_WORKSPACE;
   }
   const EvalPlanH pl = eval_plan(n_users, n_items, F);
-  Carver cv(workspace);
-  float* part_s = cv.take<float>((size_t)n_users * pl.n_lists * K);
-  int32_t* part_i = cv.take<int32_t>((size_t)n_users * pl.n_lists * K);
-  unsigned* tau_shared = cv.take<unsigned>((size_t)n_users);   // shared K-th best per user (order-preserving bits)
+  const EvalListsWs ws = eval_lists_carve(workspace, n_users, pl, K);
   hipStream_t st = as_stream(stream);
   const int rc = eval_sweep_launch("eval_recall_ndcg", n_users, user_ids, n_items, F, emb, emb_stride, itemT, train_ptr,
-                                   train_items, K, pl, part_s, part_i, tau_shared, st);
+                                   train_items, K, pl, ws.part_s, ws.part_i, ws.tau_shared, st);
   if (rc != KGAT_OK) return rc;
   hipLaunchKernelGGL(eval_merge_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, n_users, pl.n_lists, K,
-                     part_s, part_i, train_ptr, train_items, test_ptr, test_items, disc, recall_out, ndcg_out,
+                     ws.part_s, ws.part_i, train_ptr, train_items, test_ptr, test_items, disc, recall_out, ndcg_out,
                      topk_out);
   KGAT_CHECK_LAUNCH("eval_merge");
   return KGAT_OK;

@@ -1,9 +1,11 @@
-// Shared by the two evaluation translation units (kgat_eval.hip: K <= 32, recall / ndcg in the merge;
-// kgat_eval_topk.hip: K <= 128, ranked lists and metrics at several cut-offs): constants, the total order, the LDS
-// layout and the launch plan, each a function of the candidate buffer's size `cap`.  Not part of the ABI.
+// Shared by the three evaluation translation units (kgat_eval.hip: K <= 32, recall / ndcg in the merge;
+// kgat_eval_topk.hip: K <= 128, ranked lists and metrics at several cut-offs; kgat_eval_rank.hip: exact ranks at any
+// depth): constants, the total order, the LDS layout and the launch plan, each a function of the candidate buffer's
+// size `cap`, and the host side of a sweep's launch.  The sweep's device text is kgat_eval_walk.h.  Not part of the ABI.
 #pragma once
 #include <functional>
 #include <queue>
+#include <type_traits>
 #include <vector>
 #include "kgat_common.h"
 
@@ -215,7 +217,81 @@ static EvalPlanH eval_plan(int64_t n_users, int64_t n_items, int F, int cap = kE
   return p;
 }
 
-// kgat_eval.hip: the K <= 32 sweep over a plan made with the default buffer
+// ---------------------------------------------------------------------------------- launching a sweep (host)
+// (the kernels address a segment's fragments with 32-bit offsets)
+static int eval_check_segments(const char* who, const EvalPlanH& pl, int FP2) {
+  for (int y = 0; y < pl.n_lists; ++y)
+    KGAT_CHECK_ARG((int64_t)(pl.bounds.b[y + 1] - pl.bounds.b[y]) * FP2 * 256 < ((int64_t)1 << 32),
+                   "%s: a segment of %d tiles is beyond 4 GB of fragments", who, pl.bounds.b[y + 1] - pl.bounds.b[y]);
+  return KGAT_OK;
+}
+
+// The form of a width (kg = eval_reg_kg(F)) and a plan (nw = pl.nw) as compile-time values: returns fn(NW, KG), both
+// std::integral_constants.  A register form runs workgroups of REG_NW wavefronts - what eval_waves_per_block plans: 4
+// with the K <= 32 buffer and in the rank sweep, 2 with the wide buffers - the LDS form workgroups of nw.  fn is
+// instantiated for these seven forms and no other, so this ladder IS the set of kernels a family builds.
+template <int V> using EvalInt = std::integral_constant<int, V>;
+template <int REG_NW, typename Fn>
+static auto eval_with_form(int kg, int nw, Fn&& fn) {
+  if (kg == 6) return fn(EvalInt<REG_NW>{}, EvalInt<6>{});
+  if (kg == 11) return fn(EvalInt<REG_NW>{}, EvalInt<11>{});
+  if (kg == 16) return fn(EvalInt<REG_NW>{}, EvalInt<16>{});
+  if (kg == 22) return fn(EvalInt<REG_NW>{}, EvalInt<22>{});
+  if (nw == 4) return fn(EvalInt<4>{}, EvalInt<0>{});
+  if (nw == 2) return fn(EvalInt<2>{}, EvalInt<0>{});
+  return fn(EvalInt<1>{}, EvalInt<0>{});
+}
+
+// ONE launch of a sweep kernel over (blocks of 32 pl.nw columns) x (item segments), its LDS reserved first.
+template <typename Kernel, typename... Args>
+static int eval_launch_sweep(const char* who, Kernel kernel, int64_t n_cols, const EvalPlanH& pl, size_t lds_per_wave,
+                             hipStream_t st, Args... args) {
+  const size_t lds = lds_per_wave * pl.nw;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess) {
+    set_error("%s: cannot reserve %zu bytes of LDS", who, lds);
+    return KGAT_E_HIP;
+  }
+  const unsigned gx = (unsigned)((n_cols + 32 * pl.nw - 1) / (32 * pl.nw));
+  hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)pl.n_lists), dim3(pl.nw * 64), lds, st, args...);
+  return KGAT_OK;
+}
+
+// The workspace of the sweeps that keep lists: the segments' partial lists of every user, part_s / part_i
+// [n_users][pl.n_lists][K], and the shared K-th best per user (order-preserving bits), tau_shared [n_users].
+struct EvalListsWs { float* part_s; int32_t* part_i; unsigned* tau_shared; };
+static size_t eval_lists_workspace_bytes(int64_t n_users, const EvalPlanH& pl, int K) {
+  return 2 * align_up((size_t)n_users * pl.n_lists * K * 4, 256) + align_up((size_t)n_users * 4, 256) + 256;
+}
+static EvalListsWs eval_lists_carve(void* workspace, int64_t n_users, const EvalPlanH& pl, int K) {
+  Carver cv(workspace);
+  EvalListsWs ws;
+  ws.part_s = cv.take<float>((size_t)n_users * pl.n_lists * K);
+  ws.part_i = cv.take<int32_t>((size_t)n_users * pl.n_lists * K);
+  ws.tau_shared = cv.take<unsigned>((size_t)n_users);
+  return ws;
+}
+
+// The sweep of a family that keeps lists - `kernel`: eval_topk_kernel or eval_topk_wide_kernel at the plan's form, over
+// buffers of `cap` entries - into ws.
+template <typename Kernel>
+static int eval_lists_sweep(const char* who, Kernel kernel, int cap, int64_t n_users, const int32_t* user_ids,
+                            int64_t n_items, int F, const float* emb, int64_t emb_stride, const float* itemT,
+                            const int32_t* train_ptr, const int32_t* train_items, int K, const EvalPlanH& pl,
+                            const EvalListsWs& ws, hipStream_t st) {
+  const int FP2 = eval_fp2(F);
+  KGAT_RETURN_IF(eval_check_segments(who, pl, FP2));
+  if (pl.n_lists > 1 && hipMemsetAsync(ws.tau_shared, 0, (size_t)n_users * 4, st) != hipSuccess) {
+    set_error("%s: cannot clear the shared thresholds", who);
+    return KGAT_E_HIP;
+  }
+  return eval_launch_sweep(who, kernel, n_users, pl, EvalLds::per_wave_bytes(FP2, eval_reg_kg(F) > 0, cap), st, n_users,
+                           user_ids, n_items, FP2, F, pl.bounds, emb, emb_stride, itemT, train_ptr, train_items, K,
+                           ws.part_s, ws.part_i, pl.n_lists > 1 ? ws.tau_shared : nullptr);
+}
+
+// kgat_eval.hip: the K <= 32 sweep over a plan made with the default buffer (kgat_eval_topk_f32 launches it too; the
+// lists as three pointers: the library exports this name as it is)
 int eval_sweep_launch(const char* who, int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
                       int64_t emb_stride, const float* itemT, const int32_t* train_ptr, const int32_t* train_items, int K,
                       const EvalPlanH& pl, float* part_s, int32_t* part_i, unsigned* tau_shared, hipStream_t st);

@@ -15,9 +15,9 @@
 //     product is kept.  An output element of the MFMA depends on its own row and column alone, so the diagonal element
 //     carries the bits the sweep gives that pair.  (31 of 32 products are thrown away: about 1 % of the sweep's MFMAs
 //     for the test pairs, 4 % for the training pairs at the amazon-book shape.)
-//  3. eval_rank_sweep_kernel: the sweep of kgat_eval_sweep_body.h - 32 columns per wavefront, item tiles of 32, the
-//     register forms KG 6 / 11 / 16 / 22 and the LDS form, the same loads and the same MFMA chain - with the candidate
-//     handling replaced by counting: a score becomes a 64-bit key (order-preserving score bits, then the position
+//  3. eval_rank_sweep_kernel: the tile walk of the top-K sweeps (kgat_eval_walk.h, included here as there: 32 columns
+//     per wavefront, item tiles of 32, the register forms KG 6 / 11 / 16 / 22 and the LDS form) with counting in the
+//     place of the candidate handling: a score becomes a 64-bit key (order-preserving score bits, then the position
 //     descending), a threshold likewise, and `key > threshold` is ranks_before.  The sweep counts over ALL items with
 //     their raw scores; item segments add into the zeroed output with integer atomics.
 //  4. eval_rank_fix_kernel: one wavefront per user takes the training items out again (their raw scores from launch 2)
@@ -174,10 +174,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
   extern __shared__ __attribute__((aligned(16))) char s_raw[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int ul = lane & 31, half = lane >> 5;
-  constexpr bool REG = KG > 0;
-  constexpr int NT = KG > 16 ? 1 : 2;   // item tiles in flight, as the top-K sweep
   constexpr int G = kRankGroup;
-  char* base = s_raw + (size_t)w * rank_lds_per_wave(FP2, REG);
+  char* base = s_raw + (size_t)w * rank_lds_per_wave(FP2, KG > 0);
   unsigned long long* thr = reinterpret_cast<unsigned long long*>(base);   // [G][32]
   float* ub = reinterpret_cast<float*>(base + G * 32 * 8);
 
@@ -208,23 +206,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
       thr[g * 32 + ul] = key;
     }
   }
-  // B fragments: lane (slot ul, half) holds the user's elements k = 2s + half
-  float breg[REG ? KG * 8 : 1];
-  {
-    const float* row = emb + (size_t)user_ids[up] * emb_stride;
-    if constexpr (REG) {
-#pragma unroll
-      for (int s = 0; s < KG * 8; ++s) {
-        const int k = 2 * s + half;
-        breg[s] = (u_ok && k < F) ? row[k < F ? k : 0] : 0.f;
-      }
-    } else {
-      for (int s = 0; s < FP2; ++s) {
-        const int k = 2 * s + half;
-        ub[s * 64 + lane] = (u_ok && k < F) ? row[k] : 0.f;
-      }
-    }
-  }
+  const float* row = emb + (size_t)user_ids[up] * emb_stride;
+#define KGAT_EVAL_WALK_PART 1
+#include "kgat_eval_walk.h"   // REG, NT, U; breg[] / ub[] from `row`
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
 
@@ -233,125 +217,22 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
   for (int g = 0; g < G; ++g) cnt[g] = 0;
 
-  floatx16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  // acc[t][r]: slot ul, item position 32 (t0 + t) + (r & 3) + 8 (r >> 2) + 4 half
+#define KGAT_EVAL_WALK_PART 2
+#include "kgat_eval_walk.h"   // acc[NT] (acc[t][r]: slot ul), nan_padded_tail
   auto check = [&](int64_t t0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       if (t0 + t >= t_hi) break;  // wave-uniform
       const int ib = (int)((t0 + t) * kEvalTile) + 4 * half;
-      if ((t0 + t + 1) * kEvalTile > n_items) {   // the padded end of the last tile (wave-uniform): never counted
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (ib + (r & 3) + 8 * (r >> 2) >= n_items) acc[t][r] = __builtin_nanf("");
-      }
+      nan_padded_tail(t, t0 + t, ib);   // (never counted)
       if (gmax <= 4) rank_count_tile<4>(acc[t], ib, thr + ul, cnt);          // (wave-uniform)
       else if (gmax <= 8) rank_count_tile<8>(acc[t], ib, thr + ul, cnt);
       else if (gmax <= 12) rank_count_tile<12>(acc[t], ib, thr + ul, cnt);
       else rank_count_tile<kRankGroup>(acc[t], ib, thr + ul, cnt);
     }
   };
-
-  // The walk over the segment's tiles: the text of kgat_eval_sweep_body.h (same loads, same MFMA chain, same k order).
-  constexpr int U = 8;
-  typedef float floatx4 __attribute__((ext_vector_type(4)));
-  if constexpr (REG) {
-    static_assert(KG <= 22 && U == 8, "the step list below is written out for up to 2 x 22 steps of 2 halves");
-    const floatx16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float h0[4][NT], h1[4][NT], h2[4][NT], h3[4][NT];
-    const size_t seg_bytes = (size_t)(t_hi - t_lo) * KG * 2048;
-    const __amdgpu_buffer_rsrc_t seg_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(itemT) + (size_t)t_lo * KG * 512, 0, (int)(unsigned)seg_bytes, 0x00020000);
-    auto issue_half = [&](float (&a)[4][NT], int64_t tg, int g, int q) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int64_t tt = tg + t < t_hi ? tg + t : t_hi - 1;   // (a clamped duplicate tile is ignored below)
-        const unsigned soff = (unsigned)(((tt - t_lo) * KG + g) * 2 + q) * 1024u;
-        const floatx4 v = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(seg_rsrc, lane * 16, (int)soff, 0));
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[c][t] = v[c];
-      }
-    };
-    issue_half(h0, t_lo, 0, 0);
-    issue_half(h1, t_lo, 0, 1);
-    issue_half(h2, t_lo, 1, 0);
-#define KGAT_RANK_HALF(J, CUR, NXT)                                                                       \
-    if constexpr (J < 4 * KG) {                                                                           \
-      constexpr int j = J, g = (j / 2) % KG, q = j % 2, jn = j + 3, gn = (jn / 2) % KG, qn = jn % 2;      \
-      const int64_t tt = t0 + (j / 2 / KG) * NT, tn = t0 + (jn / 2 / KG) * NT;                            \
-      issue_half(NXT, tn, gn, qn);                                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                                                  \
-      if (tt < t_hi) { /* wave-uniform */                                                                 \
-        _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                     \
-          _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                  \
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(CUR[c][t], breg[g * U + 4 * q + c],             \
-                                                          (g == 0 && q == 0 && c == 0) ? zero16 : acc[t], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        if (g == KG - 1 && q == 1) check(tt);                                                             \
-      }                                                                                                   \
-    }
-#define KGAT_RANK_HALF4(J) KGAT_RANK_HALF(J, h0, h3) KGAT_RANK_HALF(J + 1, h1, h0) KGAT_RANK_HALF(J + 2, h2, h1) KGAT_RANK_HALF(J + 3, h3, h2)
-    for (int64_t t0 = t_lo; t0 < t_hi; t0 += 2 * NT) {
-      KGAT_RANK_HALF4(0) KGAT_RANK_HALF4(4) KGAT_RANK_HALF4(8) KGAT_RANK_HALF4(12) KGAT_RANK_HALF4(16) KGAT_RANK_HALF4(20)
-      KGAT_RANK_HALF4(24) KGAT_RANK_HALF4(28) KGAT_RANK_HALF4(32) KGAT_RANK_HALF4(36) KGAT_RANK_HALF4(40) KGAT_RANK_HALF4(44)
-      KGAT_RANK_HALF4(48) KGAT_RANK_HALF4(52) KGAT_RANK_HALF4(56) KGAT_RANK_HALF4(60) KGAT_RANK_HALF4(64) KGAT_RANK_HALF4(68)
-      KGAT_RANK_HALF4(72) KGAT_RANK_HALF4(76) KGAT_RANK_HALF4(80) KGAT_RANK_HALF4(84)   // (beyond 4 KG: compiled out)
-    }
-#undef KGAT_RANK_HALF4
-#undef KGAT_RANK_HALF
-  } else {
-    const floatx4* a_base = reinterpret_cast<const floatx4*>(itemT) + lane;
-    const int KGR = FP2 / U;                                     // k groups per tile group (FP2 is a multiple of U)
-    struct Pos { int64_t t0; int g; };
-    auto advance = [&](Pos& p) { if (++p.g == KGR) { p.g = 0; p.t0 += NT; } };
-    auto issue = [&](float (&a)[U][NT], const Pos& p) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int64_t tt = p.t0 + t < t_hi ? p.t0 + t : t_hi - 1;   // (a clamped duplicate tile is ignored below)
-        const floatx4* ap = a_base + ((size_t)tt * KGR + p.g) * (U / 4) * 64;
-#pragma unroll
-        for (int q = 0; q < U / 4; ++q) {
-          const floatx4 v = ap[q * 64];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) a[4 * q + c][t] = v[c];
-        }
-      }
-    };
-    auto compute = [&](const float (&a)[U][NT], const Pos& p) {
-      if (p.t0 >= t_hi) return;
-      float b[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) b[u] = ub[(p.g * U + u) * 64 + lane];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][t], b[u], acc[t], 0, 0, 0);
-      if (p.g == KGR - 1) {
-        check(p.t0);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-      }
-    };
-    float a0[U][NT], a1[U][NT];
-    Pos p0{t_lo, 0}, p1{t_lo, 0};
-    advance(p1);
-    issue(a0, p0);
-    while (p0.t0 < t_hi) {
-      issue(a1, p1);
-      compute(a0, p0);
-      advance(p0); advance(p0);
-      issue(a0, p0);
-      compute(a1, p1);
-      advance(p1); advance(p1);
-    }
-  }
+#define KGAT_EVAL_WALK_PART 3
+#include "kgat_eval_walk.h"   // the walk over tiles [t_lo, t_hi): check(t0) after a tile group's last MFMA
   // the two halves of a slot hold different items of every tile: their sum is the segment's count
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -549,10 +430,8 @@ int kgat_eval_rank_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items
   }
   const int64_t max_slots = rank_max_slots(n_users, n_test);
   const EvalPlanH pl = rank_plan(max_slots, n_items, F);
-  const int FP2 = eval_fp2(F), kg = eval_reg_kg(F), nw = pl.nw;
-  for (int y = 0; y < pl.n_lists; ++y)   // (the kernel addresses a segment's fragments with 32-bit offsets)
-    KGAT_CHECK_ARG((int64_t)(pl.bounds.b[y + 1] - pl.bounds.b[y]) * FP2 * 256 < ((int64_t)1 << 32),
-                   "eval_rank: a segment of %d tiles is beyond 4 GB of fragments", pl.bounds.b[y + 1] - pl.bounds.b[y]);
+  const int FP2 = eval_fp2(F), kg = eval_reg_kg(F);
+  KGAT_RETURN_IF(eval_check_segments("eval_rank", pl, FP2));
   Carver cv(workspace);
   int32_t* slot_base = cv.take<int32_t>((size_t)n_users + 1);
   int32_t* scan_ws = cv.take<int32_t>(scan_workspace_elems(n_users + 1));
@@ -578,27 +457,13 @@ int kgat_eval_rank_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items
                      n_items, FP2, F, emb, emb_stride, itemT, train_ptr, train_items, test_ptr, test_items, n_test, n_train,
                      drop_train, ((emb_stride & 3) == 0 && aligned16(emb)) ? 1 : 0, thr_s, train_s);
   KGAT_CHECK_LAUNCH("eval_rank_pairs");
-  const size_t lds = rank_lds_per_wave(FP2, kg > 0) * nw;
-  const unsigned gx = (unsigned)((max_slots + 32 * nw - 1) / (32 * nw));
-#define KGAT_RANK_LAUNCH(NW, KG_, WPE)                                                                                \
-  do {                                                                                                                \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(eval_rank_sweep_kernel<NW, KG_, WPE>),                      \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {                    \
-      set_error("eval_rank: cannot reserve %zu bytes of LDS", lds);                                                   \
-      return KGAT_E_HIP;                                                                                              \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((eval_rank_sweep_kernel<NW, KG_, WPE>), dim3(gx, (unsigned)pl.n_lists), dim3(NW * 64), lds, st, \
-                       n_users, (const int32_t*)slot_base, (const int32_t*)slot_user, user_ids, n_items, FP2, F,      \
-                       pl.bounds, emb, emb_stride, itemT, test_ptr, test_items, (const float*)thr_s, above);          \
-  } while (0)
-  if (kg == 6) KGAT_RANK_LAUNCH(4, 6, 2);
-  else if (kg == 11) KGAT_RANK_LAUNCH(4, 11, 2);
-  else if (kg == 16) KGAT_RANK_LAUNCH(4, 16, 1);
-  else if (kg == 22) KGAT_RANK_LAUNCH(4, 22, 1);
-  else if (nw == 4) KGAT_RANK_LAUNCH(4, 0, 2);
-  else if (nw == 2) KGAT_RANK_LAUNCH(2, 0, 2);
-  else KGAT_RANK_LAUNCH(1, 0, 2);
-#undef KGAT_RANK_LAUNCH
+  // (WPE: two wavefronts per SIMD where the registers allow - see eval_rank_sweep_kernel)
+  const auto kernel = eval_with_form<4>(kg, pl.nw, [](auto NW, auto KG) {
+    return &eval_rank_sweep_kernel<NW(), KG(), (KG() == 16 || KG() == 22) ? 1 : 2>;
+  });
+  KGAT_RETURN_IF(eval_launch_sweep("eval_rank", kernel, max_slots, pl, rank_lds_per_wave(FP2, kg > 0), st, n_users,
+                                   (const int32_t*)slot_base, (const int32_t*)slot_user, user_ids, n_items, FP2, F,
+                                   pl.bounds, emb, emb_stride, itemT, test_ptr, test_items, (const float*)thr_s, above));
   KGAT_CHECK_LAUNCH("eval_rank_sweep");
   if (n_train > 0) {
     hipLaunchKernelGGL(eval_rank_fix_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, n_users, train_ptr,

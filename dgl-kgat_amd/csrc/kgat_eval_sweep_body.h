@@ -1,15 +1,14 @@
   // The body of the sweep kernels (included inside eval_topk_kernel of kgat_eval.hip and eval_topk_wide_kernel of
   // kgat_eval_topk.hip, which declare the arguments and `constexpr int CAP`: the candidate entries per user, with
-  // CAP - K >= 24).  Shared as text, not through a template parameter: the K <= 32 instantiations
-  // keep the registers and the code they had.
+  // CAP - K >= 24): the candidate buffer, its prune, the shared threshold and the list write-out around the tile walk
+  // of kgat_eval_walk.h.  Shared as text, not through a template parameter: the K <= 32 instantiations keep the
+  // registers and the code they had.
   constexpr int EPL = CAP <= 64 ? 1 : (CAP <= 128 ? 2 : 4);   // entries per lane of the pruning wavefront (64 EPL >= CAP)
   static_assert(CAP <= 256, "at most four entries per lane");
   extern __shared__ __attribute__((aligned(16))) char s_raw[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int ul = lane & 31, half = lane >> 5;
-  constexpr bool REG = KG > 0;
-  constexpr int NT = KG > 16 ? 1 : 2;   // item tiles in flight: one where the users' rows leave no registers for two
-  char* base = s_raw + (size_t)w * EvalLds::per_wave_bytes(FP2, REG, CAP);
+  char* base = s_raw + (size_t)w * EvalLds::per_wave_bytes(FP2, KG > 0, CAP);
   float* cand_s = reinterpret_cast<float*>(base);
   int32_t* cand_i = reinterpret_cast<int32_t*>(base + 32 * CAP * 4);
   int32_t* kept = reinterpret_cast<int32_t*>(base + 32 * CAP * 8);  // entries known not to be training items
@@ -21,23 +20,9 @@
   const int64_t up = u0 + ul;
   const bool u_ok = up < n_users;
   const int64_t up_c = u_ok ? up : n_users - 1;
-  // B fragments: lane (user ul, half) holds the user's elements k = 2s + half
-  float breg[REG ? KG * 8 : 1];
-  {
-    const float* row = emb + (size_t)user_ids[up_c] * emb_stride;
-    if constexpr (REG) {
-#pragma unroll
-      for (int s = 0; s < KG * 8; ++s) {
-        const int k = 2 * s + half;
-        breg[s] = (u_ok && k < F) ? row[k < F ? k : 0] : 0.f;
-      }
-    } else {
-      for (int s = 0; s < FP2; ++s) {
-        const int k = 2 * s + half;
-        ub[s * 64 + lane] = (u_ok && k < F) ? row[k] : 0.f;
-      }
-    }
-  }
+  const float* row = emb + (size_t)user_ids[up_c] * emb_stride;
+#define KGAT_EVAL_WALK_PART 1
+#include "kgat_eval_walk.h"   // REG, NT, U; breg[] / ub[] from `row`
   if (lane < 32) kept[lane] = 0;
   const int32_t tr_lo = train_ptr[up_c], tr_hi = train_ptr[up_c + 1];
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -225,47 +210,15 @@
     }
   };
 
-  // A fragments: one coalesced 16-byte load per lane per FOUR MFMAs (itemT's layout, above).  The sweep is a flat
-  // sequence of steps (tile group, group of U k pairs); a step's loads are issued while the previous step's MFMAs run
-  // (two register buffers, the loop unrolled by two so that no buffer is copied).
-  constexpr int U = 8;
-  typedef float floatx4 __attribute__((ext_vector_type(4)));
-  const floatx4* a_base = reinterpret_cast<const floatx4*>(itemT) + lane;
-  const int KGR = FP2 / U;                                     // k groups per tile group (FP2 is a multiple of U)
-  struct Pos { int64_t t0; int g; };
-  auto advance = [&](Pos& p) { if (++p.g == KGR) { p.g = 0; p.t0 += NT; } };
-  auto issue = [&](float (&a)[U][NT], const Pos& p) {
-    // (unconditional: a load under a branch makes the compiler's counted vmcnt waits conservative - it then waited
-    // for the NEXT step's loads before this step's MFMAs; past the end the clamped tile is loaded again, unused)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int64_t tt = p.t0 + t < t_hi ? p.t0 + t : t_hi - 1;   // (a clamped duplicate tile is ignored below)
-      const floatx4* ap = a_base + ((size_t)tt * KGR + p.g) * (U / 4) * 64;
-#pragma unroll
-      for (int q = 0; q < U / 4; ++q) {
-        const floatx4 v = ap[q * 64];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[4 * q + c][t] = v[c];
-      }
-    }
-  };
-  floatx16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  // acc[t][r]: user ul, item position 32 (t0 + t) + (r & 3) + 8 (r >> 2) + 4 half
+#define KGAT_EVAL_WALK_PART 2
+#include "kgat_eval_walk.h"   // acc[NT] (acc[t][r]: user ul), nan_padded_tail
   auto check = [&](int64_t t0) {
     adopt_shared();
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       if (t0 + t >= t_hi) break;  // wave-uniform
       const int ib = (int)((t0 + t) * kEvalTile) + 4 * half;
-      if ((t0 + t + 1) * kEvalTile > n_items) {   // the padded end of the last tile (wave-uniform): never a candidate
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (ib + (r & 3) + 8 * (r >> 2) >= n_items) acc[t][r] = __builtin_nanf("");
-      }
+      nan_padded_tail(t, t0 + t, ib);   // (never a candidate)
       // the maximum of every four registers, then of all sixteen: a tile without a candidate costs the ten maxima and one
       // compare, a tile with one walks only the quads that hold it
       float mq[4];
@@ -312,96 +265,8 @@
     if (tau_shared != nullptr)   // for the next tile group's check (an L2 round trip behind that group's MFMAs)
       sh_next = from_ordered_bits(__hip_atomic_load(tau_shared + up_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));   // (past the L1)
   };
-  auto compute = [&](const float (&a)[U][NT], const Pos& p) {
-    if (p.t0 >= t_hi) return;
-    float b[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) b[u] = ub[(p.g * U + u) * 64 + lane];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][t], b[u], acc[t], 0, 0, 0);
-    if (p.g == KGR - 1) {
-      check(p.t0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;   // (here, behind the check's branch: not a select per step)
-    }
-  };
-  if constexpr (REG) {
-    // Two tile groups per loop iteration = 4 KG half steps (tile group, k group, half of the k group; 44 at KG = 11) with
-    // compile-time k groups - the register index of the B operand.  A half step is two 16-byte loads per lane (four k
-    // pairs of both tiles) and eight MFMAs; its loads are issued THREE half steps ahead into a ring of four buffers (the
-    // registers of two whole-step buffers: one step ahead was 1,024 MFMA cycles, about the L2's latency under this
-    // load; three half steps are 1,536).  4 KG is a multiple of 4: the ring position of a half step is a compile-time
-    // constant.  A group past the end re-reads the clamped last tile and is skipped.
-    // (written out, not a loop: `#pragma unroll` over the steps was declined by the optimiser, and a generic lambda
-    //  per step - the index as an integral_constant - sent every captured array to scratch)
-    static_assert(KG <= 22 && U == 8, "the step list below is written out for up to 2 x 22 steps of 2 halves");
-    const floatx16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float h0[4][NT], h1[4][NT], h2[4][NT], h3[4][NT];
-    const size_t seg_bytes = (size_t)(t_hi - t_lo) * KG * 2048;
-    const __amdgpu_buffer_rsrc_t seg_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(itemT) + (size_t)t_lo * KG * 512, 0, (int)(unsigned)seg_bytes, 0x00020000);
-    auto issue_half = [&](float (&a)[4][NT], int64_t tg, int g, int q) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int64_t tt = tg + t < t_hi ? tg + t : t_hi - 1;   // (a clamped duplicate tile is ignored below)
-        // (a buffer load: the segment's fragments as a resource, the wave-uniform offset in a scalar register, the lane's
-        //  16 bytes the only vector operand - as a global load every address was two 64-bit vector adds, six vector
-        //  instructions per half step; the host checks that a segment's fragments stay below 4 GB)
-        const unsigned soff = (unsigned)(((tt - t_lo) * KG + g) * 2 + q) * 1024u;
-        const floatx4 v = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(seg_rsrc, lane * 16, (int)soff, 0));
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[c][t] = v[c];
-      }
-    };
-    issue_half(h0, t_lo, 0, 0);
-    issue_half(h1, t_lo, 0, 1);
-    issue_half(h2, t_lo, 1, 0);
-#define KGAT_EVAL_HALF(J, CUR, NXT)                                                                       \
-    if constexpr (J < 4 * KG) {                                                                           \
-      constexpr int j = J, g = (j / 2) % KG, q = j % 2, jn = j + 3, gn = (jn / 2) % KG, qn = jn % 2;      \
-      const int64_t tt = t0 + (j / 2 / KG) * NT, tn = t0 + (jn / 2 / KG) * NT;                  \
-      issue_half(NXT, tn, gn, qn);                                                                        \
-      /* the loads go out HERE, ahead of this half step's MFMAs: left to itself the scheduler sinks them between */ \
-      /* the MFMAs and waits for each a few instructions after issuing it                                         */ \
-      __builtin_amdgcn_sched_barrier(0);                                                                  \
-      if (tt < t_hi) { /* wave-uniform */                                                                 \
-        _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                     \
-          _Pragma("unroll") for (int t = 0; t < NT; ++t)                                             \
-            /* (a tile group's first MFMA adds to the constant 0: no clearing of 32 registers per group) */ \
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(CUR[c][t], breg[g * U + 4 * q + c],             \
-                                                          (g == 0 && q == 0 && c == 0) ? zero16 : acc[t], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        if (g == KG - 1 && q == 1) check(tt);                                                             \
-      }                                                                                                   \
-    }
-#define KGAT_EVAL_HALF4(J) KGAT_EVAL_HALF(J, h0, h3) KGAT_EVAL_HALF(J + 1, h1, h0) KGAT_EVAL_HALF(J + 2, h2, h1) KGAT_EVAL_HALF(J + 3, h3, h2)
-    for (int64_t t0 = t_lo; t0 < t_hi; t0 += 2 * NT) {
-      KGAT_EVAL_HALF4(0) KGAT_EVAL_HALF4(4) KGAT_EVAL_HALF4(8) KGAT_EVAL_HALF4(12) KGAT_EVAL_HALF4(16) KGAT_EVAL_HALF4(20)
-      KGAT_EVAL_HALF4(24) KGAT_EVAL_HALF4(28) KGAT_EVAL_HALF4(32) KGAT_EVAL_HALF4(36) KGAT_EVAL_HALF4(40) KGAT_EVAL_HALF4(44)
-      KGAT_EVAL_HALF4(48) KGAT_EVAL_HALF4(52) KGAT_EVAL_HALF4(56) KGAT_EVAL_HALF4(60) KGAT_EVAL_HALF4(64) KGAT_EVAL_HALF4(68)
-      KGAT_EVAL_HALF4(72) KGAT_EVAL_HALF4(76) KGAT_EVAL_HALF4(80) KGAT_EVAL_HALF4(84)   // (beyond 4 KG: compiled out)
-    }
-#undef KGAT_EVAL_HALF4
-#undef KGAT_EVAL_HALF
-  } else {
-    float a0[U][NT], a1[U][NT];
-    Pos p0{t_lo, 0}, p1{t_lo, 0};
-    advance(p1);
-    issue(a0, p0);
-    while (p0.t0 < t_hi) {
-      issue(a1, p1);
-      compute(a0, p0);
-      advance(p0); advance(p0);
-      issue(a0, p0);
-      compute(a1, p1);
-      advance(p1); advance(p1);
-    }
-  }
+#define KGAT_EVAL_WALK_PART 3
+#include "kgat_eval_walk.h"   // the walk over tiles [t_lo, t_hi): check(t0) after a tile group's last MFMA
   // the segment's list of every user: K entries, padded with (-inf, pad)
   for (int v = 0; v < 32; ++v) {
     if (u0 + v >= n_users) break;

@@ -2,7 +2,7 @@
 // K <= 32 recall / ndcg path of kgat_eval.hip (reference metric.py:36-68; the paper reports recall, ndcg, precision
 // and hit ratio at K = 20 ... 100).  DESIGN.md 13.
 //
-//  1. eval_topk_wide_kernel: the sweep of kgat_eval.hip (kgat_eval_sweep_body.h: the same text - MFMA sweep, register
+//  1. eval_topk_wide_kernel: the sweep of kgat_eval.hip (it includes the same kgat_eval_sweep_body.h - MFMA walk, register
 //     and LDS forms, two-ended append, shared threshold, segment plan) over a candidate buffer of 128 entries per user
 //     (32 < K <= 64) or 156 (K <= 128): the pruning wavefront holds 2 / up to 3 entries per lane.  A wavefront's buffer
 //     is 32 KB / 39 KB of the CU's 160 KB, so a CU holds four wavefronts, one per SIMD (workgroups of two in the
@@ -156,46 +156,15 @@ __global__ __launch_bounds__(256) void eval_metrics_at_ks_kernel(
 // The sweep at 32 < K <= 128 over a plan made with eval_cap(K).
 static int eval_sweep_wide_launch(int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
                                   int64_t emb_stride, const float* itemT, const int32_t* train_ptr,
-                                  const int32_t* train_items, int K, const EvalPlanH& pl, float* part_s, int32_t* part_i,
-                                  unsigned* tau_shared, hipStream_t st) {
-  const int FP2 = eval_fp2(F), cap = eval_cap(K);
-  const int nw = pl.nw;
-  for (int y = 0; y < pl.n_lists; ++y)   // (the kernel addresses a segment's fragments with 32-bit offsets)
-    KGAT_CHECK_ARG((int64_t)(pl.bounds.b[y + 1] - pl.bounds.b[y]) * FP2 * 256 < ((int64_t)1 << 32),
-                   "eval_topk: a segment of %d tiles is beyond 4 GB of fragments", pl.bounds.b[y + 1] - pl.bounds.b[y]);
-  const int kg = eval_reg_kg(F);
-  const size_t lds = EvalLds::per_wave_bytes(FP2, kg > 0, cap) * nw;
-  const unsigned gx = (unsigned)((n_users + 32 * nw - 1) / (32 * nw));
-  if (pl.n_lists > 1 && hipMemsetAsync(tau_shared, 0, (size_t)n_users * 4, st) != hipSuccess) {
-    set_error("eval_topk: cannot clear the shared thresholds");
-    return KGAT_E_HIP;
-  }
-#define KGAT_EVAL_LAUNCH(NW, KG_, CAP_)                                                                               \
-  do {                                                                                                                \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(eval_topk_wide_kernel<NW, KG_, CAP_>),                      \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {                    \
-      set_error("eval_topk: cannot reserve %zu bytes of LDS", lds);                                                   \
-      return KGAT_E_HIP;                                                                                              \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((eval_topk_wide_kernel<NW, KG_, CAP_>), dim3(gx, (unsigned)pl.n_lists), dim3(NW * 64), lds,    \
-                       st, n_users, user_ids, n_items, FP2, F, pl.bounds, emb, emb_stride, itemT, train_ptr,          \
-                       train_items, K, part_s, part_i, pl.n_lists > 1 ? tau_shared : nullptr);                        \
-  } while (0)
-#define KGAT_EVAL_LAUNCH_CAP(CAP_)                      \
-  do {                                                  \
-    if (kg == 6) KGAT_EVAL_LAUNCH(2, 6, CAP_);          \
-    else if (kg == 11) KGAT_EVAL_LAUNCH(2, 11, CAP_);   \
-    else if (kg == 16) KGAT_EVAL_LAUNCH(2, 16, CAP_);   \
-    else if (kg == 22) KGAT_EVAL_LAUNCH(2, 22, CAP_);   \
-    else if (nw == 4) KGAT_EVAL_LAUNCH(4, 0, CAP_);     \
-    else if (nw == 2) KGAT_EVAL_LAUNCH(2, 0, CAP_);     \
-    else KGAT_EVAL_LAUNCH(1, 0, CAP_);                  \
-  } while (0)
-  // ONE launch over (user blocks) x (item segments)
-  if (cap == kEvalCapWide) KGAT_EVAL_LAUNCH_CAP(kEvalCapWide);
-  else KGAT_EVAL_LAUNCH_CAP(kEvalCapWidest);
-#undef KGAT_EVAL_LAUNCH_CAP
-#undef KGAT_EVAL_LAUNCH
+                                  const int32_t* train_items, int K, const EvalPlanH& pl, const EvalListsWs& ws,
+                                  hipStream_t st) {
+  const int cap = eval_cap(K), kg = eval_reg_kg(F);
+  const auto kernel =
+      cap == kEvalCapWide
+          ? eval_with_form<2>(kg, pl.nw, [](auto NW, auto KG) { return &eval_topk_wide_kernel<NW(), KG(), kEvalCapWide>; })
+          : eval_with_form<2>(kg, pl.nw, [](auto NW, auto KG) { return &eval_topk_wide_kernel<NW(), KG(), kEvalCapWidest>; });
+  KGAT_RETURN_IF(eval_lists_sweep("eval_topk", kernel, cap, n_users, user_ids, n_items, F, emb, emb_stride, itemT,
+                                  train_ptr, train_items, K, pl, ws, st));
   KGAT_CHECK_LAUNCH("eval_topk_wide");
   return KGAT_OK;
 }
@@ -212,8 +181,7 @@ int kgat_eval_topk_supported(int F, int K) {
 
 size_t kgat_eval_topk_workspace_bytes(int64_t n_users, int64_t n_items, int F, int K) {
   if (n_users <= 0 || n_items <= 0 || !kgat_eval_topk_supported(F, K)) return 256;
-  const EvalPlanH pl = eval_plan(n_users, n_items, F, eval_cap(K));
-  return 2 * align_up((size_t)n_users * pl.n_lists * K * 4, 256) + align_up((size_t)n_users * 4, 256) + 256;
+  return eval_lists_workspace_bytes(n_users, eval_plan(n_users, n_items, F, eval_cap(K)), K);
 }
 
 int kgat_eval_topk_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items, int F, const float* emb,
@@ -237,20 +205,17 @@ int kgat_eval_topk_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items
     return KGAT_E_WORKSPACE;
   }
   const EvalPlanH pl = eval_plan(n_users, n_items, F, eval_cap(K));
-  Carver cv(workspace);
-  float* part_s = cv.take<float>((size_t)n_users * pl.n_lists * K);
-  int32_t* part_i = cv.take<int32_t>((size_t)n_users * pl.n_lists * K);
-  unsigned* tau_shared = cv.take<unsigned>((size_t)n_users);   // shared K-th best per user (order-preserving bits)
+  const EvalListsWs ws = eval_lists_carve(workspace, n_users, pl, K);
   hipStream_t st = as_stream(stream);
   const int rc = K <= kEvalMaxK
                      ? eval_sweep_launch("eval_topk", n_users, user_ids, n_items, F, emb, emb_stride, itemT, train_ptr,
-                                         train_items, K, pl, part_s, part_i, tau_shared, st)
+                                         train_items, K, pl, ws.part_s, ws.part_i, ws.tau_shared, st)
                      : eval_sweep_wide_launch(n_users, user_ids, n_items, F, emb, emb_stride, itemT, train_ptr,
-                                              train_items, K, pl, part_s, part_i, tau_shared, st);
+                                              train_items, K, pl, ws, st);
   if (rc != KGAT_OK) return rc;
   const dim3 grid((unsigned)((n_users + 3) / 4));
 #define KGAT_EVAL_MERGE(E)                                                                                          \
-  hipLaunchKernelGGL(eval_topk_merge_kernel<E>, grid, dim3(256), 0, st, n_users, pl.n_lists, K, part_s, part_i,     \
+  hipLaunchKernelGGL(eval_topk_merge_kernel<E>, grid, dim3(256), 0, st, n_users, pl.n_lists, K, ws.part_s, ws.part_i, \
                      train_ptr, train_items, drop_train, topk_items, topk_scores)
   if (K <= 32) KGAT_EVAL_MERGE(1);
   else if (K <= 64) KGAT_EVAL_MERGE(2);

@@ -1464,37 +1464,70 @@ def eval_supported(F, K):
     return bool(_lib.load().kgat_eval_supported(int(F), int(K)))
 
 
+def _eval_args(who, emb, user_ids, item_ids, train_ptr, train_items, test_ptr=None, test_items=None):
+    """The arguments the evaluation wrappers share, checked (`who` names the wrapper in the message; the test lists are
+    optional).  Returns (F, stride, n_users, n_items)."""
+    if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
+        raise KGATLibraryError("%s: `emb` must be a float32 HIP matrix with unit column stride" % who)
+    _need(user_ids, torch.int32, "user_ids")
+    _need(item_ids, torch.int32, "item_ids")
+    n_users, n_items = user_ids.numel(), item_ids.numel()
+    _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
+    if test_ptr is not None:
+        _need(test_ptr, torch.int32, "test_ptr", (n_users + 1,))
+    _need(train_items, torch.int32, "train_items")
+    if test_items is not None:
+        _need(test_items, torch.int32, "test_items")
+    return emb.shape[1], emb.stride(0), n_users, n_items
+
+
+def _eval_items(lib, emb, item_ids):
+    """itemT: the item rows as the MFMA A fragments of the sweeps (kgat_eval_items_kmajor_f32)."""
+    n_items, F = item_ids.numel(), emb.shape[1]
+    itemT = torch.empty(max(int(lib.kgat_eval_items_elems(n_items, F)), 1), dtype=torch.float32, device=emb.device)
+    with _timed("eval_items_kmajor", (n_items, F)):
+        check(lib.kgat_eval_items_kmajor_f32(n_items, F, _ptr(emb), emb.stride(0), _ptr(item_ids), _ptr(itemT),
+                                             _stream(emb)), "kgat_eval_items_kmajor_f32")
+    return itemT
+
+
+def _discounts(n, dev):
+    """1 / log2(rank + 1) of the ranks 1 .. n, float64 (reference metric.py:23-34)."""
+    import numpy as np
+    return torch.as_tensor(1.0 / np.log2(np.arange(2, n + 2)), dtype=torch.float64, device=dev)
+
+
+def _eval_cutoffs(who, ks, most, bad, limit=None):
+    """`ks` as ints and as the C array, checked: 1 to `most` cut-offs, positive, ascending and (with `limit`) none
+    beyond it; `bad` words the second refusal around the list."""
+    import ctypes
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= most:
+        raise ValueError("%s: 1 to %d cut-offs, got %d" % (who, most, len(ks)))
+    if any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1 or (limit is not None and ks[-1] > limit):
+        raise ValueError("%s: %s" % (who, bad % (ks,)))
+    return ks, ctypes.cast((ctypes.c_int32 * len(ks))(*ks), ctypes.c_void_p)
+
+
 def eval_recall_ndcg(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, test_items, K, want_topk=False):
     """recall@K / ndcg@K per test user (reference metric.py:36-68) on the device: kgat_eval_items_kmajor_f32 +
     kgat_eval_recall_ndcg_f32.  `emb` (N, F) fp32 rows (row stride = emb.stride(0)); user_ids / item_ids int32 node
     ids; the CSR lists hold item POSITIONS (ascending per user).  Returns (recall, ndcg[, topk]) - float64 (n_users,)
     and int32 (n_users, K)."""
-    if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
-        raise KGATLibraryError("eval_recall_ndcg: `emb` must be a float32 HIP matrix with unit column stride")
-    F, stride = emb.shape[1], emb.stride(0)
-    user_ids = _need(user_ids, torch.int32, "user_ids")
-    item_ids = _need(item_ids, torch.int32, "item_ids")
-    n_users, n_items = user_ids.numel(), item_ids.numel()
-    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
-    test_ptr = _need(test_ptr, torch.int32, "test_ptr", (n_users + 1,))
-    train_items = _need(train_items, torch.int32, "train_items")
-    test_items = _need(test_items, torch.int32, "test_items")
+    F, stride, n_users, n_items = _eval_args("eval_recall_ndcg", emb, user_ids, item_ids, train_ptr, train_items,
+                                             test_ptr, test_items)
     lib = _lib.load()
     if not lib.kgat_eval_supported(F, K):
         raise KGATLibraryError("eval_recall_ndcg: K = %d / F = %d outside the kernel's range" % (K, F))
     dev = emb.device
-    import numpy as np
-    disc = torch.as_tensor(1.0 / np.log2(np.arange(2, K + 2)), dtype=torch.float64, device=dev)
+    disc = _discounts(K, dev)
     recall = torch.zeros(n_users, dtype=torch.float64, device=dev)
     ndcg = torch.zeros(n_users, dtype=torch.float64, device=dev)
     topk = torch.empty((n_users, K), dtype=torch.int32, device=dev) if want_topk else None
     if n_users == 0:
         return (recall, ndcg, topk) if want_topk else (recall, ndcg)
-    itemT = torch.empty(max(int(lib.kgat_eval_items_elems(n_items, F)), 1), dtype=torch.float32, device=dev)
     ws = torch.empty(lib.kgat_eval_workspace_bytes(n_users, n_items, F, K), dtype=torch.uint8, device=dev)
-    with _timed("eval_items_kmajor", (n_items, F)):
-        check(lib.kgat_eval_items_kmajor_f32(n_items, F, _ptr(emb), stride, _ptr(item_ids), _ptr(itemT), _stream(emb)),
-              "kgat_eval_items_kmajor_f32")
+    itemT = _eval_items(lib, emb, item_ids)
     with _timed("eval_recall_ndcg", (n_users, n_items, F, K)):
         check(lib.kgat_eval_recall_ndcg_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
                                             _ptr(train_ptr), _ptr(train_items), _ptr(test_ptr), _ptr(test_items), K,
@@ -1514,14 +1547,7 @@ def eval_topk(emb, user_ids, item_ids, train_ptr, train_items, K, drop_train=Fal
     reference's rule (a training item scores 0.0 and can rank; needs n_items >= K); drop_train=True never lists a
     training item and pads a short list.  Returns (topk[, scores]) - int32 item POSITIONS (n_users, K), -1 padding,
     and float32 scores, -inf padding."""
-    if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
-        raise KGATLibraryError("eval_topk: `emb` must be a float32 HIP matrix with unit column stride")
-    F, stride = emb.shape[1], emb.stride(0)
-    user_ids = _need(user_ids, torch.int32, "user_ids")
-    item_ids = _need(item_ids, torch.int32, "item_ids")
-    n_users, n_items = user_ids.numel(), item_ids.numel()
-    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
-    train_items = _need(train_items, torch.int32, "train_items")
+    F, stride, n_users, n_items = _eval_args("eval_topk", emb, user_ids, item_ids, train_ptr, train_items)
     K = int(K)
     lib = _lib.load()
     if not lib.kgat_eval_topk_supported(F, K):
@@ -1531,11 +1557,8 @@ def eval_topk(emb, user_ids, item_ids, train_ptr, train_items, K, drop_train=Fal
     scores = torch.empty((n_users, K), dtype=torch.float32, device=dev) if want_scores else None
     if n_users == 0:
         return (topk, scores) if want_scores else topk
-    itemT = torch.empty(max(int(lib.kgat_eval_items_elems(n_items, F)), 1), dtype=torch.float32, device=dev)
     ws = torch.empty(lib.kgat_eval_topk_workspace_bytes(n_users, n_items, F, K), dtype=torch.uint8, device=dev)
-    with _timed("eval_items_kmajor", (n_items, F)):
-        check(lib.kgat_eval_items_kmajor_f32(n_items, F, _ptr(emb), stride, _ptr(item_ids), _ptr(itemT), _stream(emb)),
-              "kgat_eval_items_kmajor_f32")
+    itemT = _eval_items(lib, emb, item_ids)
     with _timed("eval_topk", (n_users, n_items, F, K)):
         check(lib.kgat_eval_topk_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
                                      _ptr(train_ptr), _ptr(train_items), K, 1 if drop_train else 0, _ptr(ws),
@@ -1551,23 +1574,16 @@ def eval_metrics_at_ks(topk, test_ptr, test_items, ks):
     if topk.dtype != torch.int32 or not topk.is_cuda or topk.dim() != 2 or not topk.is_contiguous():
         raise KGATLibraryError("eval_metrics_at_ks: `topk` must be a contiguous int32 HIP matrix")
     n_users, K = topk.shape
-    ks = [int(k) for k in ks]
-    if not 1 <= len(ks) <= 8:
-        raise ValueError("eval_metrics_at_ks: 1 to 8 cut-offs, got %d" % len(ks))
-    if any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1 or ks[-1] > K:
-        raise ValueError("eval_metrics_at_ks: the cut-offs must ascend within 1..%d: %r" % (K, ks))
+    ks, ks_host = _eval_cutoffs("eval_metrics_at_ks", ks, 8, "the cut-offs must ascend within 1..%d: %%r" % K, K)
     test_ptr = _need(test_ptr, torch.int32, "test_ptr", (n_users + 1,))
     test_items = _need(test_items, torch.int32, "test_items")
-    import ctypes
-    import numpy as np
     dev = topk.device
-    disc = torch.as_tensor(1.0 / np.log2(np.arange(2, K + 2)), dtype=torch.float64, device=dev)
+    disc = _discounts(K, dev)
     out = torch.zeros((n_users, len(ks), 4), dtype=torch.float64, device=dev)
-    ks_host = (ctypes.c_int32 * len(ks))(*ks)
     with _timed("eval_metrics_at_ks", (n_users, K, len(ks))):
         check(_lib.load().kgat_eval_metrics_at_ks(n_users, K, _ptr(topk), _ptr(test_ptr), _ptr(test_items), len(ks),
-                                                  ctypes.cast(ks_host, ctypes.c_void_p), _ptr(disc), _ptr(out),
-                                                  _stream(topk)), "kgat_eval_metrics_at_ks")
+                                                  ks_host, _ptr(disc), _ptr(out), _stream(topk)),
+              "kgat_eval_metrics_at_ks")
     return out
 
 
@@ -1582,16 +1598,8 @@ def eval_rank(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, test_it
     kgat_eval_rank_f32.  Arguments as eval_recall_ndcg; drop_train as eval_topk (False: a training item is a candidate
     at score 0.0; True: it is none, and a test entry that is a training item gets -1).  Returns (above[, scores]) -
     int32 (n_test,) in test-CSR order, the rank is above + 1, and the float32 scores of the test entries."""
-    if emb.dtype != torch.float32 or not emb.is_cuda or emb.dim() != 2 or emb.stride(1) != 1:
-        raise KGATLibraryError("eval_rank: `emb` must be a float32 HIP matrix with unit column stride")
-    F, stride = emb.shape[1], emb.stride(0)
-    user_ids = _need(user_ids, torch.int32, "user_ids")
-    item_ids = _need(item_ids, torch.int32, "item_ids")
-    n_users, n_items = user_ids.numel(), item_ids.numel()
-    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
-    test_ptr = _need(test_ptr, torch.int32, "test_ptr", (n_users + 1,))
-    train_items = _need(train_items, torch.int32, "train_items")
-    test_items = _need(test_items, torch.int32, "test_items")
+    F, stride, n_users, n_items = _eval_args("eval_rank", emb, user_ids, item_ids, train_ptr, train_items, test_ptr,
+                                             test_items)
     n_train, n_test = train_items.numel(), test_items.numel()
     lib = _lib.load()
     if not lib.kgat_eval_rank_supported(F):
@@ -1601,11 +1609,8 @@ def eval_rank(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, test_it
     scores = torch.zeros(n_test, dtype=torch.float32, device=dev) if want_scores else None
     if n_users == 0 or n_test == 0:
         return (above, scores) if want_scores else above
-    itemT = torch.empty(max(int(lib.kgat_eval_items_elems(n_items, F)), 1), dtype=torch.float32, device=dev)
     ws = _workspace(lib.kgat_eval_rank_workspace_bytes(n_users, n_items, F, n_train, n_test), dev)
-    with _timed("eval_items_kmajor", (n_items, F)):
-        check(lib.kgat_eval_items_kmajor_f32(n_items, F, _ptr(emb), stride, _ptr(item_ids), _ptr(itemT), _stream(emb)),
-              "kgat_eval_items_kmajor_f32")
+    itemT = _eval_items(lib, emb, item_ids)
     with _timed("eval_rank", (n_users, n_items, F, n_test)):
         check(lib.kgat_eval_rank_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
                                      _ptr(train_ptr), _ptr(train_items), n_train, _ptr(test_ptr), _ptr(test_items),
@@ -1634,29 +1639,22 @@ def eval_rank_metrics(above, test_ptr, test_items, n_candidates, ks, n_items=Non
         n_items = int(n_candidates) if n_items is None else int(n_items)
         n_candidates = torch.full((n_users,), int(n_candidates), dtype=torch.int32, device=above.device)
     n_candidates = _need(n_candidates, torch.int32, "n_candidates", (n_users,))
-    ks = [int(k) for k in ks]
-    if not 1 <= len(ks) <= EVAL_RANK_MAX_KS:
-        raise ValueError("eval_rank_metrics: 1 to %d cut-offs, got %d" % (EVAL_RANK_MAX_KS, len(ks)))
-    if any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1:
-        raise ValueError("eval_rank_metrics: the cut-offs must be positive and ascend: %r" % (ks,))
-    import ctypes
-    import numpy as np
+    ks, ks_host = _eval_cutoffs("eval_rank_metrics", ks, EVAL_RANK_MAX_KS,
+                                "the cut-offs must be positive and ascend: %r")
     dev = above.device
     if n_items is None:
         n_items = int(n_candidates.max()) if n_users else ks[-1]
     if ks[-1] > n_items:
         raise ValueError("eval_rank_metrics: cut-off %d is beyond the %d items" % (ks[-1], n_items))
-    disc = torch.as_tensor(1.0 / np.log2(np.arange(2, ks[-1] + 2)), dtype=torch.float64, device=dev)
+    disc = _discounts(ks[-1], dev)
     at_k = torch.zeros((n_users, len(ks), 4), dtype=torch.float64, device=dev)
     scalar = torch.zeros((n_users, 4), dtype=torch.float64, device=dev)
     lib = _lib.load()
     ws = _workspace(lib.kgat_eval_rank_metrics_workspace_bytes(above.numel()), dev)
-    ks_host = (ctypes.c_int32 * len(ks))(*ks)
     with _timed("eval_rank_metrics", (n_users, above.numel(), len(ks))):
         check(lib.kgat_eval_rank_metrics(n_users, n_items, _ptr(above), _ptr(test_ptr), _ptr(test_items), above.numel(),
-                                         _ptr(n_candidates), len(ks), ctypes.cast(ks_host, ctypes.c_void_p), _ptr(disc),
-                                         _ptr(ws), ws.numel(), _ptr(at_k), _ptr(scalar), _stream(above)),
-              "kgat_eval_rank_metrics")
+                                         _ptr(n_candidates), len(ks), ks_host, _ptr(disc), _ptr(ws), ws.numel(),
+                                         _ptr(at_k), _ptr(scalar), _stream(above)), "kgat_eval_rank_metrics")
     return at_k, scalar
 
 

@@ -28,7 +28,8 @@ EXACT_SHAPES = [(33, 33, 8),            # a user block of 32 plus 1, items 32 pl
                 (129, 2100, 176),       # KG 11
                 (77, 2500, 256),        # KG 16
                 (70, 1800, 352),        # KG 22, one tile in flight
-                (260, 1500, 24)]
+                (260, 1500, 24),
+                (40, 300, 520)]         # F > 512: the LDS form with one wavefront per workgroup
 REAL_SHAPES = [(300, 5000, 176), (150, 4000, 352), (200, 3000, 64), (260, 2100, 96), (100, 1000, 24)]
 
 

@@ -22,7 +22,9 @@ TIE_SHAPES = [(33, 33, 8, 33),          # first K beyond the old limit, n_items 
               (129, 2100, 176, 100),    # KG 11
               (77, 2500, 256, 64),      # KG 16
               (70, 1800, 352, 128),     # KG 22, one tile in flight
-              (260, 1500, 24, 100)]
+              (260, 1500, 24, 100),
+              (40, 300, 520, 40),       # F > 512: the LDS form with one wavefront per workgroup, 128-entry buffer
+              (40, 300, 520, 100)]      # the same with the 156-entry buffer
 
 
 @pytest.fixture(scope="module")
