@@ -251,7 +251,7 @@ static BwdCarve bwd_carve(void* base, int64_t n_scored, int64_t n_groups, int d,
   const size_t s1 = kgat_spmm_workspace_bytes(n_scored, d), s2 = kgat_spmm_workspace_bytes(n_scored + n_groups, d);
   c.spmm_bytes = s1 > s2 ? s1 : s2;
   c.spmm_ws = cv.take<char>(c.spmm_bytes);
-  c.total = cv.off;
+  c.total = cv.off + 256;  // what kgat_att_score_bwd_workspace_bytes answers is what the entry asks for
   return c;
 }
 
@@ -267,7 +267,7 @@ int kgat_att_score_bwd_supported(int64_t n_nodes, int d, int k, int n_rel) {
 
 size_t kgat_att_score_bwd_workspace_bytes(int64_t n_nodes, int64_t n_scored, int64_t n_groups, int d, int k, int n_rel) {
   if (!kgat_att_score_bwd_supported(n_nodes, d, k, n_rel) || n_scored < 0 || n_groups < 0) return 256;
-  return bwd_carve(nullptr, n_scored, n_groups, d, k, n_rel).total + 256;
+  return bwd_carve(nullptr, n_scored, n_groups, d, k, n_rel).total;
 }
 
 int kgat_att_score_bwd_f32(int64_t n_nodes, int64_t n_scored, int64_t n_groups, int d, int k, int n_rel,

@@ -502,6 +502,11 @@ int kgat_csr_from_coo(int64_t n_nodes, int64_t n_edges, const int32_t* src, cons
   KGAT_CHECK_ARG(indptr != nullptr, "csr_from_coo: indptr is null");
   KGAT_CHECK_ARG(n_edges == 0 || (src && dst && col && eid && workspace),
                  "csr_from_coo: null pointer");
+  if (n_edges > 0 && workspace_bytes < kgat_csr_from_coo_workspace_bytes(n_nodes, n_edges)) {
+    set_error("csr_from_coo: workspace too small (%zu < %zu)", workspace_bytes,
+              kgat_csr_from_coo_workspace_bytes(n_nodes, n_edges));
+    return KGAT_E_WORKSPACE;
+  }
   hipStream_t st = as_stream(stream);
   const int32_t* sorted = nullptr;
   if (n_edges > 0) {
@@ -637,6 +642,12 @@ int kgat_fold_tiles(int64_t n_edges, int n_rel, int64_t n_groups, const int32_t*
     return KGAT_E_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
+  // the rows of `tiles` past rel_tptr[R] are no tile's: zeros, so that the whole array is written
+  if (hipMemsetAsync(tiles, 0, (size_t)kgat_fold_tiles_max(n_edges, n_groups, n_rel, cap) * 4 * sizeof(int32_t), st) !=
+      hipSuccess) {
+    set_error("fold_tiles: cannot clear the tiles");
+    return KGAT_E_HIP;
+  }
   const int64_t nb_max = fold_base_max(n_groups, n_rel);
   Carver cv(workspace);
   int32_t* gstart = cv.take<int32_t>((size_t)n_groups + 1);

@@ -383,8 +383,10 @@ int kgat_spmm_umule_max4_f32(int64_t n_rows, int64_t row0, int64_t e_begin, int6
                      (reinterpret_cast<uintptr_t>(arg_slot) & 3u) == 0,
                  "spmm_max4: X, out, arg_edge and the workspace must be 16-byte aligned, arg_slot 4-byte aligned");
   const MergePlan m = merge_plan(Q, e_end - e_begin, n_rows);
-  // (a short workspace is one of this entry's bad arguments: KGAT_E_BADARG with check_workspace's message)
-  if (check_workspace("spmm_max4", m, m.part_elems * kListBytes, workspace, workspace_bytes) != KGAT_OK) return KGAT_E_BADARG;
+  // (a short workspace is one of this entry's bad arguments: KGAT_E_BADARG with check_workspace's message; the bound
+  // is the size function's answer, as the header states it)
+  if (check_workspace("spmm_max4", m, kgat_spmm_max4_workspace_bytes(e_end - e_begin, Q), workspace, workspace_bytes) != KGAT_OK)
+    return KGAT_E_BADARG;
   Max4Args a;
   a.n_rows = n_rows; a.row0 = row0; a.e0 = e_begin; a.e1 = e_end;
   a.indptr = indptr; a.col = col; a.row_of = row_of; a.eid = eid; a.X = X; a.w = w;

@@ -279,7 +279,7 @@ class _Structure:
             plan = c[("permute_plan", name)] = (src_of, ops.permute_plan(src_of))
         tmp = c.get("permute_tmp")
         if tmp is None or tmp.numel() != src_of.numel():
-            tmp = c["permute_tmp"] = torch.empty(src_of.numel(), dtype=torch.float32, device=device)
+            tmp = c["permute_tmp"] = ops._scratch((src_of.numel(),), torch.float32, device)
         return plan[1], tmp
 
     def weight_in_csr_order(self, w_flat):

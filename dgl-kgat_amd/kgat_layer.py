@@ -418,7 +418,12 @@ class KGATPropagation(nn.Module):
                     lo % 4 == 0 and out.shape[1] % 4 == 0 and h.shape[0] > 0):
                 csr = st.csr(h.device)
                 if scratch is None or scratch.shape[1] != widths[li]:
-                    scratch = torch.empty((h.shape[0], widths[li]), dtype=torch.float32, device=h.device)
+                    # (kept with the graph's per-device structure, as the permutation's scratch is: the launches of one
+                    # stream share it, and a step allocates nothing for it)
+                    cache, key = st._cache(h.device), ("bi_scratch", h.shape[0], widths[li])
+                    scratch = cache.get(key)
+                    if scratch is None:
+                        scratch = cache[key] = ops._scratch((h.shape[0], widths[li]), torch.float32, h.device)
                 h = ops.spmm_bi_fused(csr.indptr, csr.col, csr.row_of, hc, st.csr_weights(w), W.detach(), 0.01,
                                       norm_out=norm_out, want_h=not last, scratch=scratch, self_out=self_out)
                 continue

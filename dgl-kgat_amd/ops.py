@@ -90,6 +90,15 @@ def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _scratch(shape, dtype, device):
+    """A scratch tensor of `shape` carved from `_workspace`: what a call hands to the library beside its workspace
+    (partial sums, the permutation's intermediate array) comes from the same place as the workspace itself."""
+    nbytes = dtype.itemsize
+    for s in shape:
+        nbytes *= int(s)
+    return _workspace(nbytes, device)[:nbytes].view(dtype).view(shape)
+
+
 def csr_from_coo(n_nodes, src, dst):
     """(indptr, col, eid, row_of) of the destination-major CSR; stable in edge id."""
     src = _need(src, torch.int32, "src")
@@ -212,7 +221,7 @@ def permute(plan, values, out=None, tmp=None):
     (kgat_permute_f32).  `tmp`: n floats of scratch a caller may keep between calls on one stream."""
     values = _need(values, torch.float32, "values", (plan.n,))
     out = torch.empty_like(values) if out is None else _need(out, torch.float32, "out", (plan.n,))
-    tmp = torch.empty_like(values) if tmp is None else _need(tmp, torch.float32, "tmp", (plan.n,))
+    tmp = _scratch((plan.n,), torch.float32, values.device) if tmp is None else _need(tmp, torch.float32, "tmp", (plan.n,))
     with _timed("permute", (plan.n,)):
         check(_lib.load().kgat_permute_f32(plan.n, _ptr(plan.slot_a), _ptr(plan.dst_a), _ptr(plan.slot_b), _ptr(values),
                                            _ptr(out), _ptr(tmp), _stream(values)), "kgat_permute_f32")
@@ -301,7 +310,7 @@ def att_score_split(n_nodes, rel_ptr, perm, src_g, pos_g, gid, gptr, g_node, n_g
     _need(g_node, torch.int32, "g_node")
     width = d if folded else k
     if g_tab is None:
-        g_tab = torch.empty((max(n_groups, 1), width), dtype=torch.float32, device=ent.device)
+        g_tab = _scratch((max(n_groups, 1), width), torch.float32, ent.device)
     else:
         _need(g_tab, torch.float32, "g_tab")
         if g_tab.numel() < max(n_groups, 1) * width:
@@ -370,14 +379,14 @@ def fold_tiles(rel_ptr, gid, gptr, n_groups, cap=FOLD_TILE_CAP, n_parts=None, co
     e = gid.numel()
     dev = gid.device
     t_max = max(int(lib.kgat_fold_tiles_max(e, int(n_groups), n_rel, int(cap))), 1)
-    tiles = torch.zeros((t_max, 4), dtype=torch.int32, device=dev)
-    rel_tptr = torch.zeros(n_rel + 1, dtype=torch.int32, device=dev)
+    tiles = torch.empty((t_max, 4), dtype=torch.int32, device=dev)      # (the entry clears the rows no tile takes)
+    rel_tptr = torch.empty(n_rel + 1, dtype=torch.int32, device=dev)
     ws = _workspace(lib.kgat_fold_tiles_workspace_bytes(int(n_groups), n_rel), dev)
     check(lib.kgat_fold_tiles(e, n_rel, int(n_groups), _ptr(rel_ptr), _ptr(gid), _ptr(gptr), int(cap),
                               _ptr(tiles), _ptr(rel_tptr), _ptr(ws), ws.numel(), _stream(gid)), "kgat_fold_tiles")
     if n_parts is None:
         n_parts = torch.cuda.get_device_properties(dev).multi_processor_count
-    part_tptr = torch.zeros(int(n_parts) + 1, dtype=torch.int32, device=dev)
+    part_tptr = torch.empty(int(n_parts) + 1, dtype=torch.int32, device=dev)
     ws2 = _workspace(lib.kgat_fold_tile_parts_workspace_bytes(t_max), dev)
     check(lib.kgat_fold_tile_parts(t_max, n_rel, _ptr(tiles), _ptr(rel_tptr), int(n_parts), int(cost[0]), int(cost[1]),
                                    int(cost[2]), _ptr(part_tptr), _ptr(ws2), ws2.numel(), _stream(gid)),
@@ -665,7 +674,7 @@ def edge_softmax_permuted(indptr, row_of, eid, logits, plan, in_csr_order=False,
     row_of = _need(row_of, torch.int32, "row_of", logits.shape)
     eid = _need(eid, torch.int32, "eid", logits.shape)
     out = torch.empty_like(logits) if out is None else _need(out, torch.float32, "out", (plan.n,))
-    tmp = torch.empty_like(logits) if tmp is None else _need(tmp, torch.float32, "tmp", (plan.n,))
+    tmp = _scratch((plan.n,), torch.float32, logits.device) if tmp is None else _need(tmp, torch.float32, "tmp", (plan.n,))
     out_csr = torch.empty_like(logits)
     n_nodes = indptr.numel() - 1
     lib = _lib.load()
@@ -988,9 +997,9 @@ def sage_bwd_weight(grad_pre, H, HN, want_partials=False):
     HN = _need(HN, torch.float32, "HN", (n, d_in))
     lib = _lib.load()
     nb = int(lib.kgat_bi_interaction_bwd_weight_partials(n))
-    ps = torch.empty((nb, d_out, d_in), dtype=torch.float32, device=H.device)
-    pn = torch.empty_like(ps)
-    pb = torch.empty((nb, d_out), dtype=torch.float32, device=H.device)
+    ps = _scratch((nb, d_out, d_in), torch.float32, H.device)
+    pn = _scratch((nb, d_out, d_in), torch.float32, H.device)
+    pb = _scratch((nb, d_out), torch.float32, H.device)
     with _timed("sage_bwd_weight", (n, d_in, d_out)):
         check(lib.kgat_sage_bwd_weight_f32(n, d_in, d_out, _ptr(grad_pre), _ptr(H), _ptr(HN), _ptr(ps), _ptr(pn),
                                            _ptr(pb), nb, _stream(H)), "kgat_sage_bwd_weight_f32")
@@ -1027,7 +1036,7 @@ def spmm_bi_fused(indptr, col, row_of, X, w, W2, negative_slope=0.01, h_out=None
     if self_out is not None:
         self_stride = _strided_rows(self_out, n_rows, d_in, "self_out")
     if scratch is None:
-        scratch = torch.empty((n_rows, d_in), dtype=torch.float32, device=X.device)
+        scratch = _scratch((n_rows, d_in), torch.float32, X.device)
     else:
         scratch = _need(scratch, torch.float32, "scratch", (n_rows, d_in))
     with _timed("spmm_bi_fused", (e1 - e0, n_rows, d_in, d_out)):
@@ -1306,7 +1315,7 @@ def aggregator_bwd_weight(form, grad_z, H, HN, want_partials=False):
     gzs, H, HN, n, d_in, d_out = _bwd_operands(form, grad_z, H, HN)
     nb = int(_lib.load().kgat_bi_interaction_bwd_weight_partials(n))
     k = 2 * d_in if form == FORMS["GraphSage"] else d_in
-    partials = [torch.empty((nb, d_out, k), dtype=torch.float32, device=H.device) for _ in gzs]
+    partials = [_scratch((nb, d_out, k), torch.float32, H.device) for _ in gzs]
     fn, lead, name = _entry(form, "_bwd_weight_f32")
     check(fn(*lead, n, d_in, d_out, *map(_ptr, gzs), _ptr(H), _ptr(HN), *map(_ptr, partials), nb, _stream(H)), name)
     res = partials if want_partials else [p.sum(0) for p in partials]
@@ -1521,12 +1530,12 @@ def eval_recall_ndcg(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, 
         raise KGATLibraryError("eval_recall_ndcg: K = %d / F = %d outside the kernel's range" % (K, F))
     dev = emb.device
     disc = _discounts(K, dev)
-    recall = torch.zeros(n_users, dtype=torch.float64, device=dev)
-    ndcg = torch.zeros(n_users, dtype=torch.float64, device=dev)
+    recall = torch.empty(n_users, dtype=torch.float64, device=dev)   # (the merge launch writes every user)
+    ndcg = torch.empty(n_users, dtype=torch.float64, device=dev)
     topk = torch.empty((n_users, K), dtype=torch.int32, device=dev) if want_topk else None
     if n_users == 0:
         return (recall, ndcg, topk) if want_topk else (recall, ndcg)
-    ws = torch.empty(lib.kgat_eval_workspace_bytes(n_users, n_items, F, K), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.kgat_eval_workspace_bytes(n_users, n_items, F, K), dev)
     itemT = _eval_items(lib, emb, item_ids)
     with _timed("eval_recall_ndcg", (n_users, n_items, F, K)):
         check(lib.kgat_eval_recall_ndcg_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
@@ -1557,7 +1566,7 @@ def eval_topk(emb, user_ids, item_ids, train_ptr, train_items, K, drop_train=Fal
     scores = torch.empty((n_users, K), dtype=torch.float32, device=dev) if want_scores else None
     if n_users == 0:
         return (topk, scores) if want_scores else topk
-    ws = torch.empty(lib.kgat_eval_topk_workspace_bytes(n_users, n_items, F, K), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.kgat_eval_topk_workspace_bytes(n_users, n_items, F, K), dev)
     itemT = _eval_items(lib, emb, item_ids)
     with _timed("eval_topk", (n_users, n_items, F, K)):
         check(lib.kgat_eval_topk_f32(n_users, _ptr(user_ids), n_items, F, _ptr(emb), stride, _ptr(itemT),
@@ -1605,8 +1614,8 @@ def eval_rank(emb, user_ids, item_ids, train_ptr, train_items, test_ptr, test_it
     if not lib.kgat_eval_rank_supported(F):
         raise KGATLibraryError("eval_rank: F = %d outside the kernel's range" % F)
     dev = emb.device
-    above = torch.zeros(n_test, dtype=torch.int32, device=dev)
-    scores = torch.zeros(n_test, dtype=torch.float32, device=dev) if want_scores else None
+    above = torch.empty(n_test, dtype=torch.int32, device=dev)       # (the entry clears it on the stream)
+    scores = torch.empty(n_test, dtype=torch.float32, device=dev) if want_scores else None
     if n_users == 0 or n_test == 0:
         return (above, scores) if want_scores else above
     ws = _workspace(lib.kgat_eval_rank_workspace_bytes(n_users, n_items, F, n_train, n_test), dev)
@@ -1647,8 +1656,8 @@ def eval_rank_metrics(above, test_ptr, test_items, n_candidates, ks, n_items=Non
     if ks[-1] > n_items:
         raise ValueError("eval_rank_metrics: cut-off %d is beyond the %d items" % (ks[-1], n_items))
     disc = _discounts(ks[-1], dev)
-    at_k = torch.zeros((n_users, len(ks), 4), dtype=torch.float64, device=dev)
-    scalar = torch.zeros((n_users, 4), dtype=torch.float64, device=dev)
+    at_k = torch.empty((n_users, len(ks), 4), dtype=torch.float64, device=dev)   # (every word is written)
+    scalar = torch.empty((n_users, 4), dtype=torch.float64, device=dev)
     lib = _lib.load()
     ws = _workspace(lib.kgat_eval_rank_metrics_workspace_bytes(above.numel()), dev)
     with _timed("eval_rank_metrics", (n_users, above.numel(), len(ks))):
@@ -1924,7 +1933,7 @@ def grad_norm(tensors, max_norm, norm_out=None):
     if any(c < 0 for c in counts):
         check(-1, "kgat_grad_sumsq_partials")
     total = sum(counts)
-    partials = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    partials = _scratch((max(total, 1),), torch.float32, dev)
     coef = torch.empty((), dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev), _timed("grad_norm", (len(tensors), total)):
