@@ -35,6 +35,7 @@ SOURCES = {
     "kgat_edge_weights.hip": [],
     "kgat_att_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_gat.hip": [],
+    "kgat_rgcn.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -208,6 +209,13 @@ SIGNATURES = {
                                 _p, _p, _p, _p, _sz, _p]),
     "kgat_gat_bwd_f32": (_i32, [_i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                 C.c_float, C.c_float, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
+    # dgl.nn.pytorch.conv.RelGraphConv (regularizer "basis"), the sparse part aggregate-first: one gather of a source
+    # row feeds B accumulators; backward towards x and towards the coefficients (ABI 16, additive)
+    "kgat_rgcn_supported": (_i32, [_i32, _i32, _i32]),
+    "kgat_rgcn_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "kgat_rgcn_fwd_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "kgat_rgcn_bwd_x_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "kgat_rgcn_bwd_coef_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

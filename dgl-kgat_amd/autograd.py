@@ -11,6 +11,9 @@
   in one place, inputs that would need a backward.
 * ``gat_aggregate`` - the message passing of DGL's GATConv (kgat_gat_fwd_f32 / kgat_gat_bwd_f32): logits, destination softmax,
   attention dropout and the weighted sum per head in one walk; backward towards ft, el and er.
+* ``rgcn_aggregate`` - the message passing of DGL's RelGraphConv with basis decomposition, aggregate-first
+  (kgat_rgcn_fwd_f32 / kgat_rgcn_bwd_x_f32 / kgat_rgcn_bwd_coef_f32): one gather of a source row feeds B accumulators;
+  backward towards x and the coefficients.
 * ``kgat_attention`` - the fused attention (logits + destination softmax, models.py:135-154) as one unit that
   differentiates towards the entity table, W_R and the relation embeddings.
 """
@@ -555,3 +558,87 @@ def gat_aggregate(g, ft, el, er, negative_slope=0.2, attn_drop=0.0, seed=0):
     if ops.gat_supported(ft.shape[1], ft.shape[2]):
         return _GATAggregate.apply(ft, el, er, g, float(negative_slope), float(attn_drop), int(seed))
     return _gat_restated(g._st, ft, el, er, float(negative_slope), float(attn_drop), int(seed))
+
+
+class _RGCNAggregate(torch.autograd.Function):
+    """The relational aggregation (kgat_rgcn_fwd_f32) and its two backward walks (kgat_rgcn_bwd_x_f32,
+    kgat_rgcn_bwd_coef_f32).  Saved: x and the coefficients; nothing edge-sized beyond the graph's cached streams."""
+
+    @staticmethod
+    def forward(ctx, x, coef, g, etypes, norm):
+        st = g._st
+        xc, ac = x.detach().contiguous(), coef.detach().contiguous()
+        et_csr, nm_csr, _, _ = st.rel_streams(etypes, norm, xc.device)
+        Z = ops.rgcn_forward(st.csr(xc.device), et_csr, nm_csr, xc, ac)
+        ctx.g, ctx.etypes, ctx.norm = g, etypes, norm
+        ctx.save_for_backward(xc, ac)
+        return Z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_Z):
+        x, a = ctx.saved_tensors
+        st = ctx.g._st
+        dev = g_Z.device
+        g_Z = g_Z.contiguous()
+        et_csr, nm_csr, et_rev, nm_rev = st.rel_streams(ctx.etypes, ctx.norm, dev)
+        g_x = g_a = None
+        if ctx.needs_input_grad[0]:
+            g_x = ops.rgcn_backward_x(st.csr_rev(dev), et_rev, nm_rev, g_Z, a)
+        if ctx.needs_input_grad[1]:
+            g_a = ops.rgcn_backward_coef(st.csr(dev), et_csr, nm_csr, x, g_Z, a.shape[0], a.shape[1])
+        return g_x, g_a, None, None, None
+
+
+def _rgcn_restated(st, x, coef, etypes, norm):
+    """The aggregation restated in torch operators over the COO (under torch's autograd), for shapes outside
+    ops.rgcn_supported.  torch's scatter adds are unordered atomics, so the arithmetic runs in fp64 (forward and, through
+    the casts, backward) and the results are rounded to fp32 once, as _gat_restated does and for the same reason.  One
+    index_add per basis: nothing of size E x B x D is formed."""
+    dev = x.device
+    src, dst = (t.long() for t in st.coo(dev))
+    et = etypes.reshape(-1).to(device=dev, dtype=torch.long)
+    x64, a64 = x.double(), coef.double()
+    ok = ((et >= 0) & (et < coef.shape[0])).to(torch.float64)
+    c = a64[et.clamp(0, coef.shape[0] - 1)] * ok.unsqueeze(1)              # (E, B)
+    if norm is not None:
+        c = c * norm.detach().reshape(-1, 1).to(device=dev, dtype=torch.float64)
+    xs = x64[src]
+    Z = torch.stack([torch.zeros_like(x64).index_add(0, dst, c[:, b:b + 1] * xs) for b in range(coef.shape[1])], 1)
+    return Z.to(x.dtype)
+
+
+def rgcn_aggregate(g, x, coef, etypes, norm=None):
+    """Z[v, b, :] = sum_{e: u->v} norm[e] * coef[etypes[e], b] * x[u, :]: the message passing of DGL's RelGraphConv
+    (basis regularizer) aggregate-first, as one differentiable unit (gradients to x and coef).  x (N, D), coef (R, B)
+    float32, etypes (E,) integer and norm (E,) or (E, 1) float32 (or None: 1) in edge-id order.  The layer's output is
+    Z.view(N, B * D) @ weight.view(B * D, out)."""
+    if x.dim() != 2 or coef.dim() != 2:
+        raise ValueError("rgcn_aggregate: x must be (N, D) and coef (R, B); got %s, %s" % (tuple(x.shape), tuple(coef.shape)))
+    if x.shape[0] != g.number_of_nodes():
+        raise ValueError("node feature has %d rows, graph has %d nodes" % (x.shape[0], g.number_of_nodes()))
+    e = g.number_of_edges()
+    if etypes.dim() != 1 or etypes.shape[0] != e:
+        raise ValueError("rgcn_aggregate: etypes must be (E,) = (%d,), got %s" % (e, tuple(etypes.shape)))
+    if norm is not None and tuple(norm.shape) not in ((e,), (e, 1)):
+        raise ValueError("rgcn_aggregate: norm must be (E,) or (E, 1) with E = %d, got %s" % (e, tuple(norm.shape)))
+    if g.partition is not None:
+        from .graph import DGLError
+        raise DGLError("rgcn_aggregate on a partitioned graph is not supported: a shard holds only part of a source's "
+                       "out-edges; use the unsharded graph")
+    if norm is not None and norm.requires_grad:
+        raise NotImplementedError("rgcn_aggregate: a gradient towards norm is not formed (the normaliser is a constant "
+                                  "of the graph)")
+    floats = (("x", x), ("coef", coef)) + ((("norm", norm),) if norm is not None else ())
+    for name, t in floats:
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    if etypes.is_floating_point() or etypes.dtype == torch.bool:
+        raise TypeError("etypes must be an integer tensor, got %s" % (etypes.dtype,))
+    for name, t in floats:
+        if not t.is_cuda:
+            raise ops.KGATLibraryError("%s is on %s: the relational aggregation only runs on a HIP device (no CPU "
+                                       "implementation exists in this package)" % (name, t.device))
+    if ops.rgcn_supported(x.shape[1], coef.shape[1], coef.shape[0]):
+        return _RGCNAggregate.apply(x, coef, g, etypes, norm)
+    return _rgcn_restated(g._st, x, coef, etypes, norm)

@@ -1,6 +1,7 @@
 """Make this package answer to the module names the reference imports
 (``import dgl``, ``import dgl.function as fn``, ``from dgl.nn.pytorch.softmax import
-edge_softmax``, ``from dgl.nn.pytorch.conv import SAGEConv`` - models.py:4-6, dataset.py:3 - and ``GATConv`` beside it),
+edge_softmax``, ``from dgl.nn.pytorch.conv import SAGEConv`` - models.py:4-6, dataset.py:3 - and ``GATConv`` and
+``RelGraphConv`` beside it),
 so reference-style model code runs over the HIP kernels without edits."""
 import sys
 import types
@@ -12,6 +13,7 @@ def install_as_dgl(force=False):
     import dgl_kgat_amd as pkg
     from . import function, graph, softmax
     from .gat_layer import GATConv
+    from .rgcn_layer import RelGraphConv
     from .sage_layer import SAGEConv
 
     dgl = types.ModuleType("dgl")
@@ -23,6 +25,7 @@ def install_as_dgl(force=False):
     conv = types.ModuleType("dgl.nn.pytorch.conv")
     conv.SAGEConv = SAGEConv  # models.py:6; the graphsage branch (sage_layer.py)
     conv.GATConv = GATConv    # the plain graph-attention baseline (gat_layer.py)
+    conv.RelGraphConv = RelGraphConv  # the relation-aware baseline, R-GCN with basis decomposition (rgcn_layer.py)
     nn.pytorch, pt.softmax, pt.conv = pt, softmax, conv
     dgl.nn = nn
     mods = {"dgl": dgl, "dgl.function": function, "dgl.nn": nn, "dgl.nn.pytorch": pt,

@@ -258,6 +258,28 @@ class _Structure:
             c["rel_groups"] = hit
         return hit[1]
 
+    def rel_streams(self, etypes, norm, device):
+        """(etype_csr, norm_csr, etype_rev, norm_rev): the per-edge relation ids (int32) and the normaliser (float32, or
+        None) of the relational convolution in the order of the destination-major CSR and of the reversed graph's CSR
+        (ops.gather over csr.eid / csr_rev.eid).  Cached per device on the identity + version of the two tensors handed
+        in (kept alive by the cache), so a training loop permutes them once."""
+        dev = torch.device(device)
+        c = self._cache(dev)
+        key = (etypes._version, None if norm is None else norm._version)
+        hit = c.get("rel_streams")
+        if hit is None or hit[2] is not etypes or hit[3] is not norm or hit[0] != key:
+            csr, rev = self.csr(dev), self.csr_rev(dev)
+            et32 = etypes.detach().reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+            streams = [ops.gather(csr.eid, et32), None, ops.gather(rev.eid, et32), None]
+            pending = None if norm is None else pending_csr_weights(norm, self)
+            if pending is not None:  # a still-pending lazy tensor of this graph stands for its CSR copy: left pending
+                streams[1], streams[3] = pending, self.rev_weights(norm)
+            elif norm is not None:
+                nm = norm.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+                streams[1], streams[3] = ops.gather(csr.eid, nm), ops.gather(rev.eid, nm)
+            hit = c["rel_streams"] = (key, tuple(streams), etypes, norm)
+        return hit[1]
+
     def permuted(self, name, src_of, values, out=None):
         """out[i] = values[src_of[i]] for one of the graph's static E-sized permutations (`name`: the key its plan is
         kept under; `src_of`: the cached int32 index itself).  fp32 values go through the planned two-pass form

@@ -23,6 +23,7 @@ from . import function as fn
 from .autograd import _combine, edge_softmax, u_mul_e_sum
 from .ops import BI2_FORM, FORMS
 from .options import options
+from .rgcn_layer import RelGraphConv
 from .sage_layer import SAGEConv, draw_seed
 
 
@@ -179,6 +180,10 @@ class KGATPropagation(nn.Module):
     survivors by 1 / (1 - p); one dropped adjacency per call, shared by all layers and by the backward.  The three
     add no parameter or buffer.
 
+    ``gnn_model="rgcn"`` (``num_bases``): a stack of ``RelGraphConv`` layers with ``min(num_bases, n_relations)`` bases
+    and a self-loop over the edges' types, normalised by 1 / in-degree; ``gnn`` runs it per layer (``_gnn_rgcn``), the
+    edge weights in ``edata['w']`` are not read.
+
     Draw order of a ``gnn`` call (torch's CPU generator, so ``torch.manual_seed`` reproduces a run): first the
     message-dropout seed - one ``torch.empty((), dtype=torch.int64).random_()``, drawn only by the fused training unit
     and only when the layers' dropout is > 0 -, then the node-dropout seed - one more such draw, only when node dropout
@@ -186,15 +191,15 @@ class KGATPropagation(nn.Module):
 
     def __init__(self, n_entities, n_relations, input_node_dim=64, relation_dim=64, num_gnn_layers=3,
                  n_hidden=64, dropout=0.1, reg_lambda_gnn=0.01, gnn_model="kgat", res_type="Bi", use_attention=True,
-                 adj_type="si", node_dropout=0.0):
+                 adj_type="si", node_dropout=0.0, num_bases=4):
         super().__init__()
-        if gnn_model not in ("kgat", "graphsage"):
-            raise NotImplementedError("gnn_model must be 'kgat' or 'graphsage', got %r" % (gnn_model,))
+        if gnn_model not in ("kgat", "graphsage", "rgcn"):
+            raise NotImplementedError("gnn_model must be 'kgat', 'graphsage' or 'rgcn', got %r" % (gnn_model,))
         if res_type not in RES_TYPES:
             raise NotImplementedError("res_type must be one of %s, got %r" % (", ".join(sorted(RES_TYPES)), res_type))
-        if gnn_model == "graphsage" and res_type != "Bi":
-            raise ValueError("res_type selects the aggregator of gnn_model='kgat'; gnn_model='graphsage' takes none "
-                             "(got res_type=%r)" % (res_type,))
+        if gnn_model in ("graphsage", "rgcn") and res_type != "Bi":
+            raise ValueError("res_type selects the aggregator of gnn_model='kgat'; gnn_model=%r takes none "
+                             "(got res_type=%r)" % (gnn_model, res_type))
         if adj_type not in ("si", "bi"):
             raise ValueError("adj_type must be 'si' or 'bi', got %r" % (adj_type,))
         if not 0.0 <= float(node_dropout) < 1.0:
@@ -202,6 +207,11 @@ class KGATPropagation(nn.Module):
         if gnn_model == "graphsage" and node_dropout > 0:
             raise ValueError("node_dropout scales the edge weights; gnn_model='graphsage' aggregates without weights "
                              "(got node_dropout=%r)" % (node_dropout,))
+        if gnn_model == "rgcn" and node_dropout > 0:
+            raise ValueError("node_dropout scales the attention's edge weights; gnn_model='rgcn' aggregates with the "
+                             "Laplacian normaliser (got node_dropout=%r)" % (node_dropout,))
+        if gnn_model == "rgcn" and int(num_bases) < 1:
+            raise ValueError("num_bases must be at least 1, got %r" % (num_bases,))
         self._gnn_model = gnn_model
         self._res_type = res_type
         self._use_attention, self._adj_type, self._node_dropout = bool(use_attention), adj_type, float(node_dropout)
@@ -218,6 +228,11 @@ class KGATPropagation(nn.Module):
                 act = None if i + 1 == num_gnn_layers else F.relu
                 self.layers.append(SAGEConv(d_in, n_hidden // int(math.pow(2, i)), aggregator_type="mean",
                                             feat_drop=dropout, activation=act))
+            elif gnn_model == "rgcn":  # R-GCN with basis decomposition; ReLU on every layer but the last
+                act = None if i + 1 == num_gnn_layers else F.relu
+                self.layers.append(RelGraphConv(d_in, n_hidden // int(math.pow(2, i)), n_relations,
+                                                num_bases=min(int(num_bases), n_relations), self_loop=True,
+                                                dropout=dropout, activation=act))
             else:
                 self.layers.append(KGATConv(d_in, n_hidden // int(math.pow(2, i)), dropout, res_type))
 
@@ -268,6 +283,8 @@ class KGATPropagation(nn.Module):
     def gnn(self, g, x=None, fused=None):
         if self._sage_stack():
             return self._gnn_sage(g, fused)
+        if len(self.layers) > 0 and all(isinstance(layer, RelGraphConv) for layer in self.layers):
+            return KGATPropagation._gnn_rgcn(self, g)  # (not through self: a model routed here by compat.accelerate lacks it)
         if g.partition is not None and any(_layer_dense(layer)[0] != FORMS["Bi"] for layer in self.layers):
             from .graph import DGLError
             raise DGLError("res_type %r on a partitioned graph: sharded models run the Bi aggregator only"
@@ -499,6 +516,28 @@ class KGATPropagation(nn.Module):
         if not aligned:
             out[:, :widths[0]] = self._node_embeddings(g).detach()
         return out
+
+    # -- R-GCN stack (gnn_model="rgcn": RelGraphConv layers over the typed edges; the same readout, models.py:156-168)
+    def _rgcn_stack(self):
+        return len(self.layers) > 0 and all(isinstance(layer, RelGraphConv) for layer in self.layers)
+
+    def _gnn_rgcn(self, g):
+        """The readout [h0 | normalize(h1) | ...] over a RelGraphConv stack, per layer: the relation of an edge is
+        g.edata['type'], the normaliser the random-walk Laplacian's 1 / in-degree (g.laplacian_weights("si"), what DGL's
+        R-GCN link-prediction example uses).  The dropout seed is one draw from torch's CPU generator per call, layer i
+        uses seed + i."""
+        from .graph import DGLError
+        if g.partition is not None:
+            raise DGLError("R-GCN on a partitioned graph is not supported (sharded relational convolution is out of scope)")
+        etypes = g.edata["type"]
+        norm = g.laplacian_weights("si")
+        seed = draw_seed() if any(layer.drop_p() > 0 for layer in self.layers) else 0
+        h = self._node_embeddings(g)
+        cache = [h]
+        for li, layer in enumerate(self.layers):
+            h = layer(g, h, etypes, norm, seed=seed + li)
+            cache.append(F.normalize(h, p=2, dim=1))
+        return torch.cat(cache, 1)
 
     def transR(self, h, r, pos_t, neg_t, reg_lambda_kg=0.01, fused=None):
         """TransR pairwise ranking loss of the KG phase (reference models.py:114-133 with

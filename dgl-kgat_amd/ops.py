@@ -895,6 +895,79 @@ def gat_backward(csr, csr_rev, ft, el, er, m, l, out, g_out, negative_slope=0.2,
     return g_ft, g_el, g_er
 
 
+def rgcn_supported(D, B, R):
+    """The (feature width, bases, relations) the kgat_rgcn_* entries cover: D in {16, 32, 64, 128}, 1 <= B <= 8,
+    R B <= 4096."""
+    return bool(_lib.load().kgat_rgcn_supported(int(D), int(B), int(R)))
+
+
+def _rgcn_graph(csr, etype, norm, n):
+    indptr = _need(csr.indptr, torch.int32, "indptr", (n + 1,))
+    col = _need(csr.col, torch.int32, "col")
+    row_of = _need(csr.row_of, torch.int32, "row_of", col.shape)
+    etype = _need(etype, torch.int32, "etype", col.shape)
+    if norm is not None:
+        norm = _need(norm, torch.float32, "norm", col.shape)
+    return (indptr, col, row_of, etype, norm), col.numel()
+
+
+def _rgcn_scratch(n, e, D, B, R, which, device):
+    return _workspace(_lib.load().kgat_rgcn_scratch_bytes(n, e, D, B, R, which), device)
+
+
+def rgcn_forward(csr, etype_csr, norm_csr, x, a):
+    """Z (N, B, D) of kgat_rgcn_fwd_f32: Z[v, b, :] = sum_{e: u->v} norm[e] a[etype[e], b] x[u, :] over the
+    destination-major `csr`, `etype_csr` (int32) and `norm_csr` (float32 or None: 1) in its order.  x (N, D), a (R, B)
+    float32; (D, B, R) as rgcn_supported."""
+    x = _need(x, torch.float32, "x")
+    a = _need(a, torch.float32, "a")
+    if x.dim() != 2 or a.dim() != 2:
+        raise ValueError("x must be (N, D) and a (R, B), got %s, %s" % (tuple(x.shape), tuple(a.shape)))
+    (n, D), (R, B) = x.shape, a.shape
+    graph, e = _rgcn_graph(csr, etype_csr, norm_csr, n)
+    Z = torch.empty((n, B, D), dtype=torch.float32, device=x.device)
+    ws = _rgcn_scratch(n, e, D, B, R, 0, x.device)
+    with _timed("rgcn_fwd", (e, n, D, B, R)):
+        check(_lib.load().kgat_rgcn_fwd_f32(n, e, D, B, R, *[_ptr(t) for t in graph], _ptr(x), _ptr(a), _ptr(Z),
+                                            _ptr(ws), ws.numel(), _stream(x)), "kgat_rgcn_fwd_f32")
+    return Z
+
+
+def rgcn_backward_x(csr_rev, etype_rev, norm_rev, g_Z, a):
+    """g_x (N, D) of kgat_rgcn_bwd_x_f32 from the gradient at Z (N, B, D): one walk over the reversed graph's
+    `csr_rev`, `etype_rev` / `norm_rev` in its order."""
+    g_Z = _need(g_Z, torch.float32, "g_Z")
+    a = _need(a, torch.float32, "a")
+    if g_Z.dim() != 3 or a.dim() != 2 or a.shape[1] != g_Z.shape[1]:
+        raise ValueError("g_Z must be (N, B, D) and a (R, B), got %s, %s" % (tuple(g_Z.shape), tuple(a.shape)))
+    (n, B, D), R = g_Z.shape, a.shape[0]
+    graph, e = _rgcn_graph(csr_rev, etype_rev, norm_rev, n)
+    g_x = torch.empty((n, D), dtype=torch.float32, device=g_Z.device)
+    ws = _rgcn_scratch(n, e, D, B, R, 1, g_Z.device)
+    with _timed("rgcn_bwd_x", (e, n, D, B, R)):
+        check(_lib.load().kgat_rgcn_bwd_x_f32(n, e, D, B, R, *[_ptr(t) for t in graph], _ptr(g_Z), _ptr(a), _ptr(g_x),
+                                              _ptr(ws), ws.numel(), _stream(g_Z)), "kgat_rgcn_bwd_x_f32")
+    return g_x
+
+
+def rgcn_backward_coef(csr, etype_csr, norm_csr, x, g_Z, R, B):
+    """g_a (R, B) of kgat_rgcn_bwd_coef_f32: g_a[r, b] = sum_{e: etype[e] = r} norm[e] <x[src e], g_Z[dst e, b]> over
+    the destination-major `csr`."""
+    x = _need(x, torch.float32, "x")
+    if x.dim() != 2:
+        raise ValueError("x must be (N, D), got %s" % (tuple(x.shape),))
+    n, D = x.shape
+    g_Z = _need(g_Z, torch.float32, "g_Z", (n, int(B), D))
+    R, B = int(R), int(B)
+    graph, e = _rgcn_graph(csr, etype_csr, norm_csr, n)
+    g_a = torch.empty((R, B), dtype=torch.float32, device=x.device)
+    ws = _rgcn_scratch(n, e, D, B, R, 2, x.device)
+    with _timed("rgcn_bwd_coef", (e, n, D, B, R)):
+        check(_lib.load().kgat_rgcn_bwd_coef_f32(n, e, D, B, R, *[_ptr(t) for t in graph], _ptr(x), _ptr(g_Z),
+                                                 _ptr(g_a), _ptr(ws), ws.numel(), _stream(x)), "kgat_rgcn_bwd_coef_f32")
+    return g_a
+
+
 REDUCE ={"sum": 0, "mean": 1}
 ACT = {None: 0, "none": 0, "relu": 1}
 

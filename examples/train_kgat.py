@@ -180,8 +180,11 @@ def parse_args(argv=None):
     ap.add_argument("--relation_embed_dim", type=int, default=64)
     ap.add_argument("--gnn_num_layer", type=int, default=3)
     ap.add_argument("--gnn_hidden_size", type=int, default=64)
-    ap.add_argument("--gnn_model", choices=("kgat", "graphsage"), default="kgat",
-                    help="propagation layers (reference kgat.py:23): bi-interaction KGATConv or SAGEConv (mean)")
+    ap.add_argument("--gnn_model", choices=("kgat", "graphsage", "rgcn"), default="kgat",
+                    help="propagation layers (reference kgat.py:23): bi-interaction KGATConv, SAGEConv (mean), or "
+                         "RelGraphConv (R-GCN with basis decomposition over the edge types)")
+    ap.add_argument("--num_bases", type=int, default=argparse.SUPPRESS,
+                    help="bases of the rgcn layers' relation weights (default 4; at most the number of relations)")
     ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage", "Bi2"), default="Bi",
                     help="aggregator of the kgat layers (KGATConv res_type, reference models.py:50-58): Bi-Interaction "
                          "(the reference's one-term form), GCN, GraphSage, or Bi2, the KGAT paper's two-term "
@@ -275,18 +278,22 @@ def parse_args(argv=None):
         ap.error("--explain_top ranks the walks of --explain N: give a number of users")
     if args.explain and args.gpus > 1:
         ap.error("--explain runs on one GPU: a walk crosses shards")
-    if args.explain and args.gnn_model == "graphsage":
-        ap.error("--explain follows the edge weights; --gnn_model graphsage aggregates without weights")
+    if args.explain and args.gnn_model != "kgat":
+        ap.error("--explain follows the edge weights; --gnn_model %s aggregates without them" % args.gnn_model)
     if args.res_type != "Bi" and args.gnn_model != "kgat":
-        ap.error("--res_type %s selects the aggregator of --gnn_model kgat; graphsage takes none" % args.res_type)
+        ap.error("--res_type %s selects the aggregator of --gnn_model kgat; %s takes none" % (args.res_type, args.gnn_model))
+    if getattr(args, "num_bases", 4) < 1:
+        ap.error("--num_bases takes a number of bases >= 1")
+    if args.gnn_model == "rgcn" and args.gpus > 1:
+        ap.error("--gnn_model rgcn runs on one GPU: sharded relational convolution is out of scope")
     if args.res_type != "Bi" and args.gpus > 1:
         ap.error("--res_type %s runs on one GPU: sharded models run the Bi aggregator only" % args.res_type)
     if not (0.0 <= args.grad_norm < float("inf")):
         ap.error("--grad_norm takes a finite norm > 0, or 0 for no clipping")
     if not 0.0 <= args.node_dropout < 1.0:
         ap.error("--node_dropout must be in [0, 1)")
-    if args.node_dropout > 0 and args.gnn_model == "graphsage":
-        ap.error("--node_dropout scales the edge weights; --gnn_model graphsage aggregates without weights")
+    if args.node_dropout > 0 and args.gnn_model != "kgat":
+        ap.error("--node_dropout scales the edge weights; --gnn_model %s aggregates without them" % args.gnn_model)
     if args.node_dropout > 0 and args.gpus > 1:
         ap.error("--node_dropout runs on one GPU")
     if not args.use_attention and args.adj_type == "bi" and args.gpus > 1:
@@ -298,8 +305,8 @@ def parse_args(argv=None):
             ap.error("--attention_grad 1 with --node_dropout: node dropout treats the edge weights as constants")
         if args.gpus > 1:
             ap.error("--attention_grad 1 runs on one GPU: a shard holds only part of a tail's out-edges")
-        if args.gnn_model == "graphsage":
-            ap.error("--attention_grad 1 needs --gnn_model kgat: graphsage aggregates without edge weights")
+        if args.gnn_model != "kgat":
+            ap.error("--attention_grad 1 needs --gnn_model kgat: %s aggregates without the attention" % args.gnn_model)
     return args
 
 
@@ -365,7 +372,7 @@ def _run(args, argv):
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
                               gnn_model=args.gnn_model, res_type=args.res_type, use_attention=bool(args.use_attention),
-                              adj_type=args.adj_type, node_dropout=args.node_dropout).to(dev)
+                              adj_type=args.adj_type, node_dropout=args.node_dropout, num_bases=getattr(args, "num_bases", 4)).to(dev)
 
     def replicas_agree(tag):
         """Every rank holds a replica of the parameters and runs the same optimiser on the same gradients

@@ -1120,6 +1120,39 @@ int kgat_gat_bwd_f32(int64_t n_nodes, int64_t n_edges, int H, int F, const int32
                      float drop_p, uint64_t seed, float* g_ft, float* g_el, float* g_er, void* workspace,
                      size_t workspace_bytes, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- relational graph convolution (additive within ABI 16)
+ * The sparse part of dgl.nn.pytorch.conv.RelGraphConv (DGL 0.4.x, regularizer "basis"), aggregate-first.  With
+ * W_r = sum_b a[r,b] weight[b] the layer's  h[v] = sum_{e: u->v} norm[e] (x[u] W_{etype e})  is
+ *   Z[v,b,:] = sum_{e: u->v} (norm[e] a[etype[e], b]) x[u,:]                                   kgat_rgcn_fwd_f32
+ * followed by the caller's GEMM  h = Z.view(N, B D) weight.view(B D, out): a source row (D floats, not B out) is
+ * gathered once per edge and feeds B accumulators.  x [N x D], Z and g_Z [N x B x D], a and g_a [R x B] (w_comp, or the
+ * R x R identity when B == R), etype int32 and norm float (may be NULL: 1) per edge in the order of the CSR walked.
+ *   g_x[u,:] = sum_{u->e} sum_b (norm[e] a[etype[e], b]) g_Z[dst e, b, :]                       kgat_rgcn_bwd_x_f32
+ * over the reversed CSR (rows = sources, rev_col = destinations, etype_rev / norm_rev in its order), and
+ *   g_a[r,b] = sum_{e: etype[e] = r} norm[e] <x[src e,:], g_Z[dst e, b, :]>                     kgat_rgcn_bwd_coef_f32
+ * over the forward CSR.  An edge whose type is outside [0, R) contributes nothing.  Rows without edges: 0.
+ *
+ * All walks use the sum kernel's tile decomposition with partials combined in run and tile order (bwd_coef: per
+ * wavefront tables in LDS added in edge order, then in wavefront, workgroup and chunk order): no atomics, bitwise
+ * reproducible; nothing of size E x D or E x B is written.  D in {16, 32, 64, 128}, 1 <= B <= 8, R B <= 4096
+ * (kgat_rgcn_supported), others KGAT_E_UNSUPPORTED.  The whole graph per call: indptr [N + 1], col / row_of / etype /
+ * norm [E].  x, Z, g_Z, g_x and the scratch 16-byte aligned.  Null pointer, negative size: KGAT_E_BADARG; scratch below
+ * kgat_rgcn_scratch_bytes(n_nodes, n_edges, D, B, R, pass = 0 fwd | 1 bwd_x | 2 bwd_coef): KGAT_E_WORKSPACE.  The tiles'
+ * partials live inside the scratch.  Every check precedes any device work. */
+int kgat_rgcn_supported(int D, int B, int R);
+size_t kgat_rgcn_scratch_bytes(int64_t n_nodes, int64_t n_edges, int D, int B, int R, int pass);
+int kgat_rgcn_fwd_f32(int64_t n_nodes, int64_t n_edges, int D, int B, int R, const int32_t* indptr, const int32_t* col,
+                      const int32_t* row_of, const int32_t* etype_csr, const float* norm_csr, const float* x,
+                      const float* a, float* Z, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
+int kgat_rgcn_bwd_x_f32(int64_t n_nodes, int64_t n_edges, int D, int B, int R, const int32_t* rev_indptr,
+                        const int32_t* rev_col, const int32_t* rev_row_of, const int32_t* etype_rev,
+                        const float* norm_rev, const float* g_Z, const float* a, float* g_x, void* scratch,
+                        size_t scratch_bytes, kgat_stream_t stream);
+int kgat_rgcn_bwd_coef_f32(int64_t n_nodes, int64_t n_edges, int D, int B, int R, const int32_t* indptr,
+                           const int32_t* col, const int32_t* row_of, const int32_t* etype_csr, const float* norm_csr,
+                           const float* x, const float* g_Z, float* g_a, void* scratch, size_t scratch_bytes,
+                           kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
