@@ -33,6 +33,18 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// float4 arithmetic, element by element
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 fma4(float a, const float4& x, const float4& c) {
+  return make_float4(fmaf(a, x.x, c.x), fmaf(a, x.y, c.y), fmaf(a, x.z, c.z), fmaf(a, x.w, c.w));
+}
+__device__ __forceinline__ float4 add4(const float4& a, const float4& b) {
+  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+__device__ __forceinline__ float4 mul4(const float4& a, const float4& b) {
+  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
+}
+
 // The blocks behind a launch's real work (block `first_block` on, `threads` each) clear zero[0 .. n_zero), n_zero a
 // multiple of 4: a zero fill rides beside launches that are chains of round trips on a few workgroups.
 __device__ __forceinline__ void zero_fill_behind(float* __restrict__ zero, int64_t n_zero, unsigned first_block,

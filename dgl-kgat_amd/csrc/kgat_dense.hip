@@ -72,7 +72,7 @@ struct DeferredRows {
   int32_t e0, e1;         // CSR positions of the row range
   int32_t te_shift;       // log2(edges per tile)
 };
-constexpr int kDeferLongChain = 8;  // = spmm_finish_kernel's kLongChain
+constexpr int kDeferLongChain = 8;  // = kLongChain (kgat_spmm_plan.h), which spmm_finish_kernel reads
 // COMB: how the layer's two inputs form the A operand (KGAT paper, "Information Aggregation"; the res_type of reference
 // models.py:50-58).  0 = Bi-Interaction, h * h_N (res_fc_2, d_out x d_in).  1 = GCN, h + h_N (res_fc, d_out x d_in).
 // 2 = GraphSage, [h | h_N] along K (res_fc, d_out x 2 d_in): the first KS steps of the contraction take W's columns

@@ -11,9 +11,9 @@
 // Decomposition: the sum kernel's (kgat_spmm_plan.h).  LPR = H F / 4 lanes cover a row of H F floats, a lane holds four
 // columns of ONE head (F % 4 == 0) and walks a run of consecutive CSR positions; per lane the state is (acc[4], s): the
 // weighted row sum and a per-head scalar (forward: l).  Runs' first / last rows are combined through LDS in run order,
-// tiles' first / last rows through the workspace and the finish launch in tile order (a chain of eight tiles and more:
-// the wavefront's lane groups stride over it and fold in a fixed tree).  No atomics: bitwise reproducible.  The finish
-// divides once per output element, correctly rounded.
+// tiles' first / last rows through the workspace and the finish launch in tile order.  No atomics: bitwise reproducible.
+// The finish divides once per output element, correctly rounded; it is this file's own copy of the launch that
+// kgat_tile_reduce.h states for the other reducers (below).
 //
 // The three walks are one kernel template:
 //   FWD      rows = destinations, forward CSR:  acc = sum c p ft[u],        s = sum p          -> out, l
@@ -279,14 +279,13 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void gat_tile_kernel(const GatK 
   }
 }
 
-// Finish: (a) rows that are first / last in some tile: the tile where the row starts owns it and adds the row's
-// partials over the tiles it spans, in tile order - one lane group per (tile, slot) item for short chains, the whole
-// wavefront striding over a chain of kLongChain tiles and more, folded in a fixed tree; (b) rows without edges: zeros.
+// The finish launch as kgat_tile_reduce.h describes it, kept as a copy: written as tile_finish over GatLane the
+// forward's long-chain loop waits for its first load before it issues the second.  A fix to
+// tile_finish is made here too.  Rows without edges: zeros.
 template <int LPR, int MODE>
 __global__ __launch_bounds__(spmm_threads(LPR)) void gat_finish_kernel(const GatK k) {
   constexpr int SPW = kWave / LPR;  // lane groups per wavefront
   constexpr int WPB = spmm_threads(LPR) / kWave;
-  constexpr int kLongChain = 8;
   static_assert(LPR <= kWave / 2, "a wavefront holds at least two lane groups");
   const int tid = threadIdx.x;
   const int wave = tid / kWave, lane_id = tid % kWave;

@@ -8,10 +8,9 @@
 // The dense part, h = Z.view(N, B D) @ weight.view(B D, out), is a library GEMM of the caller.  A source row is
 // gathered once per edge and feeds B accumulators; nothing of size E x D or E x B exists.
 //
-// Decomposition: the sum kernel's (kgat_spmm_plan.h).  LPR = D / 4 lanes cover a row of D floats with one 16-byte access
-// each and walk a run of consecutive CSR positions; runs' first / last rows are combined through LDS in run order,
-// tiles' first / last rows through the scratch and the finish launch in tile order (a chain of eight tiles and more: the
-// wavefront's lane groups stride over it and fold in a fixed tree).  No atomics: bitwise reproducible.
+// Decomposition: the one kgat_tile_reduce.h describes, whose finish launch FWD and BWD_X share.  LPR = D / 4 lanes cover
+// a row of D floats with one 16-byte access each; the accumulator sets go through the same LDS entries one set at a
+// time.  Every sum is added in run order, then tile order: no atomics, bitwise reproducible.
 //
 // Kernels are built for BP in {1, 2, 4, 8} accumulator sets; a call with B bases runs the next BP >= B with the
 // coefficient columns B .. BP - 1 zero in LDS.  The padding costs vector FMAs (B = 3: one set in four, B = 5: three in
@@ -23,7 +22,7 @@
 //          products per edge added into a per-wavefront R x B table in LDS in edge order; the wavefronts' tables are
 //          added in wavefront order into one partial per workgroup, the partials by a fixed chunked chain.
 // An edge whose type is outside [0, R) contributes nothing in any of the three.
-#include "kgat_spmm_plan.h"
+#include "kgat_tile_reduce.h"
 
 namespace kgat {
 namespace {
@@ -51,14 +50,6 @@ struct RgcnK {
   float* tab_part;        // COEF: per workgroup an R x B table
   int32_t tiles_per_group;
 };
-
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4s(float a, const float4& x, const float4& c) {
-  return make_float4(fmaf(a, x.x, c.x), fmaf(a, x.y, c.y), fmaf(a, x.z, c.z), fmaf(a, x.w, c.w));
-}
-__device__ __forceinline__ float4 add4s(const float4& a, const float4& b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
 
 // FWD and BWD_X: NACC accumulator sets per lane (FWD: BP, BWD_X: 1).
 template <int LPR, int BP, int MODE>
@@ -147,8 +138,8 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void rgcn_tile_kernel(const Rgcn
 #pragma unroll
           for (int b = 0; b < BP; ++b) {
             const float cb = scale * ar[b];
-            if constexpr (MODE == kFwd) acc[b] = fma4s(cb, x[i][0], acc[b]);
-            else acc[0] = fma4s(cb, x[i][b], acc[0]);
+            if constexpr (MODE == kFwd) acc[b] = fma4(cb, x[i][0], acc[b]);
+            else acc[0] = fma4(cb, x[i][b], acc[0]);
           }
         }
       }
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void rgcn_tile_kernel(const Rgcn
           const int32_t r2 = s_row[q >> 1][q & 1];
           if (r2 < 0) continue;
           if (r2 != rr) break;
-          v = add4s(v, s_part[q >> 1][q & 1][sl]);
+          v = add4(v, s_part[q >> 1][q & 1][sl]);
         }
         if (rr == first_row) k.part[(((size_t)blockIdx.x * 2 + 0) * nb + b) * LPR + sl] = v;
         else if (rr == last_row) k.part[(((size_t)blockIdx.x * 2 + 1) * nb + b) * LPR + sl] = v;
@@ -211,102 +202,51 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void rgcn_tile_kernel(const Rgcn
   }
 }
 
-// Finish of FWD / BWD_X: (a) rows that are first / last in some tile: the tile where the row starts owns it and adds
-// the row's partials over the tiles it spans, in tile order - one lane group per (tile, slot) item for short chains,
-// the whole wavefront striding over a chain of kLongChain tiles and more, folded in a fixed tree; (b) rows without
-// edges: zeros.
+// The finish launch's lane (kgat_tile_reduce.h): NACC accumulator sets of one float4, of which the first nb exist in
+// this launch; the scratch holds them per (tile, slot, block, lane).  A row without edges gets zeros.
 template <int LPR, int NACC>
-__global__ __launch_bounds__(spmm_threads(LPR)) void rgcn_finish_kernel(const RgcnK k) {
-  constexpr int SPW = kWave / LPR;  // lane groups per wavefront
-  constexpr int WPB = spmm_threads(LPR) / kWave;
-  constexpr int kLongChain = 8;
-  static_assert(LPR <= kWave / 2, "a wavefront holds at least two lane groups");
-  const int tid = threadIdx.x;
-  const int wave = tid / kWave, lane_id = tid % kWave;
-  const int q = lane_id / LPR, sl = lane_id % LPR;
-  const int nb = k.nb;
-  const int32_t te = k.te;
+struct RgcnLane {
+  const RgcnK& k;
+  int sl, nb;
   float4 acc[NACC];
-  auto reset = [&]() {
+
+  __device__ __forceinline__ RgcnLane(int sl_, const RgcnK& k_) : k(k_), sl(sl_), nb(k_.nb) {}
+
+  __device__ __forceinline__ void reset() {
 #pragma unroll
     for (int b = 0; b < NACC; ++b) acc[b] = zero4();
-  };
-  auto add_part = [&](int64_t tile, int slot) {
+  }
+  __device__ __forceinline__ void add_part(int64_t tile, int slot) {
 #pragma unroll
     for (int b = 0; b < NACC; ++b)
-      if (b < nb) acc[b] = add4s(acc[b], k.part[(((size_t)tile * 2 + slot) * nb + b) * LPR + sl]);
-  };
-  auto emit = [&](size_t row) {
+      if (b < nb) acc[b] = add4(acc[b], k.part[(((size_t)tile * 2 + slot) * nb + b) * LPR + sl]);
+  }
+  __device__ __forceinline__ void emit(size_t row) const {
 #pragma unroll
     for (int b = 0; b < NACC; ++b)
       if (b < nb) k.out[(row * nb + b) * LPR + sl] = acc[b];
-  };
-  if ((int32_t)blockIdx.x < k.fix_blocks) {
-    const int64_t item = ((int64_t)blockIdx.x * WPB + wave) * SPW + q;
-    const int32_t b = (int32_t)(item >> 1);
-    const int s = (int)(item & 1);
-    int32_t my_row = -1, my_bl = 0;
-    if (b < k.n_tiles) {
-      const int64_t t0 = (int64_t)b * te;
-      const int64_t t1 = (t0 + te < k.e1) ? t0 + te : k.e1;
-      const int32_t fr = k.row_of[t0], lr = k.row_of[t1 - 1];
-      if (!(s == 1 && lr == fr)) {
-        const int32_t r = s == 0 ? fr : lr;
-        const int64_t rb = k.indptr[r], re = k.indptr[r + 1];
-        if ((int32_t)(rb / te) == b) {  // the row starts in this tile
-          my_row = r;
-          my_bl = (int32_t)((re - 1) / te);
-        }
-      }
-    }
-    const bool is_long = my_row >= 0 && my_bl - b >= kLongChain;
-    if (my_row >= 0 && !is_long) {
-      reset();
-      add_part(b, s);
-      for (int32_t bb = b + 1; bb <= my_bl; ++bb) add_part(bb, 0);
-      emit((size_t)my_row);
-    }
-    unsigned long long todo = __ballot(is_long && sl == 0);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int32_t r = __shfl(my_row, src, kWave);
-      const int32_t bl = __shfl(my_bl, src, kWave);
-      const int32_t bo = __shfl(b, src, kWave);
-      const int so = __shfl(s, src, kWave);
-      reset();
-      for (int32_t bb = bo + q; bb <= bl; bb += SPW) add_part(bb, bb == bo ? so : 0);
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) {
-#pragma unroll
-        for (int i = 0; i < NACC; ++i) {
-          float4 o;
-          o.x = __shfl_xor(acc[i].x, off, kWave);
-          o.y = __shfl_xor(acc[i].y, off, kWave);
-          o.z = __shfl_xor(acc[i].z, off, kWave);
-          o.w = __shfl_xor(acc[i].w, off, kWave);
-          acc[i] = add4s(acc[i], o);
-        }
-      }
-      if (q == 0) emit((size_t)r);
-    }
-  } else {
-    const int64_t n_waves = (int64_t)(gridDim.x - k.fix_blocks) * WPB;
-    const int64_t wv = (int64_t)(blockIdx.x - k.fix_blocks) * WPB + wave;
+  }
+  __device__ __forceinline__ void emit_no_edges(size_t row) {
     reset();
-    for (int64_t v0 = wv * kWave; v0 < k.n_rows; v0 += n_waves * kWave) {
-      const int64_t v = v0 + lane_id;
-      const bool empty = v < k.n_rows && k.indptr[v] == k.indptr[v + 1];
-      unsigned long long m = __ballot(empty);
-      int turn = 0;
-      while (m) {
-        const int bit = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (turn == q) emit((size_t)(v0 + bit));
-        turn = turn + 1 == SPW ? 0 : turn + 1;
-      }
+    emit(row);
+  }
+  __device__ __forceinline__ void fold(int off) {
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) {
+      float4 o;
+      o.x = __shfl_xor(acc[i].x, off, kWave);
+      o.y = __shfl_xor(acc[i].y, off, kWave);
+      o.z = __shfl_xor(acc[i].z, off, kWave);
+      o.w = __shfl_xor(acc[i].w, off, kWave);
+      acc[i] = add4(acc[i], o);
     }
   }
+};
+
+template <int LPR, int NACC>
+__global__ __launch_bounds__(spmm_threads(LPR)) void rgcn_finish_kernel(const RgcnK k) {
+  tile_finish<LPR, RgcnLane<LPR, NACC>, const RgcnK&>(0, k.e1, k.te, 0, k.n_rows, k.n_tiles, k.fix_blocks, k.indptr,
+                                                     k.row_of, k);
 }
 
 // COEF: every loop bound below is uniform over the wavefront (a run shorter than C has invalid positions instead of

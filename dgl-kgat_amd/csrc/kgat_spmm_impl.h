@@ -7,16 +7,6 @@
 
 namespace kgat {
 
-__device__ __forceinline__ float4 fma4(float a, const float4& x, const float4& c) {
-  return make_float4(fmaf(a, x.x, c.x), fmaf(a, x.y, c.y), fmaf(a, x.z, c.z), fmaf(a, x.w, c.w));
-}
-__device__ __forceinline__ float4 add4(const float4& a, const float4& b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-__device__ __forceinline__ float4 mul4(const float4& a, const float4& b) {
-  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-}
-
 template <int LPR>
 struct SpmmGeom {
   static constexpr int THREADS = spmm_threads(LPR);
@@ -666,7 +656,6 @@ __global__ __launch_bounds__(SpmmGeom<LPR>::THREADS) void spmm_finish_kernel(
   constexpr int TE = NSUB * C;
   constexpr int SPW = kWave / LPR >= 1 ? kWave / LPR : 1;  // subgroups per wave
   constexpr int WPB = SpmmGeom<LPR>::THREADS / kWave;
-  constexpr int kLongChain = 8;
   constexpr bool FUSED = DO > 0;
   constexpr int DI = 4 * LPR;
   // fused form: the boundary rows this workgroup finishes (one per lane group item) are collected as P rows

@@ -14,16 +14,12 @@
 // identity is (-inf, INT32_MAX, 4); a row with an in-edge has at least four candidates, so no identity reaches `out`.
 // Nothing is assumed about the order of a source's slots or about signs.  No atomics.
 //
-// Decomposition: kgat_spmm_max.hip's, on merge_plan's tiles (kgat_spmm_plan.h) with LPR = Q lanes per row - one lane
-// per query, whose one 16-byte load is the source's four slots and which keeps a sorted list of four triples.  Runs of
-// consecutive edges with four gathers in flight, (col, row, w, id) handed round by wavefront shuffles, run-boundary
-// partials through LDS (two slots per run), the tile's first and last row to the workspace, a finish kernel that
-// merges the chain of a row cut by tiles (hub rows: the whole wavefront, with a shuffle tree) and writes the rows
-// without in-edges (out = 0, arg_edge = -1, arg_slot = 255).  "Combine" is a merge of two 4-lists: the other list's
-// entries are inserted one by one.
+// Decomposition: the one kgat_tile_reduce.h describes, whose finish launch it shares, with LPR = Q lanes per row - one
+// lane per query, whose one 16-byte load is the source's four slots and which keeps a sorted list of four triples.
+// "Combine" is a merge of two 4-lists: the other list's entries are inserted one by one.
 #include <limits.h>
 
-#include "kgat_spmm_plan.h"
+#include "kgat_tile_reduce.h"
 
 namespace kgat {
 namespace {
@@ -221,18 +217,45 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max4_tile_kernel(
   }
 }
 
-// Finish: (a) rows that are first / last in some tile: the tile where the row starts owns it and merges the row's
-// partial lists over the tiles it spans - one lane group per (tile, slot) item for short chains, the whole wavefront
-// striding over the tiles of a chain of kLongChain and more, then a shuffle tree over its lane groups; (b) rows
-// without in-edges: out = 0, arg_edge = -1, arg_slot = 255 (one lane tests one row, the rows found are written by the
-// wavefront's lane groups in turn).
-// One partial list of the workspace into t.
+// The finish launch (kgat_tile_reduce.h): the lane merges the workspace's partial lists; a row without in-edges gets
+// out = 0, arg_edge = -1, arg_slot = 255.
 template <int LPR>
-__device__ __forceinline__ void combine(Top4& t, const float4* __restrict__ bval, const int4* __restrict__ bid,
-                                        const uint32_t* __restrict__ bslot, int64_t tile, int slot, int sl) {
-  const size_t o = part_index<LPR>(tile, slot, sl);
-  merge(t, bval[o], bid[o], bslot[o]);
-}
+struct Max4FinishLane {
+  int sl;
+  float4* out;
+  int4* arg_edge;
+  uint32_t* arg_slot;
+  const float4* bval;
+  const int4* bid;
+  const uint32_t* bslot;
+  Top4 t;
+
+  __device__ __forceinline__ Max4FinishLane(int sl_, float4* out_, int4* arg_edge_, uint32_t* arg_slot_, const float4* bval_,
+                                            const int4* bid_, const uint32_t* bslot_)
+      : sl(sl_), out(out_), arg_edge(arg_edge_), arg_slot(arg_slot_), bval(bval_), bid(bid_), bslot(bslot_) {}
+
+  __device__ __forceinline__ void reset() { kgat::reset(t); }
+  __device__ __forceinline__ void add_part(int64_t tile, int slot) {
+    const size_t o = part_index<LPR>(tile, slot, sl);
+    merge(t, bval[o], bid[o], bslot[o]);
+  }
+  __device__ __forceinline__ void fold(int off) {  // both partners hold disjoint sets and end with the same list
+    float4 ov;
+    int4 oe;
+    ov.x = __shfl_xor(t.v[0], off, kWave); ov.y = __shfl_xor(t.v[1], off, kWave);
+    ov.z = __shfl_xor(t.v[2], off, kWave); ov.w = __shfl_xor(t.v[3], off, kWave);
+    oe.x = __shfl_xor(t.e[0], off, kWave); oe.y = __shfl_xor(t.e[1], off, kWave);
+    oe.z = __shfl_xor(t.e[2], off, kWave); oe.w = __shfl_xor(t.e[3], off, kWave);
+    const uint32_t os = (uint32_t)__shfl_xor((int)pack_slots(t), off, kWave);
+    merge(t, ov, oe, os);
+  }
+  __device__ __forceinline__ void emit(size_t row) const {
+    store_row<LPR>(out, arg_edge, arg_slot, row, sl, vals(t), ids(t), pack_slots(t));
+  }
+  __device__ __forceinline__ void emit_no_edges(size_t row) const {
+    store_row<LPR>(out, arg_edge, arg_slot, row, sl, make_float4(0.f, 0.f, 0.f, 0.f), make_int4(-1, -1, -1, -1), 0xffffffffu);
+  }
+};
 
 template <int LPR>
 __global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max4_finish_kernel(
@@ -240,84 +263,8 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max4_finish_kernel(
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ row_of, float4* __restrict__ out,
     int4* __restrict__ arg_edge, uint32_t* __restrict__ arg_slot, const float4* __restrict__ bval,
     const int4* __restrict__ bid, const uint32_t* __restrict__ bslot, int32_t fix_blocks) {
-  constexpr int SPW = kWave / LPR;  // lane groups per wavefront
-  constexpr int WPB = spmm_threads(LPR) / kWave;
-  constexpr int kLongChain = 8;
-  static_assert(LPR <= kWave / 2, "a wavefront holds at least two lane groups");
-  const int tid = threadIdx.x;
-  const int wave = tid / kWave, lane_id = tid % kWave;
-  const int q = lane_id / LPR, sl = lane_id % LPR;
-  Top4 t;
-  if ((int32_t)blockIdx.x < fix_blocks) {
-    const int64_t item = ((int64_t)blockIdx.x * WPB + wave) * SPW + q;
-    const int32_t b = (int32_t)(item >> 1);
-    const int s = (int)(item & 1);
-    int32_t my_row = -1, my_bl = 0;
-    if (b < n_tiles) {
-      const int64_t t0 = e0 + (int64_t)b * te;
-      const int64_t t1 = (t0 + te < e1) ? t0 + te : e1;
-      const int32_t fr = row_of[t0], lr = row_of[t1 - 1];
-      if (!(s == 1 && lr == fr)) {
-        const int32_t r = s == 0 ? fr : lr;
-        const int64_t rb = indptr[r], re = indptr[r + 1];
-        if ((int32_t)((rb - e0) / te) == b) {  // the row starts in this tile
-          my_row = r;
-          my_bl = (int32_t)((re - 1 - e0) / te);
-        }
-      }
-    }
-    const bool is_long = my_row >= 0 && my_bl - b >= kLongChain;
-    if (my_row >= 0 && !is_long) {
-      reset(t);
-      combine<LPR>(t, bval, bid, bslot, b, s, sl);
-      for (int32_t bb = b + 1; bb <= my_bl; ++bb) combine<LPR>(t, bval, bid, bslot, bb, 0, sl);
-      store_row<LPR>(out, arg_edge, arg_slot, (size_t)(my_row - row0), sl, vals(t), ids(t), pack_slots(t));
-    }
-    unsigned long long todo = __ballot(is_long && sl == 0);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int32_t r = __shfl(my_row, src, kWave);
-      const int32_t bl = __shfl(my_bl, src, kWave);
-      const int32_t bo = __shfl(b, src, kWave);
-      const int so = __shfl(s, src, kWave);
-      reset(t);
-      for (int32_t bb = bo + q; bb <= bl; bb += SPW) combine<LPR>(t, bval, bid, bslot, bb, bb == bo ? so : 0, sl);
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) {  // both partners hold disjoint sets and end with the same list
-        float4 ov;
-        int4 oe;
-        ov.x = __shfl_xor(t.v[0], off, kWave); ov.y = __shfl_xor(t.v[1], off, kWave);
-        ov.z = __shfl_xor(t.v[2], off, kWave); ov.w = __shfl_xor(t.v[3], off, kWave);
-        oe.x = __shfl_xor(t.e[0], off, kWave); oe.y = __shfl_xor(t.e[1], off, kWave);
-        oe.z = __shfl_xor(t.e[2], off, kWave); oe.w = __shfl_xor(t.e[3], off, kWave);
-        const uint32_t os = (uint32_t)__shfl_xor((int)pack_slots(t), off, kWave);
-        merge(t, ov, oe, os);
-      }
-      if (q == 0) store_row<LPR>(out, arg_edge, arg_slot, (size_t)(r - row0), sl, vals(t), ids(t), pack_slots(t));
-    }
-  } else {
-    const int64_t n_waves = (int64_t)(gridDim.x - fix_blocks) * WPB;
-    const int64_t wv = (int64_t)(blockIdx.x - fix_blocks) * WPB + wave;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int4 none = make_int4(-1, -1, -1, -1);
-    for (int64_t v0 = wv * kWave; v0 < n_rows; v0 += n_waves * kWave) {
-      const int64_t v = v0 + lane_id;
-      bool empty = false;
-      if (v < n_rows) {
-        const int32_t row = row0 + (int32_t)v;
-        empty = indptr[row] == indptr[row + 1];
-      }
-      unsigned long long m = __ballot(empty);
-      int turn = 0;
-      while (m) {
-        const int bit = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (turn == q) store_row<LPR>(out, arg_edge, arg_slot, (size_t)(v0 + bit), sl, zero, none, 0xffffffffu);
-        turn = turn + 1 == SPW ? 0 : turn + 1;
-      }
-    }
-  }
+  tile_finish<LPR, Max4FinishLane<LPR>>(e0, e1, te, row0, n_rows, n_tiles, fix_blocks, indptr, row_of, out, arg_edge,
+                                        arg_slot, bval, bid, bslot);
 }
 
 constexpr size_t kListBytes = sizeof(float4) + sizeof(int4) + sizeof(uint32_t);  // one lane's partial in the workspace

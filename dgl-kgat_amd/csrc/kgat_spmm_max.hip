@@ -9,18 +9,14 @@
 // is a strict total order and the maximum does not depend on the order in which pairs are combined: runs, tiles and
 // lane groups may combine in any grouping and every launch gives the same bits.  No atomics.
 //
-// Decomposition: the sum kernel's.  The CSR positions of the call are cut into merge_plan's tiles (kgat_spmm_plan.h),
-// one workgroup per tile; LPR lanes (a lane group) cover a row of X and walk a run of consecutive edges, U gathers in
-// flight, flushing when the destination row changes.  A run's first and last row may continue in a neighbour run:
-// those (value, id) partials are combined through LDS, each lane group looking at its own two entries.  The tile's
-// first and last row go to the workspace and the finish kernel combines them over the tiles a row spans (hub rows:
-// the whole wavefront strides over the chain); it also writes the rows without in-edges (out = 0, arg = -1).
+// Decomposition: the one kgat_tile_reduce.h describes, whose finish launch it shares; a partial is V (value, id) pairs
+// per lane.
 //
 // V = 4: D = 4 LPR, 16-byte accesses.  V = 1: any D, sixteen lanes per row and one pass per sixteen columns
 // (blockIdx.y) - the same kernels, no row is walked by one wavefront beyond a tile at any width.
 #include <limits.h>
 
-#include "kgat_spmm_plan.h"
+#include "kgat_tile_reduce.h"
 
 namespace kgat {
 namespace {
@@ -190,98 +186,51 @@ __global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max_tile_kernel(
   }
 }
 
-// Finish: (a) rows that are first / last in some tile: the tile where the row starts owns it and combines the row's
-// partials over the tiles it spans - one lane group per (tile, slot) item for short chains, the whole wavefront
-// striding over the tiles of a chain of kLongChain and more; (b) rows without in-edges: out = 0, arg = -1 (one lane
-// tests one row, the rows found are written by the wavefront's lane groups in turn).
+// The finish launch (kgat_tile_reduce.h): the lane takes the workspace partials with the tie rule; a row without in-edges
+// gets out = 0, arg = -1.
+template <int LPR, int V>
+struct MaxFinishLane {
+  const Lane<LPR, V> io;
+  int sl;
+  float* __restrict__ out;
+  int32_t* __restrict__ arg;
+  const float* __restrict__ bval;
+  const int32_t* __restrict__ barg;
+  float bv[V];
+  int32_t ba[V];
+
+  __device__ __forceinline__ MaxFinishLane(int sl_, int D, float* out_, int32_t* arg_, const float* bval_, const int32_t* barg_)
+      : io(D, sl_), sl(sl_), out(out_), arg(arg_), bval(bval_), barg(barg_) {}
+
+  __device__ __forceinline__ void reset() { kgat::reset<V>(bv, ba); }
+  __device__ __forceinline__ void add_part(int64_t tile, int slot) {
+    const size_t o = part_index<LPR, V>(tile, slot, sl);
+#pragma unroll
+    for (int i = 0; i < V; ++i) take(bv[i], ba[i], bval[o + i], barg[o + i]);
+  }
+  __device__ __forceinline__ void fold(int off) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const float ov = __shfl_xor(bv[i], off, kWave);
+      const int32_t oa = __shfl_xor(ba[i], off, kWave);
+      take(bv[i], ba[i], ov, oa);
+    }
+  }
+  __device__ __forceinline__ void emit(size_t row) const { io.store(out, arg, row, bv, ba); }
+  __device__ __forceinline__ void emit_no_edges(size_t row) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) { bv[i] = 0.f; ba[i] = -1; }
+    emit(row);
+  }
+};
+
 template <int LPR, int V>
 __global__ __launch_bounds__(spmm_threads(LPR)) void spmm_max_finish_kernel(
     int64_t e0, int64_t e1, int32_t te, int32_t row0, int32_t n_rows, int32_t n_tiles, int D,
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ row_of, float* __restrict__ out,
     int32_t* __restrict__ arg, const float* __restrict__ bval, const int32_t* __restrict__ barg, int32_t fix_blocks) {
-  constexpr int SPW = kWave / LPR;  // lane groups per wavefront
-  constexpr int WPB = spmm_threads(LPR) / kWave;
-  constexpr int kLongChain = 8;
-  static_assert(LPR <= kWave / 2, "a wavefront holds at least two lane groups");
-  const int tid = threadIdx.x;
-  const int wave = tid / kWave, lane_id = tid % kWave;
-  const int q = lane_id / LPR, sl = lane_id % LPR;
-  const Lane<LPR, V> lane(D, sl);
-  float bv[V];
-  int32_t ba[V];
-  auto combine = [&](int64_t tile, int slot) {
-    const size_t o = part_index<LPR, V>(tile, slot, sl);
-#pragma unroll
-    for (int i = 0; i < V; ++i) take(bv[i], ba[i], bval[o + i], barg[o + i]);
-  };
-  if ((int32_t)blockIdx.x < fix_blocks) {
-    const int64_t item = ((int64_t)blockIdx.x * WPB + wave) * SPW + q;
-    const int32_t b = (int32_t)(item >> 1);
-    const int s = (int)(item & 1);
-    int32_t my_row = -1, my_bl = 0;
-    if (b < n_tiles) {
-      const int64_t t0 = e0 + (int64_t)b * te;
-      const int64_t t1 = (t0 + te < e1) ? t0 + te : e1;
-      const int32_t fr = row_of[t0], lr = row_of[t1 - 1];
-      if (!(s == 1 && lr == fr)) {
-        const int32_t r = s == 0 ? fr : lr;
-        const int64_t rb = indptr[r], re = indptr[r + 1];
-        if ((int32_t)((rb - e0) / te) == b) {  // the row starts in this tile
-          my_row = r;
-          my_bl = (int32_t)((re - 1 - e0) / te);
-        }
-      }
-    }
-    const bool is_long = my_row >= 0 && my_bl - b >= kLongChain;
-    if (my_row >= 0 && !is_long) {
-      reset<V>(bv, ba);
-      combine(b, s);
-      for (int32_t bb = b + 1; bb <= my_bl; ++bb) combine(bb, 0);
-      lane.store(out, arg, (size_t)(my_row - row0), bv, ba);
-    }
-    unsigned long long todo = __ballot(is_long && sl == 0);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int32_t r = __shfl(my_row, src, kWave);
-      const int32_t bl = __shfl(my_bl, src, kWave);
-      const int32_t bo = __shfl(b, src, kWave);
-      const int so = __shfl(s, src, kWave);
-      reset<V>(bv, ba);
-      for (int32_t bb = bo + q; bb <= bl; bb += SPW) combine(bb, bb == bo ? so : 0);
-#pragma unroll
-      for (int off = LPR; off < kWave; off <<= 1) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-          const float ov = __shfl_xor(bv[i], off, kWave);
-          const int32_t oa = __shfl_xor(ba[i], off, kWave);
-          take(bv[i], ba[i], ov, oa);
-        }
-      }
-      if (q == 0) lane.store(out, arg, (size_t)(r - row0), bv, ba);
-    }
-  } else {
-    const int64_t n_waves = (int64_t)(gridDim.x - fix_blocks) * WPB;
-    const int64_t wv = (int64_t)(blockIdx.x - fix_blocks) * WPB + wave;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { bv[i] = 0.f; ba[i] = -1; }
-    for (int64_t v0 = wv * kWave; v0 < n_rows; v0 += n_waves * kWave) {
-      const int64_t v = v0 + lane_id;
-      bool empty = false;
-      if (v < n_rows) {
-        const int32_t row = row0 + (int32_t)v;
-        empty = indptr[row] == indptr[row + 1];
-      }
-      unsigned long long m = __ballot(empty);
-      int turn = 0;
-      while (m) {
-        const int bit = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (turn == q) lane.store(out, arg, (size_t)(v0 + bit), bv, ba);
-        turn = turn + 1 == SPW ? 0 : turn + 1;
-      }
-    }
-  }
+  tile_finish<LPR, MaxFinishLane<LPR, V>>(e0, e1, te, row0, n_rows, n_tiles, fix_blocks, indptr, row_of, D, out, arg, bval,
+                                          barg);
 }
 
 struct MaxArgs {
@@ -289,8 +238,8 @@ struct MaxArgs {
   int D;
   const int32_t *indptr, *col, *row_of, *eid;
   const float *X, *w;
-  float* out;
-  int32_t* arg;
+  float* __restrict__ out;
+  int32_t* __restrict__ arg;
   void* ws;
   hipStream_t st;
 };

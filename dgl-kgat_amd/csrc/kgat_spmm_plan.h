@@ -1,7 +1,8 @@
 // Host side of the merge-path reducers (u_mul_e -> sum, the fused Bi form, copy_src -> sum | mean, u_mul_e -> max and
 // -> top-4): the geometry constants, the ONE rule that cuts a call's CSR positions into tiles (MergePlan), the argument
 // checks the five entries share and their width lists.  No kernel code: kgat_spmm_impl.h (the sum / copy kernel
-// templates), kgat_spmm_max.hip and kgat_spmm_kmax.hip include it.  Not part of the ABI.
+// templates) and kgat_tile_reduce.h (the finish launch of the max, top-4 and R-GCN reducers) include it, and so
+// does kgat_gat.hip.  Not part of the ABI.
 //
 // A run-length retune is made HERE and nowhere else: the launchers, the workspace functions, kgat_spmm_tile_edges
 // and the max and top-4 reducers all read merge_plan().
@@ -21,6 +22,9 @@ constexpr int kSpmmThreads = 256;
 // also at D = 16 / 32 - 16 runs and 32 run partials per tile, as a D = 64 tile has - with the half-length runs:
 // D = 32 49.4 -> 47.6 us, D = 16 47.8 -> 44.7 (full-length runs 50.9 / 46.1, quarter-length 54.2 / 51.8); D >= 64 flat.
 constexpr int spmm_threads(int lpr) { return (lpr <= 8 && kSpmmThreads == 256) ? 128 : kSpmmThreads; }
+
+// A row cut by this many tile boundaries and more is finished by a whole wavefront instead of one lane group.
+constexpr int kLongChain = 8;
 
 // C: edges per lane-group run in the merge kernels; tiles are NSUB * C <= 2048 edges (the
 // LDS record stage of the second form holds one tile).  A launch over few edges - a destination
