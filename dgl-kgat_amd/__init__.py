@@ -21,7 +21,10 @@ from .partition import GraphedForward  # noqa: F401
 from .optim import FusedAdam, clip_grad_norm_  # noqa: F401
 from . import kg_eval  # noqa: F401
 from .kg_eval import KGRanks, KnownTriples, kg_complete, kg_metrics, kg_rank  # noqa: F401
+from . import kge_models  # noqa: F401
+from .kge_models import CFKG, CKE  # noqa: F401
 
 __all__ = ["DGLGraph", "DGLError", "ALL", "function", "explain", "edge_softmax", "KGATConv", "KGATPropagation", "SAGEConv", "GATConv",
            "RelGraphConv", "install_as_dgl", "accelerate", "KGATLibraryError", "CKGDataset", "enable_lazy_edge_weights",
-           "GraphedForward", "FusedAdam", "clip_grad_norm_", "kg_eval", "KnownTriples", "KGRanks", "kg_rank", "kg_metrics", "kg_complete"]
+           "GraphedForward", "FusedAdam", "clip_grad_norm_", "kg_eval", "KnownTriples", "KGRanks", "kg_rank", "kg_metrics", "kg_complete",
+           "kge_models", "CFKG", "CKE"]

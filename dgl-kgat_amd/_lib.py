@@ -36,6 +36,7 @@ SOURCES = {
     "kgat_att_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "kgat_gat.hip": [],
     "kgat_rgcn.hip": [],
+    "kgat_transe.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -216,6 +217,17 @@ SIGNATURES = {
     "kgat_rgcn_fwd_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_rgcn_bwd_x_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_rgcn_bwd_coef_f32": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # TransE KG embedding (the CFKG baseline): reference models.py:114-133 without the projection, kgat.py:116-136
+    # (ABI 16, additive)
+    "kgat_transe_supported": (_i32, [_i64, _i32, _i32, _i64]),
+    "kgat_transe_scratch_bytes": (_sz, [_i64, _i32, _i32]),
+    "kgat_transe_sorted_bytes": (_sz, [_i64, _i32]),
+    "kgat_transe_forward_f32": (_i32, [_i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p, _sz, _p]),
+    "kgat_transe_backward_f32": (_i32, [_i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "kgat_transe_loss_grad_f32": (_i32, [_i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, C.c_float, _p, _p, _p, _p, _sz, _p]),
+    "kgat_transe_presort_f32": (_i32, [_i64, _i32, _i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "kgat_transe_adam_step_f32": (_i32, [_i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double,
+                                         C.c_double, C.c_double, C.c_double, C.c_float, _p, _p, C.c_uint64, _p, _sz, _p]),
 }
 
 _lib = None

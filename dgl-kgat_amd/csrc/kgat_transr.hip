@@ -20,16 +20,14 @@
 #include <math.h>
 
 #include "kgat_adam_common.h"
+#include "kgat_kg_sorted.h"
 #include "kgat_lds_sort.h"
 
 namespace kgat {
 
 constexpr int kTrMaxDim = 128;    // d, k <= 128
-constexpr int kTrChunk = 64;      // samples per partial W-gradient block
-constexpr int kTrSmallSort = 8192;
 constexpr int kTrPosBits = 13;    // a position among kTrSmallSort
-constexpr int kTrMaxRel = 4096;   // relations (chunk table built by one workgroup, 4 keys per thread)
-constexpr int kTrSlotBits = 14;   // row_slot word = call tag << 14 | (first sorted position of the row's run + 1); 3 * batch <= 8192 < 2^14
+// (kTrChunk, kTrSmallSort, kTrMaxRel, kTrSlotBits and the presort's block layout: kgat_kg_sorted.h)
 
 // ---- one-workgroup stable sort of n <= 8192 keys, payload = position in the input, packed as key << 13 | position
 // (LdsSort, kgat_lds_sort.h).  Also emits, for keys in [0, n_keys], offsets[v] = first sorted position whose key
@@ -822,32 +820,6 @@ __global__ __launch_bounds__(256) void transr_reduce_kernel(int n_first, int ny,
 //  * the ordered reduction of the weight-gradient partials happens where the sum is consumed: the Adam blocks of W_R
 //    and of the relation table add a relation's partials in chunk order (the reduction launch's order) on the way.
 // Launches per iteration: per-sample kernel (+ row tags) -> weight-gradient partials + loss -> Adam (+ gradient-row sums).
-
-// the most chunks a batch's chunk table can hold: one per started kTrChunk samples of every relation
-static size_t transr_max_chunks(int64_t batch, int n_rel) {
-  return (size_t)(batch > 0 ? batch : 1) / kTrChunk + (size_t)(n_rel > 0 ? n_rel : 0) + 1;
-}
-
-// per-batch block of the presort's output (offsets in bytes, 256-byte aligned)
-struct TrSortedLayout {
-  size_t order, seg, chunk_ptr, chunks, sorted_ids, row_order, inv_pos, run_len, bytes;
-};
-static TrSortedLayout transr_sorted_layout(int64_t batch, int n_rel) {
-  const size_t b = (size_t)(batch > 0 ? batch : 1);
-  const size_t n_part = transr_max_chunks(batch, n_rel);
-  TrSortedLayout l;
-  size_t w = 0;
-  l.order = w; w += align_up(b * 4, 256);
-  l.seg = w; w += align_up(((size_t)n_rel + 2) * 4, 256);
-  l.chunk_ptr = w; w += align_up(((size_t)n_rel + 2) * 4, 256);
-  l.chunks = w; w += align_up(n_part * 8, 256);
-  l.sorted_ids = w; w += align_up(3 * b * 4, 256);
-  l.row_order = w; w += align_up(3 * b * 4, 256);
-  l.inv_pos = w; w += align_up(3 * b * 4, 256);
-  l.run_len = w; w += align_up(3 * b * 4, 256);
-  l.bytes = w;
-  return l;
-}
 
 struct TrPresortArgs {
   int32_t n_batches, batch;

@@ -1,4 +1,5 @@
-"""Link prediction with the TransR embedding of the KG phase (reference ``models.py:114-133``).
+"""Link prediction with the TransR embedding of the KG phase (reference ``models.py:114-133``), and with a translation
+model that has no projection (``kge_models.CFKG``: no ``W_R``, ``u_x = normalize(e_x)``).
 
 The score of a triple is the reference's ``|u_h + u_r - u_t|^2`` (``models.py:120-126``) with
 ``u_x = normalize(e_x W_r)`` and ``u_r = normalize(rel_r)``.  ``kg_rank`` gives the *filtered* rank of the true tail
@@ -102,13 +103,28 @@ class KnownTriples:
 
 # ---------------------------------------------------------------------------------------------- the two formulations
 def _params(model):
-    return model.entity_embed.weight.detach(), model.W_R.detach(), model.relation_embed.weight.detach()
+    """ent, W_R, rel; W_R is None for a translation model without a projection (kge_models.CFKG): u_x = normalize(e_x)."""
+    W_R = getattr(model, "W_R", None)
+    return model.entity_embed.weight.detach(), None if W_R is None else W_R.detach(), model.relation_embed.weight.detach()
 
 
 def _use_kernels(ent, W_R):
     from . import ops
+    if W_R is None:   # no projection to run: the counting kernel alone decides
+        return bool(ent.is_cuda and ent.dtype == torch.float32 and ops.transr_rank_supported(ent.shape[1]))
     return bool(ent.is_cuda and ent.dtype == torch.float32 and W_R.dtype == torch.float32 and
                 ops.transr_project_supported(W_R.shape[1], W_R.shape[2]))
+
+
+def _unit_table(ent, lo, hi):
+    """Without a projection the candidates do not depend on the relation: normalize(ent[lo:hi]) and its squared norms,
+    formed once per call."""
+    U = F.normalize(ent[lo:hi], p=2, dim=1).contiguous()
+    return U, (U * U).sum(1)
+
+
+def _unit_queries(ent, rel_row, sign, ids):
+    return (F.normalize(ent.index_select(0, ids), p=2, dim=1) + sign * F.normalize(rel_row.unsqueeze(0), p=2, dim=1)).contiguous()
 
 
 def _project_torch(ent, W_r, rel_row, sign, ids=None, rows=None):
@@ -193,7 +209,7 @@ def kg_rank(model, h, r, t, known=None, side="tail", candidates=None):
     with torch.no_grad():
         ent, W_R, rel = _params(model)
         h, r, t = _check_triples(model, h, r, t, "kg_rank")
-        n_ent, n_rel = ent.shape[0], W_R.shape[0]
+        n_ent, n_rel = ent.shape[0], rel.shape[0]
         lo, hi = _candidate_range(candidates, n_ent, "kg_rank")
         anchor, answer, sign = (h, t, 1.0) if side == "tail" else (t, h, -1.0)
         n = h.numel()
@@ -218,6 +234,9 @@ def kg_rank(model, h, r, t, known=None, side="tail", candidates=None):
         lt_s, eq_s = torch.empty_like(lt), torch.empty_like(eq)
         if kernels:
             from . import ops
+        if W_R is None:
+            P, n2 = _unit_table(ent, lo, hi)
+        elif kernels:
             ent_c, a32 = ent.contiguous(), a_s.to(torch.int32)
             P = torch.empty((hi - lo, W_R.shape[2]), dtype=torch.float32, device=dev)
             n2 = torch.empty(hi - lo, dtype=torch.float32, device=dev)
@@ -227,7 +246,13 @@ def kg_rank(model, h, r, t, known=None, side="tail", candidates=None):
                 continue
             fp = (fptr[b:e + 1] - fb[x]).contiguous()
             fi = fids[fb[x]:fb[x + 1]]
-            if kernels:
+            if W_R is None:
+                Q = _unit_queries(ent, rel[x], sign, a_s[b:e])
+                if kernels:
+                    lt_s[b:e], eq_s[b:e] = ops.transr_rank(Q, ans_s[b:e].contiguous(), P, n2, lo, fp, fi.contiguous())
+                else:
+                    lt_s[b:e], eq_s[b:e] = _rank_torch(Q, ans_s[b:e], P, n2, lo, fp, fi)
+            elif kernels:
                 W_r = W_R[x].contiguous()
                 ops.transr_project(ent_c, W_r, rows=(lo, hi), out=P, n2_out=n2)
                 Q, _ = ops.transr_project(ent_c, W_r, rel_row=rel[x].contiguous(), sign=sign, ids=a32[b:e].contiguous(),
@@ -305,7 +330,7 @@ def kg_complete(model, h, r, K, known=None, candidates=None):
             raise ValueError("kg_complete: h and r must have one length")
         if not ent.is_cuda:
             raise ops.KGATLibraryError("kg_complete: the model is on %s: the top-K sweep only runs on a HIP device" % dev)
-        n_ent, n_rel = ent.shape[0], W_R.shape[0]
+        n_ent, n_rel = ent.shape[0], rel.shape[0]
         lo, hi = _candidate_range(candidates, n_ent, "kg_complete")
         n = h.numel()
         ids = torch.full((n, K), -1, dtype=torch.int64, device=dev)
@@ -324,7 +349,8 @@ def kg_complete(model, h, r, K, known=None, candidates=None):
         qb, fb = _by_relation(r, n_rel, fptr)
         kernels = _use_kernels(ent, W_R)
         ent_c = ent.contiguous().float()
-        n_c, k = hi - lo, W_R.shape[2]
+        n_c, k = hi - lo, ent.shape[1] if W_R is None else W_R.shape[2]
+        unit = _unit_table(ent_c, lo, hi)[0] if W_R is None else None
         item_ids = torch.arange(n_c, dtype=torch.int32, device=dev)
         ids_s, dist_s = torch.empty_like(ids), torch.empty_like(dist)
         for x in range(n_rel):
@@ -332,8 +358,11 @@ def kg_complete(model, h, r, K, known=None, candidates=None):
             if b == e:
                 continue
             table = torch.empty((n_c + e - b, k), dtype=torch.float32, device=dev)   # candidates, then the queries
-            W_r = W_R[x].float().contiguous()
-            if kernels:
+            W_r = None if W_R is None else W_R[x].float().contiguous()
+            if W_R is None:
+                table[:n_c] = unit
+                table[n_c:] = _unit_queries(ent_c, rel[x].float(), 1.0, h_s[b:e])
+            elif kernels:
                 ops.transr_project(ent_c, W_r, rows=(lo, hi), want_n2=False, out=table[:n_c])
                 ops.transr_project(ent_c, W_r, rel_row=rel[x].contiguous(), ids=h_s[b:e].to(torch.int32).contiguous(),
                                    want_n2=False, out=table[n_c:])

@@ -1949,6 +1949,127 @@ def mf_adam_step(u, p, n, sorted_block, emb, exp_avg, exp_avg_sq, step, lr, beta
           "kgat_mf_adam_step_f32")
 
 
+# ---------------------------------------------------------------- TransE KG embedding, the CFKG baseline (kgat_transe_*)
+def transe_supported(n_nodes, d, n_rel, batch):
+    """Sizes of the TransE kernels: d a multiple of 4 up to 256, batch <= 2730, n_rel <= 4096, n_nodes < 2^31."""
+    return bool(_lib.load().kgat_transe_supported(int(n_nodes), int(d), int(n_rel), int(batch)))
+
+
+def transe_scratch(batch, d, n_rel, device):
+    """The scratch of every TransE entry (kgat_transe_scratch_bytes: one size for all of them)."""
+    return _workspace(_lib.load().kgat_transe_scratch_bytes(int(batch), int(d), int(n_rel)), device)
+
+
+def _transe_operands(h, r, pos_t, neg_t, ent, rel):
+    ent = _need(ent, torch.float32, "ent")
+    if ent.dim() != 2:
+        raise ValueError("ent must be (n_nodes, d)")
+    rel = _need(rel, torch.float32, "rel")
+    if rel.dim() != 2 or rel.shape[1] != ent.shape[1]:
+        raise ValueError("rel must be (n_rel, %d), got %s" % (ent.shape[1], tuple(rel.shape)))
+    h = _need(h, torch.int32, "h")
+    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
+        _need(t, torch.int32, name, (h.numel(),))
+    return ent.shape[0], rel.shape[0], ent.shape[1], h.numel()
+
+
+def transe_forward(h, r, pos_t, neg_t, ent, rel, reg_lambda, scratch=None):
+    """TransE loss of a triplet batch with the per-sample gradient rows left in the returned scratch for
+    transe_backward (kgat_transe_forward_f32).  Index tensors are int32.  Returns (loss 0-d tensor, scratch)."""
+    n, n_rel, d, b = _transe_operands(h, r, pos_t, neg_t, ent, rel)
+    lib = _lib.load()
+    loss = torch.empty((), dtype=torch.float32, device=ent.device)
+    need = lib.kgat_transe_scratch_bytes(b, d, n_rel)
+    ws = scratch if scratch is not None and scratch.numel() >= need else _workspace(need, ent.device)
+    with _timed("transe_forward", (b, d)):
+        check(lib.kgat_transe_forward_f32(n, n_rel, d, b, _ptr(h), _ptr(r), _ptr(pos_t), _ptr(neg_t), _ptr(ent), _ptr(rel),
+                                          float(reg_lambda), _ptr(loss), _ptr(ws), ws.numel(), _stream(ent)),
+              "kgat_transe_forward_f32")
+    return loss, ws
+
+
+def transe_backward(h, r, pos_t, neg_t, shapes, ws, grad_scale=None):
+    """The two dense gradients of transe_forward's loss (kgat_transe_backward_f32), times the device scalar grad_scale."""
+    (n_nodes, d), (n_rel, _) = shapes
+    dev = ws.device
+    g_ent = torch.empty((n_nodes, d), dtype=torch.float32, device=dev)
+    g_rel = torch.empty((n_rel, d), dtype=torch.float32, device=dev)
+    if grad_scale is not None:
+        grad_scale = _need(grad_scale.reshape(1), torch.float32, "grad_scale")
+    with _timed("transe_backward", (h.numel(), d)):
+        check(_lib.load().kgat_transe_backward_f32(n_nodes, n_rel, d, h.numel(), _ptr(h), _ptr(r), _ptr(pos_t), _ptr(neg_t),
+                                                   _ptr(grad_scale), _ptr(g_ent), _ptr(g_rel), _ptr(ws), ws.numel(),
+                                                   _stream(ws)), "kgat_transe_backward_f32")
+    return g_ent, g_rel
+
+
+def transe_loss_grad(h, r, pos_t, neg_t, ent, rel, reg_lambda, out=None, scratch=None):
+    """TransE loss and its dense gradients in one call (kgat_transe_loss_grad_f32): (loss, grad_ent, grad_rel), the bits
+    of transe_forward + transe_backward.  `out` = (loss, grad_ent, grad_rel) and `scratch` reuse buffers of an earlier call."""
+    n, n_rel, d, b = _transe_operands(h, r, pos_t, neg_t, ent, rel)
+    lib = _lib.load()
+    if out is not None:
+        loss, g_ent, g_rel = out
+        _need(g_ent, torch.float32, "grad_ent", ent.shape)
+        _need(g_rel, torch.float32, "grad_rel", rel.shape)
+    else:
+        loss = torch.empty((), dtype=torch.float32, device=ent.device)
+        g_ent, g_rel = torch.empty_like(ent), torch.empty_like(rel)
+    need = lib.kgat_transe_scratch_bytes(b, d, n_rel)
+    ws = scratch if scratch is not None and scratch.numel() >= need else _workspace(need, ent.device)
+    with _timed("transe", (b, d)):
+        check(lib.kgat_transe_loss_grad_f32(n, n_rel, d, b, _ptr(h), _ptr(r), _ptr(pos_t), _ptr(neg_t), _ptr(ent), _ptr(rel),
+                                            float(reg_lambda), _ptr(loss), _ptr(g_ent), _ptr(g_rel), _ptr(ws), ws.numel(),
+                                            _stream(ent)), "kgat_transe_loss_grad_f32")
+    return loss, g_ent, g_rel
+
+
+def transe_presort(h, r, pos_t, neg_t, n_nodes, n_rel):
+    """The sorts of a whole TransE phase's batches in one launch (kgat_transe_presort_f32): h, r, pos_t, neg_t are
+    (n_batches, batch) int32 tensors; returns (sorted, stride) - batch b's block is sorted[b * stride:(b + 1) * stride]."""
+    h = _need(h, torch.int32, "h")
+    if h.dim() != 2:
+        raise ValueError("h must be (n_batches, batch)")
+    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
+        _need(t, torch.int32, name, h.shape)
+    lib = _lib.load()
+    nb, b = h.shape
+    stride = int(lib.kgat_transe_sorted_bytes(b, int(n_rel)))
+    out = torch.empty(max(nb * stride, 256), dtype=torch.uint8, device=h.device)
+    with _timed("transe_presort", (nb, b)):
+        check(lib.kgat_transe_presort_f32(int(n_nodes), int(n_rel), nb, b, _ptr(h), _ptr(r), _ptr(pos_t), _ptr(neg_t),
+                                          _ptr(out), out.numel(), _stream(h)), "kgat_transe_presort_f32")
+    return out, stride
+
+
+class TransEAdamState:
+    """What a sequence of kgat_transe_adam_step_f32 calls keeps between calls: the scratch, the row_slot words (zero
+    once, never cleared: a word is valid for the call whose tag it carries) and the tag counter."""
+
+    def __init__(self, n_nodes, d, n_rel, batch, device):
+        self.key = (int(n_nodes), int(d), int(n_rel), int(batch), str(device))
+        self.scratch = transe_scratch(batch, d, n_rel, device)
+        self.row_slot = torch.zeros(int(n_nodes), dtype=torch.int64, device=device)
+        self.tag = 0
+
+
+def transe_adam_step(h, r, pos_t, neg_t, sorted_block, ent, rel, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps,
+                     reg_lambda, loss_out, state):
+    """One TransE iteration (kgat_transe_adam_step_f32): the loss of the batch into `loss_out` (a 1-element fp32 view)
+    and the Adam step on ent / rel in place.  exp_avg / exp_avg_sq: ctypes arrays of the two moment pointers (built
+    once per phase by the caller); steps: the two step counts after this step.  Shapes and dtypes are the caller's
+    responsibility here (CFKG.kg_phase validates them once per phase)."""
+    import ctypes as C
+    state.tag += 1
+    arr_t = (C.c_int64 * 2)(*steps)
+    check(_lib.load().kgat_transe_adam_step_f32(ent.shape[0], rel.shape[0], ent.shape[1], h.numel(), h.data_ptr(), r.data_ptr(),
+                                                pos_t.data_ptr(), neg_t.data_ptr(), sorted_block.data_ptr(), ent.data_ptr(),
+                                                rel.data_ptr(), exp_avg, exp_avg_sq, arr_t, float(lr), float(beta1),
+                                                float(beta2), float(eps), float(reg_lambda), loss_out.data_ptr(),
+                                                state.row_slot.data_ptr(), state.tag, state.scratch.data_ptr(),
+                                                state.scratch.numel(), _stream(ent)), "kgat_transe_adam_step_f32")
+
+
 # ---------------------------------------------------------------- global-norm gradient clipping (kgat.py:32,162)
 def __getattr__(name):
     # GRAD_NORM_CHAIN: the compile-time constant of the library (kgat_grad_norm_chain), read when first asked for

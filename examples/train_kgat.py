@@ -21,6 +21,9 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
   python examples/train_kgat.py --synthetic 1.0 --grad_norm 1.0          # clip the CF gradient's global norm (kgat.py:32,162)
   python examples/train_kgat.py --planted --epochs 6 --kg_eval 2000 --kg_holdout 0.1   # + filtered MRR / MR / Hits@10 of
                                                                           # held-out KG triples under the TransR score
+  python examples/train_kgat.py --planted --model cfkg --epochs 3 --lr 0.03 --batch_size_kg 512 --eval_before
+                                                                          # the paper's CFKG baseline (TransE over the CKG);
+                                                                          # --model cke: TransR + BPR on cf + entity rows
   python examples/train_kgat.py --planted --pretrain_epochs 5 --pretrain_lr 0.1 --pretrain_save mf.npz --epochs 3
                                                                           # BPR-MF pretraining of the table first (the paper's
                                                                           # initialisation); --pretrain_load mf.npz reuses it
@@ -183,6 +186,11 @@ def parse_args(argv=None):
     ap.add_argument("--gnn_model", choices=("kgat", "graphsage", "rgcn"), default="kgat",
                     help="propagation layers (reference kgat.py:23): bi-interaction KGATConv, SAGEConv (mean), or "
                          "RelGraphConv (R-GCN with basis decomposition over the edge types)")
+    # (absent from the namespace unless given, as --num_bases: a run without it keeps its arguments and --log_json "args")
+    ap.add_argument("--model", choices=("kgat", "cfkg", "cke"), default=argparse.SUPPRESS,
+                    help="kgat (default), or one of the KGAT paper's KG-embedding baselines: cfkg - TransE over the whole "
+                         "collaborative KG, recommendation as the ranking of (user, interact, ?) (kge_models.CFKG); cke - "
+                         "TransR over the item KG + BPR on `cf latent + entity embedding` (kge_models.CKE)")
     ap.add_argument("--num_bases", type=int, default=argparse.SUPPRESS,
                     help="bases of the rgcn layers' relation weights (default 4; at most the number of relations)")
     ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage", "Bi2"), default="Bi",
@@ -257,6 +265,20 @@ def parse_args(argv=None):
     ap.add_argument("--pretrain_load", default=None, metavar="PATH",
                     help="initialise the user / item rows from an mf.npz (before --pretrain_epochs, if both are given)")
     args = ap.parse_args(argv)
+    kind = getattr(args, "model", "kgat")
+    if kind != "kgat":
+        # a KG-embedding baseline has no propagation layers, no attention and no edge weights
+        for flag, given in (("--gnn_model", args.gnn_model != "kgat"), ("--res_type", args.res_type != "Bi"),
+                            ("--node_dropout", args.node_dropout != 0), ("--attention_grad", bool(args.attention_grad)),
+                            ("--explain", args.explain != 0), ("--use_attention 0", not args.use_attention),
+                            ("--num_bases", hasattr(args, "num_bases")), ("--grad_digest", args.grad_digest)):
+            if given:
+                ap.error("%s belongs to the propagation layers; --model %s has none" % (flag, kind))
+        if args.gpus > 1:
+            ap.error("--model %s runs on one GPU" % kind)
+        if args.pretrain_epochs or args.pretrain_save:
+            ap.error("--model %s takes --pretrain_load only: --pretrain_epochs / --pretrain_save train and write the "
+                     "table of --model kgat" % kind)
     if args.pretrain_epochs < 0 or args.pretrain_batch_size < 1:
         ap.error("--pretrain_epochs takes a number of epochs >= 0, --pretrain_batch_size a batch >= 1")
     if (args.pretrain_epochs or args.pretrain_load or args.pretrain_save) and args.gpus > 1:
@@ -369,6 +391,8 @@ def _run(args, argv):
             raise SystemExit("--kg_eval: no triple to rank")
         pick = np.random.default_rng(args.seed).permutation(len(kg_pool))[:args.kg_eval]
         kg_pool = kg_pool[pick].astype(np.int64)
+    if getattr(args, "model", "kgat") != "kgat":
+        return _run_kge(args, ds, dev, kg_pool, full if args.kg_eval else None)
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
                               gnn_model=args.gnn_model, res_type=args.res_type, use_attention=bool(args.use_attention),
@@ -617,6 +641,144 @@ def _run(args, argv):
                        "epochs": history}, f, indent=1)
     if world > 1:
         dist.destroy_process_group()
+    return history
+
+
+def _run_kge(args, ds, dev, kg_pool, full):
+    """--model cfkg / cke on one GPU.  cfkg: an epoch is a TransE KG phase over ALL training triples of the collaborative
+    KG (interactions included), then evaluation on CFKG.readout.  cke: a TransR KG phase over the item-KG triples, a CF
+    phase of BPR steps on CKE.readout, then evaluation.  Samplers, the optimiser (one FusedAdam over all parameters) and
+    the metrics are the kgat run's; the records carry the same keys where the phase exists."""
+    kind = args.model
+    off, n_items = ds.n_users, ds.n_items
+    items = (off, off + n_items)
+    trip = ds.train_KG_triplet
+    is_uv = (trip[:, 0] < off) | (trip[:, 2] < off)
+    if kind == "cfkg":
+        forward = trip[(trip[:, 0] < off) & (trip[:, 2] >= off)]
+        if len(forward) == 0:
+            raise SystemExit("--model cfkg: the training triples hold no user -> item interaction")
+        interact = int(forward[:, 1].min())
+        model = K.CFKG(ds.n_KG_entity, ds.n_KG_relation, dim=args.entity_embed_dim).to(dev)
+    else:
+        trip = trip[~is_uv]
+        if len(trip) == 0:
+            raise SystemExit("--model cke: the training triples hold no item-KG triple")
+        model = K.CKE(ds.n_KG_entity, ds.n_KG_relation, dim=args.entity_embed_dim, relation_dim=args.relation_embed_dim).to(dev)
+    print("--model %s | %d KG-phase triples" % (kind, len(trip)))
+    if args.pretrain_load:
+        model.load_pretrained(*ckg_io.load_pretrain(args.pretrain_load), ds.n_users)
+        print("Pretrain   | user / item rows from %s" % args.pretrain_load)
+    opt = K.FusedAdam(model.parameters(), lr=args.lr)
+    trip_cols = torch.as_tensor(np.ascontiguousarray(trip.T.astype(np.int32)), device=dev)
+    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
+    n_trip, n_pairs = trip_cols.shape[1], pair_cols.shape[1]
+    train_dict = user_dict(ds.train_pairs, off)
+    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
+    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
+    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
+             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
+
+    def cap(n):
+        return n if args.max_iters <= 0 else min(n, args.max_iters)
+
+    def clock():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    if args.kg_eval:
+        kg_known = K.KnownTriples(full[:, 0], full[:, 1], full[:, 2], ds.n_KG_entity, ds.n_KG_relation, device=dev)
+        kg_pool = [torch.as_tensor(np.ascontiguousarray(kg_pool[:, c]), device=dev) for c in range(3)]
+
+    def evaluate(rec):
+        t0 = clock()
+        with torch.no_grad():
+            emb = (model.readout(interact, (0, off), items) if kind == "cfkg" else model.readout(items)).contiguous()
+            for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict)):
+                if getattr(args, "rank_metrics", 0):
+                    rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
+                    rank_Ks = [k for k in rank_Ks if k <= plans[name].n_items] or [plans[name].n_items]
+                    m = metrics.calc_rank_metrics(emb, seen, held, ds.item_id_range, Ks=rank_Ks, plan=plans[name])
+                    for metric in metrics.RANK_SCALAR_NAMES:
+                        rec["%s_%s" % (name, metric)] = float(m[metric])
+                    for j, k in enumerate(rank_Ks):
+                        for metric in metrics.METRIC_NAMES:
+                            rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                    print("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f" % (
+                        name, m["auc"], m["mrr"], m["map"], m["mean_rank"]))
+                if args.Ks == [20]:
+                    rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
+                        emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
+                    print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+                    continue
+                m = metrics.calc_metrics(emb, seen, held, ds.item_id_range, Ks=args.Ks, plan=plans[name])
+                for j, k in enumerate(args.Ks):
+                    for metric in metrics.METRIC_NAMES:
+                        rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                    print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
+                        name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
+        rec["eval_s"] = clock() - t0
+        print("           | eval %.4fs" % rec["eval_s"])
+        if args.kg_eval:
+            t0 = clock()
+            m = model.kg_metrics(*kg_pool, known=kg_known, side="both", hits=(1, 3, 10))
+            rec["kg_eval_s"] = clock() - t0
+            rec["kg_mrr"], rec["kg_mr"], rec["kg_hits@10"] = m["mrr"], m["mr"], m["hits@10"]
+            print("           | KG link prediction, %d %s triples, both sides, filtered: kg_mrr %.5f kg_mr %.1f kg_hits@10 "
+                  "%.5f | %.4fs" % (kg_pool[0].numel(), "held-out" if args.kg_holdout > 0 else "TRAINING (a fit measure)",
+                                    m["mrr"], m["mr"], m["hits@10"], rec["kg_eval_s"]))
+
+    history = []
+    if args.eval_before:
+        model.eval()
+        history.append({"epoch": 0})
+        print("Epoch 0000 | (untrained)")
+        evaluate(history[-1])
+    for epoch in range(1, args.epochs + 1):
+        rec = {"epoch": epoch}
+        t_epoch = clock()
+        t0 = clock()
+        model.train()
+        n_it, bs = cap(n_trip // args.batch_size_kg + 1), min(args.batch_size_kg, n_trip)
+        idx = torch.randint(0, n_trip, (n_it, bs), device=dev)
+        neg_all = torch.randint(0, ds.n_KG_entity, (n_it, bs), device=dev, dtype=torch.int32)
+        total = model.kg_phase(trip_cols[0][idx], trip_cols[1][idx], trip_cols[2][idx], neg_all, opt).sum()
+        rec["kg_s"], rec["kg_iters"] = clock() - t0, n_it
+        rec["kg_loss"] = float(total) / n_it
+        print("Epoch %04d | KGE %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["kg_s"], n_it, 1e3 * rec["kg_s"] / n_it,
+                                                                       rec["kg_loss"]))
+        del idx, neg_all
+        if kind == "cke":
+            t0 = clock()
+            n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
+            idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
+            u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
+            n_all = torch.randint(off, off + n_items, (n_it, bs), device=dev, dtype=torch.int32)
+            total = torch.zeros((), dtype=torch.float32, device=dev)
+            for i in range(n_it):
+                loss = model.get_loss(model.readout(items), u_all[i], p_all[i], n_all[i])
+                loss.backward()
+                if args.grad_norm > 0:
+                    opt.step(max_grad_norm=args.grad_norm)
+                else:
+                    opt.step()
+                opt.zero_grad()
+                total += loss.detach()
+            rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
+            rec["cf_loss"] = float(total) / n_it
+            print("           | CF %.4fs (%d it, %.4f ms/it) loss %.4f" % (rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it, rec["cf_loss"]))
+            del idx, u_all, p_all, n_all
+        model.eval()
+        evaluate(rec)
+        rec["epoch_s"] = clock() - t_epoch
+        print("           | epoch %.4fs" % rec["epoch_s"])
+        history.append(rec)
+    if args.log_json:
+        import json
+        with open(args.log_json, "w") as f:
+            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
+                       "n_relations": ds.n_KG_relation, "n_train_triplets": int(n_trip), "n_train_pairs": int(n_pairs),
+                       "epochs": history}, f, indent=1)
     return history
 
 

@@ -1153,6 +1153,73 @@ int kgat_rgcn_bwd_coef_f32(int64_t n_nodes, int64_t n_edges, int D, int B, int R
                            const float* x, const float* g_Z, float* g_a, void* scratch, size_t scratch_bytes,
                            kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- TransE KG embedding: the CFKG baseline (additive within ABI 16)
+ * The KGAT paper's CFKG baseline trains a translation model over the collaborative KG.  Its objective here is the
+ * reference's `transR` (models.py:114-133, with _L2_loss_mean :9-11) with the projection removed: for a batch
+ * (h, r, pos_t, neg_t) with ent (n_nodes x d) and rel (n_rel x d), both contiguous,
+ *     u_x = ent[x] / max(|ent[x]|, 1e-12)  (x in h, pos_t, neg_t),   u_r = rel[r] / max(|rel[r]|, 1e-12)
+ *     loss = mean_b softplus(|u_h + u_r - u_p|^2 - |u_h + u_r - u_n|^2) + reg_lambda * sum_{v in h,r,p,n} mean_b |u_v|^2 / 2
+ * i.e. models.py:114-133 with every W_R[r] = I and d = k.  The gradient goes through the normalisation as autograd's
+ * does (F.normalize: a row whose norm is below the clamp gets g / 1e-12).  A sample with an id outside its table reads
+ * nothing, makes the loss NaN and contributes no gradient.
+ *
+ * kgat_transe_supported: d a multiple of 4 in [4, 256], 1 <= batch <= 2730 (3 * batch ids sorted by one workgroup in
+ * LDS), 1 <= n_rel <= 4096, 1 <= n_nodes < 2^31.  Other sizes: KGAT_E_UNSUPPORTED from every entry below (the Python
+ * layer then runs the torch restatement).
+ *
+ * kgat_transe_forward_f32 / kgat_transe_backward_f32: the two halves autograd needs (models.py:114-133 under
+ * loss.backward()).  The forward sorts the batch (samples by relation, the 3 x batch entity ids), runs the per-sample
+ * kernel - d / 4 lanes per sample, 16 bytes per lane and row; the relation's gradient row written at the sample's
+ * relation-sorted position, the three entity rows at the sorted positions of their ids - and the chunk sums of the
+ * relation rows (at most 64 sorted samples each), and reduces the loss (1 float at `loss`); everything the backward
+ * needs stays in `scratch`, which the caller hands to the backward unchanged with the same ids.  The backward writes
+ * grad_ent (n_nodes x d, dense: rows outside the batch zero) and grad_rel (n_rel x d, dense), times grad_scale[0] (a
+ * DEVICE scalar; NULL: 1).  kgat_transe_loss_grad_f32: both in one call, the same bits.
+ *
+ * kgat_transe_presort_f32: the sorts of a whole phase's batches - h, r, pos_t, neg_t as n_batches x batch row-major
+ * arrays - in ONE launch; batch b's result is the block of kgat_transe_sorted_bytes(batch, n_rel) bytes at sorted + b
+ * * that (the block of kgat_transr_presort_f32, which does the work).
+ *
+ * kgat_transe_adam_step_f32: one iteration (reference kgat.py:116-136: loss -> backward -> optimizer.step -> zero_grad)
+ * on batch arrays h .. neg_t and that batch's `sorted` block: the loss and the step of torch.optim.Adam on ent and rel,
+ * IN PLACE with their moments (`exp_avg_host`, `exp_avg_sq_host`: HOST arrays of two device pointers, entity table
+ * first; `steps_host`: the two step counts AFTER this step).  Dense semantics (every row moves), without a dense
+ * gradient: launch one is the per-sample kernel, beside it workgroups that tag the batch's entities in `row_slot`
+ * (n_nodes 64-bit words owned by the caller - zero before the first call, never to be cleared - a word is valid for
+ * the call whose `tag` it carries: pass a tag in [1, 2^50) that differs from every earlier call's on the same
+ * row_slot); launch two the chunk sums + the loss; launch three Adam, with g = 0 for an untagged entity row, else the
+ * sum of the row's run, and for a relation row the sum of its chunk rows.
+ *
+ * Fixed summation orders, the same in every entry: a run of equal entity ids in sorted order from 0; the samples of a
+ * relation in sorted order within a chunk from 0, then the chunks in order from 0; the loss as 256 strided sums and a
+ * tree over them.  No float atomics: bitwise reproducible, and the fused iteration has the bits of
+ * kgat_transe_loss_grad_f32 followed by kgat_adam_step_f32, i.e. of loss.backward(); optimizer.step().
+ *
+ * All entries: ent, rel, the gradients, the moments, `sorted` and `scratch` 16-byte aligned, null pointer, bad
+ * hyperparameter or tag: KGAT_E_BADARG; scratch below kgat_transe_scratch_bytes(batch, d, n_rel) - one size for all of
+ * them - or `sorted_bytes` below n_batches blocks: KGAT_E_WORKSPACE.  Every check precedes any device work. */
+int kgat_transe_supported(int64_t n_nodes, int d, int n_rel, int64_t batch);
+size_t kgat_transe_scratch_bytes(int64_t batch, int d, int n_rel);
+size_t kgat_transe_sorted_bytes(int64_t batch, int n_rel);
+int kgat_transe_forward_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, const int32_t* h, const int32_t* r,
+                            const int32_t* pos_t, const int32_t* neg_t, const float* ent, const float* rel,
+                            float reg_lambda, float* loss, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
+int kgat_transe_backward_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, const int32_t* h, const int32_t* r,
+                             const int32_t* pos_t, const int32_t* neg_t, const float* grad_scale, float* grad_ent,
+                             float* grad_rel, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
+int kgat_transe_loss_grad_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, const int32_t* h, const int32_t* r,
+                              const int32_t* pos_t, const int32_t* neg_t, const float* ent, const float* rel,
+                              float reg_lambda, float* loss, float* grad_ent, float* grad_rel, void* scratch,
+                              size_t scratch_bytes, kgat_stream_t stream);
+int kgat_transe_presort_f32(int64_t n_nodes, int n_rel, int64_t n_batches, int64_t batch, const int32_t* h,
+                            const int32_t* r, const int32_t* pos_t, const int32_t* neg_t, void* sorted,
+                            size_t sorted_bytes, kgat_stream_t stream);
+int kgat_transe_adam_step_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, const int32_t* h, const int32_t* r,
+                              const int32_t* pos_t, const int32_t* neg_t, const void* sorted, float* ent, float* rel,
+                              float* const* exp_avg_host, float* const* exp_avg_sq_host, const int64_t* steps_host,
+                              double lr, double beta1, double beta2, double eps, float reg_lambda, float* loss,
+                              uint64_t* row_slot, uint64_t tag, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
