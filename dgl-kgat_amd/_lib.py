@@ -37,6 +37,7 @@ SOURCES = {
     "kgat_gat.hip": [],
     "kgat_rgcn.hip": [],
     "kgat_transe.hip": [],
+    "kgat_bi_pool.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -228,6 +229,11 @@ SIGNATURES = {
     "kgat_transe_presort_f32": (_i32, [_i64, _i32, _i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),
     "kgat_transe_adam_step_f32": (_i32, [_i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double,
                                          C.c_double, C.c_double, C.c_double, C.c_float, _p, _p, C.c_uint64, _p, _sz, _p]),
+    # Bi-Interaction pooling over sparse feature sets (the FM / NFM baselines) and its dense backward (ABI 16, additive)
+    "kgat_bi_pool_supported": (_i32, [_i32, _i64]),
+    "kgat_bi_pool_scratch_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "kgat_bi_pool_fwd_f32": (_i32, [_i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "kgat_bi_pool_bwd_f32": (_i32, [_i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

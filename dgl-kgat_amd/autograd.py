@@ -16,6 +16,8 @@
   backward towards x and the coefficients.
 * ``kgat_attention`` - the fused attention (logits + destination softmax, models.py:135-154) as one unit that
   differentiates towards the entity table, W_R and the relation embeddings.
+* ``bi_pool`` - NFM's Bi-Interaction pooling over sparse feature sets (kgat_bi_pool_fwd_f32 / kgat_bi_pool_bwd_f32): the
+  operator of the FM and NFM baselines; backward towards the embedding table and the linear weights, dense.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -642,3 +644,47 @@ def rgcn_aggregate(g, x, coef, etypes, norm=None):
     if ops.rgcn_supported(x.shape[1], coef.shape[1], coef.shape[0]):
         return _RGCNAggregate.apply(x, coef, g, etypes, norm)
     return _rgcn_restated(g._st, x, coef, etypes, norm)
+
+
+class _BiPool(torch.autograd.Function):
+    """Bi-Interaction pooling of feature sets (kgat_bi_pool_fwd_f32) and its dense backward (kgat_bi_pool_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, V, w_lin, feats, items, extra):
+        S, bi, lin, sq = ops.bi_pool_fwd(V.detach(), None if w_lin is None else w_lin.detach(), feats, items, extra)
+        if lin is None:
+            lin = torch.zeros(items.numel(), dtype=V.dtype, device=V.device)
+        ctx.feats, ctx.has_w = feats, w_lin is not None
+        ctx.save_for_backward(V, S, items, extra)
+        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None: the entry's NULL path
+        return bi, lin, sq
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_bi, g_lin, g_sq):
+        V, S, items, extra = ctx.saved_tensors
+        need_V, need_w = ctx.needs_input_grad[0], ctx.has_w and ctx.needs_input_grad[1]
+        if not need_V:   # (the linear term alone: its gradient does not read V)
+            g_bi = g_sq = None
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_bi, g_lin if need_w else None, g_sq)]
+        grad_V, grad_w = ops.bi_pool_bwd(V.detach(), ctx.feats, items, extra, S, *g, want_w=need_w)
+        return grad_V if need_V else None, grad_w if need_w else None, None, None, None
+
+
+def bi_pool(V, w_lin, feats, items, extra=None):
+    """NFM's Bi-Interaction pooling over sparse feature sets, differentiable towards V and w_lin: pooled set m is
+    ``[extra[m]] + feats[items[m]]`` (extra first; ``extra[m] = -1`` or ``extra=None``: no extra) and the outputs are
+    ``bi[m] = ((sum_f v_f)^2 - sum_f v_f^2) / 2`` (n_sets, d), ``lin[m] = sum_f w_lin[f]`` and ``sq[m] = sum_f |v_f|^2``
+    (n_sets each; an empty set gives zeros; ``w_lin=None``: lin is zero).  `feats`: an ``fm_models.FeatureSets``; `items`
+    item positions, `extra` feature ids, any integer dtype.  On a HIP device in fp32 at a size ``ops.bi_pool_supported``
+    takes, one kernel forward and a sort plus one kernel backward, with fixed orders of addition (bitwise reproducible,
+    dense gradients whose untouched rows are 0); CPU tensors, other dtypes and sizes run ``fm_models.bi_pool_torch``."""
+    from .fm_models import _kernels_apply, bi_pool_torch
+    if V.dim() != 2:
+        raise ValueError("bi_pool: V must be (n_features, d), got %s" % (tuple(V.shape),))
+    if not _kernels_apply(V, w_lin, items.numel()):
+        return bi_pool_torch(V, w_lin, feats, items, extra)
+
+    def i32(t):
+        return t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous()
+    return _BiPool.apply(V, w_lin, feats.to(V.device), i32(items.to(V.device)), None if extra is None else i32(extra.to(V.device)))

@@ -1,0 +1,336 @@
+"""The KGAT paper's "supervised learning" baselines, FM and NFM, on fused Bi-Interaction pooling.
+
+Both take "IDs of a user, an item and its knowledge (entities connected to it) as input features": the feature
+universe is every node of the collaborative KG, one table ``V (n_nodes x d)`` and one ``w_lin (n_nodes)`` serve the
+model, and the features of the pair (u, i) are the set ``{u} + F(i)`` with ``F(i)`` the item's list in a
+``FeatureSets``.  The operator is NFM's Bi-Interaction pooling
+
+    f_BI(x) = sum_{f<g} v_f * v_g = ((sum_f v_f)^2 - sum_f v_f^2) / 2
+
+(``autograd.bi_pool``: csrc/kgat_bi_pool.hip on a HIP device in fp32, ``bi_pool_torch`` elsewhere); FM is the same
+operator with its d outputs summed.  NFM's evaluation has no dot-product form: ``NFM.scores`` evaluates the MLP per
+(user, item) pair in torch operators over user blocks - a fused all-pairs MLP sweep is out of scope."""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+
+
+POOL_CHUNK = 8192   # the sets of one kernel call (ops.bi_pool_supported)
+
+
+class FeatureSets:
+    """A CSR over item positions: ``ids[indptr[j]:indptr[j + 1]]`` are the feature ids (rows of the embedding table, in
+    [0, n_features)) of item position j.  Lists are multisets: a repeated id counts twice.  Holds device copies (int32)
+    and the graph-static reversed CSR - ``rev_items[rev_indptr[f]:rev_indptr[f + 1]]``: the item positions whose list
+    holds feature f, ascending, once per occurrence.  ``item_offset``: the node id of item position 0 (``from_kg`` sets
+    it; the models subtract it from the item ids they are given)."""
+
+    def __init__(self, indptr, ids, n_features, device="cpu", item_offset=0):
+        indptr = np.ascontiguousarray(np.asarray(indptr, dtype=np.int64))
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64))
+        if indptr.ndim != 1 or len(indptr) < 2 or indptr[0] != 0 or (np.diff(indptr) < 0).any() or indptr[-1] != len(ids):
+            raise ValueError("FeatureSets: indptr must be non-decreasing from 0 to len(ids), over at least one item")
+        n_features = int(n_features)
+        if len(ids) and (ids.min() < 0 or ids.max() >= n_features):
+            raise ValueError("FeatureSets: feature ids must lie in [0, %d)" % n_features)
+        if not (0 < n_features < 2 ** 31 - 1 and len(indptr) - 1 < 2 ** 31 - 1 and len(ids) < 2 ** 31 - 1):
+            raise ValueError("FeatureSets: sizes must stay below 2^31")
+        self.n_items, self.n_features, self.n_pairs = len(indptr) - 1, n_features, len(ids)
+        self.item_offset = int(item_offset)
+        item_of = np.repeat(np.arange(self.n_items, dtype=np.int64), np.diff(indptr))
+        order = np.argsort(ids, kind="stable")   # by feature; equal features keep ascending item position
+        rev_indptr = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=n_features))])
+        self._host = {"indptr": indptr.astype(np.int32), "ids": ids.astype(np.int32), "rev_indptr": rev_indptr.astype(np.int32),
+                      "rev_items": item_of[order].astype(np.int32)}
+        self._copies = {}
+        self._place(torch.device(device))
+
+    def _place(self, device):
+        key = str(device)
+        if key not in self._copies:
+            self._copies[key] = {k: torch.as_tensor(v).to(device) for k, v in self._host.items()}
+        self.device = device
+        for k, v in self._copies[key].items():
+            setattr(self, k, v)
+
+    def to(self, device):
+        """The same sets with their arrays on `device` (a view object: the host arrays and earlier copies are shared)."""
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        other = object.__new__(FeatureSets)
+        other.__dict__.update(self.__dict__)
+        other._place(device)
+        return other
+
+    def lists(self):
+        """The lists as host arrays, one per item position."""
+        ip, ids = self._host["indptr"], self._host["ids"]
+        return [ids[ip[j]:ip[j + 1]].astype(np.int64) for j in range(self.n_items)]
+
+    @classmethod
+    def from_kg(cls, triplets, item_range, n_nodes, include_self=True, device="cpu"):
+        """Item i of ``item_range = (lo, hi)`` gets the list ``[i] + sorted(unique tails t of the triples (i, r, t))``.
+        Triples whose tail is a user are excluded; in the collaborative KG's id layout (ckg_io) the users are the ids
+        below ``lo``."""
+        lo, hi = int(item_range[0]), int(item_range[1])
+        if not 0 <= lo < hi <= n_nodes:
+            raise ValueError("from_kg: item range %r outside [0, %d]" % ((lo, hi), n_nodes))
+        trip = np.asarray(triplets, dtype=np.int64).reshape(-1, 3)
+        keep = (trip[:, 0] >= lo) & (trip[:, 0] < hi) & (trip[:, 2] >= lo) & (trip[:, 2] < n_nodes)
+        pairs = np.unique(trip[keep][:, [0, 2]], axis=0)   # sorted by head, then tail; duplicates gone
+        if include_self:
+            own = np.arange(lo, hi, dtype=np.int64)
+            heads = np.concatenate([own, pairs[:, 0]])
+            tails = np.concatenate([own, pairs[:, 1]])
+            order = np.argsort(heads, kind="stable")       # the self entry stays in front of the item's sorted tails
+            heads, tails = heads[order], tails[order]
+        else:
+            heads, tails = pairs[:, 0], pairs[:, 1]
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(heads - lo, minlength=hi - lo))])
+        return cls(indptr, tails, n_nodes, device=device, item_offset=lo)
+
+
+def _long(t, device):
+    return torch.as_tensor(t, device=device).long()
+
+
+def bi_pool_torch(V, w_lin, feats, items, extra=None, want_S=False):
+    """Bi-Interaction pooling in torch operators (index_select / index_add_), differentiable: what the kernels are
+    compared with and what runs on the CPU, in float64 and outside ``ops.bi_pool_supported``.  Pooled set m is
+    ``[extra[m]] + feats[items[m]]`` (``extra[m] = -1``: no extra).  Returns (bi, lin, sq), or (S, bi, lin, sq)."""
+    dev = V.device
+    feats = feats.to(dev)
+    items = _long(items, dev)
+    M = items.numel()
+    indptr, ids = feats.indptr.long(), feats.ids.long()
+    beg = indptr[items]
+    cnt = indptr[items + 1] - beg
+    set_of = torch.repeat_interleave(torch.arange(M, device=dev), cnt)
+    first = torch.cumsum(cnt, 0) - cnt
+    f = ids[torch.arange(set_of.numel(), device=dev) - first[set_of] + beg[set_of]]
+    if extra is not None:
+        extra = _long(extra, dev)
+        has = extra >= 0
+        f = torch.cat([extra[has], f])
+        set_of = torch.cat([torch.arange(M, device=dev)[has], set_of])
+    rows = V.index_select(0, f)
+    S = torch.zeros(M, V.shape[1], dtype=V.dtype, device=dev).index_add_(0, set_of, rows)
+    Q = torch.zeros(M, V.shape[1], dtype=V.dtype, device=dev).index_add_(0, set_of, rows * rows)
+    bi = 0.5 * (S * S - Q)
+    lin = torch.zeros(M, dtype=V.dtype, device=dev)
+    if w_lin is not None:
+        lin = lin.index_add_(0, set_of, w_lin.index_select(0, f))
+    sq = Q.sum(1)
+    return (S, bi, lin, sq) if want_S else (bi, lin, sq)
+
+
+def _kernels_apply(V, w_lin, n_sets):
+    return (V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and V.data_ptr() % 16 == 0 and
+            (w_lin is None or (w_lin.is_contiguous() and w_lin.dtype == torch.float32)) and
+            ops.bi_pool_supported(V.shape[1], n_sets))
+
+
+def pool_items(V, w_lin, feats, chunk=POOL_CHUNK):
+    """(P, T, lin) of every item's own list without an extra - ``P = S``, ``T = bi`` - under no_grad, in calls of at most
+    `chunk` sets: the item side of ``bi({u} + F(i)) = v_u * P_i + T_i``."""
+    with torch.no_grad():
+        feats = feats.to(V.device)
+        out = []
+        for lo in range(0, feats.n_items, chunk):
+            items = torch.arange(lo, min(lo + chunk, feats.n_items), dtype=torch.int32, device=V.device)
+            if _kernels_apply(V, w_lin, items.numel()):
+                S, bi, lin, _ = ops.bi_pool_fwd(V.detach(), None if w_lin is None else w_lin.detach(), feats, items, want_sq=False)
+                if lin is None:
+                    lin = torch.zeros(items.numel(), dtype=V.dtype, device=V.device)
+            else:
+                S, bi, lin, _ = bi_pool_torch(V, w_lin, feats, items, want_S=True)
+            out.append((S, bi, lin))
+        return tuple(torch.cat(parts, 0) for parts in zip(*out))
+
+
+def _load_rows(table, user_embed, item_embed, n_users):
+    ue, ie = torch.as_tensor(user_embed), torch.as_tensor(item_embed)
+    if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != table.shape[1] or ie.shape[1] != table.shape[1] or \
+            ue.shape[0] != int(n_users) or n_users + ie.shape[0] > table.shape[0]:
+        raise ValueError("load_pretrained: embeddings must be (%d, %d) and (items, %d), got %s and %s"
+                         % (n_users, table.shape[1], table.shape[1], tuple(ue.shape), tuple(ie.shape)))
+    with torch.no_grad():
+        table[:n_users].copy_(ue.to(device=table.device, dtype=table.dtype))
+        table[n_users:n_users + ie.shape[0]].copy_(ie.to(device=table.device, dtype=table.dtype))
+
+
+class _Pooled(nn.Module):
+    """What FM and NFM share: the table ``embed`` (n_nodes x dim), ``w_lin`` (n_nodes), ``w0`` and the pooled pass of a
+    BPR batch.  Item arguments are node ids; ``feats.item_offset`` turns them into item positions."""
+
+    def __init__(self, n_nodes, feats, dim, reg_lambda):
+        super().__init__()
+        if feats.n_features != int(n_nodes):
+            raise ValueError("the feature universe (%d) must be all %d nodes" % (feats.n_features, n_nodes))
+        self.feats = feats
+        self.reg_lambda = float(reg_lambda)
+        self.embed = nn.Embedding(n_nodes, dim)
+        # Xavier rows, as CKE's tables: a set of n features sums n (n - 1) / 2 products per column, and with
+        # nn.Embedding's N(0, 1) rows the scores start at hundreds instead of near 0
+        nn.init.xavier_uniform_(self.embed.weight)
+        self.w_lin = nn.Parameter(torch.zeros(n_nodes))
+        self.w0 = nn.Parameter(torch.zeros(1))
+
+    def _positions(self, items):
+        return items.to(torch.int32) - self.feats.item_offset
+
+    def pool(self, users, items):
+        """(bi, lin, sq) of the sets ``{users[m]} + F(items[m])``: one ``bi_pool`` call (up to 8,192 sets)."""
+        from .autograd import bi_pool
+        V, w, pos, ex = self.embed.weight, self.w_lin, self._positions(items), users.to(torch.int32)
+        n = pos.numel()
+        if n <= POOL_CHUNK or not _kernels_apply(V, w, POOL_CHUNK):
+            return bi_pool(V, w, self.feats, pos, ex)
+        # beyond the kernels' sets per call: calls of POOL_CHUNK sets (autograd adds their dense gradients)
+        parts = [bi_pool(V, w, self.feats, pos[lo:lo + POOL_CHUNK], ex[lo:lo + POOL_CHUNK]) for lo in range(0, n, POOL_CHUNK)]
+        return tuple(torch.cat(t, 0) for t in zip(*parts))
+
+    def _head(self, bi):
+        raise NotImplementedError
+
+    def score(self, users, items):
+        bi, lin, _ = self.pool(users, items)
+        return self.w0 + lin + self._head(bi)
+
+    def get_loss(self, u, pos, neg):
+        """``mean_b softplus(y_neg - y_pos) + reg_lambda * mean_b (sq_pos + sq_neg) / 2``; one pooled call over the 2 B
+        sets, positives first."""
+        b = u.numel()
+        bi, lin, sq = self.pool(torch.cat([u, u]), torch.cat([pos, neg]))
+        y = self.w0 + lin + self._head(bi)
+        return F.softplus(y[b:] - y[:b]).mean() + self.reg_lambda * (0.5 * (sq[:b] + sq[b:])).mean()
+
+    def load_pretrained(self, user_embed, item_embed, n_users):
+        """BPR-MF embeddings into the user and item rows of ``embed``."""
+        _load_rows(self.embed.weight, user_embed, item_embed, n_users)
+
+
+class FM(_Pooled):
+    """Factorisation machine over ``{u} + F(i)``: ``y(u, i) = w0 + lin + sum_c bi_c``."""
+
+    def __init__(self, n_nodes, feats, dim=64, reg_lambda=1e-5):
+        super().__init__(n_nodes, feats, dim, reg_lambda)
+
+    def _head(self, bi):
+        return bi.sum(1)
+
+    @torch.no_grad()
+    def readout(self, user_range, item_range):
+        """An (n_nodes, d + 2) table whose dot products are y: user rows ``[v_u | 1 | w0 + w_u]``, item rows
+        ``[P_i | lin_i + sum_c T_i,c | 1]`` with P = S and T = bi of the set F(i) without an extra, from
+        ``bi({u} + F(i)) = v_u * P_i + T_i``; other rows zero.  The per-user constant stays: calc_recall_ndcg masks
+        training items to 0.0, so absolute scores matter.  With it ``calc_recall_ndcg``, ``calc_metrics``,
+        ``calc_rank_metrics`` and ``recommend`` evaluate FM unchanged.  Zero columns are appended where the evaluation
+        kernels - the K <= 32 sweep, the top-K lists up to K = 128 and the rank sweep alike - refuse d + 2 columns.  Not
+        differentiable."""
+        V, w = self.embed.weight, self.w_lin
+        (u0, u1), (i0, i1) = user_range, item_range
+        if not (0 <= u0 <= u1 <= V.shape[0] and 0 <= i0 <= i1 <= V.shape[0]) or max(u0, i0) < min(u1, i1):
+            raise ValueError("readout: user rows %r and item rows %r must be disjoint ranges inside [0, %d]"
+                             % ((u0, u1), (i0, i1), V.shape[0]))
+        if i0 != self.feats.item_offset or i1 - i0 != self.feats.n_items:
+            raise ValueError("readout: item rows %r are not the feature sets' items [%d, %d)"
+                             % ((i0, i1), self.feats.item_offset, self.feats.item_offset + self.feats.n_items))
+        d = V.shape[1]
+        width = d + 2
+        if V.is_cuda:
+            # a width every evaluation family takes at every cut-off it offers (the list families' buffers grow with K)
+            def taken(f):
+                return (ops.eval_supported(f, 20) and ops.eval_supported(f, 32) and ops.eval_rank_supported(f) and
+                        all(ops.eval_topk_supported(f, k) for k in (20, 64, 128)))
+            while not taken(width) and width < d + 66:
+                width += 1
+        P, T, lin = pool_items(V, w, self.feats)
+        table = torch.zeros(V.shape[0], width, dtype=V.dtype, device=V.device)
+        table[u0:u1, :d] = V[u0:u1]
+        table[u0:u1, d] = 1.0
+        table[u0:u1, d + 1] = self.w0 + w[u0:u1]
+        table[i0:i1, :d] = P
+        table[i0:i1, d] = lin + T.sum(1)
+        table[i0:i1, d + 1] = 1.0
+        return table
+
+
+class NFM(_Pooled):
+    """Neural factorisation machine: ``y = w0 + lin + h . MLP(dropout(bi))``, the MLP plain ``nn.Linear`` + ReLU."""
+
+    def __init__(self, n_nodes, feats, dim=64, layers=(64,), dropout=0.0, reg_lambda=1e-5):
+        super().__init__(n_nodes, feats, dim, reg_lambda)
+        widths = [dim] + [int(x) for x in layers]
+        mods = []
+        for a, b in zip(widths[:-1], widths[1:]):
+            mods += [nn.Linear(a, b), nn.ReLU()]
+        self.mlp = nn.Sequential(*mods)
+        self.drop = nn.Dropout(dropout)
+        self.h = nn.Parameter(torch.empty(widths[-1]))
+        # h = 1 / sqrt(width): the MLP's output enters the score at the scale of one hidden unit - with an empty `layers`
+        # and h = 1 this is FM
+        nn.init.constant_(self.h, 1.0 / float(widths[-1]) ** 0.5 if len(widths) > 1 else 1.0)
+
+    def _head(self, bi):
+        return self.mlp(self.drop(bi)) @ self.h
+
+    @torch.no_grad()
+    def scores(self, users, max_bytes=1 << 28):
+        """The (len(users), n_items) score matrix in torch operators, from ``bi({u} + F(i)) = v_u * P_i + T_i``, in user
+        blocks sized so that a block's (users x items x widest layer) tensor stays below `max_bytes`."""
+        V, w = self.embed.weight, self.w_lin
+        users = _long(users, V.device)
+        P, T, lin = pool_items(V, w, self.feats)
+        widest = max([V.shape[1]] + [m.out_features for m in self.mlp if isinstance(m, nn.Linear)])
+        block = max(1, int(max_bytes // (max(1, self.feats.n_items) * widest * V.element_size() * 2)))
+        out = []
+        was_training = self.training
+        self.eval()
+        try:
+            for lo in range(0, users.numel(), block):
+                u = users[lo:lo + block]
+                bi = V[u].unsqueeze(1) * P.unsqueeze(0) + T.unsqueeze(0)
+                out.append(self.w0 + (w[u].unsqueeze(1) + lin.unsqueeze(0)) + self._head(bi))
+        finally:
+            self.train(was_training)
+        return torch.cat(out, 0) if out else torch.zeros(0, self.feats.n_items, dtype=V.dtype, device=V.device)
+
+    @torch.no_grad()
+    def topk(self, plan, K, max_bytes=1 << 28):
+        """The K best unseen items of every user of an ``EvalPlan`` (its training items dropped), as item positions: an
+        (n_users, K) int32 tensor, best first (``torch.topk``)."""
+        n_items = self.feats.n_items
+        if plan.n_items != n_items:
+            raise ValueError("topk: the plan ranks %d items, the feature sets hold %d" % (plan.n_items, n_items))
+        if not 1 <= K <= n_items:
+            raise ValueError("topk: K must be in [1, %d]" % n_items)
+        users = plan.user_ids.long()
+        tp = plan.train_ptr.long()
+        out = []
+        step = max(1, int(max_bytes // (max(1, n_items) * 4 * 4)))
+        for lo in range(0, users.numel(), step):
+            hi = min(lo + step, users.numel())
+            sc = self.scores(users[lo:hi], max_bytes)
+            seen = plan.train_items[int(tp[lo]):int(tp[hi])].long()
+            row = torch.repeat_interleave(torch.arange(hi - lo, device=sc.device), tp[lo + 1:hi + 1] - tp[lo:hi])
+            sc[row, seen] = float("-inf")
+            out.append(torch.topk(sc, K, dim=1).indices.to(torch.int32))
+        return torch.cat(out, 0) if out else torch.zeros(0, K, dtype=torch.int32, device=self.embed.weight.device)
+
+    def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28):
+        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``: block scores,
+        training items dropped, ``torch.topk``, then the metric kernel of the other models (``ops.eval_metrics_at_ks``).
+        Returns the dict ``metrics.calc_metrics`` returns."""
+        from . import metrics
+        Ks = [int(k) for k in Ks]
+        if plan.n_users == 0:
+            raise ZeroDivisionError("no test users")
+        top = self.topk(plan, Ks[-1], max_bytes).contiguous()
+        out = ops.eval_metrics_at_ks(top, plan.test_ptr, plan.test_items, Ks)
+        mean = (out.sum(0) / plan.n_users).cpu().numpy()
+        return {name: mean[:, m].copy() for m, name in enumerate(metrics.METRIC_NAMES)}

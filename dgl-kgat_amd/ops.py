@@ -2070,6 +2070,70 @@ def transe_adam_step(h, r, pos_t, neg_t, sorted_block, ent, rel, exp_avg, exp_av
                                                 state.scratch.numel(), _stream(ent)), "kgat_transe_adam_step_f32")
 
 
+# ---------------------------------------------------------------- Bi-Interaction pooling, the FM / NFM baselines (kgat_bi_pool_*)
+def bi_pool_supported(d, n_sets):
+    """Sizes of the pooling kernels: d in {16, 32, 64, 128} and 1 <= n_sets <= 8192 (kgat_bi_pool_supported)."""
+    return bool(_lib.load().kgat_bi_pool_supported(int(d), int(n_sets)))
+
+
+def _bi_pool_operands(V, feats, items, extra):
+    V = _need(V, torch.float32, "V")
+    if V.dim() != 2 or V.shape[0] != feats.n_features:
+        raise ValueError("V must be (%d, d), got %s" % (feats.n_features, tuple(V.shape)))
+    items = _need(items, torch.int32, "items")
+    if items.dim() != 1:
+        raise ValueError("items must be one-dimensional")
+    if extra is not None:
+        _need(extra, torch.int32, "extra", items.shape)
+    for name in ("indptr", "ids", "rev_indptr", "rev_items"):
+        _need(getattr(feats, name), torch.int32, "feats." + name)
+    if feats.indptr.device != V.device:
+        raise ValueError("the feature sets are on %s, V on %s" % (feats.indptr.device, V.device))
+    return V.shape[0], V.shape[1], items.numel()
+
+
+def bi_pool_fwd(V, w_lin, feats, items, extra=None, want_lin=True, want_sq=True):
+    """Bi-Interaction pooling of the sets [extra[m]] + feats[items[m]] (kgat_bi_pool_fwd_f32): returns (S, bi, lin, sq),
+    lin / sq None where not asked for (lin also without w_lin).  `feats`: a FeatureSets on V's device; items, extra int32."""
+    n, d, m = _bi_pool_operands(V, feats, items, extra)
+    if w_lin is not None:
+        _need(w_lin, torch.float32, "w_lin", (n,))
+    dev = V.device
+    S = torch.empty((m, d), dtype=torch.float32, device=dev)
+    bi = torch.empty((m, d), dtype=torch.float32, device=dev)
+    lin = torch.empty(m, dtype=torch.float32, device=dev) if want_lin and w_lin is not None else None
+    sq = torch.empty(m, dtype=torch.float32, device=dev) if want_sq else None
+    with _timed("bi_pool_fwd", (m, d)):
+        check(_lib.load().kgat_bi_pool_fwd_f32(m, d, n, feats.n_items, feats.n_pairs, _ptr(V), _ptr(w_lin), _ptr(feats.indptr),
+                                               _ptr(feats.ids), _ptr(items), _ptr(extra), _ptr(S), _ptr(bi), _ptr(lin), _ptr(sq),
+                                               _stream(V)), "kgat_bi_pool_fwd_f32")
+    return S, bi, lin, sq
+
+
+def bi_pool_bwd(V, feats, items, extra, S, g_bi=None, g_lin=None, g_sq=None, want_w=True, scratch=None):
+    """The dense gradients of bi_pool_fwd's outputs (kgat_bi_pool_bwd_f32): (grad_V (n_nodes, d), grad_w (n_nodes) or
+    None).  g_bi (n_sets, d), g_lin, g_sq (n_sets): None = zero.  S is the forward's."""
+    n, d, m = _bi_pool_operands(V, feats, items, extra)
+    _need(S, torch.float32, "S", (m, d))
+    if g_bi is not None:
+        _need(g_bi, torch.float32, "g_bi", (m, d))
+    for name, t in (("g_lin", g_lin), ("g_sq", g_sq)):
+        if t is not None:
+            _need(t, torch.float32, name, (m,))
+    lib = _lib.load()
+    dev = V.device
+    grad_V = torch.empty((n, d), dtype=torch.float32, device=dev)
+    grad_w = torch.empty(n, dtype=torch.float32, device=dev) if want_w else None
+    need = lib.kgat_bi_pool_scratch_bytes(m, feats.n_items, n, feats.n_pairs)
+    ws = scratch if scratch is not None and scratch.numel() >= need else _workspace(need, dev)
+    with _timed("bi_pool_bwd", (m, d)):
+        check(lib.kgat_bi_pool_bwd_f32(m, d, n, feats.n_items, feats.n_pairs, _ptr(V), _ptr(feats.rev_indptr),
+                                       _ptr(feats.rev_items), _ptr(items), _ptr(extra), _ptr(g_bi), _ptr(g_lin), _ptr(g_sq),
+                                       _ptr(S), _ptr(grad_V), _ptr(grad_w), _ptr(ws), ws.numel(), _stream(V)),
+              "kgat_bi_pool_bwd_f32")
+    return grad_V, grad_w
+
+
 # ---------------------------------------------------------------- global-norm gradient clipping (kgat.py:32,162)
 def __getattr__(name):
     # GRAD_NORM_CHAIN: the compile-time constant of the library (kgat_grad_norm_chain), read when first asked for

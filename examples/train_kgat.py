@@ -24,6 +24,8 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
   python examples/train_kgat.py --planted --model cfkg --epochs 3 --lr 0.03 --batch_size_kg 512 --eval_before
                                                                           # the paper's CFKG baseline (TransE over the CKG);
                                                                           # --model cke: TransR + BPR on cf + entity rows
+  python examples/train_kgat.py --planted --model fm --epochs 3 --lr 0.03 --batch_size 512 --eval_before
+                                                                         # --model nfm: the same features under an MLP
   python examples/train_kgat.py --planted --pretrain_epochs 5 --pretrain_lr 0.1 --pretrain_save mf.npz --epochs 3
                                                                           # BPR-MF pretraining of the table first (the paper's
                                                                           # initialisation); --pretrain_load mf.npz reuses it
@@ -173,6 +175,16 @@ def _rank_cutoffs(text):
     return ks
 
 
+def _widths(text):
+    try:
+        ws = [int(x) for x in text.split(",")]
+    except ValueError:
+        ws = []
+    if not ws or min(ws) < 1:
+        raise argparse.ArgumentTypeError("layer widths: positive integers separated by commas")
+    return ws
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_dir", default=None)
@@ -187,10 +199,14 @@ def parse_args(argv=None):
                     help="propagation layers (reference kgat.py:23): bi-interaction KGATConv, SAGEConv (mean), or "
                          "RelGraphConv (R-GCN with basis decomposition over the edge types)")
     # (absent from the namespace unless given, as --num_bases: a run without it keeps its arguments and --log_json "args")
-    ap.add_argument("--model", choices=("kgat", "cfkg", "cke"), default=argparse.SUPPRESS,
-                    help="kgat (default), or one of the KGAT paper's KG-embedding baselines: cfkg - TransE over the whole "
+    ap.add_argument("--model", choices=("kgat", "cfkg", "cke", "fm", "nfm"), default=argparse.SUPPRESS,
+                    help="kgat (default), or one of the KGAT paper's baselines: cfkg - TransE over the whole "
                          "collaborative KG, recommendation as the ranking of (user, interact, ?) (kge_models.CFKG); cke - "
-                         "TransR over the item KG + BPR on `cf latent + entity embedding` (kge_models.CKE)")
+                         "TransR over the item KG + BPR on `cf latent + entity embedding` (kge_models.CKE); fm / nfm - a "
+                         "factorisation machine / neural FM over the features {user, item, the item's KG neighbours} on "
+                         "fused Bi-Interaction pooling (fm_models.FM / NFM)")
+    ap.add_argument("--nfm_layers", type=_widths, default=argparse.SUPPRESS, metavar="W[,W...]",
+                    help="--model nfm: widths of the hidden layers above the pooling (default 64)")
     ap.add_argument("--num_bases", type=int, default=argparse.SUPPRESS,
                     help="bases of the rgcn layers' relation weights (default 4; at most the number of relations)")
     ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage", "Bi2"), default="Bi",
@@ -279,6 +295,14 @@ def parse_args(argv=None):
         if args.pretrain_epochs or args.pretrain_save:
             ap.error("--model %s takes --pretrain_load only: --pretrain_epochs / --pretrain_save train and write the "
                      "table of --model kgat" % kind)
+    if kind in ("fm", "nfm"):
+        # no KG phase: nothing to rank triples with, nothing to hold out
+        if args.kg_eval or args.kg_holdout > 0:
+            ap.error("--kg_eval / --kg_holdout rank triples; --model %s has no KG phase" % kind)
+        if kind == "nfm" and getattr(args, "rank_metrics", 0):
+            ap.error("--rank_metrics sweeps a dot-product table; --model nfm scores through an MLP")
+    if hasattr(args, "nfm_layers") and kind != "nfm":
+        ap.error("--nfm_layers sets the hidden layers of --model nfm")
     if args.pretrain_epochs < 0 or args.pretrain_batch_size < 1:
         ap.error("--pretrain_epochs takes a number of epochs >= 0, --pretrain_batch_size a batch >= 1")
     if (args.pretrain_epochs or args.pretrain_load or args.pretrain_save) and args.gpus > 1:
@@ -339,7 +363,9 @@ def main(argv=None):
     try:
         return _run(args, argv)
     finally:
-        if args.attention_grad:   # leave the process-wide lazy setting as this call found it
+        # leave the process-wide lazy setting as this call found it: --attention_grad 1 turns it off inside, and a
+        # --model without propagation layers computes no attention, so the setting is not its to keep switched on
+        if args.attention_grad or getattr(args, "model", "kgat") != "kgat":
             K.enable_lazy_edge_weights(lazy_before)
 
 
@@ -391,6 +417,8 @@ def _run(args, argv):
             raise SystemExit("--kg_eval: no triple to rank")
         pick = np.random.default_rng(args.seed).permutation(len(kg_pool))[:args.kg_eval]
         kg_pool = kg_pool[pick].astype(np.int64)
+    if getattr(args, "model", "kgat") in ("fm", "nfm"):
+        return _run_fm(args, ds, dev)
     if getattr(args, "model", "kgat") != "kgat":
         return _run_kge(args, ds, dev, kg_pool, full if args.kg_eval else None)
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
@@ -779,6 +807,120 @@ def _run_kge(args, ds, dev, kg_pool, full):
             json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
                        "n_relations": ds.n_KG_relation, "n_train_triplets": int(n_trip), "n_train_pairs": int(n_pairs),
                        "epochs": history}, f, indent=1)
+    return history
+
+
+def _run_fm(args, ds, dev):
+    """--model fm / nfm on one GPU: an epoch is a CF phase of BPR steps - one pooled call over the 2 B feature sets
+    {user} + F(item), positives first, one FusedAdam over all parameters, --grad_norm honoured - then evaluation: FM on
+    its dot-product table (FM.readout) with the metrics of the other models, NFM through NFM.evaluate (block scores in
+    torch operators, torch.topk, the metric kernel).  The records carry the keys the other models' CF phase and
+    evaluation write."""
+    kind = args.model
+    off, n_items = ds.n_users, ds.n_items
+    items = (off, off + n_items)
+    feats = K.FeatureSets.from_kg(ds.train_KG_triplet, items, ds.n_KG_entity, device=dev)
+    if kind == "fm":
+        model = K.FM(ds.n_KG_entity, feats, dim=args.entity_embed_dim).to(dev)
+    else:
+        model = K.NFM(ds.n_KG_entity, feats, dim=args.entity_embed_dim, layers=tuple(getattr(args, "nfm_layers", [64])),
+                      dropout=args.dropout_rate).to(dev)
+    print("--model %s | %d items, %d (item, feature) pairs, longest list %d" % (
+        kind, feats.n_items, feats.n_pairs, int(np.diff(feats._host["indptr"]).max())))
+    if args.pretrain_load:
+        model.load_pretrained(*ckg_io.load_pretrain(args.pretrain_load), ds.n_users)
+        print("Pretrain   | user / item rows from %s" % args.pretrain_load)
+    opt = K.FusedAdam(model.parameters(), lr=args.lr)
+    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
+    n_pairs = pair_cols.shape[1]
+    train_dict = user_dict(ds.train_pairs, off)
+    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
+    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
+    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
+             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
+
+    def cap(n):
+        return n if args.max_iters <= 0 else min(n, args.max_iters)
+
+    def clock():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def evaluate(rec):
+        t0 = clock()
+        with torch.no_grad():
+            emb = model.readout((0, off), items).contiguous() if kind == "fm" else None
+            for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict)):
+                if getattr(args, "rank_metrics", 0):
+                    rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
+                    rank_Ks = [k for k in rank_Ks if k <= plans[name].n_items] or [plans[name].n_items]
+                    m = metrics.calc_rank_metrics(emb, seen, held, ds.item_id_range, Ks=rank_Ks, plan=plans[name])
+                    for metric in metrics.RANK_SCALAR_NAMES:
+                        rec["%s_%s" % (name, metric)] = float(m[metric])
+                    for j, k in enumerate(rank_Ks):
+                        for metric in metrics.METRIC_NAMES:
+                            rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                    print("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f" % (
+                        name, m["auc"], m["mrr"], m["map"], m["mean_rank"]))
+                if kind == "fm" and args.Ks == [20]:
+                    rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
+                        emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
+                    print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+                    continue
+                m = (metrics.calc_metrics(emb, seen, held, ds.item_id_range, Ks=args.Ks, plan=plans[name]) if kind == "fm"
+                     else model.evaluate(plans[name], args.Ks))
+                if args.Ks == [20]:
+                    rec[name + "_recall"], rec[name + "_ndcg"] = float(m["recall"][0]), float(m["ndcg"][0])
+                    print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+                    continue
+                for j, k in enumerate(args.Ks):
+                    for metric in metrics.METRIC_NAMES:
+                        rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                    print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
+                        name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
+        rec["eval_s"] = clock() - t0
+        print("           | eval %.4fs" % rec["eval_s"])
+
+    history = []
+    if args.eval_before:
+        model.eval()
+        history.append({"epoch": 0})
+        print("Epoch 0000 | (untrained)")
+        evaluate(history[-1])
+    for epoch in range(1, args.epochs + 1):
+        rec = {"epoch": epoch}
+        t_epoch = clock()
+        t0 = clock()
+        model.train()
+        n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
+        idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
+        u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
+        n_all = torch.randint(off, off + n_items, (n_it, bs), device=dev, dtype=torch.int32)
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        for i in range(n_it):
+            loss = model.get_loss(u_all[i], p_all[i], n_all[i])
+            loss.backward()
+            if args.grad_norm > 0:
+                opt.step(max_grad_norm=args.grad_norm)
+            else:
+                opt.step()
+            opt.zero_grad()
+            total += loss.detach()
+        rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
+        rec["cf_loss"] = float(total) / n_it
+        print("Epoch %04d | CF %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it,
+                                                                      rec["cf_loss"]))
+        del idx, u_all, p_all, n_all
+        model.eval()
+        evaluate(rec)
+        rec["epoch_s"] = clock() - t_epoch
+        print("           | epoch %.4fs" % rec["epoch_s"])
+        history.append(rec)
+    if args.log_json:
+        import json
+        with open(args.log_json, "w") as f:
+            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
+                       "n_relations": ds.n_KG_relation, "n_train_pairs": int(n_pairs), "epochs": history}, f, indent=1)
     return history
 
 

@@ -1220,6 +1220,54 @@ int kgat_transe_adam_step_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, 
                               double lr, double beta1, double beta2, double eps, float reg_lambda, float* loss,
                               uint64_t* row_slot, uint64_t tag, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- Bi-Interaction pooling: the FM / NFM baselines (additive within ABI 16)
+ * The KGAT paper's FM and NFM baselines pool the embeddings of a sparse feature set - a user, an item and the
+ * entities connected to it.  Feature lists are a CSR over item positions: ids[indptr[j] : indptr[j + 1]] are rows of
+ * V (n_nodes x d, contiguous); lists are multisets (a repeated id counts twice).  Pooled set m is
+ *     [extra[m]] (left out where extra[m] < 0 or extra is NULL)  +  the list of item position items[m],
+ * n positions with the extra first, and
+ *     S[m] = sum_f v_f    bi[m] = (S[m]^2 - sum_f v_f^2) / 2    lin[m] = sum_f w_lin[f]    sq[m] = sum_f |v_f|^2
+ * (an empty set: zeros).  The two entries replace index_select / index_add_ under autograd (float atomics, tensors of
+ * pairs x d) and a full-graph kgat_copy_reduce_f32 of [V | V^2] over every item's list.
+ *
+ * kgat_bi_pool_fwd_f32: one wavefront per set, d / 4 lanes per row and 16 bytes per lane, G = 256 / d lane groups,
+ * four rows in flight per group.  Order of additions: position p belongs to group p mod G; a group adds its rows in
+ * ascending position from 0 (v^2 through one fused multiply-add each); the G partials are combined by a butterfly
+ * (group g with g ^ G/2, then g ^ G/4, ..., g ^ 1); bi = 0.5 * fma(S, S, -sum v^2); sq is the sum of the d column sums
+ * of v^2, ((x + y) + (z + w)) per lane, then a butterfly over the d / 4 lanes.  w_lin, extra, lin, sq may be NULL.  A
+ * set whose item position or one of whose ids lies outside its table gets NaN outputs.  Nothing of size pairs x d is
+ * written.
+ *
+ * kgat_bi_pool_bwd_f32: the DENSE gradients grad_V (n_nodes x d) and grad_w (n_nodes; may be NULL) from g_bi (n_sets
+ * x d), g_lin, g_sq (n_sets each; each of the three may be NULL: zero) and the forward's S:
+ *     grad_V[f] = sum over the occurrences of f in the sets m of  g_bi[m] * (S[m] - v_f) + 2 g_sq[m] v_f
+ *     grad_w[f] = sum over the same occurrences of g_lin[m]
+ * Every row is written exactly once, rows no set touches are 0.  rev_indptr (n_nodes + 1) / rev_items is the reversed
+ * CSR: the item positions that hold feature f, ascending, once per occurrence.  The entry sorts `items` and `extra`
+ * (stable, one workgroup each) into runs of sets per item / per extra id, whose first positions go into two tables in
+ * the scratch that a memset refills first; then one wavefront per row f walks f's run as an extra followed by its
+ * reversed list, numbers the hits in that order (within a run in ascending m), gives hit h to lane group h mod G,
+ * which adds its terms in ascending h from 0, and combines the groups with the butterfly above.  A row with more than
+ * 256 sources (a feature that most items carry) is left to a second launch - its id goes through an integer counter
+ * into a list whose order reaches no sum - where 16 wavefronts share it: look k (64 sources) belongs to wavefront
+ * k mod 16, each wavefront numbers and adds its own hits as above, and the 16 sums are added in wavefront order from 0.
+ * No float atomics: both entries are bitwise reproducible.
+ *
+ * kgat_bi_pool_supported(d, n_sets): d in {16, 32, 64, 128} and 1 <= n_sets <= 8192 (the sets one workgroup sorts in
+ * LDS); others KGAT_E_UNSUPPORTED from both entries (the Python layer then runs the torch restatement).  n_nodes,
+ * n_items in [1, 2^31), n_pairs in [0, 2^31), no negative size, no null pointer other than the optional ones, V, S,
+ * bi, g_bi, grad_V and the scratch 16-byte aligned: else KGAT_E_BADARG.  Scratch below
+ * kgat_bi_pool_scratch_bytes(n_sets, n_items, n_nodes, n_pairs): KGAT_E_WORKSPACE.  Every check precedes any device work. */
+int kgat_bi_pool_supported(int d, int64_t n_sets);
+size_t kgat_bi_pool_scratch_bytes(int64_t n_sets, int64_t n_items, int64_t n_nodes, int64_t n_pairs);
+int kgat_bi_pool_fwd_f32(int64_t n_sets, int d, int64_t n_nodes, int64_t n_items, int64_t n_pairs, const float* V,
+                         const float* w_lin, const int32_t* indptr, const int32_t* ids, const int32_t* items,
+                         const int32_t* extra, float* S, float* bi, float* lin, float* sq, kgat_stream_t stream);
+int kgat_bi_pool_bwd_f32(int64_t n_sets, int d, int64_t n_nodes, int64_t n_items, int64_t n_pairs, const float* V,
+                         const int32_t* rev_indptr, const int32_t* rev_items, const int32_t* items, const int32_t* extra,
+                         const float* g_bi, const float* g_lin, const float* g_sq, const float* S, float* grad_V,
+                         float* grad_w, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
