@@ -17,7 +17,7 @@
 // without a dense gradient: kgat_mf_presort_f32 + kgat_mf_adam_step_f32, on the kernels' shared bodies.
 #include <math.h>
 
-#include "kgat_adam_common.h"
+#include "kgat_step_common.h"
 #include "kgat_lds_sort.h"
 
 namespace kgat {
@@ -557,76 +557,37 @@ __global__ __launch_bounds__(256) void mf_window_kernel(MfStepArgs a) {
     bpr_window_body<true>((int64_t)bx * 4 + (threadIdx.x >> 6), a.batch, a.n_nodes, a.F, a.emb, a.F, a.u, a.p, a.n, a.coef,
                           a.reg_lambda, nullptr, a.sorted_ids, a.order, a.compact, a.partials);
   } else if (bx < a.win_blocks + a.tag_blocks) {
-    const int64_t q = (int64_t)(bx - a.win_blocks) * 256 + threadIdx.x;
-    if (q < 3 * a.batch && a.run_len[q] > 0) {
-      const int32_t key = a.sorted_ids[q];
-      if ((uint64_t)key < (uint64_t)a.n_nodes) a.row_slot[key] = (a.tag << kMfSlotBits) | (unsigned long long)(q + 1);
-    }
+    row_tag_write<kMfSlotBits>(a.row_slot, a.tag, (int64_t)(bx - a.win_blocks) * 256 + threadIdx.x, 3 * a.batch, a.run_len,
+                               a.sorted_ids, a.n_nodes);
   } else {
     bpr_reduce_body<256>(a.batch, a.part, a.reg_lambda, a.loss);
   }
 }
 
-// third launch: dense Adam over the table, the gradient through row_slot.  4,096 elements per workgroup, 16 bytes per
-// lane and stream, as adam_kernel.
+// third launch: dense Adam over the table, the gradient through row_slot: adam_chunk_walk.
 struct MfAdamArgs {
-  float *p, *m, *v;
-  int64_t n;
+  AdamTensors<1> t;
   int F;
   int32_t total;   // 3 B
   const unsigned long long* row_slot;
   unsigned long long tag;
   const float *compact, *partials;
   const int32_t* run_len;
-  float step_size, bc2_sqrt;
 };
 
 __global__ __launch_bounds__(256) void mf_adam_kernel(MfAdamArgs a, float w1, float beta2, float w2, float eps) {
-  const int64_t base = (int64_t)blockIdx.x * 4096;
-#pragma unroll
-  for (int q4 = 0; q4 < 4; ++q4) {
-    const int64_t i = base + (int64_t)q4 * 1024 + threadIdx.x * 4;
-    if (i >= a.n) break;   // (n is a multiple of 4: F is)
-    float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
+  adam_chunk_walk(a.t, 0, w1, beta2, w2, eps, [&](int64_t i) {
     const int64_t row = i / a.F;
     const int c = (int)(i - row * a.F);
-    const unsigned long long slot = a.row_slot[row];
-    const int32_t q = (int32_t)(slot & ((1ull << kMfSlotBits) - 1ull)) - 1;
-    if ((slot >> kMfSlotBits) == a.tag && q >= 0 && q < a.total) {
-      int32_t len = a.run_len[q];
-      len = len < 1 ? 1 : (len > a.total - q ? a.total - q : len);
-      const int32_t w = q / kBprWin, last = (q + len - 1) / kBprWin;
-      if (last == w) {
-        gg = *reinterpret_cast<const float4*>(a.compact + (size_t)q * a.F + c);
-      } else {
-        // bpr_carry_kernel's order: the piece in the window where the run begins, then the following windows' first
-        // pieces in window order, eight requested together
-        gg = *reinterpret_cast<const float4*>(a.partials + ((size_t)w * 2 + 1) * a.F + c);
-        const int32_t n_follow = last - w;
-        for (int32_t j0 = 0; j0 < n_follow; j0 += 8) {
-          float4 x[8];
-#pragma unroll
-          for (int t = 0; t < 8; ++t) {
-            const int32_t wj = w + 1 + (j0 + t < n_follow ? j0 + t : n_follow - 1);
-            x[t] = *reinterpret_cast<const float4*>(a.partials + ((size_t)wj * 2 + 0) * a.F + c);
-          }
-#pragma unroll
-          for (int t = 0; t < 8; ++t)
-            if (j0 + t < n_follow) { gg.x += x[t].x; gg.y += x[t].y; gg.z += x[t].z; gg.w += x[t].w; }
-        }
-      }
-    }
-    float4 pp = *reinterpret_cast<const float4*>(a.p + i);
-    float4 mm = *reinterpret_cast<const float4*>(a.m + i);
-    float4 vv = *reinterpret_cast<const float4*>(a.v + i);
-    adam_one(pp.x, gg.x, mm.x, vv.x, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
-    adam_one(pp.y, gg.y, mm.y, vv.y, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
-    adam_one(pp.z, gg.z, mm.z, vv.z, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
-    adam_one(pp.w, gg.w, mm.w, vv.w, w1, beta2, w2, a.step_size, a.bc2_sqrt, eps);
-    *reinterpret_cast<float4*>(a.p + i) = pp;
-    *reinterpret_cast<float4*>(a.m + i) = mm;
-    *reinterpret_cast<float4*>(a.v + i) = vv;
-  }
+    const int32_t q = row_tag_position<kMfSlotBits>(a.row_slot, row, a.tag, a.total);
+    if (q < 0) return zero4();
+    const int32_t w = q / kBprWin, last = (q + run_length(a.run_len, q, a.total) - 1) / kBprWin;
+    if (last == w) return *reinterpret_cast<const float4*>(a.compact + (size_t)q * a.F + c);
+    // bpr_carry_kernel's order: the piece in the window where the run begins, then the following windows' first pieces
+    // (every second row of the partials) in window order
+    return ordered_row_sum<8>(a.partials, 2 * (size_t)a.F, w + 1, last - w, c,
+                              *reinterpret_cast<const float4*>(a.partials + ((size_t)w * 2 + 1) * a.F + c));
+  });
 }
 
 // the iteration's workspace: per-sample partials (4 B floats) | coef (B) | the compact gradient rows (3 B x F) | the
@@ -797,19 +758,17 @@ int kgat_mf_adam_step_f32(int64_t n_nodes, int F, int64_t batch, const int32_t* 
   }
   KGAT_CHECK_ARG(u && p && n && sorted && emb && exp_avg && exp_avg_sq && loss && row_slot && workspace,
                  "mf_adam_step: null pointer");
-  KGAT_CHECK_ARG(step >= 1, "mf_adam_step: the step count after this step must be >= 1");
-  KGAT_CHECK_ARG(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "mf_adam_step: bad hyperparameter");
-  KGAT_CHECK_ARG(tag >= 1 && tag < (1ull << (64 - kMfSlotBits)), "mf_adam_step: tag must be in [1, 2^47)");
-  KGAT_CHECK_ARG(aligned16(emb) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(sorted) && aligned16(workspace),
-                 "mf_adam_step: the table, its moments, the sorted block and the workspace must be 16-byte aligned");
+  KGAT_RETURN_IF(row_tag_check<kMfSlotBits>("mf_adam_step", tag));
+  MfAdamArgs ad;
+  const int64_t n_elem = n_nodes * F;
+  KGAT_RETURN_IF(adam_fill("mf_adam_step", ad.t, 1, &n_elem, &emb, &exp_avg, &exp_avg_sq, &step, lr, beta1, beta2, eps, true));
+  KGAT_CHECK_ARG(aligned16(sorted) && aligned16(workspace),
+                 "mf_adam_step: the sorted block and the workspace must be 16-byte aligned");
   const MfStepWorkspace w = mf_step_workspace(workspace, batch, F);
   if (workspace_bytes < w.bytes) {
     set_error("mf_adam_step: workspace too small");
     return KGAT_E_WORKSPACE;
   }
-  const int64_t n_elem = n_nodes * F;
-  const int64_t adam_blocks = (n_elem + 4095) / 4096;
-  KGAT_CHECK_ARG(adam_blocks < ((int64_t)1 << 31), "mf_adam_step: too many elements");
   hipStream_t st = as_stream(stream);
   const MfSortedLayout lay = mf_sorted_layout(batch);
   const unsigned char* blk = static_cast<const unsigned char*>(sorted);
@@ -831,13 +790,9 @@ int kgat_mf_adam_step_f32(int64_t n_nodes, int F, int64_t batch, const int32_t* 
   a.tag_blocks = (int)((3 * batch + 255) / 256);
   hipLaunchKernelGGL(mf_window_kernel, dim3((unsigned)(a.win_blocks + a.tag_blocks + 1)), dim3(256), 0, st, a);
   KGAT_CHECK_LAUNCH("mf_window");
-  MfAdamArgs ad;
-  ad.p = emb; ad.m = exp_avg; ad.v = exp_avg_sq; ad.n = n_elem; ad.F = F; ad.total = (int32_t)(3 * batch);
+  ad.F = F; ad.total = (int32_t)(3 * batch);
   ad.row_slot = a.row_slot; ad.tag = a.tag; ad.compact = w.compact; ad.partials = w.win_part; ad.run_len = run_len;
-  // torch.optim.adam: python floats (double), then fp32 in the kernels (as kgat_adam_step_f32)
-  ad.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
-  ad.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-  hipLaunchKernelGGL(mf_adam_kernel, dim3((unsigned)adam_blocks), dim3(256), 0, st, ad, (float)(1.0 - beta1), (float)beta2,
+  hipLaunchKernelGGL(mf_adam_kernel, dim3((unsigned)ad.t.first_block[1]), dim3(256), 0, st, ad, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps);
   KGAT_CHECK_LAUNCH("mf_adam");
   return KGAT_OK;

@@ -37,4 +37,31 @@ inline TrSortedLayout transr_sorted_layout(int64_t batch, int n_rel) {
   return l;
 }
 
+// the pieces of one block as typed pointers: const for the iterations that read it, writable for the presort
+template <typename I, typename I2>
+struct KgSortedT {
+  I *order, *seg, *chunk_ptr;
+  I2* chunks;
+  I *sorted_ids, *row_order, *inv_pos, *run_len;
+};
+using KgSorted = KgSortedT<const int32_t, const int2>;
+using KgSortedOut = KgSortedT<int32_t, int2>;
+
+template <typename I, typename I2, typename Byte>
+__host__ __device__ inline KgSortedT<I, I2> kg_sorted_at(Byte* blk, const TrSortedLayout& lay) {
+  KgSortedT<I, I2> s;
+  s.order = reinterpret_cast<I*>(blk + lay.order);
+  s.seg = reinterpret_cast<I*>(blk + lay.seg);
+  s.chunk_ptr = reinterpret_cast<I*>(blk + lay.chunk_ptr);
+  s.chunks = reinterpret_cast<I2*>(blk + lay.chunks);
+  s.sorted_ids = reinterpret_cast<I*>(blk + lay.sorted_ids);
+  s.row_order = reinterpret_cast<I*>(blk + lay.row_order);
+  s.inv_pos = reinterpret_cast<I*>(blk + lay.inv_pos);
+  s.run_len = reinterpret_cast<I*>(blk + lay.run_len);
+  return s;
+}
+inline KgSorted kg_sorted(const void* block, int64_t batch, int n_rel) {
+  return kg_sorted_at<const int32_t, const int2>(static_cast<const unsigned char*>(block), transr_sorted_layout(batch, n_rel));
+}
+
 }  // namespace kgat

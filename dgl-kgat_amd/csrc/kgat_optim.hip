@@ -16,25 +16,17 @@
 // 4,096-element chunk, one workgroup adds the chunk sums in double and writes the fp32 norm and clip coefficient to
 // device memory, and the Adam launch multiplies each gradient element by that coefficient in the register it already
 // holds.  The order of additions is fixed (no float atomics), the coefficient never visits the host.
-#include "kgat_adam_common.h"
+#include "kgat_step_common.h"
 
 #include <math.h>
 
 namespace kgat {
 
 constexpr int kAdamMaxTensors = 16;
-constexpr int kAdamChunk = 4096;  // elements per workgroup: 256 threads x 4 float4
 
 struct AdamArgs {
-  float* p[kAdamMaxTensors];
+  AdamTensors<kAdamMaxTensors> t;   // (kgat_step_common.h)
   float* g[kAdamMaxTensors];
-  float* m[kAdamMaxTensors];
-  float* v[kAdamMaxTensors];
-  int64_t n[kAdamMaxTensors];
-  int first_block[kAdamMaxTensors + 1];
-  float step_size[kAdamMaxTensors];   // lr / (1 - beta1^t)
-  float bc2_sqrt[kAdamMaxTensors];    // sqrt(1 - beta2^t)
-  int count;
 };
 
 // kClip: every gradient element is first multiplied by the device scalar *coef (a product with its own rounding, as
@@ -46,14 +38,14 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, float w1, float b
   float c = 1.0f;
   if constexpr (kClip) c = *coef;
   int t = 0;
-  while (t + 1 < a.count && (int)blockIdx.x >= a.first_block[t + 1]) ++t;
-  const int64_t base = (int64_t)(blockIdx.x - a.first_block[t]) * kAdamChunk;
-  float* __restrict__ p = a.p[t];
+  while (t + 1 < a.t.count && (int)blockIdx.x >= a.t.first_block[t + 1]) ++t;
+  const int64_t base = (int64_t)(blockIdx.x - a.t.first_block[t]) * kAdamChunk;
+  float* __restrict__ p = a.t.p[t];
   float* __restrict__ g = a.g[t];
-  float* __restrict__ m = a.m[t];
-  float* __restrict__ v = a.v[t];
-  const int64_t n = a.n[t];
-  const float ss = a.step_size[t], bs = a.bc2_sqrt[t];
+  float* __restrict__ m = a.t.m[t];
+  float* __restrict__ v = a.t.v[t];
+  const int64_t n = a.t.n[t];
+  const float ss = a.t.step_size[t], bs = a.t.bc2_sqrt[t];
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                      reinterpret_cast<uintptr_t>(v)) & 15) == 0;
 #pragma unroll
@@ -61,18 +53,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, float w1, float b
     const int64_t i = base + (int64_t)k * 1024 + threadIdx.x * 4;
     if (i >= n) break;
     if (vec && i + 4 <= n) {
-      float4 pp = *reinterpret_cast<const float4*>(p + i);
       float4 gg = *reinterpret_cast<const float4*>(g + i);
       if constexpr (kClip) { gg.x = gg.x * c; gg.y = gg.y * c; gg.z = gg.z * c; gg.w = gg.w * c; }
-      float4 mm = *reinterpret_cast<const float4*>(m + i);
-      float4 vv = *reinterpret_cast<const float4*>(v + i);
-      adam_one(pp.x, gg.x, mm.x, vv.x, w1, beta2, w2, ss, bs, eps);
-      adam_one(pp.y, gg.y, mm.y, vv.y, w1, beta2, w2, ss, bs, eps);
-      adam_one(pp.z, gg.z, mm.z, vv.z, w1, beta2, w2, ss, bs, eps);
-      adam_one(pp.w, gg.w, mm.w, vv.w, w1, beta2, w2, ss, bs, eps);
-      *reinterpret_cast<float4*>(p + i) = pp;
-      *reinterpret_cast<float4*>(m + i) = mm;
-      *reinterpret_cast<float4*>(v + i) = vv;
+      adam_four(p, m, v, i, gg, w1, beta2, w2, ss, bs, eps);
       if (zero_grads) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
       for (int64_t j = i; j < i + 4 && j < n; ++j) {
@@ -199,36 +182,20 @@ int adam_step(const char* what, int n_tensors, const int64_t* sizes_host, float*
               float* const* grads_host, float* const* exp_avg_host, float* const* exp_avg_sq_host,
               const int64_t* steps_host, double lr, double beta1, double beta2, double eps, int zero_grads, bool clip,
               const float* grad_coef, kgat_stream_t stream) {
-  KGAT_CHECK_ARG(n_tensors >= 0 && n_tensors <= kAdamMaxTensors, "%s: %d tensors (at most %d per call)", what,
-                 n_tensors, kAdamMaxTensors);
   KGAT_CHECK_ARG(!clip || grad_coef, "%s: null grad_coef", what);
   if (n_tensors == 0) return KGAT_OK;
   KGAT_CHECK_ARG(sizes_host && params_host && grads_host && exp_avg_host && exp_avg_sq_host && steps_host,
                  "%s: null pointer", what);
-  KGAT_CHECK_ARG(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "%s: bad hyperparameter", what);
   AdamArgs a;
-  a.count = 0;
-  int blocks = 0;
-  for (int t = 0; t < n_tensors; ++t) {
-    KGAT_CHECK_ARG(sizes_host[t] >= 0 && steps_host[t] >= 1, "%s: tensor %d: bad size or step", what, t);
-    if (sizes_host[t] == 0) continue;
-    KGAT_CHECK_ARG(params_host[t] && grads_host[t] && exp_avg_host[t] && exp_avg_sq_host[t],
-                   "%s: tensor %d: null pointer", what, t);
-    const int c = a.count++;
-    a.p[c] = params_host[t]; a.g[c] = grads_host[t]; a.m[c] = exp_avg_host[t]; a.v[c] = exp_avg_sq_host[t];
-    a.n[c] = sizes_host[t];
-    a.first_block[c] = blocks;
-    const int64_t nb = (sizes_host[t] + kAdamChunk - 1) / kAdamChunk;
-    KGAT_CHECK_ARG(nb + blocks < (int64_t)1 << 31, "%s: too many elements", what);
-    blocks += (int)nb;
-    // torch.optim.adam._single_tensor_adam / _multi_tensor_adam: python floats (double), then fp32 in the kernels
-    const double bc1 = 1.0 - pow(beta1, (double)steps_host[t]);
-    const double bc2 = 1.0 - pow(beta2, (double)steps_host[t]);
-    a.step_size[c] = (float)(lr / bc1);
-    a.bc2_sqrt[c] = (float)sqrt(bc2);
+  int kept[kAdamMaxTensors];
+  KGAT_RETURN_IF(adam_fill(what, a.t, n_tensors, sizes_host, params_host, exp_avg_host, exp_avg_sq_host, steps_host, lr, beta1,
+                           beta2, eps, false, kept));
+  for (int c = 0; c < a.t.count; ++c) {
+    KGAT_CHECK_ARG(grads_host[kept[c]], "%s: tensor %d: null pointer", what, kept[c]);
+    a.g[c] = grads_host[kept[c]];
   }
-  if (a.count == 0) return KGAT_OK;
-  a.first_block[a.count] = blocks;
+  if (a.t.count == 0) return KGAT_OK;
+  const int blocks = a.t.first_block[a.t.count];
   if (clip)
     hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a,
                        (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, zero_grads, grad_coef);

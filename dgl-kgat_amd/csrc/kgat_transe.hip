@@ -23,8 +23,8 @@
 // halves followed by a dense Adam step.  All arithmetic fp32 on the vector ALU.
 #include <math.h>
 
-#include "kgat_adam_common.h"
 #include "kgat_kg_sorted.h"
+#include "kgat_step_common.h"
 
 namespace kgat {
 
@@ -53,26 +53,6 @@ static TeScratch transe_scratch(void* base, int64_t batch, int d, int n_rel) {
   return s;
 }
 
-// the pieces of a presort block
-struct TeSorted {
-  const int32_t *order, *seg, *chunk_ptr;
-  const int2* chunks;
-  const int32_t *sorted_ids, *inv_pos, *run_len;
-};
-static TeSorted transe_sorted(const void* block, int64_t batch, int n_rel) {
-  const TrSortedLayout lay = transr_sorted_layout(batch, n_rel);
-  const unsigned char* blk = static_cast<const unsigned char*>(block);
-  TeSorted s;
-  s.order = reinterpret_cast<const int32_t*>(blk + lay.order);
-  s.seg = reinterpret_cast<const int32_t*>(blk + lay.seg);
-  s.chunk_ptr = reinterpret_cast<const int32_t*>(blk + lay.chunk_ptr);
-  s.chunks = reinterpret_cast<const int2*>(blk + lay.chunks);
-  s.sorted_ids = reinterpret_cast<const int32_t*>(blk + lay.sorted_ids);
-  s.inv_pos = reinterpret_cast<const int32_t*>(blk + lay.inv_pos);
-  s.run_len = reinterpret_cast<const int32_t*>(blk + lay.run_len);
-  return s;
-}
-
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
@@ -82,7 +62,6 @@ __device__ __forceinline__ float group_sum(float v) {
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
   return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
 }
-__device__ __forceinline__ int32_t clamp_i32(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct TeSampleArgs {
   int32_t batch, n_rel;
@@ -91,7 +70,7 @@ struct TeSampleArgs {
   const int32_t *h, *r, *pt, *nt;
   const float *ent, *rel;
   float lambda;
-  TeSorted so;
+  KgSorted so;
   float *losses, *GR, *DX;
   // the fused iteration: workgroups behind the samples' tag the batch's entity rows (NULL: none)
   unsigned long long* row_slot;
@@ -109,12 +88,8 @@ template <int G>
 __global__ __launch_bounds__(256) void transe_sample_kernel(TeSampleArgs a) {
   const int32_t B = a.batch;
   if ((int)blockIdx.x >= a.sample_blocks) {
-    // one thread per sorted position: the first of a run of a real row writes call tag << 14 | position + 1
-    const int32_t q = ((int)blockIdx.x - a.sample_blocks) * 256 + (int)threadIdx.x;
-    if (q < 3 * B && a.so.run_len[q] > 0) {
-      const int32_t key = a.so.sorted_ids[q];
-      if ((uint64_t)(uint32_t)key < (uint64_t)a.n_nodes) a.row_slot[key] = (a.tag << kTrSlotBits) | (unsigned long long)(q + 1);
-    }
+    row_tag_write<kTrSlotBits>(a.row_slot, a.tag, ((int)blockIdx.x - a.sample_blocks) * 256 + (int)threadIdx.x, 3 * B,
+                               a.so.run_len, a.so.sorted_ids, a.n_nodes);
     return;
   }
   constexpr int SPB = 256 / G;   // samples per workgroup
@@ -188,53 +163,16 @@ __global__ __launch_bounds__(256) void transe_sample_kernel(TeSampleArgs a) {
   }
 }
 
-// rows [q, q + len) of `rows` (d floats each), columns [c, c + 4), added one after the other from 0, eight requested
-// per look: THE order of every run sum and chunk sum of this file
-__device__ __forceinline__ float4 transe_row_sum(const float* __restrict__ rows, int64_t q, int32_t len, int d, int c) {
-  float4 acc = zero4();
-  const float* src = rows + (size_t)q * d + c;
-  for (int32_t t0 = 0; t0 < len; t0 += 8) {
-    float4 v[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = *reinterpret_cast<const float4*>(src + (size_t)(t0 + t < len ? t0 + t : len - 1) * d);
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-      if (t0 + t < len) acc = add4(acc, v[t]);
-  }
-  return acc;
-}
-
-// the gradient of relation r, columns [c, c + 4): its chunk rows in chunk order
-__device__ __forceinline__ float4 transe_rel_sum(const float* __restrict__ part, const int32_t* __restrict__ chunk_ptr,
-                                                 int n_part, int64_t r, int d, int c) {
-  const int32_t first = clamp_i32(chunk_ptr[r], 0, n_part);
-  const int32_t n_mine = clamp_i32(chunk_ptr[r + 1], first, n_part) - first;
-  return transe_row_sum(part, first, n_mine, d, c);
-}
-
-// the gradient of the entity whose run starts at sorted position q
-__device__ __forceinline__ float4 transe_run_sum(const float* __restrict__ DX, const int32_t* __restrict__ run_len,
-                                                 int32_t q, int32_t total, int d, int c) {
-  return transe_row_sum(DX, q, clamp_i32(run_len[q], 1, total - q), d, c);
-}
+constexpr int kTeLook = 8;   // rows requested per look of every run sum and chunk sum of this file (ordered_row_sum)
 
 // ---- second launch: wavefront w of the grid sums chunk w of the presort's chunk table (<= 64 relation-sorted rows of
 // GR); the last workgroup reduces the loss - the sums of 256 threads, then a tree over them: a fixed order
 __global__ __launch_bounds__(256) void transe_partial_kernel(int part_blocks, int n_part, int32_t batch, int d, int n_rel,
-                                                             TeSorted so, const float* __restrict__ GR,
+                                                             KgSorted so, const float* __restrict__ GR,
                                                              float* __restrict__ part, const float* __restrict__ losses,
                                                              float* __restrict__ loss) {
   if ((int)blockIdx.x >= part_blocks) {
-    __shared__ float s_l[256];
-    float v = 0.f;
-    for (int32_t s = threadIdx.x; s < batch; s += 256) v += losses[s];
-    s_l[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if ((int)threadIdx.x < off) s_l[threadIdx.x] += s_l[threadIdx.x + off];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = s_l[0] / (float)batch;
+    loss_mean_256(losses, batch, loss);
     return;
   }
   const int lane = threadIdx.x & 63;
@@ -245,13 +183,13 @@ __global__ __launch_bounds__(256) void transe_partial_kernel(int part_blocks, in
   const int32_t beg = clamp_i32(e.y, 0, batch), seg_end = clamp_i32(so.seg[rel + 1], beg, batch);
   const int32_t end = beg + kTrChunk < seg_end ? beg + kTrChunk : seg_end;
   const int c = 4 * lane;
-  if (c < d) *reinterpret_cast<float4*>(part + (size_t)ck * d + c) = transe_row_sum(GR, beg, end - beg, d, c);
+  if (c < d) *reinterpret_cast<float4*>(part + (size_t)ck * d + c) = ordered_row_sum<kTeLook>(GR, (size_t)d, beg, end - beg, c);
 }
 
 // ---- the dense gradients (the backward half; grad_ent zeroed by the memset in front): thread t < n_rel d / 4 one
 // 16-byte piece of grad_rel, the threads behind them one piece of the run that starts at a sorted position
 __global__ __launch_bounds__(256) void transe_grad_kernel(int32_t batch, int64_t n_nodes, int d, int n_rel, int n_part,
-                                                          TeSorted so, const float* __restrict__ DX,
+                                                          KgSorted so, const float* __restrict__ DX,
                                                           const float* __restrict__ part,
                                                           const float* __restrict__ grad_scale,
                                                           float* __restrict__ grad_ent, float* __restrict__ grad_rel) {
@@ -263,7 +201,7 @@ __global__ __launch_bounds__(256) void transe_grad_kernel(int32_t batch, int64_t
   if (t < n_rel_t) {
     const int64_t r = t / d4;
     const int c = 4 * (int)(t - r * d4);
-    v = transe_rel_sum(part, so.chunk_ptr, n_part, r, d, c);
+    v = chunk_sum<kTeLook>(part, (size_t)d, so.chunk_ptr, n_part, r, c);
     dst = grad_rel + (size_t)r * d + c;
   } else {
     const int64_t e = t - n_rel_t;
@@ -272,7 +210,7 @@ __global__ __launch_bounds__(256) void transe_grad_kernel(int32_t batch, int64_t
     const int32_t id = so.sorted_ids[q];
     if ((uint64_t)(uint32_t)id >= (uint64_t)n_nodes) return;
     const int c = 4 * (int)(e - (int64_t)q * d4);
-    v = transe_run_sum(DX, so.run_len, q, 3 * batch, d, c);
+    v = run_sum<kTeLook>(DX, so.run_len, q, 3 * batch, d, c);
     dst = grad_ent + (size_t)id * d + c;
   }
   if (grad_scale) {   // the gradient arriving at the loss (device scalar)
@@ -283,13 +221,9 @@ __global__ __launch_bounds__(256) void transe_grad_kernel(int32_t batch, int64_t
 }
 
 // ---- third launch of the fused iteration: Adam over the entity table (gradient through row_slot) and the relation
-// table (gradient = the ordered sum of the relation's chunk rows).  4,096 elements per workgroup, 16 bytes per lane
-// and stream, as adam_kernel.
+// table (gradient = the ordered sum of the relation's chunk rows): adam_chunk_walk.
 struct TeAdamArgs {
-  float *p[2], *m[2], *v[2];   // entity table, relation table
-  int64_t n[2];
-  int first_block[2];
-  float step_size[2], bc2_sqrt[2];
+  AdamTensors<2> t;   // entity table, relation table
   int d, n_part;
   int32_t total;   // 3 B
   const unsigned long long* row_slot;
@@ -299,36 +233,17 @@ struct TeAdamArgs {
 };
 
 __global__ __launch_bounds__(256) void transe_adam_kernel(TeAdamArgs a, float w1, float beta2, float w2, float eps) {
-  const int t = (int)blockIdx.x >= a.first_block[1] ? 1 : 0;
-  const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[t]) * 4096;
-  float* __restrict__ p = a.p[t];
-  float* __restrict__ m = a.m[t];
-  float* __restrict__ v = a.v[t];
-  const float ss = a.step_size[t], bs = a.bc2_sqrt[t];
-#pragma unroll
-  for (int q4 = 0; q4 < 4; ++q4) {
-    const int64_t i = base + (int64_t)q4 * 1024 + threadIdx.x * 4;
-    if (i >= a.n[t]) break;   // (n is a multiple of 4: d is)
-    const int64_t row = i / a.d;
-    const int c = (int)(i - row * a.d);
-    float4 gg = zero4();
-    if (t == 0) {
-      const unsigned long long slot = a.row_slot[row];
-      const int32_t q = (int32_t)(slot & ((1ull << kTrSlotBits) - 1ull)) - 1;
-      if ((slot >> kTrSlotBits) == a.tag && q >= 0 && q < a.total) gg = transe_run_sum(a.DX, a.run_len, q, a.total, a.d, c);
-    } else {
-      gg = transe_rel_sum(a.part, a.chunk_ptr, a.n_part, row, a.d, c);
-    }
-    float4 pp = *reinterpret_cast<const float4*>(p + i);
-    float4 mm = *reinterpret_cast<const float4*>(m + i);
-    float4 vv = *reinterpret_cast<const float4*>(v + i);
-    adam_one(pp.x, gg.x, mm.x, vv.x, w1, beta2, w2, ss, bs, eps);
-    adam_one(pp.y, gg.y, mm.y, vv.y, w1, beta2, w2, ss, bs, eps);
-    adam_one(pp.z, gg.z, mm.z, vv.z, w1, beta2, w2, ss, bs, eps);
-    adam_one(pp.w, gg.w, mm.w, vv.w, w1, beta2, w2, ss, bs, eps);
-    *reinterpret_cast<float4*>(p + i) = pp;
-    *reinterpret_cast<float4*>(m + i) = mm;
-    *reinterpret_cast<float4*>(v + i) = vv;
+  if ((int)blockIdx.x < a.t.first_block[1]) {
+    adam_chunk_walk(a.t, 0, w1, beta2, w2, eps, [&](int64_t i) {
+      const int64_t row = i / a.d;
+      const int32_t q = row_tag_position<kTrSlotBits>(a.row_slot, row, a.tag, a.total);
+      return q < 0 ? zero4() : run_sum<kTeLook>(a.DX, a.run_len, q, a.total, a.d, (int)(i - row * a.d));
+    });
+  } else {
+    adam_chunk_walk(a.t, 1, w1, beta2, w2, eps, [&](int64_t i) {
+      const int64_t row = i / a.d;
+      return chunk_sum<kTeLook>(a.part, (size_t)a.d, a.chunk_ptr, a.n_part, row, (int)(i - row * a.d));
+    });
   }
 }
 
@@ -336,7 +251,7 @@ __global__ __launch_bounds__(256) void transe_adam_kernel(TeAdamArgs a, float w1
 // sums + the loss.
 static int transe_launch_forward(const char* who, int64_t n_nodes, int n_rel, int d, int64_t batch, const int32_t* h,
                                  const int32_t* r, const int32_t* pos_t, const int32_t* neg_t, const float* ent,
-                                 const float* rel, float reg_lambda, float* loss, const TeSorted& so, const TeScratch& w,
+                                 const float* rel, float reg_lambda, float* loss, const KgSorted& so, const TeScratch& w,
                                  unsigned long long* row_slot, unsigned long long tag, hipStream_t st) {
   const int32_t B = (int32_t)batch;
   const int G = d <= 64 ? 16 : (d <= 128 ? 32 : 64);
@@ -364,7 +279,7 @@ static int transe_launch_forward(const char* who, int64_t n_nodes, int n_rel, in
   return KGAT_OK;
 }
 
-static int transe_launch_backward(const char* who, int64_t n_nodes, int n_rel, int d, int64_t batch, const TeSorted& so,
+static int transe_launch_backward(const char* who, int64_t n_nodes, int n_rel, int d, int64_t batch, const KgSorted& so,
                                   const TeScratch& w, const float* grad_scale, float* grad_ent, float* grad_rel,
                                   hipStream_t st) {
   if (hipMemsetAsync(grad_ent, 0, (size_t)n_nodes * d * sizeof(float), st) != hipSuccess) {
@@ -451,7 +366,7 @@ int kgat_transe_forward_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, co
   const int rc = kgat_transr_presort_f32(n_nodes, n_rel, 1, batch, h, r, pos_t, neg_t, w.sorted, block, stream);
   if (rc != KGAT_OK) return rc;
   return transe_launch_forward("transe_forward", n_nodes, n_rel, d, batch, h, r, pos_t, neg_t, ent, rel, reg_lambda, loss,
-                               transe_sorted(w.sorted, batch, n_rel), w, nullptr, 0ull, as_stream(stream));
+                               kg_sorted(w.sorted, batch, n_rel), w, nullptr, 0ull, as_stream(stream));
 }
 
 int kgat_transe_backward_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, const int32_t* h, const int32_t* r,
@@ -461,7 +376,7 @@ int kgat_transe_backward_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, c
   KGAT_CHECK_ARG(grad_ent && grad_rel, "transe_backward: null gradient pointer");
   KGAT_CHECK_ARG(aligned16(grad_ent) && aligned16(grad_rel), "transe_backward: the gradients must be 16-byte aligned");
   const TeScratch w = transe_scratch(scratch, batch, d, n_rel);
-  return transe_launch_backward("transe_backward", n_nodes, n_rel, d, batch, transe_sorted(w.sorted, batch, n_rel), w, grad_scale,
+  return transe_launch_backward("transe_backward", n_nodes, n_rel, d, batch, kg_sorted(w.sorted, batch, n_rel), w, grad_scale,
                                 grad_ent, grad_rel, as_stream(stream));
 }
 
@@ -477,7 +392,7 @@ int kgat_transe_loss_grad_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, 
   const size_t block = transr_sorted_layout(batch, n_rel).bytes;
   int rc = kgat_transr_presort_f32(n_nodes, n_rel, 1, batch, h, r, pos_t, neg_t, w.sorted, block, stream);
   if (rc != KGAT_OK) return rc;
-  const TeSorted so = transe_sorted(w.sorted, batch, n_rel);
+  const KgSorted so = kg_sorted(w.sorted, batch, n_rel);
   rc = transe_launch_forward("transe_loss_grad", n_nodes, n_rel, d, batch, h, r, pos_t, neg_t, ent, rel, reg_lambda, loss, so, w,
                              nullptr, 0ull, as_stream(stream));
   if (rc != KGAT_OK) return rc;
@@ -493,32 +408,16 @@ int kgat_transe_adam_step_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, 
   KGAT_RETURN_IF(transe_check("transe_adam_step", n_nodes, n_rel, d, batch, h, r, pos_t, neg_t, scratch, scratch_bytes));
   KGAT_CHECK_ARG(sorted && ent && rel && exp_avg_host && exp_avg_sq_host && steps_host && loss && row_slot,
                  "transe_adam_step: null pointer");
-  KGAT_CHECK_ARG(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "transe_adam_step: bad hyperparameter");
-  KGAT_CHECK_ARG(tag >= 1 && tag < (1ull << (64 - kTrSlotBits)), "transe_adam_step: tag must be in [1, 2^50)");
+  KGAT_RETURN_IF(row_tag_check<kTrSlotBits>("transe_adam_step", tag));
   KGAT_CHECK_ARG(aligned16(sorted), "transe_adam_step: the sorted block must be 16-byte aligned");
-  float* const ps[2] = {ent, rel};
-  for (int t = 0; t < 2; ++t) {
-    KGAT_CHECK_ARG(exp_avg_host[t] && exp_avg_sq_host[t] && steps_host[t] >= 1, "transe_adam_step: tensor %d: bad state", t);
-    KGAT_CHECK_ARG(aligned16(ps[t]) && aligned16(exp_avg_host[t]) && aligned16(exp_avg_sq_host[t]),
-                   "transe_adam_step: tensor %d: parameters and moments must be 16-byte aligned", t);
-  }
   TeAdamArgs a;
+  float* const ps[2] = {ent, rel};
   const int64_t sizes[2] = {(int64_t)n_nodes * d, (int64_t)n_rel * d};
-  int blocks = 0;
-  for (int t = 0; t < 2; ++t) {
-    a.p[t] = ps[t]; a.m[t] = exp_avg_host[t]; a.v[t] = exp_avg_sq_host[t];
-    a.n[t] = sizes[t];
-    a.first_block[t] = blocks;
-    const int64_t nb = (sizes[t] + 4095) / 4096;
-    KGAT_CHECK_ARG(nb + blocks < (int64_t)1 << 31, "transe_adam_step: too many elements");
-    blocks += (int)nb;
-    // torch.optim.adam: python floats (double), then fp32 in the kernels (as kgat_adam_step_f32)
-    a.step_size[t] = (float)(lr / (1.0 - pow(beta1, (double)steps_host[t])));
-    a.bc2_sqrt[t] = (float)sqrt(1.0 - pow(beta2, (double)steps_host[t]));
-  }
+  KGAT_RETURN_IF(adam_fill("transe_adam_step", a.t, 2, sizes, ps, exp_avg_host, exp_avg_sq_host, steps_host, lr, beta1, beta2,
+                           eps, true));
   hipStream_t st = as_stream(stream);
   const TeScratch w = transe_scratch(scratch, batch, d, n_rel);
-  const TeSorted so = transe_sorted(sorted, batch, n_rel);
+  const KgSorted so = kg_sorted(sorted, batch, n_rel);
   const int rc = transe_launch_forward("transe_adam_step", n_nodes, n_rel, d, batch, h, r, pos_t, neg_t, ent, rel, reg_lambda,
                                        loss, so, w, reinterpret_cast<unsigned long long*>(row_slot), (unsigned long long)tag, st);
   if (rc != KGAT_OK) return rc;
@@ -526,7 +425,7 @@ int kgat_transe_adam_step_f32(int64_t n_nodes, int n_rel, int d, int64_t batch, 
   a.row_slot = reinterpret_cast<const unsigned long long*>(row_slot);
   a.tag = (unsigned long long)tag;
   a.DX = w.DX; a.part = w.part; a.run_len = so.run_len; a.chunk_ptr = so.chunk_ptr;
-  hipLaunchKernelGGL(transe_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, (float)(1.0 - beta1), (float)beta2,
+  hipLaunchKernelGGL(transe_adam_kernel, dim3((unsigned)a.t.first_block[2]), dim3(256), 0, st, a, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps);
   KGAT_CHECK_LAUNCH("transe_adam");
   return KGAT_OK;

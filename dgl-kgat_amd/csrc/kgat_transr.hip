@@ -19,9 +19,9 @@
 // and latency bound, not MFMA work.
 #include <math.h>
 
-#include "kgat_adam_common.h"
 #include "kgat_kg_sorted.h"
 #include "kgat_lds_sort.h"
+#include "kgat_step_common.h"
 
 namespace kgat {
 
@@ -175,6 +175,7 @@ struct TrStepMarks {
   unsigned long long* row_slot = nullptr;
   unsigned long long tag = 0ull;
   int sample_blocks = 0;
+  int64_t n_nodes = 0;
 };
 template <bool GRAD, bool WLDS>
 __global__ __launch_bounds__(256) void transr_sample_kernel(
@@ -183,13 +184,12 @@ __global__ __launch_bounds__(256) void transr_sample_kernel(
     const float* __restrict__ ent, const float* __restrict__ W_R, const float* __restrict__ rel, float lambda,
     float* __restrict__ losses, float* __restrict__ GA, float* __restrict__ GR, float* __restrict__ DX,
     float* __restrict__ XS, const TrStepMarks mk = TrStepMarks{}) {
-  // the KG phase's form (mk.inv_pos given): workgroups behind the samples' tag the batch's entity rows in row_slot -
-  // one thread per sorted position; the first of a run writes call tag << 14 | position + 1 - and the samples' DX rows
-  // go to their SORTED positions (a row's contributions are then consecutive: the Adam launch sums them itself)
+  // the KG phase's form (mk.inv_pos given): workgroups behind the samples' tag the batch's entity rows in row_slot
+  // (row_tag_write), and the samples' DX rows go to their SORTED positions (a row's contributions are then consecutive:
+  // the Adam launch sums them itself)
   if (mk.inv_pos != nullptr && (int)blockIdx.x >= mk.sample_blocks) {
-    const int32_t q = ((int)blockIdx.x - mk.sample_blocks) * 256 + (int)threadIdx.x;
-    if (q < 3 * batch && mk.run_len[q] > 0)
-      mk.row_slot[mk.sorted_ids[q]] = (mk.tag << kTrSlotBits) | (unsigned long long)(q + 1);
+    row_tag_write<kTrSlotBits>(mk.row_slot, mk.tag, ((int)blockIdx.x - mk.sample_blocks) * 256 + (int)threadIdx.x, 3 * batch,
+                               mk.run_len, mk.sorted_ids, mk.n_nodes);
     return;
   }
   __shared__ float s_x[256 / kWave][3][kTrMaxDim];
@@ -641,16 +641,7 @@ __device__ __forceinline__ void transr_reduce_body(int bx, int by, int ny, int32
   const int r = bx;
   if (r == n_rel) {
     if (loss == nullptr || by != 0) return;
-    __shared__ float s_l[256];
-    float v = 0.f;
-    for (int32_t s = threadIdx.x; s < batch; s += 256) v += losses[s];
-    s_l[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (threadIdx.x < off) s_l[threadIdx.x] += s_l[threadIdx.x + off];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = s_l[0] / (float)batch;
+    loss_mean_256(losses, batch, loss);
     return;
   }
   if (grad_W == nullptr) return;
@@ -833,18 +824,15 @@ template <typename PT>
 __global__ __launch_bounds__(kLdsSortThreads) void transr_presort_kernel(TrPresortArgs a) {
   const int32_t b = (int32_t)(blockIdx.x >> 1);
   if (b >= a.n_batches) return;
-  unsigned char* blk = a.sorted + (size_t)b * a.lay.bytes;
+  const KgSortedOut so = kg_sorted_at<int32_t, int2>(a.sorted + (size_t)b * a.lay.bytes, a.lay);
   const size_t o = (size_t)b * a.batch;
   SortJob job;
   if ((blockIdx.x & 1) == 0) {   // samples by relation (+ the chunk table of the weight-gradient partials)
-    job = SortJob{a.batch, a.rel_bits, a.r + o, nullptr, nullptr, reinterpret_cast<int32_t*>(blk + a.lay.order), nullptr,
-                  (int32_t)a.n_rel, reinterpret_cast<int32_t*>(blk + a.lay.seg),
-                  reinterpret_cast<int32_t*>(blk + a.lay.chunk_ptr), reinterpret_cast<int2*>(blk + a.lay.chunks)};
+    job = SortJob{a.batch, a.rel_bits, a.r + o, nullptr, nullptr, so.order, nullptr, (int32_t)a.n_rel, so.seg, so.chunk_ptr,
+                  so.chunks};
   } else {                       // the 3 B entity ids (head, positive tail, negative tail of every sample)
-    job = SortJob{3 * a.batch, a.id_bits, a.h + o, a.pos_t + o, a.neg_t + o,
-                  reinterpret_cast<int32_t*>(blk + a.lay.row_order), reinterpret_cast<int32_t*>(blk + a.lay.sorted_ids), 0,
-                  nullptr, nullptr, nullptr,
-                  reinterpret_cast<int32_t*>(blk + a.lay.inv_pos), reinterpret_cast<int32_t*>(blk + a.lay.run_len)};
+    job = SortJob{3 * a.batch, a.id_bits, a.h + o, a.pos_t + o, a.neg_t + o, so.row_order, so.sorted_ids, 0,
+                  nullptr, nullptr, nullptr, so.inv_pos, so.run_len};
   }
   small_sort_body<PT>(job);
 }
@@ -871,13 +859,12 @@ __global__ __launch_bounds__(256) void transr_wgrad_step_kernel(
 }
 
 // third launch: Adam over the entity table (gradient through row_slot), W_R and the relation table (gradient = the
-// ordered sum of the relation's partials).  4,096 elements per workgroup, 16 bytes per lane and stream, as adam_kernel.
+// ordered sum of the relation's partials, transr_reduce_body's order): adam_chunk_walk.
+constexpr int kTrLook = 4;   // rows requested per look of the run sums and the partial sums (ordered_row_sum)
 struct TrAdamArgs {
-  float *p[3], *m[3], *v[3];   // entity table, W_R, relation table
-  int64_t n[3];
-  int first_block[4];
-  float step_size[3], bc2_sqrt[3];
-  int d, k, dk;
+  AdamTensors<3> t;          // entity table, W_R, relation table
+  int d, k, dk, n_part;
+  int32_t total;             // 3 B
   const unsigned long long* row_slot;
   unsigned long long tag;
   const float* DXs;          // the samples' gradient rows at their sorted positions
@@ -887,68 +874,22 @@ struct TrAdamArgs {
 };
 
 __global__ __launch_bounds__(256) void transr_adam_kernel(TrAdamArgs a, float w1, float beta2, float w2, float eps) {
-  const int t = (int)blockIdx.x >= a.first_block[2] ? 2 : ((int)blockIdx.x >= a.first_block[1] ? 1 : 0);
-  const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[t]) * 4096;
-  float* __restrict__ p = a.p[t];
-  float* __restrict__ m = a.m[t];
-  float* __restrict__ v = a.v[t];
-  const int64_t n = a.n[t];
-  const float ss = a.step_size[t], bs = a.bc2_sqrt[t];
-  const int stride = a.dk + a.k;
-#pragma unroll
-  for (int q4 = 0; q4 < 4; ++q4) {
-    const int64_t i = base + (int64_t)q4 * 1024 + threadIdx.x * 4;
-    if (i >= n) break;   // (n is a multiple of 4: d and k are)
-    float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t == 0) {
+  if ((int)blockIdx.x < a.t.first_block[1]) {
+    // the row's gradient: its run of the sorted gradient rows, added in sorted order (transr_scatter_body's order)
+    adam_chunk_walk(a.t, 0, w1, beta2, w2, eps, [&](int64_t i) {
       const int64_t row = i / a.d;
-      const unsigned long long slot = a.row_slot[row];
-      if ((slot >> kTrSlotBits) == a.tag) {
-        // the row's gradient: its run of the sorted gradient rows, added in sorted order from 0 (transr_scatter_body's
-        // order), four rows requested per look (a hub entity heads dozens of samples of an edge-uniform batch)
-        const int64_t pr = (int64_t)(slot & ((1ull << kTrSlotBits) - 1ull)) - 1;
-        const int len = a.run_len[pr];
-        const float* src = a.DXs + pr * a.d + (i - row * a.d);
-        for (int q = 0; q < len; q += 4) {
-          float4 x[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const float4*>(src + (size_t)(q + u < len ? q + u : len - 1) * a.d);
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (q + u < len) { gg.x += x[u].x; gg.y += x[u].y; gg.z += x[u].z; gg.w += x[u].w; }
-        }
-      }
-    } else {
-      const int width = t == 1 ? a.dk : a.k;
-      const int64_t r = i / width;
-      const int e = (int)(i - r * width) + (t == 1 ? 0 : a.dk);
-      const int first = a.chunk_ptr[r], n_mine = a.chunk_ptr[r + 1] - first;
-      // transr_reduce_body's order: v = 0; v += partial, chunk after chunk.  Four partials are requested together (a
-      // load per iteration made the sum a chain of L2 round trips - ten for the most frequent relation at 32-sample
-      // chunks - at the tail of the launch); the additions stay in chunk order.
-      for (int q = 0; q < n_mine; q += 4) {
-        float4 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int qq = q + u < n_mine ? q + u : n_mine - 1;
-          x[u] = *reinterpret_cast<const float4*>(a.part + (size_t)(first + qq) * stride + e);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (q + u < n_mine) { gg.x += x[u].x; gg.y += x[u].y; gg.z += x[u].z; gg.w += x[u].w; }
-      }
-    }
-    float4 pp = *reinterpret_cast<const float4*>(p + i);
-    float4 mm = *reinterpret_cast<const float4*>(m + i);
-    float4 vv = *reinterpret_cast<const float4*>(v + i);
-    adam_one(pp.x, gg.x, mm.x, vv.x, w1, beta2, w2, ss, bs, eps);
-    adam_one(pp.y, gg.y, mm.y, vv.y, w1, beta2, w2, ss, bs, eps);
-    adam_one(pp.z, gg.z, mm.z, vv.z, w1, beta2, w2, ss, bs, eps);
-    adam_one(pp.w, gg.w, mm.w, vv.w, w1, beta2, w2, ss, bs, eps);
-    *reinterpret_cast<float4*>(p + i) = pp;
-    *reinterpret_cast<float4*>(m + i) = mm;
-    *reinterpret_cast<float4*>(v + i) = vv;
+      const int32_t q = row_tag_position<kTrSlotBits>(a.row_slot, row, a.tag, a.total);
+      return q < 0 ? zero4() : run_sum<kTrLook>(a.DXs, a.run_len, q, a.total, a.d, (int)(i - row * a.d));
+    });
+    return;
   }
+  // a partial row is a chunk's d k elements of W_R's gradient, then its k of the relation table's
+  const int t = (int)blockIdx.x >= a.t.first_block[2] ? 2 : 1;
+  const int width = t == 1 ? a.dk : a.k, col0 = t == 1 ? 0 : a.dk;
+  adam_chunk_walk(a.t, t, w1, beta2, w2, eps, [&](int64_t i) {
+    const int64_t r = i / width;
+    return chunk_sum<kTrLook>(a.part, (size_t)(a.dk + a.k), a.chunk_ptr, a.n_part, r, (int)(i - r * width) + col0);
+  });
 }
 
 // ---- the workspaces.  Each is described once, as the carve of its pieces from `base`; over a null base the carve
@@ -1203,15 +1144,12 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
   }
   KGAT_CHECK_ARG(h && r && pos_t && neg_t && sorted && ent && W_R && rel && exp_avg_host && exp_avg_sq_host && steps_host &&
                      loss && row_slot && workspace, "transr_adam_step: null pointer");
-  KGAT_CHECK_ARG(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "transr_adam_step: bad hyperparameter");
-  KGAT_CHECK_ARG(tag >= 1 && tag < (1ull << (64 - kTrSlotBits)), "transr_adam_step: tag must be in [1, 2^50)");
+  KGAT_RETURN_IF(row_tag_check<kTrSlotBits>("transr_adam_step", tag));
+  TrAdamArgs a;
   float* const ps[3] = {ent, W_R, rel};
-  for (int t = 0; t < 3; ++t) {
-    KGAT_CHECK_ARG(exp_avg_host[t] && exp_avg_sq_host[t] && steps_host[t] >= 1, "transr_adam_step: tensor %d: bad state", t);
-    KGAT_CHECK_ARG(((reinterpret_cast<uintptr_t>(ps[t]) | reinterpret_cast<uintptr_t>(exp_avg_host[t]) |
-                     reinterpret_cast<uintptr_t>(exp_avg_sq_host[t])) & 15) == 0,
-                   "transr_adam_step: tensor %d: parameters and moments must be 16-byte aligned", t);
-  }
+  const int64_t sizes[3] = {(int64_t)n_nodes * d, (int64_t)n_rel * d * k, (int64_t)n_rel * k};
+  KGAT_RETURN_IF(adam_fill("transr_adam_step", a.t, 3, sizes, ps, exp_avg_host, exp_avg_sq_host, steps_host, lr, beta1, beta2,
+                           eps, true));
   const TrStepWorkspace w = transr_step_workspace(workspace, batch, d, k, n_rel);
   const TrSampleArrays& ws = w.s;
   if (workspace_bytes < w.bytes) {
@@ -1221,19 +1159,11 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
   hipStream_t st = as_stream(stream);
   const int32_t B = (int32_t)batch;
   const int n_part = ws.n_part;
-  const TrSortedLayout lay = transr_sorted_layout(batch, n_rel);
-  const unsigned char* blk = static_cast<const unsigned char*>(sorted);
-  const int32_t* order = reinterpret_cast<const int32_t*>(blk + lay.order);
-  const int32_t* seg = reinterpret_cast<const int32_t*>(blk + lay.seg);
-  const int32_t* chunk_ptr = reinterpret_cast<const int32_t*>(blk + lay.chunk_ptr);
-  const int2* chunks = reinterpret_cast<const int2*>(blk + lay.chunks);
-  const int32_t* sorted_ids = reinterpret_cast<const int32_t*>(blk + lay.sorted_ids);
-  const int32_t* inv_pos = reinterpret_cast<const int32_t*>(blk + lay.inv_pos);
-  const int32_t* run_len = reinterpret_cast<const int32_t*>(blk + lay.run_len);
+  const KgSorted so = kg_sorted(sorted, batch, n_rel);
   const unsigned sb = (unsigned)((B + 3) / 4), mark_blocks = (unsigned)((3 * B + 255) / 256);
-  const TrStepMarks mk = {inv_pos, sorted_ids, run_len, reinterpret_cast<unsigned long long*>(row_slot),
-                          (unsigned long long)tag, (int)sb};
-  transr_launch_sample(true, sb + mark_blocks, st, B, d, k, order, h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda, ws, mk);
+  const TrStepMarks mk = {so.inv_pos, so.sorted_ids, so.run_len, reinterpret_cast<unsigned long long*>(row_slot),
+                          (unsigned long long)tag, (int)sb, n_nodes};
+  transr_launch_sample(true, sb + mark_blocks, st, B, d, k, so.order, h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda, ws, mk);
   KGAT_CHECK_LAUNCH("transr_sample");
   const size_t lds = transr_stage_bytes(d, k);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(transr_wgrad_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1243,29 +1173,14 @@ int kgat_transr_adam_step_f32(int64_t n_nodes, int n_rel, int d, int k, int64_t 
   }
   const int n_split = (d % 16 == 0 && k % 16 == 0) ? (d / 16 < 4 ? d / 16 : 4) : 1;
   hipLaunchKernelGGL(transr_wgrad_step_kernel, dim3((unsigned)(n_part * n_split + 1)), dim3(256), lds, st, n_part, n_split, B,
-                     d, k, n_rel, seg, (const float*)ws.XS, (const float*)ws.GA, (const float*)ws.GR, chunk_ptr, chunks,
+                     d, k, n_rel, so.seg, (const float*)ws.XS, (const float*)ws.GA, (const float*)ws.GR, so.chunk_ptr, so.chunks,
                      ws.part, (const float*)ws.losses, loss, transr_stage_geom(d, k));
   KGAT_CHECK_LAUNCH("transr_wgrad_step");
-  TrAdamArgs a;
-  const int64_t sizes[3] = {(int64_t)n_nodes * d, (int64_t)n_rel * d * k, (int64_t)n_rel * k};
-  int blocks = 0;
-  for (int t = 0; t < 3; ++t) {
-    a.p[t] = ps[t]; a.m[t] = exp_avg_host[t]; a.v[t] = exp_avg_sq_host[t];
-    a.n[t] = sizes[t];
-    a.first_block[t] = blocks;
-    const int64_t nb = (sizes[t] + 4095) / 4096;
-    KGAT_CHECK_ARG(nb + blocks < (int64_t)1 << 31, "transr_adam_step: too many elements");
-    blocks += (int)nb;
-    // torch.optim.adam: python floats (double), then fp32 in the kernels (as kgat_adam_step_f32)
-    a.step_size[t] = (float)(lr / (1.0 - pow(beta1, (double)steps_host[t])));
-    a.bc2_sqrt[t] = (float)sqrt(1.0 - pow(beta2, (double)steps_host[t]));
-  }
-  a.first_block[3] = blocks;
-  a.d = d; a.k = k; a.dk = d * k;
+  a.d = d; a.k = k; a.dk = d * k; a.n_part = n_part; a.total = 3 * B;
   a.row_slot = reinterpret_cast<const unsigned long long*>(row_slot);
   a.tag = (unsigned long long)tag;
-  a.DXs = ws.DX; a.run_len = run_len; a.part = ws.part; a.chunk_ptr = chunk_ptr;
-  hipLaunchKernelGGL(transr_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, (float)(1.0 - beta1), (float)beta2,
+  a.DXs = ws.DX; a.run_len = so.run_len; a.part = ws.part; a.chunk_ptr = so.chunk_ptr;
+  hipLaunchKernelGGL(transr_adam_kernel, dim3((unsigned)a.t.first_block[3]), dim3(256), 0, st, a, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps);
   KGAT_CHECK_LAUNCH("transr_adam");
   return KGAT_OK;

@@ -27,6 +27,11 @@ from .rgcn_layer import RelGraphConv
 from .sage_layer import SAGEConv, draw_seed
 
 
+def _i32(ts):
+    """Id tensors as the kernels take them: contiguous int32 ones are used as they are."""
+    return [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in ts]
+
+
 # what KGATConv's res_type may be -> the form ops.aggregator* take: the ops.FORMS values and the two-term Bi-Interaction
 RES_TYPES = dict(FORMS, Bi2=BI2_FORM)
 
@@ -582,8 +587,7 @@ class KGATPropagation(nn.Module):
             optimizer.step()
             optimizer.zero_grad()
             return loss.detach()
-        ids = [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous()
-               for t in (h, r, pos_t, neg_t)]
+        ids = _i32((h, r, pos_t, neg_t))
         buf = getattr(self, "_kg_buffers", None)
         if buf is None or buf[1].shape != ent.shape or buf[1].device != ent.device:
             buf = self._kg_buffers = [torch.empty((), dtype=torch.float32, device=ent.device), torch.empty_like(ent),
@@ -614,7 +618,7 @@ class KGATPropagation(nn.Module):
         reference's autograd + torch.optim.Adam sequence.  Any other optimiser / size: a loop over ``kg_step``.
         As in ``kg_step``, parameters the KG loss does not reach get no update and their ``.grad`` is left alone."""
         from . import ops
-        from .optim import FusedAdam
+        from .optim import FusedAdam, _StepRoute, _fused_phase
         ent, W_R, rel = self.entity_embed.weight, self.W_R, self.relation_embed.weight
         if h.dim() != 2 or r.shape != h.shape or pos_t.shape != h.shape or neg_t.shape != h.shape:
             raise ValueError("kg_phase: h, r, pos_t, neg_t must share one (n_iterations, batch) shape")
@@ -628,28 +632,10 @@ class KGATPropagation(nn.Module):
                 return torch.zeros(0, dtype=torch.float32, device=ent.device)
             # (kg_step hands back its persistent loss buffer: copy it before the next iteration overwrites it)
             return torch.stack([self.kg_step(h[i], r[i], pos_t[i], neg_t[i], optimizer, reg_lambda_kg).clone() for i in range(n_it)])
-        import ctypes as C
-        ids = [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in (h, r, pos_t, neg_t)]
-        st = getattr(self, "_kg_phase_state", None)
-        key = (ent.shape[0], W_R.shape[1], W_R.shape[2], W_R.shape[0], b, str(ent.device))
-        if st is None or st.key != key:
-            st = self._kg_phase_state = ops.TransRAdamState(*key[:5], ent.device)
-        losses = torch.empty(n_it, dtype=torch.float32, device=ent.device)
-        with torch.no_grad():
-            sorted_all, stride = ops.transr_presort(*ids, ent.shape[0], W_R.shape[0])
-            states = [optimizer.state[p] for p in (ent, W_R, rel)]
-            arr_m = (C.c_void_p * 3)(*[s_["exp_avg"].data_ptr() for s_ in states])
-            arr_v = (C.c_void_p * 3)(*[s_["exp_avg_sq"].data_ptr() for s_ in states])
-            steps = [int(s_["step"]) for s_ in states]
-            e_, w_, r_ = ent.detach(), W_R.detach(), rel.detach()
-            lr, b1, b2, eps = hyper
-            for i in range(n_it):
-                steps = [t + 1 for t in steps]
-                ops.transr_adam_step(ids[0][i], ids[1][i], ids[2][i], ids[3][i], sorted_all[i * stride:(i + 1) * stride],
-                                     e_, w_, r_, arr_m, arr_v, steps, lr, b1, b2, eps, reg_lambda_kg, losses[i:i + 1], st)
-            for s_, t in zip(states, steps):
-                s_["step"].fill_(float(t))
-        return losses
+        n, n_rel, d, k = ent.shape[0], *W_R.shape
+        route = _StepRoute(lambda *ids: ops.transr_presort(*ids, n, n_rel), ops.transr_adam_step, ops.TransRAdamState,
+                           (n, d, k, n_rel, b, str(ent.device)), "_kg_phase_state")
+        return _fused_phase(self, route, (ent, W_R, rel), _i32((h, r, pos_t, neg_t)), optimizer, hyper, reg_lambda_kg)
 
     # -- BPR-MF pretraining (the KGAT paper initialises its runs from MF embeddings: the release's pretrain/<dataset>/mf.npz)
     def _mf_kernels_apply(self, batch):
@@ -683,7 +669,7 @@ class KGATPropagation(nn.Module):
             optimizer.step()
             optimizer.zero_grad()
             return loss.detach()
-        ids = [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in (u, p, n)]
+        ids = _i32((u, p, n))
         b = ids[0].numel()
         buf = getattr(self, "_mf_buffers", None)
         if buf is None or buf[0].shape != ent.shape or buf[0].device != ent.device or buf[1] != b:
@@ -716,7 +702,7 @@ class KGATPropagation(nn.Module):
         optimiser or size loops over ``mf_step``.  Parameters the MF
         loss does not reach get no update, and on the fused route their ``.grad`` is left alone."""
         from . import ops
-        from .optim import FusedAdam
+        from .optim import FusedAdam, _StepRoute, _fused_phase
         ent = self.entity_embed.weight
         if u.dim() != 2 or p.shape != u.shape or n.shape != u.shape:
             raise ValueError("mf_phase: u, p, n must share one (n_iterations, batch) shape")
@@ -730,24 +716,9 @@ class KGATPropagation(nn.Module):
                 return torch.zeros(0, dtype=torch.float32, device=ent.device)
             # (mf_step may hand back its persistent loss buffer: copy it before the next iteration overwrites it)
             return torch.stack([self.mf_step(u[i], p[i], n[i], optimizer, lam).clone() for i in range(n_it)])
-        ids = [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in (u, p, n)]
-        st = getattr(self, "_mf_phase_state", None)
-        key = (ent.shape[0], ent.shape[1], b, str(ent.device))
-        if st is None or st.key != key:
-            st = self._mf_phase_state = ops.MFAdamState(*key[:3], ent.device)
-        losses = torch.empty(n_it, dtype=torch.float32, device=ent.device)
-        with torch.no_grad():
-            sorted_all, stride = ops.mf_presort(*ids, ent.shape[0])
-            state = optimizer.state[ent]
-            step = int(state["step"])
-            e_ = ent.detach()
-            lr, b1, b2, eps = hyper
-            for i in range(n_it):
-                step += 1
-                ops.mf_adam_step(ids[0][i], ids[1][i], ids[2][i], sorted_all[i * stride:(i + 1) * stride], e_,
-                                 state["exp_avg"], state["exp_avg_sq"], step, lr, b1, b2, eps, lam, losses[i:i + 1], st)
-            state["step"].fill_(float(step))
-        return losses
+        route = _StepRoute(lambda *ids: ops.mf_presort(*ids, ent.shape[0]), ops.mf_adam_step, ops.MFAdamState,
+                           (ent.shape[0], ent.shape[1], b, str(ent.device)), "_mf_phase_state")
+        return _fused_phase(self, route, (ent,), _i32((u, p, n)), optimizer, hyper, lam)
 
     def load_pretrained(self, user_embed, item_embed, n_users):
         """Initialise from BPR-MF embeddings (the layout of the KGAT release's pretrain/<dataset>/mf.npz, ckg_io.load_pretrain):

@@ -14,11 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .kgat_layer import KGATPropagation
-
-
-def _i32(ts):
-    return [t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous() for t in ts]
+from .kgat_layer import KGATPropagation, _i32
 
 
 class _TransELoss(torch.autograd.Function):
@@ -126,7 +122,7 @@ class CFKG(nn.Module):
         per-sample kernel + row tags, chunk sums + loss, Adam on ent / rel without a dense gradient) - the bits of
         ``kg_step`` and of ``transE(...).backward(); torch.optim.Adam.step()``.  Any other optimiser or size loops over
         ``kg_step``.  ``.grad``: None on both parameters afterwards, on either route (see the class)."""
-        from .optim import FusedAdam
+        from .optim import FusedAdam, _StepRoute, _fused_phase
         ent, rel = self.entity_embed.weight, self.relation_embed.weight
         lam = self.reg_lambda_kg if reg_lambda_kg is None else reg_lambda_kg
         if h.dim() != 2 or r.shape != h.shape or pos_t.shape != h.shape or neg_t.shape != h.shape:
@@ -140,27 +136,10 @@ class CFKG(nn.Module):
                 return torch.zeros(0, dtype=torch.float32, device=ent.device)
             # (kg_step hands back its persistent loss buffer: copy it before the next iteration overwrites it)
             return torch.stack([self.kg_step(h[i], r[i], pos_t[i], neg_t[i], optimizer, lam).clone() for i in range(n_it)])
-        import ctypes as C
-        ids = _i32((h, r, pos_t, neg_t))
-        st = getattr(self, "_kg_phase_state", None)
-        key = (ent.shape[0], ent.shape[1], rel.shape[0], b, str(ent.device))
-        if st is None or st.key != key:
-            st = self._kg_phase_state = ops.TransEAdamState(*key[:4], ent.device)
-        losses = torch.empty(n_it, dtype=torch.float32, device=ent.device)
-        with torch.no_grad():
-            sorted_all, stride = ops.transe_presort(*ids, ent.shape[0], rel.shape[0])
-            states = [optimizer.state[p] for p in (ent, rel)]
-            arr_m = (C.c_void_p * 2)(*[s_["exp_avg"].data_ptr() for s_ in states])
-            arr_v = (C.c_void_p * 2)(*[s_["exp_avg_sq"].data_ptr() for s_ in states])
-            steps = [int(s_["step"]) for s_ in states]
-            e_, r_ = ent.detach(), rel.detach()
-            lr, b1, b2, eps = hyper
-            for i in range(n_it):
-                steps = [t + 1 for t in steps]
-                ops.transe_adam_step(ids[0][i], ids[1][i], ids[2][i], ids[3][i], sorted_all[i * stride:(i + 1) * stride],
-                                     e_, r_, arr_m, arr_v, steps, lr, b1, b2, eps, lam, losses[i:i + 1], st)
-            for s_, t in zip(states, steps):
-                s_["step"].fill_(float(t))
+        n, d, n_rel = ent.shape[0], ent.shape[1], rel.shape[0]
+        route = _StepRoute(lambda *ids: ops.transe_presort(*ids, n, n_rel), ops.transe_adam_step, ops.TransEAdamState,
+                           (n, d, n_rel, b, str(ent.device)), "_kg_phase_state")
+        losses = _fused_phase(self, route, (ent, rel), _i32((h, r, pos_t, neg_t)), optimizer, hyper, lam)
         ent.grad = rel.grad = None
         return losses
 

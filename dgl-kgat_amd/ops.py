@@ -501,6 +501,46 @@ def att_score_bwd(n_nodes, n_scored, n_groups, perm, src_g, gid, gstart, gptr, g
     return grad_ent, grad_W, grad_rel
 
 
+def _triplet_ids(h, r, pos_t, neg_t):
+    """The id tensors of a triplet batch: int32, contiguous, on the device, r / pos_t / neg_t as long as h.  Returns the
+    batch size."""
+    h = _need(h, torch.int32, "h")
+    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
+        _need(t, torch.int32, name, (h.numel(),))
+    return h.numel()
+
+
+def _presort(model, names, ids, n_nodes, *n_rel):
+    """The sorts of a whole phase's batches up front (kgat_<model>_presort_f32): `ids` are (n_batches, batch) int32
+    tensors called `names`; returns (sorted, stride) - batch b's block is sorted[b * stride:(b + 1) * stride]."""
+    first = _need(ids[0], torch.int32, names[0])
+    if first.dim() != 2:
+        raise ValueError("%s must be (n_batches, batch)" % names[0])
+    for name, t in zip(names[1:], ids[1:]):
+        _need(t, torch.int32, name, first.shape)
+    lib = _lib.load()
+    nb, b = first.shape
+    entry = "kgat_%s_presort_f32" % model
+    stride = int(getattr(lib, "kgat_%s_sorted_bytes" % model)(b, *n_rel))
+    out = _workspace(nb * stride, first.device)
+    with _timed(model + "_presort", (nb, b)):
+        check(getattr(lib, entry)(int(n_nodes), *n_rel, nb, b, *[_ptr(t) for t in ids], _ptr(out), out.numel(), _stream(first)),
+              entry)
+    return out, stride
+
+
+class StepState:
+    """What a sequence of fused train-and-step calls (kgat_*_adam_step_f32) keeps between calls: the step workspace, the
+    row_slot words (zero once, never cleared: a word is valid for the call whose tag it carries) and the tag counter.
+    `key`: the sizes it was made for, n_nodes first, and the device."""
+
+    def __init__(self, sizes, workspace_bytes, device):
+        self.key = tuple(int(x) for x in sizes) + (str(device),)
+        self.workspace = _workspace(workspace_bytes, device)
+        self.row_slot = torch.zeros(self.key[0], dtype=torch.int64, device=device)
+        self.tag = 0
+
+
 def transr_supported(n_nodes, d, k, n_rel, batch):
     return bool(_lib.load().kgat_transr_supported(int(n_nodes), int(d), int(k), int(n_rel), int(batch)))
 
@@ -518,10 +558,7 @@ def transr_loss_grad(h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda, want_grad=Tr
     n_rel, d, k = W_R.shape
     W_R = _need(W_R, torch.float32, "W_R")
     rel = _need(rel, torch.float32, "rel", (n_rel, k))
-    h = _need(h, torch.int32, "h")
-    b = h.numel()
-    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
-        _need(t, torch.int32, name, (b,))
+    b = _triplet_ids(h, r, pos_t, neg_t)
     lib = _lib.load()
     dev = ent.device
     if out is not None:
@@ -547,31 +584,12 @@ def transr_loss_grad(h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda, want_grad=Tr
 def transr_presort(h, r, pos_t, neg_t, n_nodes, n_rel):
     """The sorts of a whole KG phase's batches in one launch (kgat_transr_presort_f32): h, r, pos_t, neg_t are
     (n_batches, batch) int32 tensors; returns (sorted, stride) - batch b's block is sorted[b * stride:(b + 1) * stride]."""
-    h = _need(h, torch.int32, "h")
-    if h.dim() != 2:
-        raise ValueError("h must be (n_batches, batch)")
-    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
-        _need(t, torch.int32, name, h.shape)
-    lib = _lib.load()
-    nb, b = h.shape
-    stride = int(lib.kgat_transr_sorted_bytes(b, n_rel))
-    out = torch.empty(max(nb * stride, 256), dtype=torch.uint8, device=h.device)
-    with _timed("transr_presort", (nb, b)):
-        check(lib.kgat_transr_presort_f32(int(n_nodes), int(n_rel), nb, b, _ptr(h), _ptr(r), _ptr(pos_t), _ptr(neg_t),
-                                          _ptr(out), out.numel(), _stream(h)), "kgat_transr_presort_f32")
-    return out, stride
+    return _presort("transr", ("h", "r", "pos_t", "neg_t"), (h, r, pos_t, neg_t), n_nodes, int(n_rel))
 
 
-class TransRAdamState:
-    """What a sequence of kgat_transr_adam_step_f32 calls keeps between calls: the step workspace, the row_slot words
-    (zero once, never cleared: a word is valid for the call whose tag it carries) and the tag counter."""
-
-    def __init__(self, n_nodes, d, k, n_rel, batch, device):
-        lib = _lib.load()
-        self.key = (int(n_nodes), int(d), int(k), int(n_rel), int(batch), str(device))
-        self.workspace = _workspace(lib.kgat_transr_step_workspace_bytes(batch, d, k, n_rel), device)
-        self.row_slot = torch.zeros(int(n_nodes), dtype=torch.int64, device=device)
-        self.tag = 0
+def TransRAdamState(n_nodes, d, k, n_rel, batch, device):
+    """The StepState of a sequence of kgat_transr_adam_step_f32 calls."""
+    return StepState((n_nodes, d, k, n_rel, batch), _lib.load().kgat_transr_step_workspace_bytes(batch, d, k, n_rel), device)
 
 
 def transr_adam_step(h, r, pos_t, neg_t, sorted_block, ent, W_R, rel, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps,
@@ -601,10 +619,7 @@ def transr_forward(h, r, pos_t, neg_t, ent, W_R, rel, reg_lambda):
     n_rel, d, k = W_R.shape
     W_R = _need(W_R, torch.float32, "W_R")
     rel = _need(rel, torch.float32, "rel", (n_rel, k))
-    h = _need(h, torch.int32, "h")
-    b = h.numel()
-    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
-        _need(t, torch.int32, name, (b,))
+    b = _triplet_ids(h, r, pos_t, neg_t)
     lib = _lib.load()
     loss = torch.empty((), dtype=torch.float32, device=ent.device)
     ws = _workspace(lib.kgat_transr_workspace_bytes(b, d, k, n_rel), ent.device)
@@ -1909,41 +1924,25 @@ def mf_supported(n_nodes, F, batch):
 def mf_presort(u, p, n, n_nodes):
     """The sorts of a whole MF phase's batches up front (kgat_mf_presort_f32; one launch up to batch 2,730, three beyond): u, p, n are (n_batches, batch)
     int32 tensors; returns (sorted, stride) - batch b's block is sorted[b * stride:(b + 1) * stride]."""
-    u = _need(u, torch.int32, "u")
-    if u.dim() != 2:
-        raise ValueError("u must be (n_batches, batch)")
-    for name, t in (("p", p), ("n", n)):
-        _need(t, torch.int32, name, u.shape)
-    lib = _lib.load()
-    nb, b = u.shape
-    stride = int(lib.kgat_mf_sorted_bytes(b))
-    out = torch.empty(max(nb * stride, 256), dtype=torch.uint8, device=u.device)
-    with _timed("mf_presort", (nb, b)):
-        check(lib.kgat_mf_presort_f32(int(n_nodes), nb, b, _ptr(u), _ptr(p), _ptr(n), _ptr(out), out.numel(), _stream(u)),
-              "kgat_mf_presort_f32")
-    return out, stride
+    return _presort("mf", ("u", "p", "n"), (u, p, n), n_nodes)
 
 
-class MFAdamState:
-    """What a sequence of kgat_mf_adam_step_f32 calls keeps between calls: the step workspace, the row_slot words (zero
-    once, never cleared: a word is valid for the call whose tag it carries) and the tag counter."""
-
-    def __init__(self, n_nodes, F, batch, device):
-        lib = _lib.load()
-        self.key = (int(n_nodes), int(F), int(batch), str(device))
-        self.workspace = _workspace(lib.kgat_mf_step_workspace_bytes(batch, F), device)
-        self.row_slot = torch.zeros(int(n_nodes), dtype=torch.int64, device=device)
-        self.tag = 0
+def MFAdamState(n_nodes, F, batch, device):
+    """The StepState of a sequence of kgat_mf_adam_step_f32 calls."""
+    return StepState((n_nodes, F, batch), _lib.load().kgat_mf_step_workspace_bytes(batch, F), device)
 
 
 def mf_adam_step(u, p, n, sorted_block, emb, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, reg_lambda, loss_out, state):
     """One MF iteration (kgat_mf_adam_step_f32): BPR loss of the batch on the table `emb` into `loss_out` (a 1-element
-    fp32 view) and the Adam step on `emb` in place; `step`: the step count after this step.  Shapes and dtypes are the
-    caller's responsibility here (KGATPropagation.mf_phase validates them once per phase)."""
+    fp32 view) and the Adam step on `emb` in place.  exp_avg / exp_avg_sq: the moment tensors, `step`: the step count
+    after this step - or, as the KG steps take them, one-entry ctypes pointer arrays and a one-entry list (the entry
+    itself takes scalars).  Shapes and dtypes are the caller's responsibility here (KGATPropagation.mf_phase validates
+    them once per phase)."""
     state.tag += 1
+    m, v = (t.data_ptr() if isinstance(t, torch.Tensor) else t[0] for t in (exp_avg, exp_avg_sq))
     check(_lib.load().kgat_mf_adam_step_f32(emb.shape[0], emb.shape[1], u.numel(), u.data_ptr(), p.data_ptr(), n.data_ptr(),
-                                            sorted_block.data_ptr(), emb.data_ptr(), exp_avg.data_ptr(),
-                                            exp_avg_sq.data_ptr(), int(step), float(lr), float(beta1), float(beta2),
+                                            sorted_block.data_ptr(), emb.data_ptr(), m, v,
+                                            int(step if isinstance(step, int) else step[0]), float(lr), float(beta1), float(beta2),
                                             float(eps), float(reg_lambda), loss_out.data_ptr(), state.row_slot.data_ptr(),
                                             state.tag, state.workspace.data_ptr(), state.workspace.numel(), _stream(emb)),
           "kgat_mf_adam_step_f32")
@@ -1967,10 +1966,7 @@ def _transe_operands(h, r, pos_t, neg_t, ent, rel):
     rel = _need(rel, torch.float32, "rel")
     if rel.dim() != 2 or rel.shape[1] != ent.shape[1]:
         raise ValueError("rel must be (n_rel, %d), got %s" % (ent.shape[1], tuple(rel.shape)))
-    h = _need(h, torch.int32, "h")
-    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
-        _need(t, torch.int32, name, (h.numel(),))
-    return ent.shape[0], rel.shape[0], ent.shape[1], h.numel()
+    return ent.shape[0], rel.shape[0], ent.shape[1], _triplet_ids(h, r, pos_t, neg_t)
 
 
 def transe_forward(h, r, pos_t, neg_t, ent, rel, reg_lambda, scratch=None):
@@ -2027,30 +2023,12 @@ def transe_loss_grad(h, r, pos_t, neg_t, ent, rel, reg_lambda, out=None, scratch
 def transe_presort(h, r, pos_t, neg_t, n_nodes, n_rel):
     """The sorts of a whole TransE phase's batches in one launch (kgat_transe_presort_f32): h, r, pos_t, neg_t are
     (n_batches, batch) int32 tensors; returns (sorted, stride) - batch b's block is sorted[b * stride:(b + 1) * stride]."""
-    h = _need(h, torch.int32, "h")
-    if h.dim() != 2:
-        raise ValueError("h must be (n_batches, batch)")
-    for name, t in (("r", r), ("pos_t", pos_t), ("neg_t", neg_t)):
-        _need(t, torch.int32, name, h.shape)
-    lib = _lib.load()
-    nb, b = h.shape
-    stride = int(lib.kgat_transe_sorted_bytes(b, int(n_rel)))
-    out = torch.empty(max(nb * stride, 256), dtype=torch.uint8, device=h.device)
-    with _timed("transe_presort", (nb, b)):
-        check(lib.kgat_transe_presort_f32(int(n_nodes), int(n_rel), nb, b, _ptr(h), _ptr(r), _ptr(pos_t), _ptr(neg_t),
-                                          _ptr(out), out.numel(), _stream(h)), "kgat_transe_presort_f32")
-    return out, stride
+    return _presort("transe", ("h", "r", "pos_t", "neg_t"), (h, r, pos_t, neg_t), n_nodes, int(n_rel))
 
 
-class TransEAdamState:
-    """What a sequence of kgat_transe_adam_step_f32 calls keeps between calls: the scratch, the row_slot words (zero
-    once, never cleared: a word is valid for the call whose tag it carries) and the tag counter."""
-
-    def __init__(self, n_nodes, d, n_rel, batch, device):
-        self.key = (int(n_nodes), int(d), int(n_rel), int(batch), str(device))
-        self.scratch = transe_scratch(batch, d, n_rel, device)
-        self.row_slot = torch.zeros(int(n_nodes), dtype=torch.int64, device=device)
-        self.tag = 0
+def TransEAdamState(n_nodes, d, n_rel, batch, device):
+    """The StepState of a sequence of kgat_transe_adam_step_f32 calls (its workspace: the scratch of every TransE entry)."""
+    return StepState((n_nodes, d, n_rel, batch), _lib.load().kgat_transe_scratch_bytes(int(batch), int(d), int(n_rel)), device)
 
 
 def transe_adam_step(h, r, pos_t, neg_t, sorted_block, ent, rel, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps,
@@ -2066,8 +2044,8 @@ def transe_adam_step(h, r, pos_t, neg_t, sorted_block, ent, rel, exp_avg, exp_av
                                                 pos_t.data_ptr(), neg_t.data_ptr(), sorted_block.data_ptr(), ent.data_ptr(),
                                                 rel.data_ptr(), exp_avg, exp_avg_sq, arr_t, float(lr), float(beta1),
                                                 float(beta2), float(eps), float(reg_lambda), loss_out.data_ptr(),
-                                                state.row_slot.data_ptr(), state.tag, state.scratch.data_ptr(),
-                                                state.scratch.numel(), _stream(ent)), "kgat_transe_adam_step_f32")
+                                                state.row_slot.data_ptr(), state.tag, state.workspace.data_ptr(),
+                                                state.workspace.numel(), _stream(ent)), "kgat_transe_adam_step_f32")
 
 
 # ---------------------------------------------------------------- Bi-Interaction pooling, the FM / NFM baselines (kgat_bi_pool_*)

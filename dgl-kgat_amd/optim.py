@@ -10,6 +10,7 @@ Global-norm gradient clipping (reference kgat.py:32 ``--grad_norm``, kgat.py:162
 and step) comes in two forms: ``FusedAdam.step(max_grad_norm=c)``, which applies the clip coefficient inside the Adam
 launch, and ``clip_grad_norm_``, torch's function on this package's kernels for any other optimiser."""
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -152,3 +153,39 @@ class FusedAdam(torch.optim.Optimizer):
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return hyper
+
+
+# What a model's phase method hands to _fused_phase: presort(*ids) -> (sorted, stride); step = the ops.*_adam_step of
+# the model; state(*key[:-1], device) makes the ops.StepState, kept on the model as attribute `cache` while `key`
+# (sizes, then str(device)) stays the same.
+_StepRoute = namedtuple("_StepRoute", "presort step state key cache")
+
+
+def _fused_phase(model, route, params, ids, optimizer, hyper, reg_lambda):
+    """The loop of a fused phase (KGATPropagation.kg_phase / mf_phase, CFKG.kg_phase), once the method has decided
+    that the fused route applies: `ids` are contiguous int32 (n_iterations, batch) tensors, `hyper` is what
+    ``optimizer.kg_state(params)`` returned.  Every batch is sorted up front, iteration i is one ``route.step`` call on
+    row i of the ids - in place on `params` and on the optimiser's exp_avg / exp_avg_sq, whose pointers are read once -
+    and the step counts go back into the optimiser's state at the end.  Returns the n_iterations losses (device
+    tensor).  ``.grad`` is not touched: that policy is the caller's."""
+    st = getattr(model, route.cache, None)
+    if st is None or st.key != route.key:
+        st = route.state(*route.key[:-1], params[0].device)
+        setattr(model, route.cache, st)
+    n_it = ids[0].shape[0]
+    losses = torch.empty(n_it, dtype=torch.float32, device=params[0].device)
+    with torch.no_grad():
+        sorted_all, stride = route.presort(*ids)
+        states = [optimizer.state[p] for p in params]
+        arr_m = (C.c_void_p * len(params))(*[s_["exp_avg"].data_ptr() for s_ in states])
+        arr_v = (C.c_void_p * len(params))(*[s_["exp_avg_sq"].data_ptr() for s_ in states])
+        steps = [int(s_["step"]) for s_ in states]
+        data = [p.detach() for p in params]
+        lr, b1, b2, eps = hyper
+        for i in range(n_it):
+            steps = [t + 1 for t in steps]
+            route.step(*[t[i] for t in ids], sorted_all[i * stride:(i + 1) * stride], *data, arr_m, arr_v, steps, lr, b1, b2,
+                       eps, reg_lambda, losses[i:i + 1], st)
+        for s_, t in zip(states, steps):
+            s_["step"].fill_(float(t))
+    return losses
