@@ -26,8 +26,12 @@ from .kge_models import CFKG, CKE  # noqa: F401
 from . import fm_models  # noqa: F401
 from .fm_models import FM, NFM, FeatureSets  # noqa: F401
 from .autograd import bi_pool  # noqa: F401
+from . import ripple_models  # noqa: F401
+from .ripple_models import RippleNet, RippleSets  # noqa: F401
+from .autograd import ripple_hop  # noqa: F401
 
 __all__ = ["DGLGraph", "DGLError", "ALL", "function", "explain", "edge_softmax", "KGATConv", "KGATPropagation", "SAGEConv", "GATConv",
            "RelGraphConv", "install_as_dgl", "accelerate", "KGATLibraryError", "CKGDataset", "enable_lazy_edge_weights",
            "GraphedForward", "FusedAdam", "clip_grad_norm_", "kg_eval", "KnownTriples", "KGRanks", "kg_rank", "kg_metrics", "kg_complete",
-           "kge_models", "CFKG", "CKE", "fm_models", "FM", "NFM", "FeatureSets", "bi_pool"]
+           "kge_models", "CFKG", "CKE", "fm_models", "FM", "NFM", "FeatureSets", "bi_pool", "ripple_models", "RippleNet",
+           "RippleSets", "ripple_hop"]

@@ -38,6 +38,7 @@ SOURCES = {
     "kgat_rgcn.hip": [],
     "kgat_transe.hip": [],
     "kgat_bi_pool.hip": [],
+    "kgat_ripple.hip": [],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -234,6 +235,12 @@ SIGNATURES = {
     "kgat_bi_pool_scratch_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "kgat_bi_pool_fwd_f32": (_i32, [_i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "kgat_bi_pool_bwd_f32": (_i32, [_i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # ripple-set attention of one hop (the RippleNet baseline): logits, softmax and the weighted sum of the tail rows in
+    # one walk; backward towards the query table (ABI 16, additive)
+    "kgat_ripple_supported": (_i32, [_i32, _i32, _i32, _i64]),
+    "kgat_ripple_hop_fwd_f32": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "kgat_ripple_hop_bwd_f32": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                       _p, _p]),
 }
 
 _lib = None

@@ -18,6 +18,9 @@
   differentiates towards the entity table, W_R and the relation embeddings.
 * ``bi_pool`` - NFM's Bi-Interaction pooling over sparse feature sets (kgat_bi_pool_fwd_f32 / kgat_bi_pool_bwd_f32): the
   operator of the FM and NFM baselines; backward towards the embedding table and the linear weights, dense.
+* ``ripple_hop`` - RippleNet's attention of one item vector over a user's ripple set of one hop (kgat_ripple_hop_fwd_f32 /
+  kgat_ripple_hop_bwd_f32): logits, softmax and the weighted sum of the tail rows in one walk; backward towards the
+  query table and, through two incidence lists summed by the sum kernel, towards the entity table, dense.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -688,3 +691,70 @@ def bi_pool(V, w_lin, feats, items, extra=None):
     def i32(t):
         return t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous()
     return _BiPool.apply(V, w_lin, feats.to(V.device), i32(items.to(V.device)), None if extra is None else i32(extra.to(V.device)))
+
+
+class _RippleHop(torch.autograd.Function):
+    """Ripple-set attention of one hop (kgat_ripple_hop_fwd_f32), its backward towards the query table
+    (kgat_ripple_hop_bwd_f32) and towards the entity table (ops.ripple_scatter)."""
+
+    @staticmethod
+    def forward(ctx, ent, U, sets, users, hop):
+        o, p = ops.ripple_hop_fwd(ent.detach(), U.detach(), sets, users, hop)
+        ctx.sets, ctx.hop = sets, hop
+        ctx.save_for_backward(ent, U, users, p)
+        return o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_o):
+        ent, U, users, p = ctx.saved_tensors
+        need_ent, need_U = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g_o = g_o.to(torch.float32).contiguous()
+        grad_U, gl = ops.ripple_hop_bwd(ent.detach(), U.detach(), ctx.sets, users, ctx.hop, p, g_o)
+        grad_ent = ops.ripple_scatter(U.detach(), ctx.sets, users, ctx.hop, p, gl, g_o) if need_ent else None
+        return grad_ent, grad_U if need_U else None, None, None, None
+
+
+def ripple_hop_torch(ent, U, sets, users, hop, want_p=False):
+    """``ripple_hop`` in torch operators (index_select / softmax, index_add_ under autograd), differentiable: what the
+    kernels are compared with and what runs on the CPU, in float64 and outside ``ops.ripple_supported``.  Returns o, or
+    (o, p)."""
+    dev = ent.device
+    sets = sets.to(dev)
+    ul = torch.as_tensor(users, device=dev).long()
+    b, M, R = ul.numel(), sets.n_memory, sets.n_rel
+    h, r, t = (getattr(sets, name)[ul, int(hop)].long() for name in ("mem_h", "mem_r", "mem_t"))
+    H = ent.index_select(0, h.reshape(-1)).view(b, M, -1)
+    q = (torch.arange(b, device=dev).unsqueeze(1) * R + r).reshape(-1)
+    Q = U.reshape(b * R, -1).index_select(0, q).view(b, M, -1)
+    p = torch.softmax((H * Q).sum(-1), 1)
+    T = ent.index_select(0, t.reshape(-1)).view(b, M, -1)
+    o = (p.unsqueeze(-1) * T).sum(1)
+    return (o, p) if want_p else o
+
+
+def ripple_kernels_apply(ent, U, sets):
+    """Whether ``ripple_hop`` takes the kernels: fp32 on a HIP device, contiguous, 16-byte aligned, a supported size."""
+    return (ent.is_cuda and ent.dtype == torch.float32 and U.dtype == torch.float32 and ent.is_contiguous() and
+            ent.data_ptr() % 16 == 0 and U.shape[0] >= 1 and
+            ops.ripple_supported(ent.shape[1], sets.n_memory, sets.n_rel, U.shape[0]))
+
+
+def ripple_hop(ent, U, sets, users, hop):
+    """RippleNet's attention of one hop, differentiable towards ent and U: for sample b with user ``users[b]`` and the
+    hop's ripple set (h_i, r_i, t_i), ``s_i = <U[b, r_i], ent[h_i]>``, ``p = softmax(s)``, ``o[b] = sum_i p_i ent[t_i]``
+    (n_samples, d).  `sets`: a ``ripple_models.RippleSets``; U (n_samples, n_rel, d) with ``U[b, r] = v_b R_r``; `users`
+    any integer dtype.  On a HIP device in fp32 at a size ``ops.ripple_supported`` takes: one kernel forward, one kernel
+    plus two csr_from_coo + spmm sums backward, with fixed orders of addition (bitwise reproducible, dense gradients
+    whose untouched rows are 0); CPU tensors, other dtypes and sizes run ``ripple_hop_torch``."""
+    if ent.dim() != 2 or U.dim() != 3 or U.shape[1] != sets.n_rel or U.shape[2] != ent.shape[1]:
+        raise ValueError("ripple_hop: ent must be (n_nodes, d) and U (n_samples, %d, d), got %s and %s"
+                         % (sets.n_rel, tuple(ent.shape), tuple(U.shape)))
+    if not 0 <= int(hop) < sets.n_hop:
+        raise ValueError("ripple_hop: hop %d outside [0, %d)" % (hop, sets.n_hop))
+    if not ripple_kernels_apply(ent, U, sets):
+        return ripple_hop_torch(ent, U, sets, users, hop)
+    users = torch.as_tensor(users, device=ent.device)
+    if users.dtype != torch.int32 or not users.is_contiguous():
+        users = users.to(torch.int32).contiguous()
+    return _RippleHop.apply(ent, U.contiguous(), sets.to(ent.device), users, int(hop))

@@ -2112,6 +2112,81 @@ def bi_pool_bwd(V, feats, items, extra, S, g_bi=None, g_lin=None, g_sq=None, wan
     return grad_V, grad_w
 
 
+# ---------------------------------------------------------------- ripple-set attention, the RippleNet baseline (kgat_ripple_*)
+def ripple_supported(d, n_memory, n_rel, n_samples):
+    """Sizes of the ripple-set kernels: d in {16, 32, 64, 128}, 1 <= n_memory <= 128, 1 <= n_rel <= 4096, n_samples >= 1
+    (kgat_ripple_supported)."""
+    return bool(_lib.load().kgat_ripple_supported(int(d), int(n_memory), int(n_rel), int(n_samples)))
+
+
+def _ripple_operands(ent, U, sets, users):
+    ent = _need(ent, torch.float32, "ent")
+    if ent.dim() != 2 or ent.shape[0] != sets.n_nodes:
+        raise ValueError("ent must be (%d, d), got %s" % (sets.n_nodes, tuple(ent.shape)))
+    users = _need(users, torch.int32, "users")
+    if users.dim() != 1:
+        raise ValueError("users must be one-dimensional")
+    b, d = users.numel(), ent.shape[1]
+    _need(U, torch.float32, "U", (b, sets.n_rel, d))
+    for name in ("mem_h", "mem_r", "mem_t"):
+        _need(getattr(sets, name), torch.int32, "sets." + name, (sets.n_users, sets.n_hop, sets.n_memory))
+    if sets.mem_h.device != ent.device:
+        raise ValueError("the ripple sets are on %s, ent on %s" % (sets.mem_h.device, ent.device))
+    return b, d
+
+
+def ripple_hop_fwd(ent, U, sets, users, hop):
+    """Attention of every sample over its user's ripple set of hop `hop` (kgat_ripple_hop_fwd_f32): returns (o, p),
+    o (n_samples, d) and the softmax weights p (n_samples, n_memory).  `sets`: a RippleSets on ent's device; U
+    (n_samples, n_rel, d) with U[b, r] = v_b R_r; users int32."""
+    b, d = _ripple_operands(ent, U, sets, users)
+    o = torch.empty((b, d), dtype=torch.float32, device=ent.device)
+    p = torch.empty((b, sets.n_memory), dtype=torch.float32, device=ent.device)
+    with _timed("ripple_hop_fwd", (b, sets.n_memory, d)):
+        check(_lib.load().kgat_ripple_hop_fwd_f32(b, d, sets.n_memory, sets.n_rel, sets.n_hop, int(hop), sets.n_nodes,
+                                                  sets.n_users, _ptr(ent), _ptr(U), _ptr(sets.mem_h), _ptr(sets.mem_r),
+                                                  _ptr(sets.mem_t), _ptr(users), _ptr(o), _ptr(p), _stream(ent)),
+              "kgat_ripple_hop_fwd_f32")
+    return o, p
+
+
+def ripple_hop_bwd(ent, U, sets, users, hop, p, g_o):
+    """The backward of ripple_hop_fwd towards the query table and the logits (kgat_ripple_hop_bwd_f32): returns
+    (grad_U (n_samples, n_rel, d), every row written, and gl (n_samples, n_memory), the gradient of the logits).  The
+    gradient towards ent is ripple_scatter's."""
+    b, d = _ripple_operands(ent, U, sets, users)
+    _need(p, torch.float32, "p", (b, sets.n_memory))
+    _need(g_o, torch.float32, "g_o", (b, d))
+    grad_U = torch.empty((b, sets.n_rel, d), dtype=torch.float32, device=ent.device)
+    gl = torch.empty((b, sets.n_memory), dtype=torch.float32, device=ent.device)
+    with _timed("ripple_hop_bwd", (b, sets.n_memory, d)):
+        check(_lib.load().kgat_ripple_hop_bwd_f32(b, d, sets.n_memory, sets.n_rel, sets.n_hop, int(hop), sets.n_nodes,
+                                                  sets.n_users, _ptr(ent), _ptr(U), _ptr(sets.mem_h), _ptr(sets.mem_r),
+                                                  _ptr(sets.mem_t), _ptr(users), _ptr(p), _ptr(g_o), _ptr(grad_U), _ptr(gl),
+                                                  _stream(ent)), "kgat_ripple_hop_bwd_f32")
+    return grad_U, gl
+
+
+def ripple_scatter(U, sets, users, hop, p, gl, g_o):
+    """The dense gradient of ripple_hop_fwd towards ent, (n_nodes, d): grad_ent[t_i] += p[b, i] g_o[b] and
+    grad_ent[h_i] += gl[b, i] U[b, r_i] as two incidence lists in (sample, slot) order, each turned into a node-major
+    CSR (csr_from_coo, stable in entry order) and summed by spmm - the merge-path sum, no float atomics - and the two
+    dense results added."""
+    b, n_rel, d = U.shape
+    if b * n_rel >= 2 ** 31:
+        raise ValueError("ripple_scatter: n_samples * n_rel must stay below 2^31")
+    M, n = sets.n_memory, sets.n_nodes
+    ul = users.long()
+    sample = torch.arange(b, dtype=torch.int32, device=U.device).unsqueeze(1)
+    h, r, t = (getattr(sets, name)[ul, int(hop)] for name in ("mem_h", "mem_r", "mem_t"))
+    out = None
+    for row, source, weight, table in ((t, sample.expand(b, M), p, g_o), (h, sample * n_rel + r, gl, U.view(b * n_rel, d))):
+        indptr, col, eid, row_of = csr_from_coo(n, source.reshape(-1).contiguous(), row.reshape(-1).contiguous())
+        part = spmm(indptr, col, row_of, table, weight.reshape(-1), eid=eid)
+        out = part if out is None else out.add_(part)
+    return out
+
+
 # ---------------------------------------------------------------- global-norm gradient clipping (kgat.py:32,162)
 def __getattr__(name):
     # GRAD_NORM_CHAIN: the compile-time constant of the library (kgat_grad_norm_chain), read when first asked for

@@ -26,6 +26,8 @@ in eval mode (the reference never leaves training mode, so its evaluation passes
                                                                           # --model cke: TransR + BPR on cf + entity rows
   python examples/train_kgat.py --planted --model fm --epochs 3 --lr 0.03 --batch_size 512 --eval_before
                                                                          # --model nfm: the same features under an MLP
+  python examples/train_kgat.py --planted --model ripplenet --ripple_inverse 1 --entity_embed_dim 16 --epochs 3 --lr 0.03 \
+      --batch_size 512 --eval_before                                     # the path-based baseline on ripple-set attention
   python examples/train_kgat.py --planted --pretrain_epochs 5 --pretrain_lr 0.1 --pretrain_save mf.npz --epochs 3
                                                                           # BPR-MF pretraining of the table first (the paper's
                                                                           # initialisation); --pretrain_load mf.npz reuses it
@@ -185,6 +187,9 @@ def _widths(text):
     return ws
 
 
+RIPPLE_FLAGS = ("n_hop", "n_memory", "kge_weight", "item_update_mode", "using_all_hops", "ripple_inverse")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_dir", default=None)
@@ -199,12 +204,27 @@ def parse_args(argv=None):
                     help="propagation layers (reference kgat.py:23): bi-interaction KGATConv, SAGEConv (mean), or "
                          "RelGraphConv (R-GCN with basis decomposition over the edge types)")
     # (absent from the namespace unless given, as --num_bases: a run without it keeps its arguments and --log_json "args")
-    ap.add_argument("--model", choices=("kgat", "cfkg", "cke", "fm", "nfm"), default=argparse.SUPPRESS,
+    ap.add_argument("--model", choices=("kgat", "cfkg", "cke", "fm", "nfm", "ripplenet"), default=argparse.SUPPRESS,
                     help="kgat (default), or one of the KGAT paper's baselines: cfkg - TransE over the whole "
                          "collaborative KG, recommendation as the ranking of (user, interact, ?) (kge_models.CFKG); cke - "
                          "TransR over the item KG + BPR on `cf latent + entity embedding` (kge_models.CKE); fm / nfm - a "
                          "factorisation machine / neural FM over the features {user, item, the item's KG neighbours} on "
-                         "fused Bi-Interaction pooling (fm_models.FM / NFM)")
+                         "fused Bi-Interaction pooling (fm_models.FM / NFM); ripplenet - RippleNet, the path-based "
+                         "baseline: the item vector attends over the user's ripple sets of KG triples, hop by hop, on fused "
+                         "ripple-set attention (ripple_models.RippleNet; the paper ran it at --entity_embed_dim 16)")
+    ap.add_argument("--n_hop", type=int, default=argparse.SUPPRESS, help="--model ripplenet: hops of the ripple sets, 1..4 (default 2)")
+    ap.add_argument("--n_memory", type=int, default=argparse.SUPPRESS,
+                    help="--model ripplenet: triples of a ripple set, 1..128 (default 32)")
+    ap.add_argument("--kge_weight", type=float, default=argparse.SUPPRESS,
+                    help="--model ripplenet: weight of the KGE term -mean sigmoid(h^T R t) (default 0.01; 0 skips it)")
+    ap.add_argument("--item_update_mode", choices=("replace", "plus", "replace_transform", "plus_transform"),
+                    default=argparse.SUPPRESS, help="--model ripplenet: the item vector between hops (default plus_transform)")
+    ap.add_argument("--using_all_hops", type=int, choices=(0, 1), default=argparse.SUPPRESS,
+                    help="--model ripplenet: 1 (default) scores with the sum of every hop's response, 0 with the last hop's")
+    ap.add_argument("--ripple_inverse", type=int, choices=(0, 1), default=argparse.SUPPRESS,
+                    help="--model ripplenet: 1 adds the inverse (t, r + n, h) of every KG triple to the ripple sets' adjacency "
+                         "(the planted CKG holds item -> attribute triples only and needs it; the KGAT release's "
+                         "kg_final.txt already contains the inverses).  Default 0")
     ap.add_argument("--nfm_layers", type=_widths, default=argparse.SUPPRESS, metavar="W[,W...]",
                     help="--model nfm: widths of the hidden layers above the pooling (default 64)")
     ap.add_argument("--num_bases", type=int, default=argparse.SUPPRESS,
@@ -301,6 +321,18 @@ def parse_args(argv=None):
             ap.error("--kg_eval / --kg_holdout rank triples; --model %s has no KG phase" % kind)
         if kind == "nfm" and getattr(args, "rank_metrics", 0):
             ap.error("--rank_metrics sweeps a dot-product table; --model nfm scores through an MLP")
+    if kind == "ripplenet":
+        if args.kg_eval or args.kg_holdout > 0:
+            ap.error("--kg_eval / --kg_holdout rank triples; --model ripplenet has no KG phase")
+        if getattr(args, "rank_metrics", 0):
+            ap.error("--rank_metrics sweeps a dot-product table; --model ripplenet scores through its ripple sets")
+        if args.pretrain_load:
+            ap.error("--pretrain_load fills user rows; --model ripplenet has none")
+        if not 1 <= getattr(args, "n_hop", 2) <= 4 or not 1 <= getattr(args, "n_memory", 32) <= 128:
+            ap.error("--n_hop takes 1..4 hops, --n_memory 1..128 triples")
+    for flag in RIPPLE_FLAGS:
+        if hasattr(args, flag) and kind != "ripplenet":
+            ap.error("--%s belongs to --model ripplenet" % flag)
     if hasattr(args, "nfm_layers") and kind != "nfm":
         ap.error("--nfm_layers sets the hidden layers of --model nfm")
     if args.pretrain_epochs < 0 or args.pretrain_batch_size < 1:
@@ -419,6 +451,8 @@ def _run(args, argv):
         kg_pool = kg_pool[pick].astype(np.int64)
     if getattr(args, "model", "kgat") in ("fm", "nfm"):
         return _run_fm(args, ds, dev)
+    if getattr(args, "model", "kgat") == "ripplenet":
+        return _run_ripple(args, ds, dev)
     if getattr(args, "model", "kgat") != "kgat":
         return _run_kge(args, ds, dev, kg_pool, full if args.kg_eval else None)
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
@@ -878,6 +912,97 @@ def _run_fm(args, ds, dev):
                         rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
                     print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
                         name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
+        rec["eval_s"] = clock() - t0
+        print("           | eval %.4fs" % rec["eval_s"])
+
+    history = []
+    if args.eval_before:
+        model.eval()
+        history.append({"epoch": 0})
+        print("Epoch 0000 | (untrained)")
+        evaluate(history[-1])
+    for epoch in range(1, args.epochs + 1):
+        rec = {"epoch": epoch}
+        t_epoch = clock()
+        t0 = clock()
+        model.train()
+        n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
+        idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
+        u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
+        n_all = torch.randint(off, off + n_items, (n_it, bs), device=dev, dtype=torch.int32)
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        for i in range(n_it):
+            loss = model.get_loss(u_all[i], p_all[i], n_all[i])
+            loss.backward()
+            if args.grad_norm > 0:
+                opt.step(max_grad_norm=args.grad_norm)
+            else:
+                opt.step()
+            opt.zero_grad()
+            total += loss.detach()
+        rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
+        rec["cf_loss"] = float(total) / n_it
+        print("Epoch %04d | CF %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it,
+                                                                      rec["cf_loss"]))
+        del idx, u_all, p_all, n_all
+        model.eval()
+        evaluate(rec)
+        rec["epoch_s"] = clock() - t_epoch
+        print("           | epoch %.4fs" % rec["epoch_s"])
+        history.append(rec)
+    if args.log_json:
+        import json
+        with open(args.log_json, "w") as f:
+            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
+                       "n_relations": ds.n_KG_relation, "n_train_pairs": int(n_pairs), "epochs": history}, f, indent=1)
+    return history
+
+
+def _run_ripple(args, ds, dev):
+    """--model ripplenet on one GPU: the ripple sets are built once on the host; an epoch is a CF phase of steps on the
+    pair stream of the other baselines - one pass over the 2 B samples, positives first, BCE with 1:1 negatives plus the
+    KGE and L2 terms (RippleNet.get_loss), one FusedAdam over all parameters, --grad_norm honoured - then evaluation
+    through RippleNet.evaluate (block scores in torch operators, torch.topk, the metric kernel).  The records carry the
+    keys the other models' CF phase and evaluation write."""
+    off, n_items = ds.n_users, ds.n_items
+    t0 = time.perf_counter()
+    sets = K.RippleSets.build(ds.train_KG_triplet, ds.train_pairs, ds.n_users, ds.n_KG_entity, n_hop=getattr(args, "n_hop", 2),
+                              n_memory=getattr(args, "n_memory", 32), seed=args.seed,
+                              add_inverse=bool(getattr(args, "ripple_inverse", 0)), device=dev)
+    print("--model ripplenet | %d hops x %d triples per user, %d relations, %d of %d users without a triple, built in %.2fs" % (
+        sets.n_hop, sets.n_memory, sets.n_rel, int((~sets.valid).sum()), sets.n_users, time.perf_counter() - t0))
+    model = K.RippleNet(ds.n_KG_entity, sets, dim=args.entity_embed_dim, kge_weight=getattr(args, "kge_weight", 0.01),
+                        item_update_mode=getattr(args, "item_update_mode", "plus_transform"),
+                        using_all_hops=bool(getattr(args, "using_all_hops", 1)), item_range=(off, off + n_items)).to(dev)
+    opt = K.FusedAdam(model.parameters(), lr=args.lr)
+    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
+    n_pairs = pair_cols.shape[1]
+    train_dict = user_dict(ds.train_pairs, off)
+    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
+    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
+    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
+             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
+
+    def cap(n):
+        return n if args.max_iters <= 0 else min(n, args.max_iters)
+
+    def clock():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def evaluate(rec):
+        t0 = clock()
+        for name in ("valid", "test"):
+            m = model.evaluate(plans[name], args.Ks)
+            if args.Ks == [20]:
+                rec[name + "_recall"], rec[name + "_ndcg"] = float(m["recall"][0]), float(m["ndcg"][0])
+                print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+                continue
+            for j, k in enumerate(args.Ks):
+                for metric in metrics.METRIC_NAMES:
+                    rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
+                    name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
         rec["eval_s"] = clock() - t0
         print("           | eval %.4fs" % rec["eval_s"])
 

@@ -1268,6 +1268,50 @@ int kgat_bi_pool_bwd_f32(int64_t n_sets, int d, int64_t n_nodes, int64_t n_items
                          const float* g_bi, const float* g_lin, const float* g_sq, const float* S, float* grad_V,
                          float* grad_w, void* scratch, size_t scratch_bytes, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- ripple-set attention: the RippleNet baseline (additive within ABI 16)
+ * RippleNet (Wang et al., CIKM 2018), the KGAT paper's path-based baseline, attends with one item vector over a user's
+ * ripple set of every hop: n_memory triples (h_i, r_i, t_i) of the knowledge graph.  The sets are graph-static int32
+ * arrays mem_h, mem_r, mem_t of shape [n_users, n_hop, n_memory]; inside every (user, hop) the triples are sorted
+ * ascending by (r, h, t), so equal relations are consecutive - the backward relies on it.  For sample b with user
+ * users[b], hop `hop` and the query table U (n_samples x n_rel x d, contiguous; U[b, r] = v_b R_r, a matmul of the caller):
+ *     s_i = <U[b, r_i], ent[h_i]>      p[b] = softmax_i(s) (maximum subtracted)      o[b] = sum_i p_i ent[t_i]
+ * and, given g_o (n_samples x d):
+ *     gp_i = <ent[t_i], g_o[b]>        gl[b, i] = p_i (gp_i - sum_j p_j gp_j)
+ *     grad_U[b, r] = sum_{i : r_i = r} gl_i ent[h_i]      (+0.0 rows for the relations the set lacks)
+ * The gradient towards ent - grad_ent[t_i] += p_i g_o[b], grad_ent[h_i] += gl_i U[b, r_i] - is two incidence lists the
+ * caller sums with kgat_csr_from_coo + kgat_spmm_umule_sum_f32; no entry here forms it.
+ *
+ * Both entries: one wavefront per sample, d / 4 lanes per row and 16 bytes per lane, G = 256 / d lane groups, four rows
+ * in flight per group; nothing of size n_samples x n_memory x d is written.
+ * kgat_ripple_hop_fwd_f32 writes o (n_samples x d) and p (n_samples x n_memory).  Order of additions: slot i belongs to
+ * group i mod G.  A logit is, per lane, fma(x3, q3, fma(x2, q2, fma(x1, q1, x0 * q0))) over its four columns, then a
+ * butterfly over the d / 4 lanes of the group (strides d / 8, ..., 1).  Softmax: lane j of the wavefront holds slots j and
+ * j + 64, adds e_j + e_{j + 64}, and a butterfly over the 64 lanes (strides 32, ..., 1) gives the sum; p = e / sum.  o: a
+ * group adds p_i * ent[t_i], one fma per column, in ascending i from 0; the G partials are combined by a butterfly
+ * (group g with g ^ G/2, then g ^ G/4, ..., g ^ 1).  The first four tail rows of every group are requested before the
+ * softmax's reductions.
+ * kgat_ripple_hop_bwd_f32 writes gl (n_samples x n_memory) and EVERY row of grad_U (n_samples x n_rel x d) exactly
+ * once - no memset.  gp as the logits above; lane j forms fma(p_{j + 64}, gp_{j + 64}, p_j * gp_j) and the 64-lane
+ * butterfly gives sum_j p_j gp_j.  Relation r belongs to group r mod G, which finds r's run of slots (two binary
+ * searches) and adds gl_i * ent[h_i], one fma per column, in ascending i from the run's first slot; groups are not
+ * combined.  U is part of the argument list (it is checked) and is not read.
+ * No float atomics: both entries are bitwise reproducible.  A sample whose user id lies outside [0, n_users), or whose
+ * set holds an id outside [0, n_nodes) / [0, n_rel), reads nothing there and gets NaN outputs.
+ *
+ * kgat_ripple_supported(d, n_memory, n_rel, n_samples): d in {16, 32, 64, 128}, 1 <= n_memory <= 128, 1 <= n_rel <=
+ * 4096, 1 <= n_samples with (n_samples + 3) / 4 workgroups inside the grid; others KGAT_E_UNSUPPORTED from both entries
+ * (the Python layer then runs the torch restatement).  Negative size, n_hop < 1, hop outside [0, n_hop), n_nodes or
+ * n_users outside [1, 2^31), a null pointer, ent / U / o / g_o / grad_U not 16-byte aligned: KGAT_E_BADARG.  Every
+ * check precedes any device work. */
+int kgat_ripple_supported(int d, int n_memory, int n_rel, int64_t n_samples);
+int kgat_ripple_hop_fwd_f32(int64_t n_samples, int d, int n_memory, int n_rel, int n_hop, int hop, int64_t n_nodes,
+                            int64_t n_users, const float* ent, const float* U, const int32_t* mem_h, const int32_t* mem_r,
+                            const int32_t* mem_t, const int32_t* users, float* o, float* p, kgat_stream_t stream);
+int kgat_ripple_hop_bwd_f32(int64_t n_samples, int d, int n_memory, int n_rel, int n_hop, int hop, int64_t n_nodes,
+                            int64_t n_users, const float* ent, const float* U, const int32_t* mem_h, const int32_t* mem_r,
+                            const int32_t* mem_t, const int32_t* users, const float* p, const float* g_o, float* grad_U,
+                            float* gl, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
