@@ -71,6 +71,23 @@ def _pretrain_pair(ue, ie, path):
     return np.ascontiguousarray(ue), np.ascontiguousarray(ie)
 
 
+def load_pretrained_rows(table, user_embed, item_embed, n_users):
+    """BPR-MF embeddings (arrays or tensors, the pair ``load_pretrain`` returns) into an (n_nodes, d) table in the node
+    layout above: ``user_embed`` (n_users, d) goes to rows [0, n_users), ``item_embed`` (n_items, d) to rows
+    [n_users, n_users + n_items); the attribute entities' rows after them stay as they are.  In place and outside
+    autograd; what every model's ``load_pretrained`` runs on the table its readout ranks with."""
+    ue, ie = torch.as_tensor(user_embed), torch.as_tensor(item_embed)
+    if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != table.shape[1] or ie.shape[1] != table.shape[1]:
+        raise ValueError("load_pretrained: embeddings must be (rows, %d), got %s and %s"
+                         % (table.shape[1], tuple(ue.shape), tuple(ie.shape)))
+    if ue.shape[0] != int(n_users) or n_users + ie.shape[0] > table.shape[0]:
+        raise ValueError("load_pretrained: %d user rows for n_users = %d, %d item rows, %d table rows"
+                         % (ue.shape[0], n_users, ie.shape[0], table.shape[0]))
+    with torch.no_grad():
+        table[:n_users].copy_(ue.to(device=table.device, dtype=table.dtype))
+        table[n_users:n_users + ie.shape[0]].copy_(ie.to(device=table.device, dtype=table.dtype))
+
+
 def _uv_triplets(uv, offset_rel, n_uv_rel, symmetric=True):
     """dataset.py:165-185: [u, R, v] rows, then (symmetric) the reversed [v, R + n_uv_rel, u] rows."""
     rel = np.zeros(len(uv), np.int32) if uv.shape[1] == 2 else uv[:, 2]

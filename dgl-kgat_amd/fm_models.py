@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import metrics, ops
+from .ckg_io import load_pretrained_rows
 
 
 POOL_CHUNK = 8192   # the sets of one kernel call (ops.bi_pool_supported)
@@ -152,17 +153,6 @@ def pool_items(V, w_lin, feats, chunk=POOL_CHUNK):
         return tuple(torch.cat(parts, 0) for parts in zip(*out))
 
 
-def _load_rows(table, user_embed, item_embed, n_users):
-    ue, ie = torch.as_tensor(user_embed), torch.as_tensor(item_embed)
-    if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != table.shape[1] or ie.shape[1] != table.shape[1] or \
-            ue.shape[0] != int(n_users) or n_users + ie.shape[0] > table.shape[0]:
-        raise ValueError("load_pretrained: embeddings must be (%d, %d) and (items, %d), got %s and %s"
-                         % (n_users, table.shape[1], table.shape[1], tuple(ue.shape), tuple(ie.shape)))
-    with torch.no_grad():
-        table[:n_users].copy_(ue.to(device=table.device, dtype=table.dtype))
-        table[n_users:n_users + ie.shape[0]].copy_(ie.to(device=table.device, dtype=table.dtype))
-
-
 class _Pooled(nn.Module):
     """What FM and NFM share: the table ``embed`` (n_nodes x dim), ``w_lin`` (n_nodes), ``w0`` and the pooled pass of a
     BPR batch.  Item arguments are node ids; ``feats.item_offset`` turns them into item positions."""
@@ -211,7 +201,7 @@ class _Pooled(nn.Module):
 
     def load_pretrained(self, user_embed, item_embed, n_users):
         """BPR-MF embeddings into the user and item rows of ``embed``."""
-        _load_rows(self.embed.weight, user_embed, item_embed, n_users)
+        load_pretrained_rows(self.embed.weight, user_embed, item_embed, n_users)
 
 
 class FM(_Pooled):
@@ -300,37 +290,11 @@ class NFM(_Pooled):
             self.train(was_training)
         return torch.cat(out, 0) if out else torch.zeros(0, self.feats.n_items, dtype=V.dtype, device=V.device)
 
-    @torch.no_grad()
     def topk(self, plan, K, max_bytes=1 << 28):
-        """The K best unseen items of every user of an ``EvalPlan`` (its training items dropped), as item positions: an
-        (n_users, K) int32 tensor, best first (``torch.topk``)."""
-        n_items = self.feats.n_items
-        if plan.n_items != n_items:
-            raise ValueError("topk: the plan ranks %d items, the feature sets hold %d" % (plan.n_items, n_items))
-        if not 1 <= K <= n_items:
-            raise ValueError("topk: K must be in [1, %d]" % n_items)
-        users = plan.user_ids.long()
-        tp = plan.train_ptr.long()
-        out = []
-        step = max(1, int(max_bytes // (max(1, n_items) * 4 * 4)))
-        for lo in range(0, users.numel(), step):
-            hi = min(lo + step, users.numel())
-            sc = self.scores(users[lo:hi], max_bytes)
-            seen = plan.train_items[int(tp[lo]):int(tp[hi])].long()
-            row = torch.repeat_interleave(torch.arange(hi - lo, device=sc.device), tp[lo + 1:hi + 1] - tp[lo:hi])
-            sc[row, seen] = float("-inf")
-            out.append(torch.topk(sc, K, dim=1).indices.to(torch.int32))
-        return torch.cat(out, 0) if out else torch.zeros(0, K, dtype=torch.int32, device=self.embed.weight.device)
+        """The K best unseen items of every user of an ``EvalPlan`` (``metrics.topk_unseen`` over ``scores``)."""
+        return metrics.topk_unseen(self.scores, self.feats.n_items, plan, K, max_bytes)
 
     def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28):
-        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``: block scores,
-        training items dropped, ``torch.topk``, then the metric kernel of the other models (``ops.eval_metrics_at_ks``).
-        Returns the dict ``metrics.calc_metrics`` returns."""
-        from . import metrics
-        Ks = [int(k) for k in Ks]
-        if plan.n_users == 0:
-            raise ZeroDivisionError("no test users")
-        top = self.topk(plan, Ks[-1], max_bytes).contiguous()
-        out = ops.eval_metrics_at_ks(top, plan.test_ptr, plan.test_items, Ks)
-        mean = (out.sum(0) / plan.n_users).cpu().numpy()
-        return {name: mean[:, m].copy() for m, name in enumerate(metrics.METRIC_NAMES)}
+        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``
+        (``metrics.calc_metrics_unseen`` over ``scores``): the dict ``metrics.calc_metrics`` returns."""
+        return metrics.calc_metrics_unseen(self.scores, self.feats.n_items, plan, Ks, max_bytes)

@@ -379,3 +379,20 @@ def kg_complete(model, h, r, K, known=None, candidates=None):
             dist_s[b:e] = torch.where(pos >= 0, q2 + 1.0 - 2.0 * score, torch.full_like(score, float("inf")))
         ids[order], dist[order] = ids_s, dist_s
         return ids, dist
+
+
+class LinkPrediction:
+    """The three functions above as methods of a model that holds ``entity_embed``, ``relation_embed`` and, for a
+    projected score, ``W_R`` (``_params``): inherited by ``KGATPropagation``, ``kge_models.CFKG`` and ``kge_models.CKE``."""
+
+    def kg_rank(self, h, r, t, known=None, side="tail", candidates=None):
+        """Filtered ranks of the triples under the model's translation score (``kg_rank``): KGRanks(lt, eq, rank)."""
+        return kg_rank(self, h, r, t, known=known, side=side, candidates=candidates)
+
+    def kg_metrics(self, h, r, t, known=None, side="both", hits=(1, 3, 10), batch=2048):
+        """MR / MRR / Hits@k of the filtered ranks (``kg_metrics``)."""
+        return kg_metrics(self, h, r, t, known=known, side=side, hits=hits, batch=batch)
+
+    def kg_complete(self, h, r, K, known=None, candidates=None):
+        """The K entities closest to (h, r, ?) with their distances (``kg_complete``)."""
+        return kg_complete(self, h, r, K, known=known, candidates=candidates)

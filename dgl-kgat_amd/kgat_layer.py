@@ -21,6 +21,8 @@ import torch.nn.functional as F
 
 from . import function as fn
 from .autograd import _combine, edge_softmax, u_mul_e_sum
+from .ckg_io import load_pretrained_rows
+from .kg_eval import LinkPrediction
 from .ops import BI2_FORM, FORMS
 from .options import options
 from .rgcn_layer import RelGraphConv
@@ -172,7 +174,7 @@ class KGATConv(nn.Module):
         return self.mess_drop(out)
 
 
-class KGATPropagation(nn.Module):
+class KGATPropagation(LinkPrediction, nn.Module):
     """The hot-path part of the reference's ``Model`` (models.py:72-111,135-168): embeddings,
     W_R, the KGATConv stack, ``compute_attention`` and ``gnn``.  The TransR / BPR losses of the
     reference (models.py:114-133,170-178) are outside this path; ``get_loss`` is kept because the
@@ -725,17 +727,7 @@ class KGATPropagation(nn.Module):
         ``user_embed`` (n_users, d) goes to rows [0, n_users) of the entity table, ``item_embed`` (n_items, d) to rows
         [n_users, n_users + n_items) - the node layout of ckg_io: users first, then the items, then the attribute entities,
         whose rows stay as they are."""
-        ent = self.entity_embed.weight
-        ue, ie = torch.as_tensor(user_embed), torch.as_tensor(item_embed)
-        if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != ent.shape[1] or ie.shape[1] != ent.shape[1]:
-            raise ValueError("load_pretrained: embeddings must be (rows, %d), got %s and %s"
-                             % (ent.shape[1], tuple(ue.shape), tuple(ie.shape)))
-        if ue.shape[0] != int(n_users) or n_users + ie.shape[0] > ent.shape[0]:
-            raise ValueError("load_pretrained: %d user rows for n_users = %d, %d item rows, %d table rows"
-                             % (ue.shape[0], n_users, ie.shape[0], ent.shape[0]))
-        with torch.no_grad():
-            ent[:n_users].copy_(ue.to(device=ent.device, dtype=ent.dtype))
-            ent[n_users:n_users + ie.shape[0]].copy_(ie.to(device=ent.device, dtype=ent.dtype))
+        load_pretrained_rows(self.entity_embed.weight, user_embed, item_embed, n_users)
 
     def pretrained_embeddings(self, n_users, n_items):
         """The user and item blocks of the entity table as float32 CPU numpy arrays (for ckg_io.save_pretrain)."""
@@ -744,22 +736,6 @@ class KGATPropagation(nn.Module):
             raise ValueError("pretrained_embeddings: %d users + %d items exceed the table's %d rows" % (n_users, n_items, ent.shape[0]))
         t = ent[:n_users + n_items].to(device="cpu", dtype=torch.float32).numpy()
         return t[:n_users].copy(), t[n_users:].copy()
-
-    # -- link prediction with the TransR embedding (kg_eval.py)
-    def kg_rank(self, h, r, t, known=None, side="tail", candidates=None):
-        """Filtered ranks of the triples under the TransR score (kg_eval.kg_rank): KGRanks(lt, eq, rank)."""
-        from .kg_eval import kg_rank
-        return kg_rank(self, h, r, t, known=known, side=side, candidates=candidates)
-
-    def kg_metrics(self, h, r, t, known=None, side="both", hits=(1, 3, 10), batch=2048):
-        """MR / MRR / Hits@k of the filtered ranks (kg_eval.kg_metrics)."""
-        from .kg_eval import kg_metrics
-        return kg_metrics(self, h, r, t, known=known, side=side, hits=hits, batch=batch)
-
-    def kg_complete(self, h, r, K, known=None, candidates=None):
-        """The K entities closest to (h, r, ?) with their distances (kg_eval.kg_complete)."""
-        from .kg_eval import kg_complete
-        return kg_complete(self, h, r, K, known=known, candidates=candidates)
 
     def _gnn_fused_sharded(self, g):
         """No-grad path on a destination-range shard: per layer the local aggregation, the

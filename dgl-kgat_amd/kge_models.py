@@ -14,6 +14,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .ckg_io import load_pretrained_rows
+from .kg_eval import LinkPrediction
 from .kgat_layer import KGATPropagation, _i32
 
 
@@ -53,7 +55,7 @@ def transe_loss_torch(ent, rel, h, r, pos_t, neg_t, reg_lambda):
     return loss + reg_lambda * reg
 
 
-class CFKG(nn.Module):
+class CFKG(LinkPrediction, nn.Module):
     """TransE over the collaborative KG.  Parameters: ``entity_embed`` (n_entities x dim), ``relation_embed``
     (n_relations x dim).
 
@@ -161,25 +163,12 @@ class CFKG(nn.Module):
         shift[u0:u1] = F.normalize(rel[int(interaction_relation)].unsqueeze(0), p=2, dim=1)
         return table + shift
 
-    # -- link prediction (kg_eval.py: a model without W_R ranks with u_x = normalize(e_x))
-    def kg_rank(self, h, r, t, known=None, side="tail", candidates=None):
-        from .kg_eval import kg_rank
-        return kg_rank(self, h, r, t, known=known, side=side, candidates=candidates)
-
-    def kg_metrics(self, h, r, t, known=None, side="both", hits=(1, 3, 10), batch=2048):
-        from .kg_eval import kg_metrics
-        return kg_metrics(self, h, r, t, known=known, side=side, hits=hits, batch=batch)
-
-    def kg_complete(self, h, r, K, known=None, candidates=None):
-        from .kg_eval import kg_complete
-        return kg_complete(self, h, r, K, known=known, candidates=candidates)
-
     def load_pretrained(self, user_embed, item_embed, n_users):
         """BPR-MF embeddings into the user and item rows of the entity table (the table ``readout`` ranks with)."""
-        KGATPropagation.load_pretrained(self, user_embed, item_embed, n_users)
+        load_pretrained_rows(self.entity_embed.weight, user_embed, item_embed, n_users)
 
 
-class CKE(nn.Module):
+class CKE(LinkPrediction, nn.Module):
     """Collaborative knowledge-base embedding: a TransR part - ``entity_embed``, ``relation_embed``, ``W_R``, trained by
     ``KGATPropagation``'s own ``transR`` / ``kg_step`` / ``kg_phase`` - and a CF table ``cf_embed`` (n_entities x dim);
     an item's vector is its CF row plus its entity embedding.  ``get_loss`` is the fused BPR loss
@@ -207,9 +196,6 @@ class CKE(nn.Module):
     kg_step = KGATPropagation.kg_step
     kg_phase = KGATPropagation.kg_phase
     get_loss = KGATPropagation.get_loss
-    kg_rank = KGATPropagation.kg_rank
-    kg_metrics = KGATPropagation.kg_metrics
-    kg_complete = KGATPropagation.kg_complete
 
     def readout(self, item_range):
         """``cf_embed`` with ``entity_embed`` added on the item rows [lo, hi): differentiable."""
@@ -221,12 +207,4 @@ class CKE(nn.Module):
 
     def load_pretrained(self, user_embed, item_embed, n_users):
         """BPR-MF embeddings into the user and item rows of ``cf_embed`` (the table ``readout`` ranks with)."""
-        ue, ie = torch.as_tensor(user_embed), torch.as_tensor(item_embed)
-        cf = self.cf_embed.weight
-        if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != cf.shape[1] or ie.shape[1] != cf.shape[1] or \
-                ue.shape[0] != int(n_users) or n_users + ie.shape[0] > cf.shape[0]:
-            raise ValueError("load_pretrained: embeddings must be (%d, %d) and (items, %d), got %s and %s"
-                             % (n_users, cf.shape[1], cf.shape[1], tuple(ue.shape), tuple(ie.shape)))
-        with torch.no_grad():
-            cf[:n_users].copy_(ue.to(device=cf.device, dtype=cf.dtype))
-            cf[n_users:n_users + ie.shape[0]].copy_(ie.to(device=cf.device, dtype=cf.dtype))
+        load_pretrained_rows(self.cf_embed.weight, user_embed, item_embed, n_users)

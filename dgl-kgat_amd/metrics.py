@@ -163,6 +163,45 @@ def calc_metrics(embedding, train_user_dict, test_user_dict, all_item_id_range, 
     return {name: mean[:, m].copy() for m, name in enumerate(METRIC_NAMES)}
 
 
+@torch.no_grad()
+def topk_unseen(scores, n_items, plan, K, max_bytes=1 << 28):
+    """The K best unseen items of every user of an ``EvalPlan`` (its training items dropped), as item positions: an
+    (n_users, K) int32 tensor, best first (``torch.topk``) - for a model whose scores are no dot product of table rows
+    (``fm_models.NFM``, ``ripple_models.RippleNet``).  ``scores(users, max_bytes)`` returns the (len(users), n_items)
+    score matrix of a block of user node ids (int64, on the plan's device); the blocks are sized so that a block's
+    matrix, its mask indices and ``torch.topk``'s outputs stay below `max_bytes`."""
+    if plan.n_items != n_items:
+        raise ValueError("topk: the plan ranks %d items, the model scores %d" % (plan.n_items, n_items))
+    if not 1 <= K <= n_items:
+        raise ValueError("topk: K must be in [1, %d]" % n_items)
+    users = plan.user_ids.long()
+    tp = plan.train_ptr.long()
+    out = []
+    step = max(1, int(max_bytes // (max(1, n_items) * 4 * 4)))
+    for lo in range(0, users.numel(), step):
+        hi = min(lo + step, users.numel())
+        sc = scores(users[lo:hi], max_bytes)
+        seen = plan.train_items[int(tp[lo]):int(tp[hi])].long()
+        row = torch.repeat_interleave(torch.arange(hi - lo, device=sc.device), tp[lo + 1:hi + 1] - tp[lo:hi])
+        sc[row, seen] = float("-inf")
+        out.append(torch.topk(sc, K, dim=1).indices.to(torch.int32))
+    return torch.cat(out, 0) if out else torch.zeros(0, K, dtype=torch.int32, device=users.device)
+
+
+def calc_metrics_unseen(scores, n_items, plan, Ks=(20,), max_bytes=1 << 28):
+    """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan`` and a block score
+    function: ``topk_unseen`` at the largest cut-off, then the metric kernel of ``calc_metrics``
+    (``ops.eval_metrics_at_ks``).  Returns the dict ``calc_metrics`` returns."""
+    from . import ops
+    Ks = [int(k) for k in Ks]
+    if plan.n_users == 0:
+        raise ZeroDivisionError("no test users")
+    top = topk_unseen(scores, n_items, plan, Ks[-1], max_bytes).contiguous()
+    out = ops.eval_metrics_at_ks(top, plan.test_ptr, plan.test_items, Ks)
+    mean = (out.sum(0) / plan.n_users).cpu().numpy()
+    return {name: mean[:, m].copy() for m, name in enumerate(METRIC_NAMES)}
+
+
 RANK_SCALAR_NAMES = ("mrr", "map", "auc", "mean_rank")
 
 

@@ -15,6 +15,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import metrics
+from .fm_models import _long
+
 UPDATE_MODES = ("replace", "plus", "replace_transform", "plus_transform")
 
 
@@ -137,10 +140,6 @@ class RippleSets:
 
 def _L2_loss_mean(x):
     return torch.mean(torch.sum(torch.pow(x, 2), dim=1, keepdim=False) / 2.0)
-
-
-def _long(t, device):
-    return torch.as_tensor(t, device=device).long()
 
 
 class RippleNet(nn.Module):
@@ -279,37 +278,11 @@ class RippleNet(nn.Module):
             out.append(self._predict(v, o_list))
         return torch.cat(out, 0) if out else torch.zeros(0, n_items, dtype=ent.dtype, device=ent.device)
 
-    @torch.no_grad()
     def topk(self, plan, K, max_bytes=1 << 28):
-        """The K best unseen items of every user of an ``EvalPlan`` (its training items dropped), as item positions: an
-        (n_users, K) int32 tensor, best first (``torch.topk``)."""
-        n_items = self.n_items
-        if plan.n_items != n_items:
-            raise ValueError("topk: the plan ranks %d items, item_range holds %d" % (plan.n_items, n_items))
-        if not 1 <= K <= n_items:
-            raise ValueError("topk: K must be in [1, %d]" % n_items)
-        users = plan.user_ids.long()
-        tp = plan.train_ptr.long()
-        out = []
-        step = max(1, int(max_bytes // (max(1, n_items) * 4 * 4)))
-        for lo in range(0, users.numel(), step):
-            hi = min(lo + step, users.numel())
-            sc = self.scores(users[lo:hi], max_bytes)
-            seen = plan.train_items[int(tp[lo]):int(tp[hi])].long()
-            row = torch.repeat_interleave(torch.arange(hi - lo, device=sc.device), tp[lo + 1:hi + 1] - tp[lo:hi])
-            sc[row, seen] = float("-inf")
-            out.append(torch.topk(sc, K, dim=1).indices.to(torch.int32))
-        return torch.cat(out, 0) if out else torch.zeros(0, K, dtype=torch.int32, device=self.entity_emb.weight.device)
+        """The K best unseen items of every user of an ``EvalPlan`` (``metrics.topk_unseen`` over ``scores``)."""
+        return metrics.topk_unseen(self.scores, self.n_items, plan, K, max_bytes)
 
     def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28):
-        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``: block scores,
-        training items dropped, ``torch.topk``, then the metric kernel of the other models (``ops.eval_metrics_at_ks``).
-        Returns the dict ``metrics.calc_metrics`` returns."""
-        from . import metrics, ops
-        Ks = [int(k) for k in Ks]
-        if plan.n_users == 0:
-            raise ZeroDivisionError("no test users")
-        top = self.topk(plan, Ks[-1], max_bytes).contiguous()
-        out = ops.eval_metrics_at_ks(top, plan.test_ptr, plan.test_items, Ks)
-        mean = (out.sum(0) / plan.n_users).cpu().numpy()
-        return {name: mean[:, m].copy() for m, name in enumerate(metrics.METRIC_NAMES)}
+        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``
+        (``metrics.calc_metrics_unseen`` over ``scores``): the dict ``metrics.calc_metrics`` returns."""
+        return metrics.calc_metrics_unseen(self.scores, self.n_items, plan, Ks, max_bytes)

@@ -38,15 +38,21 @@ batches (same seed); the attention refresh and the CF forward run on the local s
 layer-output exchange per layer, the CF backward sums the per-rank gradients of the replicated
 operands (all-reduce), so all ranks apply the one-GPU run's update.  The KG phase (dense TransR
 batches, no graph) runs replicated.
+
+Every ``--model`` runs through one ``Driver`` (samplers, phase loops, recorders, epoch skeleton, ``--log_json``); a model
+is a ``Family``: its phases and what its evaluation ranks.
 """
 import argparse
+import json
 import os
 import sys
 import tempfile
 import time
+from collections import namedtuple
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -388,6 +394,260 @@ def parse_args(argv=None):
     return args
 
 
+# ---- the epoch driver: what every --model shares.  A model supplies a `Family`; the driver draws the batches, runs and
+# times the phases, evaluates, prints and keeps the records.  The torch.randint calls of an epoch are the run's only
+# random draws on the device, so their order and arguments ARE its reproducibility: the KG phase draws before the CF
+# phase, a phase draws its row indices before its negatives, and the negatives are drawn as int32.
+class Splits(namedtuple("Splits", "train_dict valid_dict test_dict train_valid_dict plans")):
+    def of(self, name):
+        """(seen, held, plan) of the split "valid" or "test"."""
+        seen, held = (self.train_dict, self.valid_dict) if name == "valid" else (self.train_valid_dict, self.test_dict)
+        return seen, held, self.plans[name]
+
+
+def eval_splits(ds, dev):
+    """The user -> items dicts of the data's three files and the evaluation's static side (users, item lists as CSR
+    arrays; once per split, not once per call): validation ranks the items a user has not trained on, test the items it
+    has neither trained nor validated on."""
+    off = ds.n_users
+    train_dict = user_dict(ds.train_pairs, off)
+    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
+    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
+    plans = {name: metrics.EvalPlan(seen, held, ds.item_id_range, dev)
+             for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict))}
+    return Splits(train_dict, valid_dict, test_dict, train_valid_dict, plans)
+
+
+def cap(n, max_iters):
+    return n if max_iters <= 0 else min(n, max_iters)
+
+
+def clock(dev):
+    """The host clock once `dev` has run everything queued on it (a CPU queues nothing)."""
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    return time.perf_counter()
+
+
+def id_columns(rows, dev):
+    """A sampled table column by column (int32 ids go to the kernels as they are): a phase's batches are rows of ONE
+    gather per column, so a step's host work is the two library calls, not five indexing launches."""
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(rows).T.astype(np.int32)), device=dev)
+
+
+def draw_pairs(pair_cols, batch, item_range, max_iters):
+    """A phase's (user, positive, negative) batches, drawn up front: ``(n_it, u, p, n)``, each (n_it, batch) - uniform
+    training pairs, then uniformly random negative items."""
+    n_pairs, dev = pair_cols.shape[1], pair_cols.device
+    n_it, bs = cap(n_pairs // batch + 1, max_iters), min(batch, n_pairs)
+    idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
+    neg = torch.randint(item_range[0], item_range[1], (n_it, bs), device=dev, dtype=torch.int32)
+    return n_it, pair_cols[0][idx], pair_cols[1][idx], neg
+
+
+def draw_triples(trip_cols, batch, n_entities, max_iters):
+    """A KG phase's batches, drawn up front: ``(n_it, h, r, t, neg)`` - uniform training triples, then uniformly random
+    negative tails among all entities."""
+    n_trip, dev = trip_cols.shape[1], trip_cols.device
+    n_it, bs = cap(n_trip // batch + 1, max_iters), min(batch, n_trip)
+    idx = torch.randint(0, n_trip, (n_it, bs), device=dev)
+    neg = torch.randint(0, n_entities, (n_it, bs), device=dev, dtype=torch.int32)
+    return n_it, trip_cols[0][idx], trip_cols[1][idx], trip_cols[2][idx], neg
+
+
+# What a model gives the driver.  `phases`: the epoch's training phases in order, each a callable (epoch, rec) - built from
+# Driver.kg_phase / Driver.cf_phase, or the model's own; `eval_inputs()`: what ranks the validation and then the test
+# split - an embedding table whose dot products are the scores, or the metric dict of the model's own `evaluate`;
+# `n_train_triplets`: the KG phase's table size for the --log_json header (None: no KG phase).
+Family = namedtuple("Family", "model phases eval_inputs n_train_triplets")
+
+
+class Driver:
+    """The run's shared state - arguments, data, device, evaluation splits, the training pairs' columns - and the pieces
+    every model's epoch is made of.  `kg_pool` (n, 3): the triples --kg_eval ranks after every evaluation, filtered by
+    `kg_true`, every triple that counts as true.  Only rank 0 prints and writes."""
+
+    def __init__(self, args, ds, dev, rank=0, kg_pool=None, kg_true=None):
+        self.args, self.ds, self.dev, self.rank = args, ds, dev, rank
+        self.say = print if rank == 0 else (lambda *a, **k: None)
+        self.splits = eval_splits(ds, dev)
+        self.pair_cols = id_columns(ds.train_pairs[:, :2], dev)
+        self.items = (ds.n_users, ds.n_users + ds.n_items)
+        self.kg_pool = self.kg_known = None
+        if kg_pool is not None:
+            self.kg_known = K.KnownTriples(kg_true[:, 0], kg_true[:, 1], kg_true[:, 2], ds.n_KG_entity, ds.n_KG_relation,
+                                           device=dev)
+            self.kg_pool = [torch.as_tensor(np.ascontiguousarray(kg_pool[:, c]), device=dev) for c in range(3)]
+        self._lead = ""
+
+    def head(self):
+        """The left margin of a phase's line: the epoch number on the epoch's first line, blank after it."""
+        lead, self._lead = self._lead, "           |"
+        return lead
+
+    def kg_phase(self, rec, model, opt, trip_cols):
+        """The KG phase (kgat.py:116-136) as ``model.kg_phase``: every iteration = loss -> backward -> step -> zero_grad
+        of kgat.py:127-131 - one launch sorts all batches, then one library call (three launches) per iteration.  The
+        reference reads loss.item() after every step (a host round trip per iteration, kgat.py:132); here the losses stay
+        on the device and their sum is read once per phase."""
+        args, dev = self.args, self.dev
+        t0 = clock(dev)
+        n_it, h_all, r_all, t_all, neg_all = draw_triples(trip_cols, args.batch_size_kg, self.ds.n_KG_entity, args.max_iters)
+        total = model.kg_phase(h_all, r_all, t_all, neg_all, opt).sum()
+        rec["kg_s"], rec["kg_iters"] = clock(dev) - t0, n_it
+        rec["kg_loss"] = float(total) / n_it
+        self.say("%s KGE %.4fs (%d it, %.4f ms/it) loss %.4f" % (self.head(), rec["kg_s"], n_it, 1e3 * rec["kg_s"] / n_it,
+                                                                rec["kg_loss"]))
+
+    def cf_phase(self, epoch, rec, opt, loss_of, label="CF", kgat=None):
+        """The CF phase (kgat.py:146-168): per batch ``loss_of(u, p, n)`` -> backward -> step -> zero_grad, --grad_norm
+        clipping the gradient's global norm inside the step (clip_grad_norm_ of kgat.py:162); the running loss stays on
+        the device and is read once.  `kgat`: a KGATPropagation, for which the phase also keeps every step's gradient norm
+        (one readback at the end of the phase), records how far W_R moved, and prints --grad_digest."""
+        args, dev, say = self.args, self.dev, self.say
+        t0 = clock(dev)
+        n_it, u_all, p_all, n_all = draw_pairs(self.pair_cols, args.batch_size, self.items, args.max_iters)
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        w_r_before = kgat.W_R.detach().clone() if kgat is not None else None
+        norms = torch.zeros(n_it, dtype=torch.float32, device=dev) if kgat is not None and args.grad_norm > 0 else None
+        for i in range(n_it):
+            loss = loss_of(u_all[i], p_all[i], n_all[i])
+            loss.backward()
+            if kgat is not None and args.grad_digest and epoch == 1 and i == 0:
+                say("           | grad digest: loss %.9g  " % loss.item() + "  ".join(
+                    "%s %.9g" % (k, p.grad.double().abs().sum().item()) for k, p in kgat.named_parameters()
+                    if p.grad is not None))
+            if norms is not None:
+                opt.step(max_grad_norm=args.grad_norm, norm_out=norms[i])
+            elif args.grad_norm > 0:
+                opt.step(max_grad_norm=args.grad_norm)
+            else:
+                opt.step()
+            opt.zero_grad()
+            total += loss.detach()
+        rec["cf_s"], rec["cf_iters"] = clock(dev) - t0, n_it
+        rec["cf_loss"] = float(total) / n_it
+        if kgat is not None:
+            rec["cf_W_R_change"] = float((kgat.W_R.detach() - w_r_before).abs().max())   # 0 unless --attention_grad 1
+        if norms is not None:
+            seen = norms.cpu().numpy()
+            if not np.isfinite(seen).all():
+                raise RuntimeError("epoch %d: the gradient norm of CF step %d is %r" % (
+                    epoch, int(np.flatnonzero(~np.isfinite(seen))[0]), float(seen[~np.isfinite(seen)][0])))
+            rec["cf_grad_norm_max"], rec["cf_grad_norm_mean"] = float(seen.max()), float(seen.mean())
+            # (the test the kernel applies: coef = min(c / (norm + 1e-6), 1) in fp32 is below 1)
+            c32 = np.float32(args.grad_norm)
+            rec["cf_clipped_steps"] = int((c32 / (seen + np.float32(1e-6)) < np.float32(1)).sum())
+            say("           | grad norm max %.4g mean %.4g, %d of %d steps clipped at %g" % (
+                rec["cf_grad_norm_max"], rec["cf_grad_norm_mean"], rec["cf_clipped_steps"], n_it, args.grad_norm))
+        say("%s %s %.4fs (%d it, %.4f ms/it) loss %.4f" % (self.head(), label, rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it,
+                                                          rec["cf_loss"]))
+
+    def record_split(self, rec, name, given):
+        """Record and print the metrics of the split `name`.  `given`: an embedding table - ranked here, with
+        --rank_metrics also by the exact rank of every held-out item - or the dict of means ``metrics.calc_metrics``
+        returns, already computed by a model that scores otherwise."""
+        args, say = self.args, self.say
+        seen, held, plan = self.splits.of(name)
+        items = self.ds.item_id_range
+        if isinstance(given, dict):
+            m = given
+        else:
+            if getattr(args, "rank_metrics", 0):
+                rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
+                rank_Ks = [k for k in rank_Ks if k <= plan.n_items] or [plan.n_items]
+                m = metrics.calc_rank_metrics(given, seen, held, items, Ks=rank_Ks, plan=plan)
+                for metric in metrics.RANK_SCALAR_NAMES:
+                    rec["%s_%s" % (name, metric)] = float(m[metric])
+                for j, k in enumerate(rank_Ks):
+                    for metric in metrics.METRIC_NAMES:
+                        rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
+                say("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f | %s" % (
+                    name, m["auc"], m["mrr"], m["map"], m["mean_rank"],
+                    " ".join("recall@%d %.5f ndcg@%d %.5f" % (k, m["recall"][j], k, m["ndcg"][j]) for j, k in enumerate(rank_Ks))))
+            if args.Ks == [20]:
+                recall, ndcg = metrics.calc_recall_ndcg(given, seen, held, items, K=20, plan=plan)
+                m = {"recall": [recall], "ndcg": [ndcg]}
+            else:
+                m = metrics.calc_metrics(given, seen, held, items, Ks=args.Ks, plan=plan)
+        if args.Ks == [20]:
+            rec[name + "_recall"], rec[name + "_ndcg"] = float(m["recall"][0]), float(m["ndcg"][0])
+            say("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
+            return
+        for j, k in enumerate(args.Ks):
+            for metric in metrics.METRIC_NAMES:
+                rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
+            say("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
+                name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
+
+    def record_kg(self, rec, model):
+        """--kg_eval: record and print the filtered link-prediction metrics of the fixed triples, both sides."""
+        dev = self.dev
+        t0 = clock(dev)
+        m = model.kg_metrics(*self.kg_pool, known=self.kg_known, side="both", hits=(1, 3, 10))
+        rec["kg_eval_s"] = clock(dev) - t0
+        rec["kg_mrr"], rec["kg_mr"], rec["kg_hits@10"] = m["mrr"], m["mr"], m["hits@10"]
+        self.say("           | KG link prediction, %d %s triples, both sides, filtered: kg_mrr %.5f kg_mr %.1f kg_hits@10 %.5f "
+                 "| %.4fs" % (self.kg_pool[0].numel(), "held-out" if self.args.kg_holdout > 0 else "TRAINING (a fit measure)",
+                              m["mrr"], m["mr"], m["hits@10"], rec["kg_eval_s"]))
+
+    def evaluate(self, fam, rec):
+        """Evaluation (kgat.py:53-62, 171-196) of the validation and the test split, then --kg_eval."""
+        t0 = clock(self.dev)
+        with torch.no_grad():
+            for name, given in zip(("valid", "test"), fam.eval_inputs()):
+                self.record_split(rec, name, given)
+        rec["eval_s"] = clock(self.dev) - t0
+        self.say("           | eval %.4fs" % rec["eval_s"])
+        if self.kg_pool is not None:
+            self.record_kg(rec, fam.model)
+
+    def run(self, fam, history=None):
+        """The epochs: --eval_before, then per epoch the model's phases in training mode and the evaluation in eval mode.
+        Returns the records, appended to `history` (a record of epoch 0 already there takes --eval_before's metrics)."""
+        args, dev = self.args, self.dev
+        history = [] if history is None else history
+        if args.eval_before:
+            fam.model.eval()
+            if not history:
+                history.append({"epoch": 0})
+            self.say("Epoch 0000 | (untrained)")
+            self.evaluate(fam, history[-1])
+        for epoch in range(1, args.epochs + 1):
+            rec = {"epoch": epoch}
+            t_epoch = clock(dev)
+            self._lead = "Epoch %04d |" % epoch
+            fam.model.train()
+            for phase in fam.phases:
+                phase(epoch, rec)
+            fam.model.eval()
+            self.evaluate(fam, rec)
+            rec["epoch_s"] = clock(dev) - t_epoch
+            self.say("           | epoch %.4fs" % rec["epoch_s"])
+            history.append(rec)
+        return history
+
+    def write_log(self, fam, history):
+        """--log_json: the arguments, the data's sizes and the per-epoch records."""
+        args, ds = self.args, self.ds
+        if not args.log_json or self.rank != 0:
+            return
+        log = {"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
+               "n_relations": ds.n_KG_relation}
+        if fam.n_train_triplets is not None:
+            log["n_train_triplets"] = int(fam.n_train_triplets)
+        log.update(n_train_pairs=int(self.pair_cols.shape[1]), epochs=history)
+        with open(args.log_json, "w") as f:
+            json.dump(log, f, indent=1)
+
+
+def load_mf(drv, model):
+    """--pretrain_load: the user / item rows of the table the model ranks with, from an mf.npz."""
+    if drv.args.pretrain_load:
+        model.load_pretrained(*ckg_io.load_pretrain(drv.args.pretrain_load), drv.ds.n_users)
+        drv.say("Pretrain   | user / item rows from %s" % drv.args.pretrain_load)
+
+
 def main(argv=None):
     args = parse_args(argv)
     # the attention refresh hands back its edge-id-ordered copy unwritten (nothing here reads it)
@@ -420,7 +680,6 @@ def _run(args, argv):
     dev = torch.device("cuda", int(os.environ.get("KGAT_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0"))))
     torch.cuda.set_device(dev)
     if world > 1:
-        import torch.distributed as dist
         backend = os.environ.get("KGAT_DIST_BACKEND", "nccl")
         dist.init_process_group(backend, rank=rank, world_size=world, **({"device_id": dev} if backend == "nccl" else {}))
     say = print if rank == 0 else (lambda *a, **k: None)
@@ -429,7 +688,7 @@ def _run(args, argv):
     ds = ckg_io.CKGDataset(args.data_dir)
     say("users %d items %d | CKG: %d entities, %d relations, %d train triplets" % (
         ds.n_users, ds.n_items, ds.n_KG_entity, ds.n_KG_relation, len(ds.train_KG_triplet)))
-    kg_pool = kg_known = None
+    kg_pool = full = None
     if args.kg_eval:
         # every triple that counts as true, before anything is held out; n_KG_entity / n_KG_relation stay the full data's
         full = np.unique(np.vstack([ds.train_KG_triplet, ds.test_KG_triplet]), axis=0)
@@ -449,12 +708,22 @@ def _run(args, argv):
             raise SystemExit("--kg_eval: no triple to rank")
         pick = np.random.default_rng(args.seed).permutation(len(kg_pool))[:args.kg_eval]
         kg_pool = kg_pool[pick].astype(np.int64)
-    if getattr(args, "model", "kgat") in ("fm", "nfm"):
-        return _run_fm(args, ds, dev)
-    if getattr(args, "model", "kgat") == "ripplenet":
-        return _run_ripple(args, ds, dev)
-    if getattr(args, "model", "kgat") != "kgat":
-        return _run_kge(args, ds, dev, kg_pool, full if args.kg_eval else None)
+    drv = Driver(args, ds, dev, rank, kg_pool, full)
+    kind = getattr(args, "model", "kgat")
+    if kind == "kgat":
+        return _run_kgat(drv, world)
+    fam = {"cfkg": _kge_family, "cke": _kge_family, "fm": _fm_family, "nfm": _fm_family, "ripplenet": _ripple_family}[kind](drv)
+    history = drv.run(fam)
+    drv.write_log(fam, history)
+    return history
+
+
+def _run_kgat(drv, world):
+    """--model kgat, on `world` GPUs: an epoch is the KG phase (TransR), the attention refresh under no_grad, the CF phase
+    (full-graph ``gnn`` + BPR loss per batch) and the evaluation on the propagated embeddings of the training / the test
+    graph.  Only this model starts ranks, shards its graphs, pretrains its table and explains its recommendations."""
+    args, ds, dev, say, splits = drv.args, drv.ds, drv.dev, drv.say, drv.splits
+    rank = drv.rank
     model = K.KGATPropagation(ds.n_KG_entity, ds.n_KG_relation, args.entity_embed_dim, args.relation_embed_dim,
                               args.gnn_num_layer, args.gnn_hidden_size, args.dropout_rate,
                               gnn_model=args.gnn_model, res_type=args.res_type, use_attention=bool(args.use_attention),
@@ -483,73 +752,7 @@ def _run(args, argv):
     if world > 1:
         from dgl_kgat_amd import partition
         train_g, test_g = partition.shard_graph(train_g, rank, world)[0], partition.shard_graph(test_g, rank, world)[0]
-    # the sampled tables column by column (int32 ids go to the kernels as they are): a phase's batches are rows of
-    # ONE gather per column, so a step's host work is the two library calls, not five indexing launches
-    trip_cols = torch.as_tensor(np.ascontiguousarray(ds.train_KG_triplet.T.astype(np.int32)), device=dev)
-    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
-    n_trip, n_pairs = trip_cols.shape[1], pair_cols.shape[1]
-    off = ds.n_users
-    train_dict = user_dict(ds.train_pairs, off)
-    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
-    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
-    # the evaluation's static side (users, item lists as CSR arrays) once per split, not once per call
-    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
-             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
-
-    def cap(n):
-        return n if args.max_iters <= 0 else min(n, args.max_iters)
-
-    def clock():
-        torch.cuda.synchronize()
-        return time.perf_counter()
-
-    if args.kg_eval:
-        kg_known = K.KnownTriples(full[:, 0], full[:, 1], full[:, 2], ds.n_KG_entity, ds.n_KG_relation, device=dev)
-        kg_pool = [torch.as_tensor(np.ascontiguousarray(kg_pool[:, c]), device=dev) for c in range(3)]
-
-    def kg_evaluate(rec):
-        t0 = clock()
-        m = model.kg_metrics(*kg_pool, known=kg_known, side="both", hits=(1, 3, 10))
-        rec["kg_eval_s"] = clock() - t0
-        rec["kg_mrr"], rec["kg_mr"], rec["kg_hits@10"] = m["mrr"], m["mr"], m["hits@10"]
-        say("           | KG link prediction, %d %s triples, both sides, filtered: kg_mrr %.5f kg_mr %.1f kg_hits@10 %.5f "
-            "| %.4fs" % (kg_pool[0].numel(), "held-out" if args.kg_holdout > 0 else "TRAINING (a fit measure)",
-                         m["mrr"], m["mr"], m["hits@10"], rec["kg_eval_s"]))
-
-    def evaluate(rec):
-        t0 = clock()
-        with torch.no_grad():
-            for name, g, seen, held in (("valid", train_g, train_dict, valid_dict), ("test", test_g, train_valid_dict, test_dict)):
-                g.edata["w"] = model.compute_attention(g)
-                emb = model.gnn(g, g.ndata["id"])
-                if getattr(args, "rank_metrics", 0):
-                    rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
-                    rank_Ks = [k for k in rank_Ks if k <= plans[name].n_items] or [plans[name].n_items]
-                    m = metrics.calc_rank_metrics(emb, seen, held, ds.item_id_range, Ks=rank_Ks, plan=plans[name])
-                    for metric in metrics.RANK_SCALAR_NAMES:
-                        rec["%s_%s" % (name, metric)] = float(m[metric])
-                    for j, k in enumerate(rank_Ks):
-                        for metric in metrics.METRIC_NAMES:
-                            rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                    say("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f | %s" % (
-                        name, m["auc"], m["mrr"], m["map"], m["mean_rank"],
-                        " ".join("recall@%d %.5f ndcg@%d %.5f" % (k, m["recall"][j], k, m["ndcg"][j])
-                                 for j, k in enumerate(rank_Ks))))
-                if args.Ks == [20]:
-                    rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
-                        emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
-                    say("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
-                    continue
-                m = metrics.calc_metrics(emb, seen, held, ds.item_id_range, Ks=args.Ks, plan=plans[name])
-                for j, k in enumerate(args.Ks):
-                    for metric in metrics.METRIC_NAMES:
-                        rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                    say("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
-                        name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
-        rec["eval_s"] = clock() - t0
-        say("           | eval %.4fs" % rec["eval_s"])
-        if args.kg_eval:
-            kg_evaluate(rec)
+    trip_cols = id_columns(ds.train_KG_triplet, dev)
 
     history = []
     if args.pretrain_epochs or args.pretrain_load or args.pretrain_save:
@@ -557,16 +760,15 @@ def _run(args, argv):
         # pretrain/<dataset>/mf.npz): get_loss on the raw table -> backward -> Adam, batches drawn as the CF phase's
         def evaluate_table(rec):
             emb = model.entity_embed.weight.detach()
-            for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict)):
+            for name in ("valid", "test"):
+                seen, held, plan = splits.of(name)
                 rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
-                    emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
+                    emb, seen, held, ds.item_id_range, K=20, plan=plan)
             return "test recall@20 %.5f ndcg@20 %.5f | valid recall@20 %.5f" % (
                 rec["test_recall"], rec["test_ndcg"], rec["valid_recall"])
 
         pre = {"loaded": args.pretrain_load, "saved": args.pretrain_save, "epochs": []}
-        if args.pretrain_load:
-            model.load_pretrained(*ckg_io.load_pretrain(args.pretrain_load), ds.n_users)
-            say("Pretrain   | user / item rows from %s" % args.pretrain_load)
+        load_mf(drv, model)
         pre["before"] = {}
         say("Pretrain 0000 | raw table: %s" % evaluate_table(pre["before"]))
         if args.pretrain_epochs:
@@ -574,103 +776,43 @@ def _run(args, argv):
             mf_opt = K.FusedAdam([model.entity_embed.weight], lr=args.lr if args.pretrain_lr is None else args.pretrain_lr)
             model.train()
         for ep in range(1, args.pretrain_epochs + 1):
-            t0 = clock()
-            n_it, bs = cap(n_pairs // args.pretrain_batch_size + 1), min(args.pretrain_batch_size, n_pairs)
-            idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
-            u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
-            n_all = torch.randint(off, off + ds.n_items, (n_it, bs), device=dev, dtype=torch.int32)
+            t0 = clock(dev)
+            n_it, u_all, p_all, n_all = draw_pairs(drv.pair_cols, args.pretrain_batch_size, drv.items, args.max_iters)
             total = model.mf_phase(u_all, p_all, n_all, mf_opt, reg_lambda=args.pretrain_regs).sum()
-            rec = {"epoch": ep, "mf_s": clock() - t0, "mf_iters": n_it}
+            rec = {"epoch": ep, "mf_s": clock(dev) - t0, "mf_iters": n_it}
             rec["mf_loss"] = float(total) / n_it
             say("Pretrain %04d | MF %.4fs (%d it, %.4f ms/it) mf_loss %.4f | %s" % (
                 ep, rec["mf_s"], n_it, 1e3 * rec["mf_s"] / n_it, rec["mf_loss"], evaluate_table(rec)))
             pre["epochs"].append(rec)
-            del idx, u_all, p_all, n_all
+            del u_all, p_all, n_all
         if args.pretrain_save:
             ckg_io.save_pretrain(args.pretrain_save, *model.pretrained_embeddings(ds.n_users, ds.n_items))
             say("Pretrain   | user / item rows written to %s" % args.pretrain_save)
         history.append({"epoch": 0, "pretrain": pre})
-    if args.eval_before:
-        model.eval()
-        if not history:
-            history.append({"epoch": 0})
-        say("Epoch 0000 | (untrained)")
-        evaluate(history[-1])
-    for epoch in range(1, args.epochs + 1):
-        rec = {"epoch": epoch}
-        t_epoch = clock()
-        # ---- KG phase (kgat.py:116-136).  The reference reads loss.item() after every step (a host round trip per
-        # iteration, kgat.py:132); here the running sum stays on the device and is read once per phase.
-        t0 = clock()
-        model.train()
-        n_it, bs = cap(n_trip // args.batch_size_kg + 1), min(args.batch_size_kg, n_trip)
-        idx = torch.randint(0, n_trip, (n_it, bs), device=dev)
-        h_all, r_all, t_all = trip_cols[0][idx], trip_cols[1][idx], trip_cols[2][idx]
-        neg_all = torch.randint(0, ds.n_KG_entity, (n_it, bs), device=dev, dtype=torch.int32)
-        # every iteration = transR -> backward -> step -> zero_grad of kgat.py:127-131: one launch sorts all batches,
-        # then one library call (three launches) per iteration; the losses stay on the device (kg_phase)
-        total = model.kg_phase(h_all, r_all, t_all, neg_all, opt).sum()
-        rec["kg_s"], rec["kg_iters"] = clock() - t0, n_it
-        rec["kg_loss"] = float(total) / n_it
-        say("Epoch %04d | KGE %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["kg_s"], n_it, 1e3 * rec["kg_s"] / n_it,
-                                                                     rec["kg_loss"]))
-        del idx, h_all, r_all, t_all, neg_all
+
+    def refresh(epoch, rec):
         # ---- attention refresh (kgat.py:139-145)
-        t0 = clock()
+        t0 = clock(dev)
         if not args.attention_grad:   # (--attention_grad 1: every CF step computes its own, differentiable weights)
             with torch.no_grad():
                 train_g.edata["w"] = model.compute_attention(train_g)
-        rec["attention_s"] = clock() - t0
+        rec["attention_s"] = clock(dev) - t0
         say("           | attention %.4fs" % rec["attention_s"])
-        # ---- CF phase (kgat.py:146-168): full-graph gnn for every batch
-        t0 = clock()
-        n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
-        idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
-        u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
-        n_all = torch.randint(off, off + ds.n_items, (n_it, bs), device=dev, dtype=torch.int32)
-        total = torch.zeros((), dtype=torch.float32, device=dev)
-        w_r_before = model.W_R.detach().clone()
-        # --grad_norm: every step leaves its gradient norm here; one readback at the end of the phase
-        norms = torch.zeros(n_it, dtype=torch.float32, device=dev) if args.grad_norm > 0 else None
-        for i in range(n_it):
-            if args.attention_grad:
-                train_g.edata["w"] = model.compute_attention(train_g, differentiable=True)
-            emb = model.gnn(train_g, train_g.ndata["id"])
-            loss = model.get_loss(emb, u_all[i], p_all[i], n_all[i])
-            loss.backward()
-            if args.grad_digest and epoch == 1 and i == 0:
-                say("           | grad digest: loss %.9g  " % loss.item() + "  ".join(
-                    "%s %.9g" % (k, p.grad.double().abs().sum().item()) for k, p in model.named_parameters()
-                    if p.grad is not None))
-            if norms is not None:   # clip_grad_norm_(model.parameters(), args.grad_norm) of kgat.py:162, inside the step
-                opt.step(max_grad_norm=args.grad_norm, norm_out=norms[i])
-            else:
-                opt.step()
-            opt.zero_grad()
-            total += loss.detach()
-        rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
-        rec["cf_loss"] = float(total) / n_it
-        rec["cf_W_R_change"] = float((model.W_R.detach() - w_r_before).abs().max())   # 0 unless --attention_grad 1
-        if norms is not None:
-            seen = norms.cpu().numpy()
-            if not np.isfinite(seen).all():
-                raise RuntimeError("epoch %d: the gradient norm of CF step %d is %r" % (
-                    epoch, int(np.flatnonzero(~np.isfinite(seen))[0]), float(seen[~np.isfinite(seen)][0])))
-            rec["cf_grad_norm_max"], rec["cf_grad_norm_mean"] = float(seen.max()), float(seen.mean())
-            # (the test the kernel applies: coef = min(c / (norm + 1e-6), 1) in fp32 is below 1)
-            c32 = np.float32(args.grad_norm)
-            rec["cf_clipped_steps"] = int((c32 / (seen + np.float32(1e-6)) < np.float32(1)).sum())
-            say("           | grad norm max %.4g mean %.4g, %d of %d steps clipped at %g" % (
-                rec["cf_grad_norm_max"], rec["cf_grad_norm_mean"], rec["cf_clipped_steps"], n_it, args.grad_norm))
-        say("           | GNN %.4fs (%d it, %.4f ms/it) loss %.4f" % (rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it, rec["cf_loss"]))
-        del idx, u_all, p_all, n_all
-        replicas_agree("epoch %d" % epoch)
-        # ---- evaluation (kgat.py:53-62, 171-196)
-        model.eval()
-        evaluate(rec)
-        rec["epoch_s"] = clock() - t_epoch
-        say("           | epoch %.4fs" % rec["epoch_s"])
-        history.append(rec)
+
+    def cf_loss(u, p, n):   # full-graph gnn for every batch
+        if args.attention_grad:
+            train_g.edata["w"] = model.compute_attention(train_g, differentiable=True)
+        return model.get_loss(model.gnn(train_g, train_g.ndata["id"]), u, p, n)
+
+    def eval_inputs():
+        for g in (train_g, test_g):
+            g.edata["w"] = model.compute_attention(g)
+            yield model.gnn(g, g.ndata["id"])
+
+    fam = Family(model, [lambda epoch, rec: drv.kg_phase(rec, model, opt, trip_cols), refresh,
+                         lambda epoch, rec: drv.cf_phase(epoch, rec, opt, cf_loss, label="GNN", kgat=model),
+                         lambda epoch, rec: replicas_agree("epoch %d" % epoch)], eval_inputs, trip_cols.shape[1])
+    drv.run(fam, history)
     if args.explain:
         # why the top-1 item?  the walk of highest attention product from it to the user, within as many hops as the
         # model has layers (test graph, the weights of the last evaluation's parameters)
@@ -678,8 +820,8 @@ def _run(args, argv):
         with torch.no_grad():
             test_g.edata["w"] = model.compute_attention(test_g)
             emb = model.gnn(test_g, test_g.ndata["id"])
-            users = sorted(test_dict)[:args.explain]
-            top1 = metrics.recommend(emb, users, ds.item_id_range, 1, seen=train_valid_dict)[0][:, 0].tolist()
+            users = sorted(splits.test_dict)[:args.explain]
+            top1 = metrics.recommend(emb, users, ds.item_id_range, 1, seen=splits.train_valid_dict)[0][:, 0].tolist()
             if args.explain_top == 1:
                 paths, ranked = model.explain(test_g, users, [max(i, 0) for i in top1]), None
             else:
@@ -695,27 +837,19 @@ def _run(args, argv):
                     break
                 say("explain+ | user %d item %d | rank %d | len %d | score %.6g | %s"
                     % (u, i, r + 1, int(ranked.ranked_len[q, r]), float(ranked.ranked_score[q, r]), ranked.describe(q, r)))
-    if args.log_json and rank == 0:
-        import json
-        with open(args.log_json, "w") as f:
-            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
-                       "n_relations": ds.n_KG_relation, "n_train_triplets": int(n_trip), "n_train_pairs": int(n_pairs),
-                       "epochs": history}, f, indent=1)
+    drv.write_log(fam, history)
     if world > 1:
         dist.destroy_process_group()
     return history
 
 
-def _run_kge(args, ds, dev, kg_pool, full):
-    """--model cfkg / cke on one GPU.  cfkg: an epoch is a TransE KG phase over ALL training triples of the collaborative
-    KG (interactions included), then evaluation on CFKG.readout.  cke: a TransR KG phase over the item-KG triples, a CF
-    phase of BPR steps on CKE.readout, then evaluation.  Samplers, the optimiser (one FusedAdam over all parameters) and
-    the metrics are the kgat run's; the records carry the same keys where the phase exists."""
-    kind = args.model
-    off, n_items = ds.n_users, ds.n_items
-    items = (off, off + n_items)
+def _kge_family(drv):
+    """--model cfkg / cke.  cfkg: an epoch is a TransE KG phase over ALL training triples of the collaborative KG
+    (interactions included), then evaluation on CFKG.readout.  cke: a TransR KG phase over the item-KG triples, a CF
+    phase of BPR steps on CKE.readout, then evaluation.  One FusedAdam over all parameters."""
+    args, ds, dev = drv.args, drv.ds, drv.dev
+    kind, off, items = args.model, ds.n_users, drv.items
     trip = ds.train_KG_triplet
-    is_uv = (trip[:, 0] < off) | (trip[:, 2] < off)
     if kind == "cfkg":
         forward = trip[(trip[:, 0] < off) & (trip[:, 2] >= off)]
         if len(forward) == 0:
@@ -723,136 +857,33 @@ def _run_kge(args, ds, dev, kg_pool, full):
         interact = int(forward[:, 1].min())
         model = K.CFKG(ds.n_KG_entity, ds.n_KG_relation, dim=args.entity_embed_dim).to(dev)
     else:
-        trip = trip[~is_uv]
+        trip = trip[~((trip[:, 0] < off) | (trip[:, 2] < off))]
         if len(trip) == 0:
             raise SystemExit("--model cke: the training triples hold no item-KG triple")
         model = K.CKE(ds.n_KG_entity, ds.n_KG_relation, dim=args.entity_embed_dim, relation_dim=args.relation_embed_dim).to(dev)
     print("--model %s | %d KG-phase triples" % (kind, len(trip)))
-    if args.pretrain_load:
-        model.load_pretrained(*ckg_io.load_pretrain(args.pretrain_load), ds.n_users)
-        print("Pretrain   | user / item rows from %s" % args.pretrain_load)
+    load_mf(drv, model)
     opt = K.FusedAdam(model.parameters(), lr=args.lr)
-    trip_cols = torch.as_tensor(np.ascontiguousarray(trip.T.astype(np.int32)), device=dev)
-    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
-    n_trip, n_pairs = trip_cols.shape[1], pair_cols.shape[1]
-    train_dict = user_dict(ds.train_pairs, off)
-    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
-    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
-    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
-             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
+    trip_cols = id_columns(trip, dev)
+    phases = [lambda epoch, rec: drv.kg_phase(rec, model, opt, trip_cols)]
+    if kind == "cke":
+        phases.append(lambda epoch, rec: drv.cf_phase(
+            epoch, rec, opt, lambda u, p, n: model.get_loss(model.readout(items), u, p, n)))
 
-    def cap(n):
-        return n if args.max_iters <= 0 else min(n, args.max_iters)
+    def eval_inputs():
+        emb = (model.readout(interact, (0, off), items) if kind == "cfkg" else model.readout(items)).contiguous()
+        return emb, emb
 
-    def clock():
-        torch.cuda.synchronize()
-        return time.perf_counter()
-
-    if args.kg_eval:
-        kg_known = K.KnownTriples(full[:, 0], full[:, 1], full[:, 2], ds.n_KG_entity, ds.n_KG_relation, device=dev)
-        kg_pool = [torch.as_tensor(np.ascontiguousarray(kg_pool[:, c]), device=dev) for c in range(3)]
-
-    def evaluate(rec):
-        t0 = clock()
-        with torch.no_grad():
-            emb = (model.readout(interact, (0, off), items) if kind == "cfkg" else model.readout(items)).contiguous()
-            for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict)):
-                if getattr(args, "rank_metrics", 0):
-                    rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
-                    rank_Ks = [k for k in rank_Ks if k <= plans[name].n_items] or [plans[name].n_items]
-                    m = metrics.calc_rank_metrics(emb, seen, held, ds.item_id_range, Ks=rank_Ks, plan=plans[name])
-                    for metric in metrics.RANK_SCALAR_NAMES:
-                        rec["%s_%s" % (name, metric)] = float(m[metric])
-                    for j, k in enumerate(rank_Ks):
-                        for metric in metrics.METRIC_NAMES:
-                            rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                    print("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f" % (
-                        name, m["auc"], m["mrr"], m["map"], m["mean_rank"]))
-                if args.Ks == [20]:
-                    rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
-                        emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
-                    print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
-                    continue
-                m = metrics.calc_metrics(emb, seen, held, ds.item_id_range, Ks=args.Ks, plan=plans[name])
-                for j, k in enumerate(args.Ks):
-                    for metric in metrics.METRIC_NAMES:
-                        rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                    print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
-                        name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
-        rec["eval_s"] = clock() - t0
-        print("           | eval %.4fs" % rec["eval_s"])
-        if args.kg_eval:
-            t0 = clock()
-            m = model.kg_metrics(*kg_pool, known=kg_known, side="both", hits=(1, 3, 10))
-            rec["kg_eval_s"] = clock() - t0
-            rec["kg_mrr"], rec["kg_mr"], rec["kg_hits@10"] = m["mrr"], m["mr"], m["hits@10"]
-            print("           | KG link prediction, %d %s triples, both sides, filtered: kg_mrr %.5f kg_mr %.1f kg_hits@10 "
-                  "%.5f | %.4fs" % (kg_pool[0].numel(), "held-out" if args.kg_holdout > 0 else "TRAINING (a fit measure)",
-                                    m["mrr"], m["mr"], m["hits@10"], rec["kg_eval_s"]))
-
-    history = []
-    if args.eval_before:
-        model.eval()
-        history.append({"epoch": 0})
-        print("Epoch 0000 | (untrained)")
-        evaluate(history[-1])
-    for epoch in range(1, args.epochs + 1):
-        rec = {"epoch": epoch}
-        t_epoch = clock()
-        t0 = clock()
-        model.train()
-        n_it, bs = cap(n_trip // args.batch_size_kg + 1), min(args.batch_size_kg, n_trip)
-        idx = torch.randint(0, n_trip, (n_it, bs), device=dev)
-        neg_all = torch.randint(0, ds.n_KG_entity, (n_it, bs), device=dev, dtype=torch.int32)
-        total = model.kg_phase(trip_cols[0][idx], trip_cols[1][idx], trip_cols[2][idx], neg_all, opt).sum()
-        rec["kg_s"], rec["kg_iters"] = clock() - t0, n_it
-        rec["kg_loss"] = float(total) / n_it
-        print("Epoch %04d | KGE %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["kg_s"], n_it, 1e3 * rec["kg_s"] / n_it,
-                                                                       rec["kg_loss"]))
-        del idx, neg_all
-        if kind == "cke":
-            t0 = clock()
-            n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
-            idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
-            u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
-            n_all = torch.randint(off, off + n_items, (n_it, bs), device=dev, dtype=torch.int32)
-            total = torch.zeros((), dtype=torch.float32, device=dev)
-            for i in range(n_it):
-                loss = model.get_loss(model.readout(items), u_all[i], p_all[i], n_all[i])
-                loss.backward()
-                if args.grad_norm > 0:
-                    opt.step(max_grad_norm=args.grad_norm)
-                else:
-                    opt.step()
-                opt.zero_grad()
-                total += loss.detach()
-            rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
-            rec["cf_loss"] = float(total) / n_it
-            print("           | CF %.4fs (%d it, %.4f ms/it) loss %.4f" % (rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it, rec["cf_loss"]))
-            del idx, u_all, p_all, n_all
-        model.eval()
-        evaluate(rec)
-        rec["epoch_s"] = clock() - t_epoch
-        print("           | epoch %.4fs" % rec["epoch_s"])
-        history.append(rec)
-    if args.log_json:
-        import json
-        with open(args.log_json, "w") as f:
-            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
-                       "n_relations": ds.n_KG_relation, "n_train_triplets": int(n_trip), "n_train_pairs": int(n_pairs),
-                       "epochs": history}, f, indent=1)
-    return history
+    return Family(model, phases, eval_inputs, len(trip))
 
 
-def _run_fm(args, ds, dev):
-    """--model fm / nfm on one GPU: an epoch is a CF phase of BPR steps - one pooled call over the 2 B feature sets
-    {user} + F(item), positives first, one FusedAdam over all parameters, --grad_norm honoured - then evaluation: FM on
-    its dot-product table (FM.readout) with the metrics of the other models, NFM through NFM.evaluate (block scores in
-    torch operators, torch.topk, the metric kernel).  The records carry the keys the other models' CF phase and
-    evaluation write."""
-    kind = args.model
-    off, n_items = ds.n_users, ds.n_items
-    items = (off, off + n_items)
+def _fm_family(drv):
+    """--model fm / nfm: an epoch is a CF phase of BPR steps - one pooled call over the 2 B feature sets {user} + F(item),
+    positives first, one FusedAdam over all parameters - then evaluation: FM on its dot-product table (FM.readout) with
+    the metrics of the other models, NFM through NFM.evaluate (block scores in torch operators, torch.topk, the metric
+    kernel)."""
+    args, ds, dev = drv.args, drv.ds, drv.dev
+    kind, items = args.model, drv.items
     feats = K.FeatureSets.from_kg(ds.train_KG_triplet, items, ds.n_KG_entity, device=dev)
     if kind == "fm":
         model = K.FM(ds.n_KG_entity, feats, dim=args.entity_embed_dim).to(dev)
@@ -861,110 +892,24 @@ def _run_fm(args, ds, dev):
                       dropout=args.dropout_rate).to(dev)
     print("--model %s | %d items, %d (item, feature) pairs, longest list %d" % (
         kind, feats.n_items, feats.n_pairs, int(np.diff(feats._host["indptr"]).max())))
-    if args.pretrain_load:
-        model.load_pretrained(*ckg_io.load_pretrain(args.pretrain_load), ds.n_users)
-        print("Pretrain   | user / item rows from %s" % args.pretrain_load)
+    load_mf(drv, model)
     opt = K.FusedAdam(model.parameters(), lr=args.lr)
-    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
-    n_pairs = pair_cols.shape[1]
-    train_dict = user_dict(ds.train_pairs, off)
-    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
-    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
-    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
-             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
 
-    def cap(n):
-        return n if args.max_iters <= 0 else min(n, args.max_iters)
+    def eval_inputs():
+        if kind == "nfm":
+            return (model.evaluate(drv.splits.plans[name], args.Ks) for name in ("valid", "test"))
+        emb = model.readout((0, ds.n_users), items).contiguous()
+        return emb, emb
 
-    def clock():
-        torch.cuda.synchronize()
-        return time.perf_counter()
-
-    def evaluate(rec):
-        t0 = clock()
-        with torch.no_grad():
-            emb = model.readout((0, off), items).contiguous() if kind == "fm" else None
-            for name, seen, held in (("valid", train_dict, valid_dict), ("test", train_valid_dict, test_dict)):
-                if getattr(args, "rank_metrics", 0):
-                    rank_Ks = getattr(args, "rank_Ks", [20, 200, 1000])
-                    rank_Ks = [k for k in rank_Ks if k <= plans[name].n_items] or [plans[name].n_items]
-                    m = metrics.calc_rank_metrics(emb, seen, held, ds.item_id_range, Ks=rank_Ks, plan=plans[name])
-                    for metric in metrics.RANK_SCALAR_NAMES:
-                        rec["%s_%s" % (name, metric)] = float(m[metric])
-                    for j, k in enumerate(rank_Ks):
-                        for metric in metrics.METRIC_NAMES:
-                            rec["%s_rank_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                    print("           | rank_metrics %s auc %.5f mrr %.5f map %.5f mean_rank %.1f" % (
-                        name, m["auc"], m["mrr"], m["map"], m["mean_rank"]))
-                if kind == "fm" and args.Ks == [20]:
-                    rec[name + "_recall"], rec[name + "_ndcg"] = metrics.calc_recall_ndcg(
-                        emb, seen, held, ds.item_id_range, K=20, plan=plans[name])
-                    print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
-                    continue
-                m = (metrics.calc_metrics(emb, seen, held, ds.item_id_range, Ks=args.Ks, plan=plans[name]) if kind == "fm"
-                     else model.evaluate(plans[name], args.Ks))
-                if args.Ks == [20]:
-                    rec[name + "_recall"], rec[name + "_ndcg"] = float(m["recall"][0]), float(m["ndcg"][0])
-                    print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
-                    continue
-                for j, k in enumerate(args.Ks):
-                    for metric in metrics.METRIC_NAMES:
-                        rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                    print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
-                        name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
-        rec["eval_s"] = clock() - t0
-        print("           | eval %.4fs" % rec["eval_s"])
-
-    history = []
-    if args.eval_before:
-        model.eval()
-        history.append({"epoch": 0})
-        print("Epoch 0000 | (untrained)")
-        evaluate(history[-1])
-    for epoch in range(1, args.epochs + 1):
-        rec = {"epoch": epoch}
-        t_epoch = clock()
-        t0 = clock()
-        model.train()
-        n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
-        idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
-        u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
-        n_all = torch.randint(off, off + n_items, (n_it, bs), device=dev, dtype=torch.int32)
-        total = torch.zeros((), dtype=torch.float32, device=dev)
-        for i in range(n_it):
-            loss = model.get_loss(u_all[i], p_all[i], n_all[i])
-            loss.backward()
-            if args.grad_norm > 0:
-                opt.step(max_grad_norm=args.grad_norm)
-            else:
-                opt.step()
-            opt.zero_grad()
-            total += loss.detach()
-        rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
-        rec["cf_loss"] = float(total) / n_it
-        print("Epoch %04d | CF %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it,
-                                                                      rec["cf_loss"]))
-        del idx, u_all, p_all, n_all
-        model.eval()
-        evaluate(rec)
-        rec["epoch_s"] = clock() - t_epoch
-        print("           | epoch %.4fs" % rec["epoch_s"])
-        history.append(rec)
-    if args.log_json:
-        import json
-        with open(args.log_json, "w") as f:
-            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
-                       "n_relations": ds.n_KG_relation, "n_train_pairs": int(n_pairs), "epochs": history}, f, indent=1)
-    return history
+    return Family(model, [lambda epoch, rec: drv.cf_phase(epoch, rec, opt, model.get_loss)], eval_inputs, None)
 
 
-def _run_ripple(args, ds, dev):
-    """--model ripplenet on one GPU: the ripple sets are built once on the host; an epoch is a CF phase of steps on the
-    pair stream of the other baselines - one pass over the 2 B samples, positives first, BCE with 1:1 negatives plus the
-    KGE and L2 terms (RippleNet.get_loss), one FusedAdam over all parameters, --grad_norm honoured - then evaluation
-    through RippleNet.evaluate (block scores in torch operators, torch.topk, the metric kernel).  The records carry the
-    keys the other models' CF phase and evaluation write."""
-    off, n_items = ds.n_users, ds.n_items
+def _ripple_family(drv):
+    """--model ripplenet: the ripple sets are built once on the host; an epoch is a CF phase of steps on the pair stream
+    of the other baselines - one pass over the 2 B samples, positives first, BCE with 1:1 negatives plus the KGE and L2
+    terms (RippleNet.get_loss), one FusedAdam over all parameters - then evaluation through RippleNet.evaluate (block
+    scores in torch operators, torch.topk, the metric kernel)."""
+    args, ds, dev = drv.args, drv.ds, drv.dev
     t0 = time.perf_counter()
     sets = K.RippleSets.build(ds.train_KG_triplet, ds.train_pairs, ds.n_users, ds.n_KG_entity, n_hop=getattr(args, "n_hop", 2),
                               n_memory=getattr(args, "n_memory", 32), seed=args.seed,
@@ -973,80 +918,10 @@ def _run_ripple(args, ds, dev):
         sets.n_hop, sets.n_memory, sets.n_rel, int((~sets.valid).sum()), sets.n_users, time.perf_counter() - t0))
     model = K.RippleNet(ds.n_KG_entity, sets, dim=args.entity_embed_dim, kge_weight=getattr(args, "kge_weight", 0.01),
                         item_update_mode=getattr(args, "item_update_mode", "plus_transform"),
-                        using_all_hops=bool(getattr(args, "using_all_hops", 1)), item_range=(off, off + n_items)).to(dev)
+                        using_all_hops=bool(getattr(args, "using_all_hops", 1)), item_range=drv.items).to(dev)
     opt = K.FusedAdam(model.parameters(), lr=args.lr)
-    pair_cols = torch.as_tensor(np.ascontiguousarray(ds.train_pairs[:, :2].T.astype(np.int32)), device=dev)
-    n_pairs = pair_cols.shape[1]
-    train_dict = user_dict(ds.train_pairs, off)
-    valid_dict, test_dict = user_dict(ds.valid_pairs, off), user_dict(ds.test_pairs, off)
-    train_valid_dict = user_dict(np.vstack([ds.train_pairs, ds.valid_pairs]), off)
-    plans = {"valid": metrics.EvalPlan(train_dict, valid_dict, ds.item_id_range, dev),
-             "test": metrics.EvalPlan(train_valid_dict, test_dict, ds.item_id_range, dev)}
-
-    def cap(n):
-        return n if args.max_iters <= 0 else min(n, args.max_iters)
-
-    def clock():
-        torch.cuda.synchronize()
-        return time.perf_counter()
-
-    def evaluate(rec):
-        t0 = clock()
-        for name in ("valid", "test"):
-            m = model.evaluate(plans[name], args.Ks)
-            if args.Ks == [20]:
-                rec[name + "_recall"], rec[name + "_ndcg"] = float(m["recall"][0]), float(m["ndcg"][0])
-                print("           | %s recall@20 %.5f ndcg@20 %.5f" % (name, rec[name + "_recall"], rec[name + "_ndcg"]))
-                continue
-            for j, k in enumerate(args.Ks):
-                for metric in metrics.METRIC_NAMES:
-                    rec["%s_%s@%d" % (name, metric, k)] = float(m[metric][j])
-                print("           | %s recall@%d %.5f ndcg@%d %.5f precision@%d %.5f hit_ratio@%d %.5f" % (
-                    name, k, m["recall"][j], k, m["ndcg"][j], k, m["precision"][j], k, m["hit_ratio"][j]))
-        rec["eval_s"] = clock() - t0
-        print("           | eval %.4fs" % rec["eval_s"])
-
-    history = []
-    if args.eval_before:
-        model.eval()
-        history.append({"epoch": 0})
-        print("Epoch 0000 | (untrained)")
-        evaluate(history[-1])
-    for epoch in range(1, args.epochs + 1):
-        rec = {"epoch": epoch}
-        t_epoch = clock()
-        t0 = clock()
-        model.train()
-        n_it, bs = cap(n_pairs // args.batch_size + 1), min(args.batch_size, n_pairs)
-        idx = torch.randint(0, n_pairs, (n_it, bs), device=dev)
-        u_all, p_all = pair_cols[0][idx], pair_cols[1][idx]
-        n_all = torch.randint(off, off + n_items, (n_it, bs), device=dev, dtype=torch.int32)
-        total = torch.zeros((), dtype=torch.float32, device=dev)
-        for i in range(n_it):
-            loss = model.get_loss(u_all[i], p_all[i], n_all[i])
-            loss.backward()
-            if args.grad_norm > 0:
-                opt.step(max_grad_norm=args.grad_norm)
-            else:
-                opt.step()
-            opt.zero_grad()
-            total += loss.detach()
-        rec["cf_s"], rec["cf_iters"] = clock() - t0, n_it
-        rec["cf_loss"] = float(total) / n_it
-        print("Epoch %04d | CF %.4fs (%d it, %.4f ms/it) loss %.4f" % (epoch, rec["cf_s"], n_it, 1e3 * rec["cf_s"] / n_it,
-                                                                      rec["cf_loss"]))
-        del idx, u_all, p_all, n_all
-        model.eval()
-        evaluate(rec)
-        rec["epoch_s"] = clock() - t_epoch
-        print("           | epoch %.4fs" % rec["epoch_s"])
-        history.append(rec)
-    if args.log_json:
-        import json
-        with open(args.log_json, "w") as f:
-            json.dump({"args": vars(args), "n_users": ds.n_users, "n_items": ds.n_items, "n_entities": ds.n_KG_entity,
-                       "n_relations": ds.n_KG_relation, "n_train_pairs": int(n_pairs), "epochs": history}, f, indent=1)
-    return history
+    return Family(model, [lambda epoch, rec: drv.cf_phase(epoch, rec, opt, model.get_loss)],
+                  lambda: (model.evaluate(drv.splits.plans[name], args.Ks) for name in ("valid", "test")), None)
 
 
 if __name__ == "__main__":
