@@ -39,6 +39,7 @@ SOURCES = {
     "kgat_transe.hip": [],
     "kgat_bi_pool.hip": [],
     "kgat_ripple.hip": [],
+    "kgat_nfm_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -241,6 +242,11 @@ SIGNATURES = {
     "kgat_ripple_hop_fwd_f32": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "kgat_ripple_hop_bwd_f32": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                        _p, _p]),
+    # all-pairs evaluation of a one-hidden-layer NFM: MLP scores into the K best unseen items (ABI 16, additive)
+    "kgat_nfm_eval_supported": (_i32, [_i32, _i32, _i32]),
+    "kgat_nfm_eval_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "kgat_nfm_eval_topk_f32": (_i32, [_i64, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _sz,
+                                      _p, _p, _p]),
 }
 
 _lib = None

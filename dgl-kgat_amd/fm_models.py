@@ -9,7 +9,9 @@ model, and the features of the pair (u, i) are the set ``{u} + F(i)`` with ``F(i
 
 (``autograd.bi_pool``: csrc/kgat_bi_pool.hip on a HIP device in fp32, ``bi_pool_torch`` elsewhere); FM is the same
 operator with its d outputs summed.  NFM's evaluation has no dot-product form: ``NFM.scores`` evaluates the MLP per
-(user, item) pair in torch operators over user blocks - a fused all-pairs MLP sweep is out of scope."""
+(user, item) pair in torch operators over user blocks (the default route); for a one-hidden-layer NFM on a HIP device
+``fused=True`` runs the all-pairs sweep of csrc/kgat_nfm_eval.hip instead (``ops.nfm_eval_topk``: MLP scores into the
+top-K lists, nothing of size users x items written)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -290,11 +292,88 @@ class NFM(_Pooled):
             self.train(was_training)
         return torch.cat(out, 0) if out else torch.zeros(0, self.feats.n_items, dtype=V.dtype, device=V.device)
 
-    def topk(self, plan, K, max_bytes=1 << 28):
-        """The K best unseen items of every user of an ``EvalPlan`` (``metrics.topk_unseen`` over ``scores``)."""
-        return metrics.topk_unseen(self.scores, self.feats.n_items, plan, K, max_bytes)
+    def _fused_refusal(self, K):
+        """Why the fused sweep cannot evaluate this model at depth K (None: it can)."""
+        linear = [m for m in self.mlp if isinstance(m, nn.Linear)]
+        V = self.embed.weight
+        if len(linear) != 1:
+            return "the fused sweep evaluates ONE hidden layer, the model has %d (layers=%r)" % (
+                len(linear), tuple(m.out_features for m in linear))
+        if not V.is_cuda:
+            return "the parameters are on %s: the fused sweep only runs on a HIP device (CPU tensors)" % V.device
+        if V.dtype != torch.float32:
+            return "the parameters are %s, the fused sweep is float32" % V.dtype
+        if not 1 <= int(K) <= ops.NFM_EVAL_MAX_K:
+            return "K = %d is outside 1..%d" % (K, ops.NFM_EVAL_MAX_K)
+        d, hidden = V.shape[1], linear[0].out_features
+        if not ops.nfm_eval_supported(d, hidden, K):
+            return "widths d = %d, hidden = %d: the fused sweep takes d in (16, 32, 64, 128), hidden in (16, 32, 64)" % (d, hidden)
+        return None
 
-    def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28):
-        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``
-        (``metrics.calc_metrics_unseen`` over ``scores``): the dict ``metrics.calc_metrics`` returns."""
-        return metrics.calc_metrics_unseen(self.scores, self.feats.n_items, plan, Ks, max_bytes)
+    @torch.no_grad()
+    def _fused_topk(self, what, user_ids, train_ptr, train_items, K, want_scores=True):
+        """``ops.nfm_eval_topk`` for rows `user_ids` (int32 node ids) of the table: the item side pooled once, one addmm
+        for ``C = T W1^T + b1``, the sweep.  No dropout, as ``scores``."""
+        why = self._fused_refusal(K)
+        if why is not None:
+            raise ops.KGATLibraryError("%s(fused=True): %s" % (what, why))
+        V, w = self.embed.weight.detach(), self.w_lin.detach()
+        fc = self.mlp[0]
+        P, T, lin = pool_items(V, w, self.feats)
+        W1 = fc.weight.detach().contiguous()
+        bias = fc.bias.detach() if fc.bias is not None else torch.zeros(W1.shape[0], dtype=V.dtype, device=V.device)
+        C = torch.addmm(bias, T, W1.t())
+        const = (self.w0.detach() + w[user_ids.long()]).contiguous()
+        return ops.nfm_eval_topk(V, user_ids, W1, P.contiguous(), C, self.h.detach().contiguous(), lin.contiguous(), const,
+                                 train_ptr, train_items, K, want_scores=want_scores)
+
+    def _check_plan(self, plan):
+        if plan.n_items != self.feats.n_items:
+            raise ValueError("topk: the plan ranks %d items, the model scores %d" % (plan.n_items, self.feats.n_items))
+
+    def topk(self, plan, K, max_bytes=1 << 28, fused=False):
+        """The K best unseen items of every user of an ``EvalPlan`` as item positions, (n_users, K) int32.  Default:
+        ``metrics.topk_unseen`` over ``scores`` (``torch.topk``).  ``fused=True``: the all-pairs sweep
+        (``ops.nfm_eval_topk``) - score descending, equal scores by item position, ``-1`` where a user has fewer than K
+        unseen items; ``KGATLibraryError`` naming the reason where the model or the device is outside its envelope."""
+        if not fused:
+            return metrics.topk_unseen(self.scores, self.feats.n_items, plan, K, max_bytes)
+        self._check_plan(plan)
+        return self._fused_topk("topk", plan.user_ids, plan.train_ptr, plan.train_items, K, want_scores=False)[0]
+
+    def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28, fused=False):
+        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``: the dict
+        ``metrics.calc_metrics`` returns.  Default: ``metrics.calc_metrics_unseen`` over ``scores``.  ``fused=True``:
+        ``topk(fused=True)`` at the largest cut-off, then ``ops.eval_metrics_at_ks``."""
+        if not fused:
+            return metrics.calc_metrics_unseen(self.scores, self.feats.n_items, plan, Ks, max_bytes)
+        Ks = [int(k) for k in Ks]
+        if plan.n_users == 0:
+            raise ZeroDivisionError("no test users")
+        self._check_plan(plan)
+        top = self._fused_topk("evaluate", plan.user_ids, plan.train_ptr, plan.train_items, Ks[-1], want_scores=False)[0]
+        out = ops.eval_metrics_at_ks(top, plan.test_ptr, plan.test_items, Ks)
+        mean = (out.sum(0) / plan.n_users).cpu().numpy()
+        return {name: mean[:, m].copy() for m, name in enumerate(metrics.METRIC_NAMES)}
+
+    def recommend(self, user_ids, K, seen=None):
+        """The K best items of every user of ``user_ids`` (node ids) that the user has not seen, on the fused sweep:
+        ``(items, scores)`` - int64 item NODE ids ``(len(user_ids), K)`` in rank order (score descending, equal scores by
+        item position) and their float32 scores ``y(u, i)``; ``-1`` / ``-inf`` at the end where fewer than K items are
+        unseen.  ``seen`` maps a user id to the item positions to leave out (None: nothing).  The counterpart of
+        ``metrics.recommend``; one hidden layer, HIP tensors, 1 <= K <= 128 (``KGATLibraryError`` otherwise)."""
+        users = [int(u) for u in np.asarray(user_ids).reshape(-1)]
+        why = self._fused_refusal(K)
+        if why is not None:
+            raise ops.KGATLibraryError("recommend: %s" % why)
+        lo = self.feats.item_offset
+        item_ids = np.arange(lo, lo + self.feats.n_items)
+        plan = metrics.EvalPlan(seen if seen is not None else {}, dict.fromkeys(users, metrics._EMPTY), item_ids,
+                                self.embed.weight.device)
+        if len(plan.user_ids) != len(users):
+            raise ValueError("recommend: a user is listed twice")
+        if plan.n_users and plan.max_node_id >= self.embed.weight.shape[0]:
+            raise IndexError("user / item node id %d outside the table's %d rows" % (plan.max_node_id, self.embed.weight.shape[0]))
+        pos, scores = self._fused_topk("recommend", plan.user_ids, plan.train_ptr, plan.train_items, K)
+        pos = pos.long()
+        return torch.where(pos >= 0, pos + lo, pos), scores

@@ -2112,6 +2112,71 @@ def bi_pool_bwd(V, feats, items, extra, S, g_bi=None, g_lin=None, g_sq=None, wan
     return grad_V, grad_w
 
 
+# ---------------------------------------------------------------- all-pairs NFM evaluation: MLP scores into top-K (kgat_nfm_eval_*)
+NFM_EVAL_MAX_K = 128
+
+
+def nfm_eval_supported(d, hidden, K):
+    """Sizes of the fused NFM evaluation sweep: d in {16, 32, 64, 128}, ONE hidden layer of 16, 32 or 64 units, 1 <= K <=
+    128.  The library's own envelope (kgat_nfm_eval_supported) starts at hidden = 32; nfm_eval_topk pads 16 units to 32
+    with zero rows of W1, zero columns of C and zero entries of h, which is exact (0 * relu(0) = 0)."""
+    hidden = int(hidden)
+    return bool(_lib.load().kgat_nfm_eval_supported(int(d), 32 if hidden == 16 else hidden, int(K)))
+
+
+def nfm_eval_topk(V, user_ids, W1, P, C, h, item_lin, user_const, train_ptr, train_items, K, want_scores=True):
+    """The K best unseen items of every user under a one-hidden-layer NFM (kgat_eval_items_kmajor_f32 over P +
+    kgat_nfm_eval_topk_f32; the arithmetic is stated in include/kgat_hip.h).  V (N, d) fp32 rows, user_ids int32 rows of
+    V; W1 (hidden, d), h (hidden); P (n_items, d), C = T W1^T + b1 (n_items, hidden), item_lin (n_items): the item side
+    of fm_models.pool_items; user_const (n_users) or None: added to every listed score; the train CSR holds ascending
+    item positions per user.  Returns (items, scores): int32 positions (n_users, K), -1 padding, and float32 scores, -inf
+    padding (None without want_scores)."""
+    if V.dtype != torch.float32 or not V.is_cuda or V.dim() != 2 or V.stride(1) != 1:
+        raise KGATLibraryError("nfm_eval_topk: `V` must be a float32 HIP matrix with unit column stride")
+    d, K = V.shape[1], int(K)
+    user_ids = _need(user_ids, torch.int32, "user_ids")
+    n_users = user_ids.numel()
+    W1 = _need(W1, torch.float32, "W1")
+    if W1.dim() != 2 or W1.shape[1] != d:
+        raise ValueError("W1 must be (hidden, %d), got %s" % (d, tuple(W1.shape)))
+    hidden = W1.shape[0]
+    P = _need(P, torch.float32, "P")
+    if P.dim() != 2 or P.shape[1] != d:
+        raise ValueError("P must be (n_items, %d), got %s" % (d, tuple(P.shape)))
+    n_items = P.shape[0]
+    C = _need(C, torch.float32, "C", (n_items, hidden))
+    h = _need(h, torch.float32, "h", (hidden,))
+    item_lin = _need(item_lin, torch.float32, "item_lin", (n_items,))
+    if user_const is not None:
+        user_const = _need(user_const, torch.float32, "user_const", (n_users,))
+    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_users + 1,))
+    train_items = _need(train_items, torch.int32, "train_items")
+    if not nfm_eval_supported(d, hidden, K):
+        raise KGATLibraryError("nfm_eval_topk: d = %d (16, 32, 64, 128), hidden = %d (16, 32, 64) or K = %d (1..%d) outside "
+                               "the kernel's range" % (d, hidden, K, NFM_EVAL_MAX_K))
+    if n_items < 1:
+        raise KGATLibraryError("nfm_eval_topk: no items to rank")
+    lib = _lib.load()
+    dev = V.device
+    if hidden == 16:   # zero units up to the kernel's block of 32
+        W1 = torch.cat([W1, torch.zeros_like(W1)], 0)
+        C = torch.cat([C, torch.zeros_like(C)], 1).contiguous()
+        h = torch.cat([h, torch.zeros_like(h)], 0)
+        hidden = 32
+    topk = torch.empty((n_users, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((n_users, K), dtype=torch.float32, device=dev) if want_scores else None
+    if n_users == 0:
+        return topk, scores
+    ws = _workspace(lib.kgat_nfm_eval_scratch_bytes(n_users, n_items, d, hidden, K), dev)
+    itemT = _eval_items(lib, P, torch.arange(n_items, dtype=torch.int32, device=dev))
+    with _timed("nfm_eval_topk", (n_users, n_items, d, hidden, K)):
+        check(lib.kgat_nfm_eval_topk_f32(n_users, _ptr(user_ids), n_items, d, hidden, _ptr(V), V.stride(0), _ptr(W1),
+                                         _ptr(itemT), _ptr(C), _ptr(h), _ptr(item_lin), _ptr(user_const), _ptr(train_ptr),
+                                         _ptr(train_items), K, _ptr(ws), ws.numel(), _ptr(topk), _ptr(scores),
+                                         _stream(V)), "kgat_nfm_eval_topk_f32")
+    return topk, scores
+
+
 # ---------------------------------------------------------------- ripple-set attention, the RippleNet baseline (kgat_ripple_*)
 def ripple_supported(d, n_memory, n_rel, n_samples):
     """Sizes of the ripple-set kernels: d in {16, 32, 64, 128}, 1 <= n_memory <= 128, 1 <= n_rel <= 4096, n_samples >= 1

@@ -233,6 +233,10 @@ def parse_args(argv=None):
                          "kg_final.txt already contains the inverses).  Default 0")
     ap.add_argument("--nfm_layers", type=_widths, default=argparse.SUPPRESS, metavar="W[,W...]",
                     help="--model nfm: widths of the hidden layers above the pooling (default 64)")
+    ap.add_argument("--nfm_eval", choices=("torch", "fused"), default=argparse.SUPPRESS,
+                    help="--model nfm: how an epoch is evaluated - torch (default): block scores in torch operators and "
+                         "torch.topk; fused: the all-pairs sweep of kgat_nfm_eval.hip (one hidden layer of 16, 32 or 64 "
+                         "units, cut-offs up to 128)")
     ap.add_argument("--num_bases", type=int, default=argparse.SUPPRESS,
                     help="bases of the rgcn layers' relation weights (default 4; at most the number of relations)")
     ap.add_argument("--res_type", choices=("Bi", "GCN", "GraphSage", "Bi2"), default="Bi",
@@ -341,6 +345,8 @@ def parse_args(argv=None):
             ap.error("--%s belongs to --model ripplenet" % flag)
     if hasattr(args, "nfm_layers") and kind != "nfm":
         ap.error("--nfm_layers sets the hidden layers of --model nfm")
+    if hasattr(args, "nfm_eval") and kind != "nfm":
+        ap.error("--nfm_eval chooses the evaluation route of --model nfm")
     if args.pretrain_epochs < 0 or args.pretrain_batch_size < 1:
         ap.error("--pretrain_epochs takes a number of epochs >= 0, --pretrain_batch_size a batch >= 1")
     if (args.pretrain_epochs or args.pretrain_load or args.pretrain_save) and args.gpus > 1:
@@ -881,7 +887,7 @@ def _fm_family(drv):
     """--model fm / nfm: an epoch is a CF phase of BPR steps - one pooled call over the 2 B feature sets {user} + F(item),
     positives first, one FusedAdam over all parameters - then evaluation: FM on its dot-product table (FM.readout) with
     the metrics of the other models, NFM through NFM.evaluate (block scores in torch operators, torch.topk, the metric
-    kernel)."""
+    kernel; with --nfm_eval fused the all-pairs sweep instead of the first two)."""
     args, ds, dev = drv.args, drv.ds, drv.dev
     kind, items = args.model, drv.items
     feats = K.FeatureSets.from_kg(ds.train_KG_triplet, items, ds.n_KG_entity, device=dev)
@@ -897,7 +903,8 @@ def _fm_family(drv):
 
     def eval_inputs():
         if kind == "nfm":
-            return (model.evaluate(drv.splits.plans[name], args.Ks) for name in ("valid", "test"))
+            fused = getattr(args, "nfm_eval", "torch") == "fused"
+            return (model.evaluate(drv.splits.plans[name], args.Ks, fused=fused) for name in ("valid", "test"))
         emb = model.readout((0, ds.n_users), items).contiguous()
         return emb, emb
 

@@ -1312,6 +1312,48 @@ int kgat_ripple_hop_bwd_f32(int64_t n_samples, int d, int n_memory, int n_rel, i
                             const int32_t* mem_t, const int32_t* users, const float* p, const float* g_o, float* grad_U,
                             float* gl, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- all-pairs NFM evaluation: MLP scores into top-K (additive within ABI 16)
+ * The K best unseen items of every user under a one-hidden-layer NFM, y(u, i) = w0 + w_lin[u] + lin_i + sum_j h_j
+ * relu(pre[u, i, j]), without a users x items tensor.  With (P, T, lin) the pooled item side (bi({u} + F(i)) = v_u * P_i +
+ * T_i) the caller passes itemT = kgat_eval_items_kmajor_f32(emb = P, F = d, item_ids = 0 .. n_items - 1), C = T W1^T +
+ * b1 (n_items x hidden, row-major, contiguous), W1 (hidden x d, row-major, contiguous), h (hidden), item_lin (n_items),
+ * V with row stride v_stride (user_ids are rows of V), the users' ascending training lists as a CSR over positions in
+ * user_ids (train_ptr: n_users + 1) of item positions, and optionally user_const (n_users; w0 + w_lin[u]).
+ *
+ * The arithmetic, to the operation order (all fp32, inputs finite):
+ *     a[j, c]  = fl(W1[j, c] * V[user, c])                                             one multiply
+ *     pre[j]   = fma(a[j, d-1], P_i[d-1], ... fma(a[j, 1], P_i[1], fma(a[j, 0], P_i[0], C_i[j])))   ascending c from C
+ *                (v_mfma_f32_32x32x2_f32: an exact fmaf chain in k order)
+ *     r[j]     = max(pre[j], 0)
+ *     s_i      = A + B, where hidden unit j = 32 b + 8 q + 4 m + e (e < 4, m < 2, q < 4, b < hidden / 32) belongs to
+ *                half m, A (m = 0) and B (m = 1) each start from 0 and add their units by p = fma(h_j, r[j], p) in
+ *                ascending (b, q, e)
+ *     key_i    = s_i + item_lin[i]
+ *     score    = key_i + user_const[u]   (key_i itself where user_const is NULL), formed once per listed item
+ * Items are ordered by (key descending, IEEE compare with -0 = +0; equal keys: ascending item position); training
+ * items are never listed; a user with fewer than K unseen items gets -1 / -inf at the end of topk_items /
+ * topk_scores (n_users x K each; topk_scores may be NULL).  The order is total and no float atomic is used: the lists
+ * are bitwise reproducible and independent of how the entry cuts the items into segments, of the other users of the
+ * call, and of K as far as the shorter list reaches.  A user id may repeat.
+ *
+ * The entry lays C out in the scratch (a lane's sixteen accumulator values as 16-byte loads), sweeps one user per
+ * wavefront over item tiles of 32 (one 16-byte fragment load feeds 4 x hidden / 32 MFMAs), keeps per user a candidate
+ * buffer of 256 entries in LDS that a selection prunes to K, and merges the segments' lists with one wavefront per user.
+ *
+ * kgat_nfm_eval_supported(d, hidden, K): d in {16, 32, 64, 128}, hidden in {32, 64}, 1 <= K <= 128.  hidden = 16 is served
+ * by the caller padding W1's rows, C's columns and h with zeros to 32 (exact: 0 * relu(0) = 0); hidden = 128 and deeper
+ * MLPs are not offered.  n_users < 0, n_items outside [1, 2^31 - 32), v_stride < d, a null pointer other than
+ * user_const / topk_scores / train_items (no training item at all), itemT or scratch not 16-byte aligned: KGAT_E_BADARG; outside the envelope:
+ * KGAT_E_UNSUPPORTED; scratch below kgat_nfm_eval_scratch_bytes(n_users, n_items, d, hidden, K): KGAT_E_WORKSPACE.
+ * Every check precedes any device work. */
+int kgat_nfm_eval_supported(int d, int hidden, int K);
+size_t kgat_nfm_eval_scratch_bytes(int64_t n_users, int64_t n_items, int d, int hidden, int K);
+int kgat_nfm_eval_topk_f32(int64_t n_users, const int32_t* user_ids, int64_t n_items, int d, int hidden, const float* V,
+                           int64_t v_stride, const float* W1, const float* itemT, const float* C, const float* h,
+                           const float* item_lin, const float* user_const, const int32_t* train_ptr,
+                           const int32_t* train_items, int K, void* scratch, size_t scratch_bytes, int32_t* topk_items,
+                           float* topk_scores, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
