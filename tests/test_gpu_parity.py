@@ -11,6 +11,7 @@ import torch
 
 from conftest import (readout_abs_bar, GOLDEN_CASES, blocks, blocks_rel_err_inf, load_golden, parity_8c, parity_8c_robust, rel_err,
                       rel_err_inf, sum_err)
+import _spmm_fwd_ref as fwd
 from oracle import c_oracle as co
 from oracle import kgat_oracle as orc
 
@@ -174,14 +175,20 @@ def test_spmm_vs_oracle(K, dev, D, name, n, e, hub, iso):
     Xd, wd = tf(X, dev), tf(w, dev)
     w_csr = ops.gather(eid, wd) if e else wd
     algos = ["generic"] + (["merge", "merge1", "rows"] if D in (4, 8, 16, 32, 64, 128, 256) else [])
+    deg = np.bincount(dst, minlength=n)
     for algo in algos:
+        # beside the relative bar: every row within gamma_{L+1} of ITS sum of |terms| (tests/_spmm_fwd_ref.py)
+        what = "%s D=%d %s " % (name, D, algo)
         out = ops.spmm(indptr, col, row_of, Xd, w_csr, algo=algo).cpu().numpy()
         assert out.shape == (n, D)
         assert sum_err(out, ref, ref_abs) < TOL, (algo, "csr-order w")
+        fwd.check_gamma(out, ref, ref_abs, deg, 0, what + "csr-order w")
         out = ops.spmm(indptr, col, row_of, Xd, wd, eid=eid, algo=algo).cpu().numpy()
         assert sum_err(out, ref, ref_abs) < TOL, (algo, "edge-id-order w")
+        fwd.check_gamma(out, ref, ref_abs, deg, 0, what + "edge-id-order w")
         out = ops.spmm(indptr, col, row_of, Xd, w_csr, algo=algo, mul_self=True).cpu().numpy()
         assert sum_err(out, ref_self, ref_self_abs) < TOL, (algo, "mul_self")
+        fwd.check_gamma(out, ref_self, ref_self_abs, deg, 1, what + "mul_self")
         # destinations without in-edges are written as exact zeros, on a dirty output buffer
         dirty = torch.full((n, D), 7.0, device=dev)
         ops.spmm(indptr, col, row_of, Xd, w_csr, out=dirty, algo=algo)
@@ -190,6 +197,7 @@ def test_spmm_vs_oracle(K, dev, D, name, n, e, hub, iso):
         order = ops.row_order_by_degree(indptr)
         out = ops.spmm(indptr, col, row_of, Xd, w_csr, algo="rows", order=order).cpu().numpy()
         assert sum_err(out, ref, ref_abs) < TOL
+        fwd.check_gamma(out, ref, ref_abs, deg, 0, "%s D=%d rows, ordered" % (name, D))
         # the rows kernel adds in CSR order with one fma per edge: bit-exact vs the C restatement
         cref = co.spmm(n, indptr.cpu().numpy(), col.cpu().numpy(), None, X, w_csr.cpu().numpy())
         assert np.array_equal(out, cref)
@@ -201,11 +209,17 @@ def test_spmm_vs_oracle(K, dev, D, name, n, e, hub, iso):
 
 @pytest.mark.parametrize("D", [4, 8, 16, 32, 64, 128, 256])
 def test_spmm_long_runs_every_width(K, dev, D):
-    """Launches over few edges take a quarter of the run length (kgat_spmm.hip: short_run_len), so
-    the graphs above exercise the short runs; this one is large enough (4.3 M edges) for the full
-    run length at every width, hubs and empty rows included."""
-    from dgl_kgat_amd import ops
+    """Launches over few edges take a quarter of the run length (kgat_spmm_plan.h: short_run_len), so
+    the graphs above exercise the short runs; this one (4.3 M edges, hubs and empty rows included) is past them
+    at every width: the full run length at D = 4, 8, 64, 128 and 256, the HALF-length runs at D = 16 and 32,
+    whose full-length kernels take more than 8,388,608 edges - tests/test_gpu_sparse_forward.py runs those
+    (and every other class of every width) on its 8.4 M-edge graph, at exact and worst-case bars."""
+    from dgl_kgat_amd import _lib, ops
     n, e = 20000, 4_300_000
+    cls, _, te = fwd.tile_rule(D, e)
+    assert (cls, te) == (("half", 512) if D in (16, 32) else ("full", fwd.CLASS_TABLE[D][2])), (D, cls, te)
+    if D in (16, 32, 64, 128):   # the widths the library answers for: half at 16 and 32, full at 64 (1,024) and 128 (512)
+        assert int(_lib.load().kgat_spmm_tile_edges(e, D)) == te
     src, dst = random_graph(31, n, e, hub=600_000, isolated_tail=500)
     rng = np.random.default_rng(32)
     X = rng.standard_normal((n, D)).astype(np.float32)
@@ -242,6 +256,7 @@ def test_spmm_row_range_shard(K, dev):
                            e_range=(int(ip[lo]), int(ip[hi])), algo=algo).cpu().numpy()
             assert out.shape == (hi - lo, D)
             assert sum_err(out, ref[lo:hi], ref_abs[lo:hi]) < TOL, (lo, hi, algo)
+            fwd.check_gamma(out, ref[lo:hi], ref_abs[lo:hi], np.diff(ip)[lo:hi], 0, "shard [%d, %d) %s" % (lo, hi, algo))
 
 
 @pytest.mark.parametrize("D", [16, 32, 64, 128])

@@ -14,6 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import _spmm_fwd_ref as fwd  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -91,6 +93,10 @@ def test_copy_reduce_matches_fp64_and_is_reproducible(dev, kind, D):
             continue
         assert _scale_err(a.cpu().numpy(), ref) <= 1e-6, (kind, D, reduce, _scale_err(a.cpu().numpy(), ref))
         deg = np.bincount(dst, minlength=n)
+        # beside the tensor-scale bar: every row within gamma_{L+1} (sum) / gamma_{L+2} (mean: one division) of ITS sum
+        # of |terms| (tests/_spmm_fwd_ref.py), so a wrong short row beside the hub row shows
+        A = _copy_reduce_ref(n, src, dst, np.abs(Xh), reduce)
+        fwd.check_gamma(a.cpu().numpy(), ref, A, deg, int(reduce == "mean"), "%s D=%d %s" % (kind, D, reduce))
         assert not a[torch.as_tensor(deg == 0, device=dev)].any()
         # a row range and its edge range (what a destination shard launches)
         ip = csr.indptr.cpu().numpy()
@@ -99,6 +105,8 @@ def test_copy_reduce_matches_fp64_and_is_reproducible(dev, kind, D):
                                   e_range=(int(ip[row0]), int(ip[row0 + nr])))
             err = float(np.abs(sub.cpu().numpy() - ref[row0:row0 + nr]).max()) / max(np.abs(ref).max(), 1e-30)
             assert err <= 1e-6, (kind, D, reduce, row0, err)
+            fwd.check_gamma(sub.cpu().numpy(), ref[row0:row0 + nr], A[row0:row0 + nr], deg[row0:row0 + nr],
+                            int(reduce == "mean"), "%s D=%d %s rows [%d, +%d)" % (kind, D, reduce, row0, nr))
 
 
 def test_update_all_copy_src_mean_and_its_backward(dev):
