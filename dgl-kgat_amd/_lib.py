@@ -40,6 +40,7 @@ SOURCES = {
     "kgat_bi_pool.hip": [],
     "kgat_ripple.hip": [],
     "kgat_nfm_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "kgat_ripple_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "kgat_hip.h")
 
@@ -247,6 +248,13 @@ SIGNATURES = {
     "kgat_nfm_eval_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "kgat_nfm_eval_topk_f32": (_i32, [_i64, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _sz,
                                       _p, _p, _p]),
+    # all-pairs evaluation of RippleNet: per-user key table, then attention scores into the K best unseen items (ABI 16,
+    # additive)
+    "kgat_eval_ripple_supported": (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    "kgat_eval_ripple_keys_f32": (_i32, [_i64, _p, _i32, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "kgat_eval_ripple_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "kgat_eval_ripple_topk_f32": (_i32, [_i64, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p,
+                                         _p, _i32, _p, _sz, _p, _p, _p]),
 }
 
 _lib = None

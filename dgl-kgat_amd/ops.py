@@ -2252,6 +2252,105 @@ def ripple_scatter(U, sets, users, hop, p, gl, g_o):
     return out
 
 
+# ---------------------------------------------------------------- all-pairs RippleNet evaluation: attention scores into top-K (kgat_eval_ripple_*)
+RIPPLE_EVAL_MAX_K = 128
+RIPPLE_EVAL_MODES = ("replace", "plus", "replace_transform", "plus_transform")
+
+
+def ripple_eval_supported(d, n_memory, n_hop, mode, K):
+    """Sizes of the fused RippleNet evaluation sweep: d in {16, 32, 64}, 1 <= n_memory <= 64, n_hop in {1, 2}, mode 0..3
+    (the position in RIPPLE_EVAL_MODES), 1 <= K <= 128 (kgat_eval_ripple_supported)."""
+    return bool(_lib.load().kgat_eval_ripple_supported(int(d), int(n_memory), int(n_hop), int(mode), int(K)))
+
+
+def _ripple_eval_operands(who, ent, sets, user_ids):
+    if not isinstance(ent, torch.Tensor) or ent.dtype != torch.float32 or not ent.is_cuda or ent.dim() != 2 or \
+            not ent.is_contiguous():
+        raise KGATLibraryError("%s: `ent` must be a contiguous float32 HIP matrix" % who)
+    if ent.shape[0] != sets.n_nodes:
+        raise ValueError("ent must be (%d, d), got %s" % (sets.n_nodes, tuple(ent.shape)))
+    user_ids = _need(user_ids, torch.int32, "user_ids")
+    if user_ids.dim() != 1:
+        raise ValueError("user_ids must be one-dimensional")
+    for name in ("mem_h", "mem_r", "mem_t"):
+        _need(getattr(sets, name), torch.int32, "sets." + name, (sets.n_users, sets.n_hop, sets.n_memory))
+    if sets.mem_h.device != ent.device:
+        raise ValueError("the ripple sets are on %s, ent on %s" % (sets.mem_h.device, ent.device))
+    return user_ids
+
+
+def ripple_eval_keys(ent, relation_emb, sets, user_ids):
+    """The key table of the users `user_ids` (int32): keys[u, k, i] = R_{r_i} ent[h_i] over every hop's set,
+    (len(user_ids), n_hop, n_memory, d) float32 (kgat_eval_ripple_keys_f32; one fmaf chain per element in ascending
+    column order).  relation_emb: (n_rel, d * d)."""
+    user_ids = _ripple_eval_operands("ripple_eval_keys", ent, sets, user_ids)
+    d = ent.shape[1]
+    relation_emb = _need(relation_emb, torch.float32, "relation_emb", (sets.n_rel, d * d))
+    if not ripple_eval_supported(d, sets.n_memory, sets.n_hop, 0, 1):
+        raise KGATLibraryError("ripple_eval_keys: d = %d (16, 32, 64), n_memory = %d (1..64) or n_hop = %d (1, 2) outside "
+                               "the kernel's range" % (d, sets.n_memory, sets.n_hop))
+    n_call = user_ids.numel()
+    keys = torch.empty((n_call, sets.n_hop, sets.n_memory, d), dtype=torch.float32, device=ent.device)
+    with _timed("ripple_eval_keys", (n_call, sets.n_hop, sets.n_memory, d)):
+        check(_lib.load().kgat_eval_ripple_keys_f32(n_call, _ptr(user_ids), d, sets.n_memory, sets.n_hop, sets.n_rel,
+                                                    sets.n_nodes, sets.n_users, _ptr(ent), _ptr(relation_emb),
+                                                    _ptr(sets.mem_h), _ptr(sets.mem_r), _ptr(keys), _stream(ent)),
+              "kgat_eval_ripple_keys_f32")
+    return keys
+
+
+def ripple_eval_items(ent, item_lo, item_hi):
+    """The rows ent[item_lo:item_hi] as the sweep's item fragments (kgat_eval_items_kmajor_f32): laid out once per
+    evaluation, shared by every user block."""
+    if not isinstance(ent, torch.Tensor) or ent.dtype != torch.float32 or not ent.is_cuda or ent.dim() != 2 or \
+            ent.stride(1) != 1:
+        raise KGATLibraryError("ripple_eval_items: `ent` must be a float32 HIP matrix with unit column stride")
+    return _eval_items(_lib.load(), ent, torch.arange(int(item_lo), int(item_hi), dtype=torch.int32, device=ent.device))
+
+
+def ripple_eval_topk(ent, sets, user_ids, keys, itemT, n_items, W, mode, all_hops, train_ptr, train_items, K,
+                     want_scores=True):
+    """The K best unseen items of every user of `user_ids` under RippleNet (kgat_eval_ripple_topk_f32; the arithmetic is
+    stated in include/kgat_hip.h).  keys = ripple_eval_keys(.., user_ids), itemT = ripple_eval_items(ent, lo, lo +
+    n_items); W (d, d) or None (modes 0, 1); mode 0..3; the train CSR holds ascending item positions per user.  Returns
+    (items, scores): int32 positions (n_users, K), -1 padding, and float32 scores, -inf padding (None without
+    want_scores)."""
+    user_ids = _ripple_eval_operands("ripple_eval_topk", ent, sets, user_ids)
+    d, K, mode, n_items = ent.shape[1], int(K), int(mode), int(n_items)
+    n_call = user_ids.numel()
+    if not ripple_eval_supported(d, sets.n_memory, sets.n_hop, mode, K):
+        raise KGATLibraryError("ripple_eval_topk: d = %d (16, 32, 64), n_memory = %d (1..64), n_hop = %d (1, 2), mode = %d "
+                               "(0..3) or K = %d (1..%d) outside the kernel's range"
+                               % (d, sets.n_memory, sets.n_hop, mode, K, RIPPLE_EVAL_MAX_K))
+    if n_items < 1:
+        raise KGATLibraryError("ripple_eval_topk: no items to rank")
+    keys = _need(keys, torch.float32, "keys", (n_call, sets.n_hop, sets.n_memory, d))
+    itemT = _need(itemT, torch.float32, "itemT")
+    lib = _lib.load()
+    if itemT.numel() < int(lib.kgat_eval_items_elems(n_items, d)):
+        raise ValueError("itemT holds %d elements, %d items of width %d need %d"
+                         % (itemT.numel(), n_items, d, int(lib.kgat_eval_items_elems(n_items, d))))
+    if mode >= 2:
+        W = _need(W, torch.float32, "W", (d, d))
+    elif W is not None:
+        W = _need(W, torch.float32, "W", (d, d))
+    train_ptr = _need(train_ptr, torch.int32, "train_ptr", (n_call + 1,))
+    train_items = _need(train_items, torch.int32, "train_items")
+    dev = ent.device
+    topk = torch.empty((n_call, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((n_call, K), dtype=torch.float32, device=dev) if want_scores else None
+    if n_call == 0:
+        return topk, scores
+    ws = _workspace(lib.kgat_eval_ripple_scratch_bytes(n_call, n_items, d, sets.n_memory, sets.n_hop, K), dev)
+    with _timed("ripple_eval_topk", (n_call, n_items, d, sets.n_memory, sets.n_hop, K)):
+        check(lib.kgat_eval_ripple_topk_f32(n_call, _ptr(user_ids), n_items, d, sets.n_memory, sets.n_hop, mode,
+                                            1 if all_hops else 0, sets.n_nodes, sets.n_users, _ptr(itemT), _ptr(keys),
+                                            _ptr(ent), _ptr(sets.mem_t), _ptr(W), _ptr(train_ptr), _ptr(train_items), K,
+                                            _ptr(ws), ws.numel(), _ptr(topk), _ptr(scores), _stream(ent)),
+              "kgat_eval_ripple_topk_f32")
+    return topk, scores
+
+
 # ---------------------------------------------------------------- global-norm gradient clipping (kgat.py:32,162)
 def __getattr__(name):
     # GRAD_NORM_CHAIN: the compile-time constant of the library (kgat_grad_norm_chain), read when first asked for

@@ -8,8 +8,10 @@ model scores a (user, item) pair by letting the item vector v attend over each h
 
 updating v between hops, and ``y = <v, sum_k o_k>``.  The attention is one operator, ``autograd.ripple_hop``
 (csrc/kgat_ripple.hip on a HIP device in fp32, ``ripple_hop_torch`` elsewhere); the per-relation queries
-``U[b, r] = v_b R_r`` are one matmul per hop.  The evaluation scores all (user, item) pairs in torch operators over user
-blocks, using that a ripple set depends on the user only - a fused all-pairs sweep is out of scope."""
+``U[b, r] = v_b R_r`` are one matmul per hop.  The evaluation scores all (user, item) pairs using that a ripple set
+depends on the user only: by default in torch operators over user blocks (``scores``), with ``fused=True`` on the
+all-pairs sweep of csrc/kgat_ripple_eval.hip (``ops.ripple_eval_keys`` + ``ops.ripple_eval_topk``: per user the items
+attend over the hops' memories on the fp32 MFMA and the K best unseen items are selected on chip)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -278,11 +280,109 @@ class RippleNet(nn.Module):
             out.append(self._predict(v, o_list))
         return torch.cat(out, 0) if out else torch.zeros(0, n_items, dtype=ent.dtype, device=ent.device)
 
-    def topk(self, plan, K, max_bytes=1 << 28):
-        """The K best unseen items of every user of an ``EvalPlan`` (``metrics.topk_unseen`` over ``scores``)."""
-        return metrics.topk_unseen(self.scores, self.n_items, plan, K, max_bytes)
+    def _fused_refusal(self, K):
+        """Why the fused sweep cannot evaluate this model at depth K (None: it can)."""
+        from . import ops
+        ent, sets = self.entity_emb.weight, self.sets
+        if not ent.is_cuda:
+            return "the parameters are on %s: the fused sweep only runs on a HIP device (CPU tensors)" % ent.device
+        if ent.dtype != torch.float32:
+            return "the parameters are %s, the fused sweep is float32" % ent.dtype
+        if not 1 <= int(K) <= ops.RIPPLE_EVAL_MAX_K:
+            return "K = %d is outside 1..%d" % (K, ops.RIPPLE_EVAL_MAX_K)
+        if not ops.ripple_eval_supported(self.dim, sets.n_memory, sets.n_hop, UPDATE_MODES.index(self.item_update_mode), K):
+            return "d = %d, n_memory = %d, n_hop = %d: the fused sweep takes d in (16, 32, 64), n_memory in 1..64, n_hop " \
+                   "in (1, 2)" % (self.dim, sets.n_memory, sets.n_hop)
+        return None
 
-    def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28):
-        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``
-        (``metrics.calc_metrics_unseen`` over ``scores``): the dict ``metrics.calc_metrics`` returns."""
-        return metrics.calc_metrics_unseen(self.scores, self.n_items, plan, Ks, max_bytes)
+    @torch.no_grad()
+    def _fused_topk(self, what, user_ids, train_ptr, train_items, K, max_bytes=1 << 28, want_scores=True):
+        """``ops.ripple_eval_topk`` for the users `user_ids` (int32): the items laid out once, then per user block - sized
+        so that its key table stays below `max_bytes` - the keys pass and the sweep."""
+        from . import ops
+        why = self._fused_refusal(K)
+        if why is not None:
+            raise ops.KGATLibraryError("%s(fused=True): %s" % (what, why))
+        ent = self.entity_emb.weight.detach().contiguous()
+        sets = self.sets.to(ent.device)
+        rel = self.relation_emb.weight.detach().contiguous()
+        mode = UPDATE_MODES.index(self.item_update_mode)
+        W = self.transform_matrix.weight.detach().contiguous() if mode >= 2 else None
+        lo, hi = self.item_range
+        itemT = ops.ripple_eval_items(ent, lo, hi)
+        n = user_ids.numel()
+        block = max(1, int(max_bytes // (4 * sets.n_hop * sets.n_memory * self.dim)))
+        ptr = train_ptr.cpu() if n > block else None
+        tops, scs = [], []
+        for b0 in range(0, n, block):
+            b1 = min(b0 + block, n)
+            us = user_ids[b0:b1].contiguous()
+            if ptr is None:
+                tp, ti = train_ptr, train_items
+            else:
+                first, last = int(ptr[b0]), int(ptr[b1])
+                tp, ti = (train_ptr[b0:b1 + 1] - first).contiguous(), train_items[first:last].contiguous()
+            keys = ops.ripple_eval_keys(ent, rel, sets, us)
+            top, sc = ops.ripple_eval_topk(ent, sets, us, keys, itemT, hi - lo, W, mode, self.using_all_hops, tp, ti, K,
+                                           want_scores=want_scores)
+            tops.append(top)
+            scs.append(sc)
+        if not tops:
+            return (torch.zeros(0, K, dtype=torch.int32, device=ent.device),
+                    torch.zeros(0, K, dtype=torch.float32, device=ent.device) if want_scores else None)
+        if len(tops) == 1:
+            return tops[0], scs[0]
+        return torch.cat(tops, 0), (torch.cat(scs, 0) if want_scores else None)
+
+    def _check_plan(self, plan):
+        if plan.n_items != self.n_items:
+            raise ValueError("topk: the plan ranks %d items, the model scores %d" % (plan.n_items, self.n_items))
+
+    def topk(self, plan, K, max_bytes=1 << 28, fused=False):
+        """The K best unseen items of every user of an ``EvalPlan`` as item positions, (n_users, K) int32.  Default:
+        ``metrics.topk_unseen`` over ``scores`` (``torch.topk``).  ``fused=True``: the all-pairs sweep
+        (``ops.ripple_eval_topk``) - score descending, equal scores by item position, ``-1`` where a user has fewer than
+        K unseen items; ``KGATLibraryError`` naming the reason where the model or the device is outside its envelope."""
+        if not fused:
+            return metrics.topk_unseen(self.scores, self.n_items, plan, K, max_bytes)
+        self._check_plan(plan)
+        return self._fused_topk("topk", plan.user_ids, plan.train_ptr, plan.train_items, K, max_bytes, want_scores=False)[0]
+
+    def evaluate(self, plan, Ks=(20,), max_bytes=1 << 28, fused=False):
+        """Mean recall / ndcg / precision / hit_ratio at the ascending cut-offs `Ks` for an ``EvalPlan``: the dict
+        ``metrics.calc_metrics`` returns.  Default: ``metrics.calc_metrics_unseen`` over ``scores``.  ``fused=True``:
+        ``topk(fused=True)`` at the largest cut-off, then ``ops.eval_metrics_at_ks``."""
+        if not fused:
+            return metrics.calc_metrics_unseen(self.scores, self.n_items, plan, Ks, max_bytes)
+        from . import ops
+        Ks = [int(k) for k in Ks]
+        if plan.n_users == 0:
+            raise ZeroDivisionError("no test users")
+        self._check_plan(plan)
+        top = self._fused_topk("evaluate", plan.user_ids, plan.train_ptr, plan.train_items, Ks[-1], max_bytes,
+                               want_scores=False)[0].contiguous()
+        out = ops.eval_metrics_at_ks(top, plan.test_ptr, plan.test_items, Ks)
+        mean = (out.sum(0) / plan.n_users).cpu().numpy()
+        return {name: mean[:, m].copy() for m, name in enumerate(metrics.METRIC_NAMES)}
+
+    def recommend(self, user_ids, K, seen=None):
+        """The K best items of every user of ``user_ids`` that the user has not seen, on the fused sweep: ``(items,
+        scores)`` - int64 item NODE ids ``(len(user_ids), K)`` in rank order (score descending, equal scores by item
+        position) and their float32 scores ``y(u, i)``; ``-1`` / ``-inf`` at the end where fewer than K items are unseen.
+        ``seen`` maps a user id to the item positions to leave out (None: nothing).  HIP tensors, 1 <= K <= 128
+        (``KGATLibraryError`` otherwise)."""
+        from . import ops
+        users = [int(u) for u in np.asarray(user_ids).reshape(-1)]
+        why = self._fused_refusal(K)
+        if why is not None:
+            raise ops.KGATLibraryError("recommend: %s" % why)
+        lo, hi = self.item_range
+        plan = metrics.EvalPlan(seen if seen is not None else {}, dict.fromkeys(users, metrics._EMPTY), np.arange(lo, hi),
+                                self.entity_emb.weight.device)
+        if len(plan.user_ids) != len(users):
+            raise ValueError("recommend: a user is listed twice")
+        if users and not 0 <= min(users) <= max(users) < self.sets.n_users:
+            raise IndexError("user id outside the ripple sets' %d users" % self.sets.n_users)
+        pos, scores = self._fused_topk("recommend", plan.user_ids, plan.train_ptr, plan.train_items, K)
+        pos = pos.long()
+        return torch.where(pos >= 0, pos + lo, pos), scores

@@ -231,6 +231,10 @@ def parse_args(argv=None):
                     help="--model ripplenet: 1 adds the inverse (t, r + n, h) of every KG triple to the ripple sets' adjacency "
                          "(the planted CKG holds item -> attribute triples only and needs it; the KGAT release's "
                          "kg_final.txt already contains the inverses).  Default 0")
+    ap.add_argument("--ripple_eval", choices=("torch", "fused"), default=argparse.SUPPRESS,
+                    help="--model ripplenet: how an epoch is evaluated - torch (default): block scores in torch operators "
+                         "and torch.topk; fused: the all-pairs sweep of kgat_ripple_eval.hip (d 16, 32 or 64, up to 64 "
+                         "triples per hop, 1 or 2 hops, cut-offs up to 128)")
     ap.add_argument("--nfm_layers", type=_widths, default=argparse.SUPPRESS, metavar="W[,W...]",
                     help="--model nfm: widths of the hidden layers above the pooling (default 64)")
     ap.add_argument("--nfm_eval", choices=("torch", "fused"), default=argparse.SUPPRESS,
@@ -343,6 +347,8 @@ def parse_args(argv=None):
     for flag in RIPPLE_FLAGS:
         if hasattr(args, flag) and kind != "ripplenet":
             ap.error("--%s belongs to --model ripplenet" % flag)
+    if hasattr(args, "ripple_eval") and kind != "ripplenet":
+        ap.error("--ripple_eval chooses the evaluation route of --model ripplenet")
     if hasattr(args, "nfm_layers") and kind != "nfm":
         ap.error("--nfm_layers sets the hidden layers of --model nfm")
     if hasattr(args, "nfm_eval") and kind != "nfm":
@@ -915,7 +921,8 @@ def _ripple_family(drv):
     """--model ripplenet: the ripple sets are built once on the host; an epoch is a CF phase of steps on the pair stream
     of the other baselines - one pass over the 2 B samples, positives first, BCE with 1:1 negatives plus the KGE and L2
     terms (RippleNet.get_loss), one FusedAdam over all parameters - then evaluation through RippleNet.evaluate (block
-    scores in torch operators, torch.topk, the metric kernel)."""
+    scores in torch operators, torch.topk, the metric kernel; with --ripple_eval fused the all-pairs sweep instead of the
+    first two)."""
     args, ds, dev = drv.args, drv.ds, drv.dev
     t0 = time.perf_counter()
     sets = K.RippleSets.build(ds.train_KG_triplet, ds.train_pairs, ds.n_users, ds.n_KG_entity, n_hop=getattr(args, "n_hop", 2),
@@ -927,8 +934,12 @@ def _ripple_family(drv):
                         item_update_mode=getattr(args, "item_update_mode", "plus_transform"),
                         using_all_hops=bool(getattr(args, "using_all_hops", 1)), item_range=drv.items).to(dev)
     opt = K.FusedAdam(model.parameters(), lr=args.lr)
-    return Family(model, [lambda epoch, rec: drv.cf_phase(epoch, rec, opt, model.get_loss)],
-                  lambda: (model.evaluate(drv.splits.plans[name], args.Ks) for name in ("valid", "test")), None)
+    fused = getattr(args, "ripple_eval", "torch") == "fused"
+
+    def eval_inputs():
+        return (model.evaluate(drv.splits.plans[name], args.Ks, fused=fused) for name in ("valid", "test"))
+
+    return Family(model, [lambda epoch, rec: drv.cf_phase(epoch, rec, opt, model.get_loss)], eval_inputs, None)
 
 
 if __name__ == "__main__":

@@ -1354,6 +1354,64 @@ int kgat_nfm_eval_topk_f32(int64_t n_users, const int32_t* user_ids, int64_t n_i
                            const int32_t* train_items, int K, void* scratch, size_t scratch_bytes, int32_t* topk_items,
                            float* topk_scores, kgat_stream_t stream);
 
+/* ---------------------------------------------------------------- all-pairs RippleNet evaluation: attention scores into top-K (additive within ABI 16)
+ * The K best unseen items of every user under RippleNet, without a users x items tensor.  For the user's hop k
+ * (0-based, n_hop hops of n_memory = M triples (h_i, r_i, t_i) each; mem_h / mem_r / mem_t: n_users x n_hop x M, int32,
+ * the relations of a set ascending) and an item with row v_0 = ent[item]:
+ *     key[k, i, :] = R_{r_i} ent[h_i]                  R_r = relation_emb[r] as a d x d row-major matrix
+ *     s_i = <v_k, key[k, i]>    p = softmax_i(s)    o_k = sum_i p_i ent[t_i]
+ *     v_{k+1} = o_k | v_k + o_k | W o_k | W (v_k + o_k)        mode 0..3; (W x)[a] = sum_c W[a, c] x[c], W d x d row-major
+ *     y = <v_H, o_{H-1}>   or   <v_H, sum_k o_k>               (all_hops != 0)
+ *
+ * kgat_eval_ripple_keys_f32 writes keys (n_call x n_hop x M x d, contiguous) for the users user_ids[0 .. n_call):
+ *     key[a] = fma(R[a, d-1], h[d-1], ... fma(R[a, 1], h[1], fma(R[a, 0], h[0], 0)))      ascending c from 0, all fp32
+ * A user id outside [0, n_users) reads nothing and gets zeros; a set entry outside [0, n_nodes) / [0, n_rel) reads
+ * nothing and gets NaN.
+ *
+ * kgat_eval_ripple_topk_f32 takes itemT = kgat_eval_items_kmajor_f32(emb = the ranked item rows, F = d, item_ids =
+ * 0 .. n_items - 1), the key table of the SAME user_ids, ent (n_nodes x d, contiguous) and mem_t for the tail rows, W
+ * (may be NULL for modes 0 and 1), and the users' ascending training lists as a CSR over positions in user_ids
+ * (train_ptr: n_call + 1) of item positions.  The arithmetic, to the operation order (all fp32, inputs finite), per
+ * (user, item); every sum over an index below is a chain of v_mfma_f32_32x32x2_f32 steps in ascending index order
+ * from 0 (an exact fmaf chain in k order, as in the NFM block above):
+ *     s_i   = sum_c key[k, i, c] v_k[c]                                   c ascending from 0, start 0
+ *     mx    = max_i s_i                                                   over the M slots (exact)
+ *     e_i   = exp(s_i - mx)                                               the fast exponential (v_exp_f32 of x log2 e)
+ *     sum   = A + B, A over the even slots and B over the odd slots, each from 0 in ascending slot order, one add each
+ *     p_i   = e_i * fl(1 / sum)
+ *     o_k[c] = sum_i ent[t_i][c] p_i                                      i ascending from 0, start 0
+ *     x     = o_k (modes 0, 2), fl(v_k + o_k) (modes 1, 3);  v_{k+1} = x (modes 0, 1), sum_c W[a, c] x[c] (modes 2, 3)
+ *     z     = o_{H-1}, or with all_hops fl(.. fl(fl(0 + o_0) + o_1) ..)
+ *     y     = A + B, A over the even columns and B over the odd columns, each p = fma(v_H[c], z[c], p) from 0 ascending
+ * Slots are padded to a multiple of 32 inside the kernel; a padded slot is masked by its index and has e = 0 exactly.
+ * Items are ordered by (y descending, IEEE compare with -0 = +0; equal y: ascending item position); training items
+ * are never listed; a user with fewer than K unseen items gets -1 / -inf at the end of topk_items / topk_scores
+ * (n_call x K each; topk_scores may be NULL).  The order is total and no float atomic is used: the lists are bitwise
+ * reproducible and independent of how the entry cuts the items into segments, of the other users of the call, and of
+ * K as far as the shorter list reaches.  A user id may repeat; one outside [0, n_users) gets an empty list.
+ *
+ * The entry runs one workgroup per (user, item segment): the user's keys, tail rows and W are laid out in LDS as MFMA
+ * A operands once, four wavefronts split the segment's item tiles of 32, every product has the item on the lane and
+ * takes the previous accumulator registers as its B operand; each wavefront keeps a candidate buffer of 256 entries
+ * that a selection prunes to K, and one wavefront per user merges the lists.
+ *
+ * kgat_eval_ripple_supported(d, n_memory, n_hop, mode, K): d in {16, 32, 64}, 1 <= n_memory <= 64, n_hop in {1, 2}, mode
+ * 0..3, 1 <= K <= 128 (d = 128, longer sets and deeper hops are not offered).  n_call < 0, n_items outside [1, 2^31 -
+ * 32), n_nodes / n_users outside [1, 2^31), n_rel < 1, a null pointer other than topk_scores / train_items (no training
+ * item at all) / W (modes 0, 1), ent / relation_emb / keys / itemT / scratch not 16-byte aligned: KGAT_E_BADARG;
+ * outside the envelope: KGAT_E_UNSUPPORTED; scratch below kgat_eval_ripple_scratch_bytes(n_call, n_items, d,
+ * n_memory, n_hop, K): KGAT_E_WORKSPACE.  Every check precedes any device work. */
+int kgat_eval_ripple_supported(int d, int n_memory, int n_hop, int mode, int K);
+int kgat_eval_ripple_keys_f32(int64_t n_call, const int32_t* user_ids, int d, int n_memory, int n_hop, int n_rel,
+                              int64_t n_nodes, int64_t n_users, const float* ent, const float* relation_emb,
+                              const int32_t* mem_h, const int32_t* mem_r, float* keys, kgat_stream_t stream);
+size_t kgat_eval_ripple_scratch_bytes(int64_t n_call, int64_t n_items, int d, int n_memory, int n_hop, int K);
+int kgat_eval_ripple_topk_f32(int64_t n_call, const int32_t* user_ids, int64_t n_items, int d, int n_memory, int n_hop,
+                              int mode, int all_hops, int64_t n_nodes, int64_t n_users, const float* itemT,
+                              const float* keys, const float* ent, const int32_t* mem_t, const float* W,
+                              const int32_t* train_ptr, const int32_t* train_items, int K, void* scratch,
+                              size_t scratch_bytes, int32_t* topk_items, float* topk_scores, kgat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
